@@ -7,12 +7,18 @@ before the timed region.  A step = one full pass: clear the table, count every k
 resident batch, (N>1: exchange owner segments over RCCL and merge), sync.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|k63|c5] [--reads R] ...
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds what
+the headline does not need: the CPU baseline with its prefix-parity check and the end-to-end CLI
+run (N = 1), and the weak-scaling pass (N > 1).  `--dump-outputs DIR` writes what the last timed
+step counted as DIR/*.npy (float64; a fixed, seeded sample of the keys, see dump_outputs()).
 
 `--gpus N` (N > 1) from a bare shell starts the N ranks itself: the parent spawns one child per GPU
 BEFORE it imports torch or touches HIP and only waits for them (replaces the pthread fan-out of
-/root/reference/src/main.cu:277-295).  Under torchrun (RANK / WORLD_SIZE already set) the process is
+the reference's src/main.cu:277-295).  Under torchrun (RANK / WORLD_SIZE already set) the process is
 a rank.  N > 1 reports BASELINE configs[3] as written -- the SAME reads split over the GPUs (strong
-scaling) -- as the headline, with the weak-scaling measurement under the key "weak".
+scaling) -- as the headline; with --full the weak-scaling measurement follows under the key "weak".
 """
 import argparse
 import json
@@ -46,9 +52,9 @@ def parse():
     p.add_argument("--uniform", action="store_true", help="uniform random reads (all-distinct variant)")
     p.add_argument("--no-canonical", action="store_true")
     p.add_argument("--cpu-reads", type=int, default=10_000_000,
-                   help="reads of the same generator timed on the host cores (0: skip)")
+                   help="--full: reads of the same generator timed on the host cores (0: skip)")
     p.add_argument("--e2e-reads", type=int, default=10_000_000,
-                   help="N = 1 only, outside the timed region: reads of a FASTA FILE written with the same generator and "
+                   help="--full, N = 1 only, outside the timed region: reads of a FASTA FILE written with the same generator and "
                         "counted by the `cfrk` CLI (parse + H2D + count + export + write) -> the `end_to_end` object; "
                         "0 or --cpu-reads 0: skip")
     p.add_argument("--cpu-threads", type=int, default=0)
@@ -61,9 +67,15 @@ def parse():
                    help="with --gpus 1: a one-rank process group, and the step goes through the exchange (this rank owns "
                         "every leaf) -- on a one-GPU box the only way the collectives execute over RCCL (tests)")
     p.add_argument("--scaling", default="", choices=["", "weak", "strong", "both"],
-                   help="N > 1 only.  strong (BASELINE configs[3]): the reads are split over the GPUs; "
-                        "weak: every GPU gets the config's reads; both (default): strong is the "
+                   help="N > 1 only.  strong (BASELINE configs[3]; default): the reads are split over the GPUs; "
+                        "weak: every GPU gets the config's reads; both (default with --full): strong is the "
                         "headline and the weak measurement is reported under \"weak\"")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: N = 1: cpu_baseline + prefix_parity "
+                        "(--cpu-reads) and end_to_end (--e2e-reads); N > 1: the weak-scaling pass")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last step counted to DIR/*.npy (float64, <= 64 MB: "
+                        "a fixed, seeded sample of the keys with their counts, and the digest)")
     p.add_argument("--owner-hash", action="store_true",
                    help="force the generic hash-owner exchange + HBM-table merge")
     p.add_argument("--debug-runs-budget", default="", metavar="RANK:BYTES",
@@ -75,6 +87,8 @@ def parse():
                    help="N > 1: what the ranks exchange.  runs (auto for 16 <= k <= 64): deduplicated "
                         "runs, counted by the leaf's owner; leaf: counted per-leaf lists; owner: counted keys")
     a = p.parse_args()
+    if a.dump_outputs and a.gpus != 1:
+        p.error("--dump-outputs needs --gpus 1 (with N > 1 every rank holds only its owner shard of the result)")
     reads, L, k, glen = CONFIGS[a.config]
     # configs[4] is defined per GPU (125 M reads each: gpus x 125 M reads in all, whatever --scaling
     # says); every other config names the job's total
@@ -182,6 +196,59 @@ def measured_traffic(R, L, k, canonical, glen):
     return None, None
 
 
+DUMP_SAMPLE = 1 << 19        # keys aimed at by the --dump-outputs sample
+DUMP_CAP = 1 << 20           # ... and never more (<= 40 MB of float64 at four key words + count)
+
+
+def dump_outputs(g, digest, k, dev, outdir):
+    """What a caller of the counting path receives -- every distinct key with its count, and the digest --
+    written as float64 .npy files to `outdir`.  A full export does not fit 64 MB, so the keys are a fixed, seeded
+    sample chosen by a hash of the key itself (independent of the order the unsorted device export produces):
+    1 in 2^b keys, b the smallest with distinct / 2^b <= DUMP_SAMPLE, sorted like cfrk_global_export (by hi, lo).
+      kmer_keys.npy   (n, 2) or, for k > 32, (n, 4): the key's 32-bit words, least significant first (exact in float64)
+      kmer_counts.npy (n,)
+      digest.npy      (8,): cfrk_global_digest's four 64-bit words (distinct, sum of counts, two hashes), 32-bit
+                      halves, low half first"""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    two = k > 32
+    distinct = int(digest[0])
+    n = max(distinct, 1)
+    lo = torch.empty(n, dtype=torch.int64, device=dev)
+    hi = torch.empty(n, dtype=torch.int64, device=dev) if two else None
+    cnt = torch.empty(n, dtype=torch.int32, device=dev)
+    got = g.export_device(lo.data_ptr(), hi.data_ptr() if two else 0, cnt.data_ptr(), n, 1)[0]
+    if got != distinct:
+        raise SystemExit(f"--dump-outputs: export returned {got} entries, the digest says {distinct}")
+    lo, cnt = lo[:got], cnt[:got]
+    m32 = 0xFFFFFFFF
+    words = [lo & m32, (lo >> 32) & m32]
+    if two:
+        hi = hi[:got]
+        words += [hi & m32, (hi >> 32) & m32]
+    h = torch.full_like(lo, 0x2545F491)                   # the seed
+    for w in words:                                       # (< 2^32 times < 2^31: no int64 overflow)
+        h = ((h ^ w) * 0x5BD1E995) & m32
+        h = h ^ (h >> 15)
+    bits = 0
+    while (got >> bits) > DUMP_SAMPLE:
+        bits += 1
+    sel = (h & ((1 << bits) - 1)) == 0
+    words = [w[sel] for w in words]
+    cnt = cnt[sel]
+    # unsigned order of (hi, lo) = lexicographic order of the words, most significant first (stable sorts)
+    order = torch.arange(words[0].numel(), device=dev)
+    for w in words:
+        order = order[torch.sort(w[order], stable=True).indices]
+    order = order[:DUMP_CAP]
+    keys = torch.stack([w[order] for w in words], dim=1)
+    np.save(os.path.join(outdir, "kmer_keys.npy"), keys.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(outdir, "kmer_counts.npy"), cnt[order].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(outdir, "digest.npy"),
+            np.array([float((x >> s) & m32) for x in digest for s in (0, 32)], dtype=np.float64))
+
+
 def config_label(args, world, scaling):
     base = (args.reads, args.L, args.k, args.glen or args.reads, args.uniform, args.no_canonical)
     for name, (reads, L, k, glen) in CONFIGS.items():
@@ -249,8 +316,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(scaling):
-        """W warm-up + K timed steps of the job under `scaling`; returns rank 0's result dict"""
+    def measure(scaling, dump_dir=""):
+        """W warm-up + K timed steps of the job under `scaling`; returns rank 0's result dict
+        (dump_dir: what the last timed step counted goes there, see dump_outputs())"""
         # total reads of the job (a per-GPU config has the same job under both scalings)
         R = args.reads * world if (scaling == "weak" or args.per_gpu) else args.reads
         glen = args.glen or args.reads
@@ -484,6 +552,8 @@ def main():
             digest = sharded.merge_digests(digest, "cpu" if wire else dev)
         del d_data, d_start, d_length, eng
         torch.cuda.empty_cache()
+        if dump_dir:
+            dump_outputs(final, digest, k, dev, dump_dir)
 
         D = digest[0]
         ok = digest[1] == kmers_total
@@ -539,10 +609,10 @@ def main():
             out["msp_info"] = info
         return out, ok, kmers_total
 
-    scaling = args.scaling or "both"
+    scaling = args.scaling or ("both" if args.full else "strong")
     parity = None
     if world == 1:
-        out, ok, total = measure("strong")
+        out, ok, total = measure("strong", args.dump_outputs)
     elif scaling == "both" and not args.per_gpu:
         out, ok, total = measure("strong")
         # The headline is safe from here on: if the weak pass (N x the per-GPU memory) dies or
@@ -561,7 +631,7 @@ def main():
     _PENDING["line"] = None
 
     if rank == 0:
-        if world == 1 and not multi and args.cpu_reads > 0:
+        if args.full and world == 1 and not multi and args.cpu_reads > 0:
             def gpu_digest_of_prefix(Rp):
                 nNp = Rp * (L + 1)
                 d = torch.empty(nNp + 64, dtype=torch.int8, device=dev)

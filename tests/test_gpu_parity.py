@@ -450,9 +450,52 @@ def test_bench_self_launches_two_ranks_and_matches_the_one_gpu_digest():
     assert one["sum_count_ok"] and two["sum_count_ok"]
     assert two["n_gpus"] == 2 and two["scaling"] == "strong"
     assert two["digest"] == one["digest"]
-    both = _bench_line(["--gpus", "2", "--same-gpu", "--dist-backend", "gloo"] + common)
+    both = _bench_line(["--gpus", "2", "--same-gpu", "--dist-backend", "gloo", "--full"] + common)
     assert both["scaling"] == "strong" and both["digest"] == one["digest"]
     assert both["weak"]["config"]["reads"] == 4_000_000 and both["weak"]["sum_count_ok"]
+
+
+def test_bench_plain_run_measures_the_headline_only_and_full_adds_the_rest(tmp_path):
+    """a plain `bench.py --gpus 1` run times exactly --steps steps and prints the headline without the CPU baseline,
+    the prefix-parity check or the end-to-end CLI run; --full adds them, and the oracle agrees on the prefix"""
+    common = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--reads", "400000"]
+    plain = _bench_line(common)
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["ms_per_step"] > 0 and plain["sum_count_ok"]
+    assert plain["cpu_baseline"] is None and "prefix_parity" not in plain and "end_to_end" not in plain
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert key in plain
+    full = _bench_line(common + ["--full", "--cpu-reads", "200000", "--cpu-runs", "1", "--e2e-reads", "100000"])
+    assert full["digest"] == plain["digest"] and full["prefix_parity"] is True
+    assert full["cpu_baseline"]["value"] > 0 and "error" not in full["end_to_end"]
+
+
+@pytest.mark.parametrize("k", [31, 63])
+def test_bench_dump_outputs_is_a_deterministic_sample_of_the_oracle_counts(tmp_path, k):
+    """`--dump-outputs DIR`: float64 .npy files of what the last timed step counted -- a hash-chosen sample of the
+    keys (32-bit words) with their counts and the digest.  Two runs give the same files, the digest is the result
+    line's, and every sampled key carries the oracle's count of the same generated reads."""
+    R, L, G = 200_000, 150, 2_000_000      # ~2 M distinct keys: more than one sample's worth
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "0", "--reads", str(R), "--glen", str(G), "--k", str(k)]
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        lines.append(_bench_line(common + ["--dump-outputs", str(d)]))
+        dumps.append({f: np.load(d / f) for f in ("kmer_keys.npy", "kmer_counts.npy", "digest.npy")})
+    for f in dumps[0]:
+        assert dumps[0][f].dtype == np.float64 and (dumps[0][f] == dumps[1][f]).all(), f
+    keys, cnt, dig = dumps[0]["kmer_keys.npy"], dumps[0]["kmer_counts.npy"], dumps[0]["digest.npy"]
+    w = dig.astype(np.uint64)
+    assert [f"{x:016x}" for x in (w[0::2] | (w[1::2] << np.uint64(32))).tolist()] == lines[0]["digest"]
+    assert keys.shape == (len(cnt), 4 if k > 32 else 2) and 0 < len(cnt) < lines[0]["distinct"]
+    kw = keys.astype(np.uint64)
+    klo = kw[:, 0] | (kw[:, 1] << np.uint64(32))
+    khi = (kw[:, 2] | (kw[:, 3] << np.uint64(32))) if k > 32 else np.zeros_like(klo)
+    assert (np.lexsort((klo, khi)) == np.arange(len(klo))).all()
+    data, _, _ = orc.synth_reads(0, R, L, G)
+    wlo, whi, wcnt = orc.global_count(data, k, orc.ORC_CANONICAL)
+    assert len(wlo) == lines[0]["distinct"]
+    want = dict(zip(zip(whi.tolist(), wlo.tolist()), wcnt.tolist()))
+    assert all(want.get((h, lo)) == c for h, lo, c in zip(khi.tolist(), klo.tolist(), cnt.astype(np.uint64).tolist()))
 
 
 def test_bench_rank_whose_runs_only_add_is_refused_makes_all_ranks_take_the_leaf_exchange():

@@ -14,7 +14,7 @@ Writes a configs[1]-sized FASTA (10 M x 150 bp from the SURVEY 8d generator, 1.6
   cfrk in.fasta out4.cfrk 4 T 8192 --timing                               (the reference's own mode: compat, k = 4)
   cfrk first-1M-reads.fasta out4all.cfrk 4 T 8192 --all-chunks --timing   (every chunk written)
 and prints one JSON object: per run the phases `cfrk --timing` reports, as seconds and GB/s.
-`measure(reads, ...)` is what bench.py calls for the `end_to_end` object of its default line.
+`measure(reads, ...)` is what `bench.py --full` calls for the `end_to_end` object of its line.
 """
 import json
 import os
