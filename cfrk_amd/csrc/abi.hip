@@ -503,23 +503,37 @@ int cfrk_global_export_device(cfrk_ctx *ctx, uint64_t *d_lo, uint64_t *d_hi, uin
 
 int cfrk_global_export(cfrk_ctx *ctx, uint64_t *keys_lo, uint64_t *keys_hi, uint32_t *counts,
                        uint64_t cap, uint64_t *n_out) {
+  return cfrk_global_export_range(ctx, 1, CFRK_COUNT_MAX, keys_lo, keys_hi, counts, cap, n_out);
+}
+
+int cfrk_global_export_range(cfrk_ctx *ctx, uint32_t min_count, uint32_t max_count, uint64_t *keys_lo,
+                             uint64_t *keys_hi, uint32_t *counts, uint64_t cap, uint64_t *n_out) {
   if (!ctx || !n_out) return CFRK_ERR_ARG;
+  if (min_count == 0) min_count = 1;
   uint64_t n = 0;
   int rc = cfrk_global_finish(ctx, &n);
   const bool saturated = rc == CFRK_ERR_COUNT_OVERFLOW;   // the result is exported all the same, the code returned at the end
   if (rc && !saturated) return rc;
+  auto done = [&]() { return saturated ? cfrk_fail(ctx, CFRK_ERR_COUNT_OVERFLOW, "a key occurred 2^32 - 2 times or more: its count is held at 0xFFFFFFFE") : CFRK_OK; };
+  *n_out = 0;
+  if (n == 0 || min_count > max_count) return done();
+  // entries kept (one read pass; the digest above resolved the result, so this resolves to the same source)
+  ResultSrc src;
+  bool use_list = false;
+  if ((rc = cfrk_msp_resolve(ctx, &src, &use_list))) return rc;
+  const ResultSrc *sp = use_list ? &src : nullptr;
+  if ((rc = cfrk_result_export_count(ctx, sp, min_count, max_count, 1, &n))) return rc;
   *n_out = n;
   if (n > cap) return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "%llu entries, room for %llu", (unsigned long long)n, (unsigned long long)cap);
-  if (n == 0) return CFRK_OK;
+  if (n == 0) return done();
   if (!keys_lo || !counts) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
   void *d_lo, *d_hi = nullptr, *d_cnt;
   if ((rc = cfrk_pool_get(ctx, BUF_EXPORT_LO, n * 8, &d_lo))) return rc;
   if (ctx->g_two && (rc = cfrk_pool_get(ctx, BUF_EXPORT_HI, n * 8, &d_hi))) return rc;
   if ((rc = cfrk_pool_get(ctx, BUF_EXPORT_CNT, n * 4, &d_cnt))) return rc;
-  uint64_t pc = 0;
-  rc = cfrk_global_export_device(ctx, (uint64_t *)d_lo, (uint64_t *)d_hi, (uint32_t *)d_cnt, n, 1, &pc);
-  if (rc) return rc;
-  // sorted on the device (export_sort.hip), then copied straight into the caller's buffers
+  if ((rc = cfrk_result_export_scatter(ctx, sp, min_count, max_count, 1, &n, (uint64_t *)d_lo, (uint64_t *)d_hi,
+                                       (uint32_t *)d_cnt))) return rc;
+  // only the kept entries are sorted on the device (export_sort.hip) and copied straight into the caller's buffers
   const uint64_t *s_lo, *s_hi;
   const uint32_t *s_cnt;
   if ((rc = cfrk_sort_export(ctx, (const uint64_t *)d_lo, ctx->g_two ? (const uint64_t *)d_hi : nullptr,
@@ -531,7 +545,23 @@ int cfrk_global_export(cfrk_ctx *ctx, uint64_t *keys_lo, uint64_t *keys_hi, uint
   }
   HIP_TRY(ctx, hipMemcpyAsync(counts, s_cnt, n * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (saturated) return cfrk_fail(ctx, CFRK_ERR_COUNT_OVERFLOW, "a key occurred 2^32 - 2 times or more: its count is held at 0xFFFFFFFE");
+  return done();
+}
+
+int cfrk_global_histogram(cfrk_ctx *ctx, uint64_t *hist, uint32_t nbins) {
+  if (!ctx) return CFRK_ERR_ARG;
+  if (!hist) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (nbins < 2 || nbins > (1u << 24)) return cfrk_fail(ctx, CFRK_ERR_ARG, "nbins=%u outside 2..2^24", nbins);
+  if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "histogram before begin");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ResultSrc src;
+  bool use_list = false;
+  int rc = cfrk_msp_resolve(ctx, &src, &use_list);
+  if (rc) return rc;
+  uint64_t st[ST_NWORDS];
+  if ((rc = cfrk_result_histogram(ctx, use_list ? &src : nullptr, nbins, hist, st))) return rc;
+  if (st[ST_OVERFLOW]) return cfrk_fail(ctx, CFRK_ERR_TABLE_FULL, "table of %llu slots overflowed", (unsigned long long)ctx->g_cap);
+  if (st[ST_SAT]) return cfrk_fail(ctx, CFRK_ERR_COUNT_OVERFLOW, "a key occurred 2^32 - 2 times or more: its count is held at 0xFFFFFFFE");
   return CFRK_OK;
 }
 

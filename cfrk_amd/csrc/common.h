@@ -105,6 +105,14 @@ struct ResultSrc;   // table.h: the table itself (NULL) or a compact (key,count)
 int cfrk_result_scan(cfrk_ctx *ctx, const ResultSrc *src, uint64_t stats_host[ST_NWORDS]);
 int cfrk_result_export(cfrk_ctx *ctx, const ResultSrc *src, uint64_t *d_lo, uint64_t *d_hi,
                        uint32_t *d_cnt, uint64_t cap, int parts, uint64_t *part_counts);
+// count-range export in two steps: entries with min_count <= count <= max_count per owner part (host part_counts;
+// synchronises), then the scatter into the owner segments of d_lo / d_hi / d_cnt (room for sum(part_counts) entries)
+int cfrk_result_export_count(cfrk_ctx *ctx, const ResultSrc *src, uint32_t min_count, uint32_t max_count, int parts,
+                             uint64_t *part_counts);
+int cfrk_result_export_scatter(cfrk_ctx *ctx, const ResultSrc *src, uint32_t min_count, uint32_t max_count, int parts,
+                               const uint64_t *part_counts, uint64_t *d_lo, uint64_t *d_hi, uint32_t *d_cnt);
+// abundance histogram of the result into host hist[nbins] (2 <= nbins <= 2^24), the stats words into stats_host
+int cfrk_result_histogram(cfrk_ctx *ctx, const ResultSrc *src, uint32_t nbins, uint64_t *hist, uint64_t stats_host[ST_NWORDS]);
 
 // ---- device helpers -----------------------------------------------------------------------
 #ifdef __HIPCC__

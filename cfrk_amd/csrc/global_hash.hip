@@ -157,6 +157,67 @@ __global__ __launch_bounds__(256) void result_scan_kernel(ResultSrc r) {
   }
 }
 
+// Abundance histogram (k-mer spectrum): hist[min(c, nbins - 1)] += 1 for every entry, hist[0] untouched.  A persistent
+// grid of two workgroups per CU; each keeps the first W = min(nbins, HIST_LDS_BINS) bins as uint32 in dynamic LDS (64 KB
+// at most: two workgroups fit the 160 KB of a CU) and sends the few counts >= W straight to the global uint64 bins.
+// Error-rich data puts most entries on bin 1: a wave adds its count-1 lanes by one LDS atomic (ballot + popcount), not
+// 64 same-address ones.  At the end a workgroup adds only its non-zero LDS bins to the global array.  Each lane keeps
+// HIST_UNROLL entries in flight: 8 waves per CU with one load each would leave HBM idle.
+constexpr uint32_t HIST_LDS_BINS = 16384;
+constexpr int HIST_UNROLL = 4;
+
+__global__ __launch_bounds__(256) void result_histogram_kernel(ResultSrc r, uint32_t nbins, unsigned long long *hist) {
+  extern __shared__ uint32_t lds_bins[];
+  const uint32_t W = nbins < HIST_LDS_BINS ? nbins : HIST_LDS_BINS;
+  const uint32_t top = nbins - 1;
+  for (uint32_t b = threadIdx.x; b < W; b += blockDim.x) lds_bins[b] = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+  const uint64_t span = 64 * HIST_UNROLL;
+  bool sat = false;
+  for (uint64_t base = wave * span; base < r.n; base += nwaves * span) {
+    uint32_t c[HIST_UNROLL];
+    bool occ[HIST_UNROLL];
+#pragma unroll
+    for (int u = 0; u < HIST_UNROLL; ++u) {
+      const uint64_t i = base + 64 * u + lane;
+      uint64_t lo, hi;
+      occ[u] = i < r.n && src_read(r, i, lo, hi, c[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < HIST_UNROLL; ++u) {
+      const uint32_t bin = occ[u] ? min(c[u], top) : 0u;
+      sat |= occ[u] && c[u] >= CFRK_COUNT_MAX;
+      const unsigned long long ones = __ballot(bin == 1);
+      if (lane == 0 && ones) atomicAdd(&lds_bins[1], (uint32_t)__popcll(ones));
+      if (bin > 1) {
+        if (bin < W) atomicAdd(&lds_bins[bin], 1u);
+        else atomicAdd(&hist[bin], 1ull);
+      }
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && r.kind != 1 && r.kind != 3) {
+    const uint32_t ones = sat_ones(r.stats[ST_ONES]);
+    if (ones) {
+      sat |= ones >= CFRK_COUNT_MAX;
+      const uint32_t bin = min(ones, top);
+      if (bin < W) atomicAdd(&lds_bins[bin], 1u);
+      else atomicAdd(&hist[bin], 1ull);
+    }
+  }
+  if (sat) r.stats[ST_SAT] = 1;
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < W; b += blockDim.x) {
+    const uint32_t v = lds_bins[b];
+    if (v) atomicAdd(&hist[b], (unsigned long long)v);
+  }
+}
+
+// the export's count filter: min_count <= c <= max_count ([1, CFRK_COUNT_MAX] keeps every entry)
+__device__ __forceinline__ bool in_range(uint32_t c, uint32_t cmin, uint32_t cmax) { return c >= cmin && c <= cmax; }
+
 __device__ __forceinline__ uint32_t owner_of(uint64_t lo, uint64_t hi, bool two, int parts) {
   const uint64_t m = two ? dev_mix64(lo ^ dev_mix64(hi)) : dev_mix64(lo);
   return (uint32_t)((m & 0xFFFFFFFFull) % (uint32_t)parts);
@@ -167,7 +228,7 @@ __device__ __forceinline__ uint32_t owner_of(uint64_t lo, uint64_t hi, bool two,
 constexpr int MAX_FAST_PARTS = 16;
 
 // pass 1: entries per owner part
-__global__ __launch_bounds__(256) void result_export_count_kernel(ResultSrc r, int parts,
+__global__ __launch_bounds__(256) void result_export_count_kernel(ResultSrc r, int parts, uint32_t cmin, uint32_t cmax,
                                                                   unsigned long long *part_n) {
   const int lane = threadIdx.x & 63;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -176,7 +237,7 @@ __global__ __launch_bounds__(256) void result_export_count_kernel(ResultSrc r, i
   for (uint64_t base = (uint64_t)tid - lane; base < r.n; base += nthreads) {
     const uint64_t i = base + lane;
     uint64_t lo = 0, hi = 0; uint32_t c = 0;
-    const bool occ = (i < r.n) && src_read(r, i, lo, hi, c);
+    const bool occ = (i < r.n) && src_read(r, i, lo, hi, c) && in_range(c, cmin, cmax);
     const uint32_t own = (occ && parts > 1) ? owner_of(lo, hi, two, parts) : 0u;
     if (parts <= MAX_FAST_PARTS) {
       for (int p = 0; p < parts; ++p) {
@@ -187,12 +248,12 @@ __global__ __launch_bounds__(256) void result_export_count_kernel(ResultSrc r, i
       atomicAdd(&part_n[own], 1ull);
     }
   }
-  if (tid == 0 && !two && r.stats[ST_ONES])
+  if (tid == 0 && !two && r.stats[ST_ONES] && in_range(sat_ones(r.stats[ST_ONES]), cmin, cmax))
     atomicAdd(&part_n[owner_of(CFRK_EMPTY_KEY, 0, false, parts)], 1ull);
 }
 
 // pass 2: scatter into the owner segments (part_cursor starts at the exclusive prefix)
-__global__ __launch_bounds__(256) void result_export_scatter_kernel(ResultSrc r, int parts,
+__global__ __launch_bounds__(256) void result_export_scatter_kernel(ResultSrc r, int parts, uint32_t cmin, uint32_t cmax,
                                                                     unsigned long long *part_cursor,
                                                                     uint64_t *__restrict__ out_lo,
                                                                     uint64_t *__restrict__ out_hi,
@@ -204,7 +265,7 @@ __global__ __launch_bounds__(256) void result_export_scatter_kernel(ResultSrc r,
   for (uint64_t base = (uint64_t)tid - lane; base < r.n; base += nthreads) {
     const uint64_t i = base + lane;
     uint64_t lo = 0, hi = 0; uint32_t c = 0;
-    const bool occ = (i < r.n) && src_read(r, i, lo, hi, c);
+    const bool occ = (i < r.n) && src_read(r, i, lo, hi, c) && in_range(c, cmin, cmax);
     const uint32_t own = (occ && parts > 1) ? owner_of(lo, hi, two, parts) : 0u;
     unsigned long long dst = 0;
     if (parts <= MAX_FAST_PARTS) {
@@ -227,7 +288,7 @@ __global__ __launch_bounds__(256) void result_export_scatter_kernel(ResultSrc r,
   }
   if (tid == 0 && !two) {
     const uint64_t ones = r.stats[ST_ONES];
-    if (ones) {
+    if (ones && in_range(sat_ones(ones), cmin, cmax)) {
       const unsigned long long dst = atomicAdd(&part_cursor[owner_of(CFRK_EMPTY_KEY, 0, false, parts)], 1ull);
       out_lo[dst] = CFRK_EMPTY_KEY;
       out_cnt[dst] = sat_ones(ones);
@@ -295,8 +356,26 @@ int cfrk_result_scan(cfrk_ctx *ctx, const ResultSrc *src, uint64_t st[ST_NWORDS]
   return CFRK_OK;
 }
 
-int cfrk_result_export(cfrk_ctx *ctx, const ResultSrc *src, uint64_t *d_lo, uint64_t *d_hi,
-                       uint32_t *d_cnt, uint64_t cap, int parts, uint64_t *part_counts) {
+int cfrk_result_histogram(cfrk_ctx *ctx, const ResultSrc *src, uint32_t nbins, uint64_t *hist, uint64_t st[ST_NWORDS]) {
+  ResultSrc r = src ? *src : table_src(ctx);
+  void *scratch;
+  int rc = cfrk_pool_get(ctx, BUF_SCRATCH, (size_t)nbins * 8, &scratch);
+  if (rc) return rc;
+  unsigned long long *d_hist = (unsigned long long *)scratch;
+  HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, (size_t)nbins * 8, ctx->stream));
+  const uint32_t W = std::min(nbins, HIST_LDS_BINS);
+  const int64_t per_block = 256 * HIST_UNROLL;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)r.n + per_block - 1) / per_block, (int64_t)ctx->num_cus * 2));
+  hipLaunchKernelGGL(result_histogram_kernel, dim3(grid), dim3(256), (size_t)W * sizeof(uint32_t), ctx->stream, r, nbins, d_hist);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(hist, d_hist, (size_t)nbins * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(st, ctx->g_stats, ST_NWORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CFRK_OK;
+}
+
+int cfrk_result_export_count(cfrk_ctx *ctx, const ResultSrc *src, uint32_t min_count, uint32_t max_count, int parts,
+                             uint64_t *part_counts) {
   ResultSrc r = src ? *src : table_src(ctx);
   void *scratch;
   int rc = cfrk_pool_get(ctx, BUF_SCRATCH, (size_t)parts * 8, &scratch);
@@ -304,18 +383,39 @@ int cfrk_result_export(cfrk_ctx *ctx, const ResultSrc *src, uint64_t *d_lo, uint
   unsigned long long *d_part = (unsigned long long *)scratch;
   const int grid = grid_for(ctx, 256 * 16, (int64_t)r.n);
   HIP_TRY(ctx, hipMemsetAsync(d_part, 0, (size_t)parts * 8, ctx->stream));
-  hipLaunchKernelGGL(result_export_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, r, parts, d_part);
+  hipLaunchKernelGGL(result_export_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, r, parts, min_count, max_count, d_part);
   HIP_TRY(ctx, hipGetLastError());
-  std::vector<uint64_t> n(parts), cur(parts);
-  HIP_TRY(ctx, hipMemcpyAsync(n.data(), d_part, (size_t)parts * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(part_counts, d_part, (size_t)parts * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CFRK_OK;
+}
+
+int cfrk_result_export_scatter(cfrk_ctx *ctx, const ResultSrc *src, uint32_t min_count, uint32_t max_count, int parts,
+                               const uint64_t *part_counts, uint64_t *d_lo, uint64_t *d_hi, uint32_t *d_cnt) {
+  ResultSrc r = src ? *src : table_src(ctx);
+  std::vector<uint64_t> cur(parts);
   uint64_t total = 0;
-  for (int p = 0; p < parts; ++p) { cur[p] = total; total += n[p]; part_counts[p] = n[p]; }
-  if (total > cap) return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "%llu entries, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+  for (int p = 0; p < parts; ++p) { cur[p] = total; total += part_counts[p]; }
   if (total == 0) return CFRK_OK;
+  void *scratch;
+  int rc = cfrk_pool_get(ctx, BUF_SCRATCH, (size_t)parts * 8, &scratch);
+  if (rc) return rc;
+  unsigned long long *d_part = (unsigned long long *)scratch;
+  const int grid = grid_for(ctx, 256 * 16, (int64_t)r.n);
   HIP_TRY(ctx, hipMemcpyAsync(d_part, cur.data(), (size_t)parts * 8, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(result_export_scatter_kernel, dim3(grid), dim3(256), 0, ctx->stream, r, parts, d_part, d_lo, d_hi, d_cnt);
+  hipLaunchKernelGGL(result_export_scatter_kernel, dim3(grid), dim3(256), 0, ctx->stream, r, parts, min_count, max_count,
+                     d_part, d_lo, d_hi, d_cnt);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return CFRK_OK;
+}
+
+int cfrk_result_export(cfrk_ctx *ctx, const ResultSrc *src, uint64_t *d_lo, uint64_t *d_hi,
+                       uint32_t *d_cnt, uint64_t cap, int parts, uint64_t *part_counts) {
+  int rc = cfrk_result_export_count(ctx, src, 1, CFRK_COUNT_MAX, parts, part_counts);
+  if (rc) return rc;
+  uint64_t total = 0;
+  for (int p = 0; p < parts; ++p) total += part_counts[p];
+  if (total > cap) return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "%llu entries, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+  return cfrk_result_export_scatter(ctx, src, 1, CFRK_COUNT_MAX, parts, part_counts, d_lo, d_hi, d_cnt);
 }

@@ -30,6 +30,12 @@
 //                    (H2D copy + kernels), in the export (device sort + D2H) and in formatting + writing the output --
 //                    the wall-clock breakdown the reference has as commented-out printf()s (src/main.cu:259-268,303-305)
 //   --parse-threads N  host threads of the FASTA parser (default min(hardware threads, 64))
+//   --histo FILE     (global) the exact abundance histogram (k-mer spectrum) of the result: "c<TAB>n_c" lines, ascending in
+//                    c, for every c with n_c > 0 (`jellyfish histo`'s shape without its upper cut-off)
+//   --histo-only     (global, with --histo) write the spectrum only: the counts are not exported and the output path is
+//                    left untouched
+//   --min-count N / --max-count N  (global) write only the entries with N_min <= count <= N_max (text and --binary; the
+//                    binary header's n and sum describe the records written)
 //   --batch N        the Swift/T workflow's loop (swift/cfrk.swf:15-20) in one process: for i < N
 //                    count <dataset_prefix>_<i>.fasta into <out_prefix>_<i>.cfrk
 // Chunk pipeline: every device runs two contexts (two HIP streams), each on a host thread of its
@@ -61,11 +67,14 @@ struct Options {
   long chunk_size = 8192;
   bool all_chunks = false, native = false, global = false, canonical = false, same_device = false, binary = false, timing = false;
   int device = 0, gpus = 1;
+  const char *histo = nullptr;       // --histo FILE
+  bool histo_only = false;
+  uint32_t min_count = 1, max_count = CFRK_COUNT_MAX;
 };
 
 // --timing: wall-clock seconds by phase (one file; with --batch the last file's)
 struct Timing {
-  double parse = 0, add_call = 0, finish_wait = 0, export_ = 0, format = 0, write = 0, per_read = 0, total = 0;
+  double parse = 0, add_call = 0, finish_wait = 0, export_ = 0, format = 0, write = 0, per_read = 0, total = 0, histo = 0;
   double close = 0, free_batch = 0, open = 0;
   double contexts = 0, begin = 0, wait_parse = 0;   // context creation (beside the parse), cfrk_global_begin, the main thread's wait for the parser
   float count_kernels_ms = 0;
@@ -82,6 +91,19 @@ struct Worker {            // one context (= one HIP stream + buffer pool) on on
 int die(cfrk_ctx *ctx, int rc, const char *what) {
   fprintf(stderr, "cfrk: %s: %s (%s)\n", what, cfrk_strerror(rc), ctx ? cfrk_last_error(ctx) : "");
   return 2;
+}
+
+// a count option's value: decimal digits only, below 2^32
+bool parse_count(const char *v, uint32_t *out) {
+  if (!*v || strlen(v) > 10) return false;
+  uint64_t x = 0;
+  for (const char *p = v; *p; ++p) {
+    if (*p < '0' || *p > '9') return false;
+    x = x * 10 + (uint64_t)(*p - '0');
+  }
+  if (x > 0xFFFFFFFFull) return false;
+  *out = (uint32_t)x;
+  return true;
 }
 
 struct ChunkRange { int64_t first, count; };
@@ -175,6 +197,47 @@ int run_per_read(const Options &o, const cfrk_batch &batch, std::vector<Worker> 
   return failed;
 }
 
+// --histo: the exact spectrum without a user-set bound.  The device histogram covers counts below HISTO_W; the few keys
+// counted HISTO_W times or more are fetched by a count-range export and binned on the host.  Owners of a multi-device
+// job hold disjoint key sets: their spectra add.
+constexpr uint32_t HISTO_W = 16384;
+struct Spectrum {
+  std::vector<uint64_t> hist = std::vector<uint64_t>(HISTO_W, 0);   // exact bins 0 .. HISTO_W - 1
+  std::vector<uint32_t> tail;                                       // one count per key counted HISTO_W times or more
+  void add(const Spectrum &o) {
+    for (uint32_t c = 0; c < HISTO_W; ++c) hist[c] += o.hist[c];
+    tail.insert(tail.end(), o.tail.begin(), o.tail.end());
+  }
+};
+
+// 0, or the exit status (the error reported)
+int result_spectrum(cfrk_ctx *ctx, Spectrum &sp) {
+  std::vector<uint64_t> h(HISTO_W + 1);
+  int rc = cfrk_global_histogram(ctx, h.data(), HISTO_W + 1);
+  if (rc && rc != CFRK_ERR_COUNT_OVERFLOW) return die(ctx, rc, "cfrk_global_histogram");
+  const uint64_t nt = h[HISTO_W];
+  for (uint32_t c = 0; c < HISTO_W; ++c) sp.hist[c] += h[c];
+  if (!nt) return 0;
+  std::vector<uint64_t> lo(nt);
+  std::vector<uint32_t> cnt(nt);
+  uint64_t got = 0;
+  rc = cfrk_global_export_range(ctx, HISTO_W, CFRK_COUNT_MAX, lo.data(), nullptr, cnt.data(), nt, &got);
+  if (rc && rc != CFRK_ERR_COUNT_OVERFLOW) return die(ctx, rc, "cfrk_global_export_range");
+  sp.tail.insert(sp.tail.end(), cnt.begin(), cnt.begin() + (ptrdiff_t)got);
+  return 0;
+}
+
+int write_histo(const Options &o, const Spectrum &sp) {
+  std::string buf;
+  buf.resize(cfrk_host_format_histo(sp.hist.data(), HISTO_W, sp.tail.data(), sp.tail.size(), nullptr, 0));
+  cfrk_host_format_histo(sp.hist.data(), HISTO_W, sp.tail.data(), sp.tail.size(), &buf[0], buf.size());
+  FILE *f = fopen(o.histo, "wb");
+  if (!f) { fprintf(stderr, "cfrk: cannot write %s\n", o.histo); return 1; }
+  const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+  if (fclose(f) != 0 || !ok) { fprintf(stderr, "cfrk: cannot write %s\n", o.histo); return 1; }
+  return 0;
+}
+
 // the global result (ascending keys) as sparse text or in the binary form
 void write_global(const Options &o, const uint64_t *lo, const uint64_t *hi, const uint32_t *cnt, uint64_t n, FILE *out) {
   const uint64_t *hi2 = (o.k > 32) ? hi : nullptr;
@@ -218,17 +281,26 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
     if (rc == CFRK_ERR_TABLE_FULL && hint < hint_max) { hint = std::min<uint64_t>(hint * 8, hint_max); continue; }
     break;
   }
-  if (early_free && owned) *early_free = std::thread([owned] { cfrk_host_free_batch(owned); });
   // (counts are 32-bit and saturate: the result is complete, the user is told)
   if (rc == CFRK_ERR_COUNT_OVERFLOW) fprintf(stderr, "cfrk: warning: %s\n", cfrk_last_error(ctx));
   else if (rc) return die(ctx, rc, "cfrk_global_finish");
   const double t2 = now_s();
+  // the spectrum is taken before the batch is freed: its copies do not wait behind the page returns
+  if (o.histo) {
+    Spectrum sp;
+    if ((rc = result_spectrum(ctx, sp)) || (rc = write_histo(o, sp))) return rc;
+  }
+  g_timing.histo = now_s() - t2;
+  if (early_free && owned) *early_free = std::thread([owned] { cfrk_host_free_batch(owned); });
   cfrk_global_last_add_ms(ctx, &g_timing.count_kernels_ms);
+  g_timing.add_call = t1 - t0; g_timing.finish_wait = t2 - t1;
+  if (o.histo_only) return 0;
+  const double t3 = now_s();
   std::vector<uint64_t> keys(n), hi(n);
   std::vector<uint32_t> cnt(n);
-  rc = cfrk_global_export(ctx, keys.data(), hi.data(), cnt.data(), n, &n);
-  if (rc && rc != CFRK_ERR_COUNT_OVERFLOW) return die(ctx, rc, "cfrk_global_export");
-  g_timing.add_call = t1 - t0; g_timing.finish_wait = t2 - t1; g_timing.export_ = now_s() - t2;
+  rc = cfrk_global_export_range(ctx, o.min_count, o.max_count, keys.data(), hi.data(), cnt.data(), n, &n);
+  if (rc && rc != CFRK_ERR_COUNT_OVERFLOW) return die(ctx, rc, "cfrk_global_export_range");
+  g_timing.export_ = now_s() - t3;
   write_global(o, keys.data(), hi.data(), cnt.data(), n, out);
   return 0;
 }
@@ -297,6 +369,8 @@ int run_global_multi(const Options &o, const cfrk_batch &batch, std::vector<std:
   }
   std::vector<std::vector<uint64_t>> keys((size_t)N), his((size_t)N);
   std::vector<std::vector<uint32_t>> cnts((size_t)N);
+  std::vector<Spectrum> spec(o.histo ? (size_t)N : 0);
+  std::vector<double> histo_s((size_t)N, 0), export_s((size_t)N, 0);
   {
     // owner ow gathers its segment of every shard DEVICE TO DEVICE (xGMI peer-to-peer between the
     // devices of the node; replaces the host staging of round 2), then expands and counts its leaves
@@ -330,9 +404,17 @@ int run_global_multi(const Options &o, const cfrk_batch &batch, std::vector<std:
         if (rc == CFRK_ERR_COUNT_OVERFLOW) fprintf(stderr, "cfrk: warning: %s\n", cfrk_last_error(ctx));
         else if (rc == CFRK_ERR_TABLE_FULL) { refused[(size_t)ow] = 1; return; }       // (more distinct k-mers than announced)
         else if (rc) { status[(size_t)ow] = die(ctx, rc, "cfrk_global_finish"); return; }
+        const double h0 = now_s();
+        if (o.histo && (rc = result_spectrum(ctx, spec[(size_t)ow]))) { status[(size_t)ow] = rc; return; }
+        histo_s[(size_t)ow] = now_s() - h0;
+        if (o.histo_only) return;
+        const double e0 = now_s();
         keys[(size_t)ow].resize(n); cnts[(size_t)ow].resize(n); his[(size_t)ow].resize(n);
-        rc = cfrk_global_export(ctx, keys[(size_t)ow].data(), his[(size_t)ow].data(), cnts[(size_t)ow].data(), n, &n);
-        if (rc && rc != CFRK_ERR_COUNT_OVERFLOW) status[(size_t)ow] = die(ctx, rc, "cfrk_global_export");
+        rc = cfrk_global_export_range(ctx, o.min_count, o.max_count, keys[(size_t)ow].data(), his[(size_t)ow].data(),
+                                      cnts[(size_t)ow].data(), n, &n);
+        if (rc && rc != CFRK_ERR_COUNT_OVERFLOW) { status[(size_t)ow] = die(ctx, rc, "cfrk_global_export_range"); return; }
+        keys[(size_t)ow].resize(n); cnts[(size_t)ow].resize(n); his[(size_t)ow].resize(n);
+        export_s[(size_t)ow] = now_s() - e0;
       });
     for (auto &t : th) t.join();
     free_packed();
@@ -343,6 +425,14 @@ int run_global_multi(const Options &o, const cfrk_batch &batch, std::vector<std:
         return run_global(o, batch, per_dev[0][0], out);
       }
   }
+  g_timing.export_ = *std::max_element(export_s.begin(), export_s.end());
+  if (o.histo) {
+    const double h0 = now_s();
+    for (int ow = 1; ow < N; ++ow) spec[0].add(spec[(size_t)ow]);
+    if (int r = write_histo(o, spec[0])) return r;
+    g_timing.histo = *std::max_element(histo_s.begin(), histo_s.end()) + (now_s() - h0);
+  }
+  if (o.histo_only) return 0;
   // N ascending lists with disjoint keys -> one ascending list
   size_t total = 0;
   for (auto &kk : keys) total += kk.size();
@@ -403,15 +493,15 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
   { FILE *f = fopen(in, "rb"); if (f) { fseek(f, 0, SEEK_END); g_timing.fasta_bytes = (int64_t)ftell(f); fclose(f); } }
   std::thread freer;                                  // (global mode: frees the batch beside the export)
   const double to0 = now_s();
-  FILE *out = fopen(outp, "wb");                      // PrintFreq opens with "w" even when empty
+  FILE *out = o.histo_only ? nullptr : fopen(outp, "wb");   // PrintFreq opens with "w" even when empty
   const double t_open = now_s() - to0;
-  if (!out) { fprintf(stderr, "cfrk: cannot write %s\n", outp); cfrk_host_free_batch(&batch); return 1; }
+  if (!out && !o.histo_only) { fprintf(stderr, "cfrk: cannot write %s\n", outp); cfrk_host_free_batch(&batch); return 1; }
   if (o.global && per_dev && per_dev->size() > 1 && o.k >= 16 && o.k <= 64 && batch.nS >= (int64_t)per_dev->size()) rc = run_global_multi(o, batch, *per_dev, out);
   else if (o.global) rc = run_global(o, batch, workers[0], out, &freer, &batch);
   else { const double p0 = now_s(); rc = run_per_read(o, batch, workers, out); g_timing.per_read = now_s() - p0; }
   if (!o.global) { fflush(out); g_timing.out_bytes = (uint64_t)ftell(out); }
   const double tf0 = now_s();
-  fclose(out);
+  if (out) fclose(out);
   const double tf1 = now_s();
   if (freer.joinable()) freer.join();
   else cfrk_host_free_batch(&batch);
@@ -421,11 +511,11 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
     fprintf(stderr, "cfrk-timing {\"fasta_bytes\": %lld, \"reads\": %lld, \"code_bytes\": %lld, \"parse_s\": %.4f, \"add_call_s\": %.4f, "
             "\"finish_wait_s\": %.4f, \"count_kernels_ms\": %.3f, \"export_s\": %.4f, \"format_s\": %.4f, \"write_s\": %.4f, "
             "\"per_read_pipeline_s\": %.4f, \"entries\": %llu, \"out_bytes\": %llu, \"contexts_s\": %.4f, \"wait_for_parser_s\": %.4f, "
-            "\"begin_s\": %.4f, \"open_out_s\": %.4f, \"close_out_s\": %.4f, \"free_batch_s\": %.4f, \"wall_s\": %.4f}\n",
+            "\"begin_s\": %.4f, \"open_out_s\": %.4f, \"close_out_s\": %.4f, \"free_batch_s\": %.4f, \"histo_s\": %.4f, \"wall_s\": %.4f}\n",
             (long long)g_timing.fasta_bytes, (long long)g_timing.nS, (long long)g_timing.nN, g_timing.parse, g_timing.add_call,
             g_timing.finish_wait, (double)g_timing.count_kernels_ms, g_timing.export_, g_timing.format, g_timing.write,
             g_timing.per_read, (unsigned long long)g_timing.entries, (unsigned long long)g_timing.out_bytes, g_timing.contexts,
-            g_timing.wait_parse, g_timing.begin, g_timing.open, g_timing.close, g_timing.free_batch, g_timing.total);
+            g_timing.wait_parse, g_timing.begin, g_timing.open, g_timing.close, g_timing.free_batch, g_timing.histo, g_timing.total);
   return rc;
 }
 
@@ -435,6 +525,7 @@ int main(int argc, char **argv) {
   std::vector<const char *> pos;
   Options o;
   int batch_n = -1;
+  bool range_set = false;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--all-chunks")) o.all_chunks = true;
     else if (!strcmp(argv[i], "--native")) o.native = true;
@@ -447,8 +538,30 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--device") && i + 1 < argc) o.device = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) o.gpus = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--batch") && i + 1 < argc) batch_n = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--histo-only")) o.histo_only = true;
+    else if (!strcmp(argv[i], "--histo") || !strcmp(argv[i], "--min-count") || !strcmp(argv[i], "--max-count")) {
+      if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
+      const char *opt = argv[i], *v = argv[++i];
+      if (!strcmp(opt, "--histo")) { o.histo = v; continue; }
+      uint32_t x;
+      if (!parse_count(v, &x)) { fprintf(stderr, "cfrk: %s needs a count (an integer from 0 to 4294967295), not '%s'\n", opt, v); return 1; }
+      if (!strcmp(opt, "--min-count")) o.min_count = x;     // (0 reads as 1: cfrk_global_export_range)
+      else o.max_count = x;
+      range_set = true;
+    }
     else pos.push_back(argv[i]);
   }
+  // (refused here: before the input is parsed or a device is opened)
+  if ((o.histo || o.histo_only || range_set) && !o.global) {
+    fprintf(stderr, "cfrk: --histo, --histo-only, --min-count and --max-count need --global\n");
+    return 1;
+  }
+  if (o.histo_only && !o.histo) { fprintf(stderr, "cfrk: --histo-only needs --histo FILE\n"); return 1; }
+  if (o.min_count > o.max_count) {
+    fprintf(stderr, "cfrk: --min-count %u is above --max-count %u\n", o.min_count, o.max_count);
+    return 1;
+  }
+  if (o.histo && batch_n >= 0) { fprintf(stderr, "cfrk: --histo writes one file: not with --batch\n"); return 1; }
   if (pos.size() < 3) {
     // src/main.cu:239-243
     printf("Usage: ./cfrk [dataset.fasta] [file_out.cfrk] [k] <number of threads: Default 12> <chunkSize: Default 8192>");

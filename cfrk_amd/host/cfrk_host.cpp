@@ -412,6 +412,34 @@ size_t cfrk_host_format_sparse_mt(const uint64_t *keys_lo, const uint64_t *keys_
   return total;
 }
 
+size_t cfrk_host_format_histo(const uint64_t *hist, uint64_t nbins, const uint32_t *tail_counts, uint64_t n_tail,
+                              char *buf, size_t cap) {
+  // the tail: one count per key, binned here (sorted, then runs of equal counts)
+  std::vector<uint32_t> t(tail_counts, tail_counts + (tail_counts ? n_tail : 0));
+  std::sort(t.begin(), t.end());
+  size_t j = 0;
+  while (j < t.size() && t[j] == 0) ++j;
+  size_t s = 0;
+  char *p = buf;
+  (void)cap;
+  auto line = [&](uint64_t c, uint64_t n) {
+    if (!n) return;
+    if (buf) { p = put_u64(p, c); *p++ = '\t'; p = put_u64(p, n); *p++ = '\n'; }
+    else s += len_u64(c) + 1 + len_u64(n) + 1;
+  };
+  for (uint64_t c = 1; c < (hist ? nbins : 0); ++c) {
+    uint64_t n = hist[c];
+    while (j < t.size() && t[j] == c) { ++n; ++j; }
+    line(c, n);
+  }
+  while (j < t.size()) {
+    const size_t j0 = j;
+    while (j < t.size() && t[j] == t[j0]) ++j;
+    line(t[j0], j - j0);
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
 static void put_le(char *p, uint64_t x, int bytes) { for (int i = 0; i < bytes; ++i) p[i] = (char)(x >> (8 * i)); }
 static uint64_t get_le(const char *p, int bytes) {
   uint64_t x = 0;

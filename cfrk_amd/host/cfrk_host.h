@@ -62,6 +62,13 @@ size_t cfrk_host_format_sparse2(const uint64_t *keys_lo, const uint64_t *keys_hi
 size_t cfrk_host_format_sparse_mt(const uint64_t *keys_lo, const uint64_t *keys_hi, const uint32_t *counts,
                                   uint64_t n, char *buf, size_t cap, int threads);
 
+/* Abundance histogram (k-mer spectrum) as text: "<c>\t<n_c>\n" for every c >= 1 with n_c > 0, ascending in c (the shape
+ * of `jellyfish histo`).  n_c = hist[c] for c < nbins (hist[0] is ignored; hist may be NULL with nbins 0) plus the keys of
+ * tail_counts (one count per key, any order; those below nbins are added to their bin).  Returns bytes needed /
+ * written (buf may be NULL to size). */
+size_t cfrk_host_format_histo(const uint64_t *hist, uint64_t nbins, const uint32_t *tail_counts, uint64_t n_tail,
+                              char *buf, size_t cap);
+
 /* Binary global form, little endian, everything in one file:
  *   header, 32 bytes:  char magic[8] = "CFRKGLB1"; uint32 k; uint32 flags (bit 0: canonical counting,
  *                      bit 1: two-word keys, i.e. k > 32); uint64 n (records); uint64 sum of counts

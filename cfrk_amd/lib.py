@@ -85,6 +85,8 @@ def load_library():
         "cfrk_global_merge_device": ([vp, vp, vp, vp, i64], C.c_int),
         "cfrk_global_finish": ([vp, C.POINTER(u64)], C.c_int),
         "cfrk_global_export": ([vp, vp, vp, vp, u64, C.POINTER(u64)], C.c_int),
+        "cfrk_global_export_range": ([vp, C.c_uint32, C.c_uint32, vp, vp, vp, u64, C.POINTER(u64)], C.c_int),
+        "cfrk_global_histogram": ([vp, vp, C.c_uint32], C.c_int),
         "cfrk_global_export_device": ([vp, vp, vp, vp, u64, C.c_int, C.POINTER(u64)], C.c_int),
         "cfrk_global_digest": ([vp, C.POINTER(u64)], C.c_int),
         "cfrk_global_last_add_ms": ([vp, C.POINTER(C.c_float)], C.c_int),
@@ -338,18 +340,49 @@ class GlobalCounter:
         self.ctx.check(self._L.cfrk_global_last_add_ms(self.ctx._h, C.byref(ms)), "cfrk_global_last_add_ms")
         return ms.value
 
-    def export(self, allow_saturated=False):
-        """-> (keys_lo, keys_hi, counts) sorted by (hi, lo)"""
+    def export(self, allow_saturated=False, min_count=1, max_count=CFRK_COUNT_MAX):
+        """-> (keys_lo, keys_hi, counts) sorted by (hi, lo); only entries with min_count <= count <= max_count
+        (min_count 0 reads as 1)"""
         n = self.finish(allow_saturated)
         lo = np.empty(n, np.uint64)
         hi = np.empty(n, np.uint64)
         cnt = np.empty(n, np.uint32)
         got = C.c_uint64()
-        rc = self._L.cfrk_global_export(self.ctx._h, _ptr(lo), _ptr(hi), _ptr(cnt), n, C.byref(got))
+        rc = self._L.cfrk_global_export_range(self.ctx._h, int(min_count), int(max_count), _ptr(lo), _ptr(hi),
+                                              _ptr(cnt), n, C.byref(got))
         if not (allow_saturated and rc == CFRK_ERR_COUNT_OVERFLOW):
-            self.ctx.check(rc, "cfrk_global_export")
-        assert got.value == n
-        return lo, hi, cnt
+            self.ctx.check(rc, "cfrk_global_export_range")
+        m = got.value
+        assert m <= n
+        return lo[:m], hi[:m], cnt[:m]
+
+    def export_range(self, min_count, max_count, cap, allow_saturated=False):
+        """cfrk_global_export_range into buffers of `cap` entries -> (keys_lo, keys_hi, counts); raises CfrkError
+        (CFRK_ERR_SMALL_BUF, with .n_out = entries kept) when they do not fit"""
+        lo = np.empty(cap, np.uint64)
+        hi = np.empty(cap, np.uint64)
+        cnt = np.empty(cap, np.uint32)
+        got = C.c_uint64()
+        rc = self._L.cfrk_global_export_range(self.ctx._h, int(min_count), int(max_count), _ptr(lo), _ptr(hi),
+                                              _ptr(cnt), cap, C.byref(got))
+        if not (allow_saturated and rc == CFRK_ERR_COUNT_OVERFLOW):
+            try:
+                self.ctx.check(rc, "cfrk_global_export_range")
+            except CfrkError as e:
+                e.n_out = got.value
+                raise
+        m = got.value
+        return lo[:m], hi[:m], cnt[:m]
+
+    def histogram(self, nbins, allow_saturated=False):
+        """abundance histogram (k-mer spectrum) -> np.uint64[nbins]: h[c] = keys counted c times, the last bin
+        every key counted nbins - 1 times or more (2 <= nbins <= 2^24)"""
+        nbins = int(nbins)
+        h = np.zeros(nbins if 2 <= nbins <= 1 << 24 else 1, np.uint64)
+        rc = self._L.cfrk_global_histogram(self.ctx._h, _ptr(h), nbins if 0 <= nbins < 1 << 32 else 0)
+        if not (allow_saturated and rc == CFRK_ERR_COUNT_OVERFLOW):
+            self.ctx.check(rc, "cfrk_global_histogram")
+        return h
 
     def export_device(self, d_lo, d_hi, d_cnt, cap, parts=1):
         pc = (C.c_uint64 * parts)()

@@ -171,6 +171,19 @@ int cfrk_global_finish(cfrk_ctx *ctx, uint64_t *n_distinct);
 int cfrk_global_export(cfrk_ctx *ctx, uint64_t *keys_lo, uint64_t *keys_hi, uint32_t *counts,
                        uint64_t cap, uint64_t *n_out);
 
+/* cfrk_global_export restricted to entries with min_count <= count <= max_count (min_count 0 reads as 1; min > max
+ * keeps nothing).  Sorted ascending by (hi, lo); *n_out = entries kept; CFRK_ERR_SMALL_BUF when they exceed cap
+ * (*n_out set); CFRK_ERR_COUNT_OVERFLOW as cfrk_global_export.  Only the kept entries are sorted and copied. */
+int cfrk_global_export_range(cfrk_ctx *ctx, uint32_t min_count, uint32_t max_count, uint64_t *keys_lo,
+                             uint64_t *keys_hi, uint32_t *counts, uint64_t cap, uint64_t *n_out);
+
+/* Abundance histogram of the job's result (k-mer spectrum).  hist[c] = distinct keys counted exactly c times for
+ * 1 <= c <= nbins-2, hist[nbins-1] = distinct keys counted nbins-1 times or more, hist[0] = 0; sum(hist) = distinct.
+ * 2 <= nbins <= 2^24.  Errors as cfrk_global_digest: CFRK_ERR_TABLE_FULL, CFRK_ERR_STATE (before begin, RUNS_ONLY job);
+ * CFRK_ERR_COUNT_OVERFLOW with hist filled (saturated keys land in the top bin).  Read-only: may be called any number
+ * of times, before or after digest / export.  One read pass over the result on the device; synchronises. */
+int cfrk_global_histogram(cfrk_ctx *ctx, uint64_t *hist, uint32_t nbins);
+
 /* Unsorted export into device buffers, grouped into `parts` contiguous segments by
  * owner(key) = (mix(key) >> 32) % parts (key-owner partition for the multi-GPU
  * merge).  part_counts (host, `parts` entries) receives the segment sizes.  Synchronises. */
