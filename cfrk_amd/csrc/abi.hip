@@ -252,6 +252,7 @@ int cfrk_global_begin(cfrk_ctx *ctx, int k, int flags, uint64_t capacity_hint) {
   if ((flags & CFRK_RUNS_ONLY) && (k < 16 || k > 64 || (flags & CFRK_FORCE_HASH)))
     return cfrk_fail(ctx, CFRK_ERR_ARG, "CFRK_RUNS_ONLY needs a partitioned path (16 <= k <= 64)");
   if ((flags & CFRK_RUNS_DEFER) && !(flags & CFRK_RUNS_ONLY)) return cfrk_fail(ctx, CFRK_ERR_ARG, "CFRK_RUNS_DEFER goes with CFRK_RUNS_ONLY");
+  ctx->q_valid = false;     // (every call that may change the result drops the query index: the next query rebuilds it)
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   // Was the HBM table left untouched by the previous job (the partitioned path only writes it
@@ -297,6 +298,7 @@ int cfrk_global_begin(cfrk_ctx *ctx, int k, int flags, uint64_t capacity_hint) {
 int cfrk_global_add_device(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN) {
   if (!ctx) return CFRK_ERR_ARG;
   if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "cfrk_global_add before cfrk_global_begin");
+  ctx->q_valid = false;
   if (nN < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
   if (nN == 0) return CFRK_OK;
   if (!d_data) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
@@ -454,6 +456,7 @@ int cfrk_global_merge_device(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t
                              const uint32_t *d_cnt, int64_t n) {
   if (!ctx) return CFRK_ERR_ARG;
   if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "merge before begin");
+  ctx->q_valid = false;
   if (n < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
   if (n == 0) return CFRK_OK;
   if (!d_lo || !d_cnt || (ctx->g_two && !d_hi)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
@@ -562,6 +565,75 @@ int cfrk_global_histogram(cfrk_ctx *ctx, uint64_t *hist, uint32_t nbins) {
   if ((rc = cfrk_result_histogram(ctx, use_list ? &src : nullptr, nbins, hist, st))) return rc;
   if (st[ST_OVERFLOW]) return cfrk_fail(ctx, CFRK_ERR_TABLE_FULL, "table of %llu slots overflowed", (unsigned long long)ctx->g_cap);
   if (st[ST_SAT]) return cfrk_fail(ctx, CFRK_ERR_COUNT_OVERFLOW, "a key occurred 2^32 - 2 times or more: its count is held at 0xFFFFFFFE");
+  return CFRK_OK;
+}
+
+static int query_check(cfrk_ctx *ctx, int64_t n) {
+  if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "query before begin");
+  if (ctx->g_flags & CFRK_RUNS_ONLY) return cfrk_fail(ctx, CFRK_ERR_STATE, "a CFRK_RUNS_ONLY job holds runs, not counts");
+  if (n < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  return CFRK_OK;
+}
+
+int cfrk_global_query_device(cfrk_ctx *ctx, const uint64_t *d_keys_lo, const uint64_t *d_keys_hi, int64_t n,
+                             uint32_t *d_counts) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = query_check(ctx, n);
+  if (rc || n == 0) return rc;
+  if (!d_keys_lo || !d_counts || (ctx->g_two && !d_keys_hi)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_query_keys(ctx, d_keys_lo, d_keys_hi, n, d_counts);
+}
+
+int cfrk_global_query(cfrk_ctx *ctx, const uint64_t *keys_lo, const uint64_t *keys_hi, int64_t n, uint32_t *counts) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = query_check(ctx, n);
+  if (rc || n == 0) return rc;
+  if (!keys_lo || !counts || (ctx->g_two && !keys_hi)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  void *d_in, *d_out;
+  const size_t bytes = (size_t)n * 8;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_IN, keys_hi ? 2 * bytes : bytes, &d_in))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, (size_t)n * 4, &d_out))) return rc;
+  uint64_t *d_lo = (uint64_t *)d_in, *d_hi = keys_hi ? d_lo + n : nullptr;
+  HIP_TRY(ctx, hipMemcpyAsync(d_lo, keys_lo, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (keys_hi) HIP_TRY(ctx, hipMemcpyAsync(d_hi, keys_hi, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = cfrk_query_keys(ctx, d_lo, d_hi, n, (uint32_t *)d_out))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(counts, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CFRK_OK;
+}
+
+int cfrk_global_query_reads_device(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, uint32_t *d_counts) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = query_check(ctx, nN);
+  if (rc || nN == 0) return rc;
+  if (!d_data || !d_counts) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (((uintptr_t)d_data & 15) != 0) return cfrk_fail(ctx, CFRK_ERR_ALIGN, "d_data %p", (const void *)d_data);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_query_reads(ctx, d_data, nN, d_counts);
+}
+
+int cfrk_global_query_reads(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
+                            int64_t nN, int64_t nS, uint32_t *counts) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = query_check(ctx, nN);
+  if (rc) return rc;
+  if (nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (nN == 0) return CFRK_OK;
+  if (!data || !counts) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  LayoutCheck lc;      // (the add's check of the struct-read layout, beside the copy)
+  if (start && length) lc.begin(data, start, length, nN, nS);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  void *d_data, *d_out;
+  // (staged through slots of their own: BUF_DATA may still be read by the job's last add)
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_IN, (size_t)nN + 64, &d_data))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, (size_t)nN * 4, &d_out))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
+  if (lc.failed(ctx)) return CFRK_ERR_LAYOUT;
+  if ((rc = cfrk_query_reads(ctx, (const int8_t *)d_data, nN, (uint32_t *)d_out))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(counts, d_out, (size_t)nN * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return CFRK_OK;
 }
 

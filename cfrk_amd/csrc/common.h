@@ -24,6 +24,8 @@ enum {  // pool slots
   BUF_MSP_OVF,                                // records that did not fit their leaf stream (a few)
   BUF_MSP_OVF1, BUF_MSP_LAYOUT1,              // the same for the level-1 regions
   BUF_RUNS_AUX,                               // pipelined runs exchange: segment cursors, used rows per group
+  BUF_QUERY_INDEX,                            // read-only lookup index of the result (query.hip)
+  BUF_QUERY_IN, BUF_QUERY_OUT,                // staging of the host query calls (keys or reads in, counts out)
   BUF_NSLOTS
 };
 
@@ -76,6 +78,9 @@ struct cfrk_ctx {
   uint32_t dbg_flags;    // cfrk_debug_set_flags
   size_t mem_budget;     // 0 = what the device has free; else a cap on the partitioned paths' buffers (diagnostics)
   double dbg_param[4];   // cfrk_debug_set_param (0 = the library's own choice)
+  // query index (query.hip): built on the first query of a job, cleared by every call that changes the result
+  bool q_valid;
+  int q_log2cap;         // hash index: log2 of its slots (0: the dense array of k <= 12)
 };
 
 int cfrk_fail(cfrk_ctx *ctx, int code, const char *fmt, ...);
@@ -113,6 +118,10 @@ int cfrk_result_export_scatter(cfrk_ctx *ctx, const ResultSrc *src, uint32_t min
                                const uint64_t *part_counts, uint64_t *d_lo, uint64_t *d_hi, uint32_t *d_cnt);
 // abundance histogram of the result into host hist[nbins] (2 <= nbins <= 2^24), the stats words into stats_host
 int cfrk_result_histogram(cfrk_ctx *ctx, const ResultSrc *src, uint32_t nbins, uint64_t *hist, uint64_t stats_host[ST_NWORDS]);
+// query.hip: counts of keys / of every read window from the lookup index, built (synchronising) when it is not valid;
+// the lookup kernel is left enqueued.  Arguments are checked by the callers (abi.hip).
+int cfrk_query_keys(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t *d_hi, int64_t n, uint32_t *d_out);
+int cfrk_query_reads(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, uint32_t *d_out);
 
 // ---- device helpers -----------------------------------------------------------------------
 #ifdef __HIPCC__

@@ -101,20 +101,6 @@ __global__ __launch_bounds__(256) void hash_merge_kernel(const uint64_t *__restr
   }
 }
 
-__device__ __forceinline__ bool src_read(const ResultSrc &r, uint64_t s, uint64_t &lo, uint64_t &hi,
-                                         uint32_t &c) {
-  c = r.cnt[s];
-  hi = 0;
-  if (r.kind == 1 || r.kind == 3) {     // two-word table (count word = slot state) / two-word list
-    if (c == 0) return false;
-    lo = r.lo[s]; hi = r.hi[s];
-    return true;
-  }
-  lo = r.lo[s];
-  if (r.kind == 2) return c != 0;
-  return lo != CFRK_EMPTY_KEY && c != 0;
-}
-
 __device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o);
   return v;

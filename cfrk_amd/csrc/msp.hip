@@ -2861,6 +2861,7 @@ extern "C" int cfrk_global_merge_leaves_device(cfrk_ctx *ctx, const uint64_t *d_
                                                const uint32_t *d_leaf_counts, int parts) {
   if (!ctx || parts < 1 || parts > NLEAF || !recv_counts || !d_leaf_counts) return CFRK_ERR_ARG;
   if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "merge_leaves needs an active job");
+  ctx->q_valid = false;
   if (ctx->g_two && !d_keys_hi) return cfrk_fail(ctx, CFRK_ERR_ARG, "two-word keys need d_keys_hi");
   cfrk_msp *ms = cfrk_msp_get(ctx);
   if (!ms) return cfrk_fail(ctx, CFRK_ERR_NOMEM, "host allocation failed");
@@ -2974,6 +2975,7 @@ extern "C" int cfrk_global_export_runs_device(cfrk_ctx *ctx, void *d_packed, uin
 extern "C" int cfrk_global_merge_runs_device(cfrk_ctx *ctx, const void *d_packed, const uint64_t *recv_rows, int parts) {
   if (!ctx || parts < 1 || parts > 64 || !recv_rows || !d_packed) return CFRK_ERR_ARG;
   if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "merge_runs needs an active job");
+  ctx->q_valid = false;
   if (cfrk_msp2_usable(ctx) && !(ctx->g_flags & CFRK_RUNS_ONLY)) return cfrk_msp2_merge_runs(ctx, d_packed, recv_rows, parts);
   if (!cfrk_msp_usable(ctx) || (ctx->g_flags & CFRK_RUNS_ONLY)) return cfrk_fail(ctx, CFRK_ERR_ARG, "merge_runs needs a counting job with 16 <= k <= 64");
   cfrk_msp *ms = cfrk_msp_get(ctx);
@@ -3086,6 +3088,7 @@ extern "C" int cfrk_global_export_runs_wait(cfrk_ctx *ctx, int group, uint64_t *
 extern "C" int cfrk_global_merge_runs_group_device(cfrk_ctx *ctx, const void *d_recv, const uint64_t *recv_rows, int parts, int group, int ngroups) {
   if (!ctx || parts < 1 || parts > 64 || !recv_rows || !d_recv || ngroups < 1 || ngroups > CFRK_RUNS_MAX_GROUPS || group < 0 || group >= ngroups) return CFRK_ERR_ARG;
   if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "merge_runs_group needs an active job");
+  ctx->q_valid = false;
   if (ctx->g_two && !(ctx->g_flags & (CFRK_RUNS_ONLY | CFRK_FORCE_HASH))) return cfrk_msp2_merge_runs_group(ctx, d_recv, recv_rows, parts, group, ngroups);
   if (!cfrk_msp_usable(ctx) || (ctx->g_flags & CFRK_RUNS_ONLY)) return cfrk_fail(ctx, CFRK_ERR_ARG, "merge_runs_group needs a counting job with 16 <= k <= 64");
   cfrk_msp *ms = cfrk_msp_get(ctx);

@@ -113,3 +113,18 @@ struct ResultSrc {
   int kind;          // 0: one-word table, 1: two-word table, 2: one-word list, 3: two-word list
   uint64_t *stats;
 };
+
+// entry s of the result: false for an empty slot / entry (the all-T side word ST_ONES is not an entry)
+__device__ __forceinline__ bool src_read(const ResultSrc &r, uint64_t s, uint64_t &lo, uint64_t &hi,
+                                         uint32_t &c) {
+  c = r.cnt[s];
+  hi = 0;
+  if (r.kind == 1 || r.kind == 3) {     // two-word table (count word = slot state) / two-word list
+    if (c == 0) return false;
+    lo = r.lo[s]; hi = r.hi[s];
+    return true;
+  }
+  lo = r.lo[s];
+  if (r.kind == 2) return c != 0;
+  return lo != CFRK_EMPTY_KEY && c != 0;
+}

@@ -36,6 +36,13 @@
 //                    left untouched
 //   --min-count N / --max-count N  (global) write only the entries with N_min <= count <= N_max (text and --binary; the
 //                    binary header's n and sum describe the records written)
+//   --query QFILE --query-out OFILE  (global) how often does each k-mer of the reads of QFILE (FASTA, clean parse) occur
+//                    in the whole result (whatever --min-count / --max-count keep)?  OFILE: one line per query record, in
+//                    record order, the counts of its windows separated by single spaces, "-" for a window that holds a
+//                    non-ACGT base; a record shorter than k gives an empty line
+//   --query-only     (with --query) write OFILE only: the counts are not exported and the output path is left untouched
+//   --query-db DB.bin  (with --query, no positional arguments) query a saved --binary count file without recounting; k and
+//                    the canonical bit come from its header
 //   --batch N        the Swift/T workflow's loop (swift/cfrk.swf:15-20) in one process: for i < N
 //                    count <dataset_prefix>_<i>.fasta into <out_prefix>_<i>.cfrk
 // Chunk pipeline: every device runs two contexts (two HIP streams), each on a host thread of its
@@ -70,11 +77,14 @@ struct Options {
   const char *histo = nullptr;       // --histo FILE
   bool histo_only = false;
   uint32_t min_count = 1, max_count = CFRK_COUNT_MAX;
+  const char *query = nullptr, *query_out = nullptr, *query_db = nullptr;   // --query QFILE --query-out OFILE --query-db DB
+  bool query_only = false;
 };
 
 // --timing: wall-clock seconds by phase (one file; with --batch the last file's)
 struct Timing {
   double parse = 0, add_call = 0, finish_wait = 0, export_ = 0, format = 0, write = 0, per_read = 0, total = 0, histo = 0;
+  double query = 0;
   double close = 0, free_batch = 0, open = 0;
   double contexts = 0, begin = 0, wait_parse = 0;   // context creation (beside the parse), cfrk_global_begin, the main thread's wait for the parser
   float count_kernels_ms = 0;
@@ -238,6 +248,30 @@ int write_histo(const Options &o, const Spectrum &sp) {
   return 0;
 }
 
+// --query: the query reads (parsed once, clean FASTA) and the answers of one result for every window of them
+cfrk_batch g_qreads{};
+
+// 0, or the exit status (the error reported)
+int query_answers(cfrk_ctx *ctx, std::vector<uint32_t> &ans) {
+  ans.assign((size_t)g_qreads.nN, CFRK_QUERY_NONE);
+  if (g_qreads.nN == 0) return 0;
+  const int rc = cfrk_global_query_reads(ctx, g_qreads.data, g_qreads.start, g_qreads.length, g_qreads.nN, g_qreads.nS,
+                                         ans.data());
+  return rc ? die(ctx, rc, "cfrk_global_query_reads") : 0;
+}
+
+int write_query(const Options &o, int k, const uint32_t *ans) {
+  std::string buf;
+  const cfrk_batch &q = g_qreads;
+  buf.resize(cfrk_host_format_query(ans, q.start, q.length, q.nS, k, nullptr, 0));
+  cfrk_host_format_query(ans, q.start, q.length, q.nS, k, &buf[0], buf.size());
+  FILE *f = fopen(o.query_out, "wb");
+  if (!f) { fprintf(stderr, "cfrk: cannot write %s\n", o.query_out); return 1; }
+  const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+  if (fclose(f) != 0 || !ok) { fprintf(stderr, "cfrk: cannot write %s\n", o.query_out); return 1; }
+  return 0;
+}
+
 // the global result (ascending keys) as sparse text or in the binary form
 void write_global(const Options &o, const uint64_t *lo, const uint64_t *hi, const uint32_t *cnt, uint64_t n, FILE *out) {
   const uint64_t *hi2 = (o.k > 32) ? hi : nullptr;
@@ -291,10 +325,16 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
     if ((rc = result_spectrum(ctx, sp)) || (rc = write_histo(o, sp))) return rc;
   }
   g_timing.histo = now_s() - t2;
+  if (o.query) {
+    const double q0 = now_s();
+    std::vector<uint32_t> ans;
+    if ((rc = query_answers(ctx, ans)) || (rc = write_query(o, o.k, ans.data()))) return rc;
+    g_timing.query = now_s() - q0;
+  }
   if (early_free && owned) *early_free = std::thread([owned] { cfrk_host_free_batch(owned); });
   cfrk_global_last_add_ms(ctx, &g_timing.count_kernels_ms);
   g_timing.add_call = t1 - t0; g_timing.finish_wait = t2 - t1;
-  if (o.histo_only) return 0;
+  if (o.histo_only || o.query_only) return 0;
   const double t3 = now_s();
   std::vector<uint64_t> keys(n), hi(n);
   std::vector<uint32_t> cnt(n);
@@ -370,7 +410,8 @@ int run_global_multi(const Options &o, const cfrk_batch &batch, std::vector<std:
   std::vector<std::vector<uint64_t>> keys((size_t)N), his((size_t)N);
   std::vector<std::vector<uint32_t>> cnts((size_t)N);
   std::vector<Spectrum> spec(o.histo ? (size_t)N : 0);
-  std::vector<double> histo_s((size_t)N, 0), export_s((size_t)N, 0);
+  std::vector<double> histo_s((size_t)N, 0), export_s((size_t)N, 0), query_s((size_t)N, 0);
+  std::vector<std::vector<uint32_t>> qans(o.query ? (size_t)N : 0);
   {
     // owner ow gathers its segment of every shard DEVICE TO DEVICE (xGMI peer-to-peer between the
     // devices of the node; replaces the host staging of round 2), then expands and counts its leaves
@@ -407,7 +448,10 @@ int run_global_multi(const Options &o, const cfrk_batch &batch, std::vector<std:
         const double h0 = now_s();
         if (o.histo && (rc = result_spectrum(ctx, spec[(size_t)ow]))) { status[(size_t)ow] = rc; return; }
         histo_s[(size_t)ow] = now_s() - h0;
-        if (o.histo_only) return;
+        const double q0 = now_s();
+        if (o.query && (rc = query_answers(ctx, qans[(size_t)ow]))) { status[(size_t)ow] = rc; return; }
+        query_s[(size_t)ow] = now_s() - q0;
+        if (o.histo_only || o.query_only) return;
         const double e0 = now_s();
         keys[(size_t)ow].resize(n); cnts[(size_t)ow].resize(n); his[(size_t)ow].resize(n);
         rc = cfrk_global_export_range(ctx, o.min_count, o.max_count, keys[(size_t)ow].data(), his[(size_t)ow].data(),
@@ -432,7 +476,17 @@ int run_global_multi(const Options &o, const cfrk_batch &batch, std::vector<std:
     if (int r = write_histo(o, spec[0])) return r;
     g_timing.histo = *std::max_element(histo_s.begin(), histo_s.end()) + (now_s() - h0);
   }
-  if (o.histo_only) return 0;
+  if (o.query) {
+    // owners hold disjoint key sets: at most one answers a window with a count, the others 0; NONE is everyone's
+    const double q0 = now_s();
+    std::vector<uint32_t> &ans = qans[0];
+    for (int ow = 1; ow < N; ++ow)
+      for (size_t p = 0; p < ans.size(); ++p)
+        if (ans[p] != CFRK_QUERY_NONE) ans[p] += qans[(size_t)ow][p];
+    if (int r = write_query(o, o.k, ans.data())) return r;
+    g_timing.query = *std::max_element(query_s.begin(), query_s.end()) + (now_s() - q0);
+  }
+  if (o.histo_only || o.query_only) return 0;
   // N ascending lists with disjoint keys -> one ascending list
   size_t total = 0;
   for (auto &kk : keys) total += kk.size();
@@ -493,9 +547,10 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
   { FILE *f = fopen(in, "rb"); if (f) { fseek(f, 0, SEEK_END); g_timing.fasta_bytes = (int64_t)ftell(f); fclose(f); } }
   std::thread freer;                                  // (global mode: frees the batch beside the export)
   const double to0 = now_s();
-  FILE *out = o.histo_only ? nullptr : fopen(outp, "wb");   // PrintFreq opens with "w" even when empty
+  const bool no_out = o.histo_only || o.query_only;
+  FILE *out = no_out ? nullptr : fopen(outp, "wb");   // PrintFreq opens with "w" even when empty
   const double t_open = now_s() - to0;
-  if (!out && !o.histo_only) { fprintf(stderr, "cfrk: cannot write %s\n", outp); cfrk_host_free_batch(&batch); return 1; }
+  if (!out && !no_out) { fprintf(stderr, "cfrk: cannot write %s\n", outp); cfrk_host_free_batch(&batch); return 1; }
   if (o.global && per_dev && per_dev->size() > 1 && o.k >= 16 && o.k <= 64 && batch.nS >= (int64_t)per_dev->size()) rc = run_global_multi(o, batch, *per_dev, out);
   else if (o.global) rc = run_global(o, batch, workers[0], out, &freer, &batch);
   else { const double p0 = now_s(); rc = run_per_read(o, batch, workers, out); g_timing.per_read = now_s() - p0; }
@@ -507,16 +562,63 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
   else cfrk_host_free_batch(&batch);
   g_timing.total = now_s() - t0;
   g_timing.close = tf1 - tf0; g_timing.free_batch = now_s() - tf1; g_timing.open = t_open;
+  char query_field[64] = "";     // (only with --query: the line is unchanged otherwise)
+  if (o.query) snprintf(query_field, sizeof query_field, "\"query_s\": %.4f, ", g_timing.query);
   if (o.timing)
     fprintf(stderr, "cfrk-timing {\"fasta_bytes\": %lld, \"reads\": %lld, \"code_bytes\": %lld, \"parse_s\": %.4f, \"add_call_s\": %.4f, "
             "\"finish_wait_s\": %.4f, \"count_kernels_ms\": %.3f, \"export_s\": %.4f, \"format_s\": %.4f, \"write_s\": %.4f, "
             "\"per_read_pipeline_s\": %.4f, \"entries\": %llu, \"out_bytes\": %llu, \"contexts_s\": %.4f, \"wait_for_parser_s\": %.4f, "
-            "\"begin_s\": %.4f, \"open_out_s\": %.4f, \"close_out_s\": %.4f, \"free_batch_s\": %.4f, \"histo_s\": %.4f, \"wall_s\": %.4f}\n",
+            "\"begin_s\": %.4f, \"open_out_s\": %.4f, \"close_out_s\": %.4f, \"free_batch_s\": %.4f, \"histo_s\": %.4f, %s\"wall_s\": %.4f}\n",
             (long long)g_timing.fasta_bytes, (long long)g_timing.nS, (long long)g_timing.nN, g_timing.parse, g_timing.add_call,
             g_timing.finish_wait, (double)g_timing.count_kernels_ms, g_timing.export_, g_timing.format, g_timing.write,
             g_timing.per_read, (unsigned long long)g_timing.entries, (unsigned long long)g_timing.out_bytes, g_timing.contexts,
-            g_timing.wait_parse, g_timing.begin, g_timing.open, g_timing.close, g_timing.free_batch, g_timing.histo, g_timing.total);
+            g_timing.wait_parse, g_timing.begin, g_timing.open, g_timing.close, g_timing.free_batch, g_timing.histo, query_field, g_timing.total);
   return rc;
+}
+
+// --query-db: a saved CFRKGLB1 count file merged into a fresh job on one device, then queried
+int run_query_db(const Options &o) {
+  std::string img;
+  {
+    FILE *f = fopen(o.query_db, "rb");
+    if (!f) { fprintf(stderr, "cfrk: cannot read %s\n", o.query_db); return 1; }
+    char tmp[1 << 16];
+    size_t got;
+    while ((got = fread(tmp, 1, sizeof tmp, f)) > 0) img.append(tmp, got);
+    fclose(f);
+  }
+  int k = 0, bflags = 0;
+  uint64_t n = 0;
+  if (cfrk_host_read_binary(img.data(), img.size(), &k, &bflags, &n, nullptr, nullptr, nullptr) || k < 1 || k > 64) {
+    fprintf(stderr, "cfrk: %s is not a CFRKGLB1 count file\n", o.query_db);
+    return 1;
+  }
+  std::vector<uint64_t> lo(n), hi(n);
+  std::vector<uint32_t> cnt(n);
+  cfrk_host_read_binary(img.data(), img.size(), &k, &bflags, &n, lo.data(), hi.data(), cnt.data());
+  img.clear();
+  img.shrink_to_fit();
+  cfrk_ctx *ctx = nullptr;
+  int rc;
+  if ((rc = cfrk_ctx_create(o.device, nullptr, &ctx))) return die(nullptr, rc, "cfrk_ctx_create");
+  struct Destroy { cfrk_ctx *c; ~Destroy() { cfrk_ctx_destroy(c); } } destroy{ctx};
+  const double q0 = now_s();
+  if ((rc = cfrk_global_begin(ctx, k, (bflags & CFRK_BIN_CANONICAL) ? CFRK_CANONICAL : 0, n + 1024)))
+    return die(ctx, rc, "cfrk_global_begin");
+  if (n) {
+    void *d_lo = nullptr, *d_hi = nullptr, *d_cnt = nullptr;
+    if (!(rc = cfrk_device_alloc(ctx, n * 8, &d_lo)) && !(rc = cfrk_device_alloc(ctx, n * 8, &d_hi)) &&
+        !(rc = cfrk_device_alloc(ctx, n * 4, &d_cnt)) && !(rc = cfrk_memcpy_h2d(ctx, d_lo, lo.data(), n * 8)) &&
+        !(rc = cfrk_memcpy_h2d(ctx, d_hi, hi.data(), n * 8)) && !(rc = cfrk_memcpy_h2d(ctx, d_cnt, cnt.data(), n * 4)) &&
+        !(rc = cfrk_global_merge_device(ctx, (const uint64_t *)d_lo, (const uint64_t *)d_hi, (const uint32_t *)d_cnt, (int64_t)n)))
+      rc = cfrk_ctx_sync(ctx);
+    for (void *d : {d_lo, d_hi, d_cnt}) if (d) cfrk_device_free(ctx, d);
+    if (rc) return die(ctx, rc, "loading the count file");
+  }
+  std::vector<uint32_t> ans;
+  if ((rc = query_answers(ctx, ans)) || (rc = write_query(o, k, ans.data()))) return rc;
+  if (o.timing) fprintf(stderr, "cfrk-timing {\"entries\": %llu, \"query_s\": %.4f}\n", (unsigned long long)n, now_s() - q0);
+  return 0;
 }
 
 }  // namespace
@@ -539,6 +641,14 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) o.gpus = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--batch") && i + 1 < argc) batch_n = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--histo-only")) o.histo_only = true;
+    else if (!strcmp(argv[i], "--query-only")) o.query_only = true;
+    else if (!strcmp(argv[i], "--query") || !strcmp(argv[i], "--query-out") || !strcmp(argv[i], "--query-db")) {
+      if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
+      const char *opt = argv[i], *v = argv[++i];
+      if (!strcmp(opt, "--query")) o.query = v;
+      else if (!strcmp(opt, "--query-out")) o.query_out = v;
+      else o.query_db = v;
+    }
     else if (!strcmp(argv[i], "--histo") || !strcmp(argv[i], "--min-count") || !strcmp(argv[i], "--max-count")) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
       const char *opt = argv[i], *v = argv[++i];
@@ -562,6 +672,20 @@ int main(int argc, char **argv) {
     return 1;
   }
   if (o.histo && batch_n >= 0) { fprintf(stderr, "cfrk: --histo writes one file: not with --batch\n"); return 1; }
+  if (o.query && !o.global && !o.query_db) { fprintf(stderr, "cfrk: --query needs --global or --query-db\n"); return 1; }
+  if ((o.query_out || o.query_only || o.query_db) && !o.query) {
+    fprintf(stderr, "cfrk: --query-out, --query-only and --query-db need --query QFILE\n");
+    return 1;
+  }
+  if (o.query && !o.query_out) { fprintf(stderr, "cfrk: --query needs --query-out OFILE\n"); return 1; }
+  if (o.query && batch_n >= 0) { fprintf(stderr, "cfrk: --query writes one file: not with --batch\n"); return 1; }
+  if (o.query_db && !pos.empty()) { fprintf(stderr, "cfrk: --query-db takes no positional arguments\n"); return 1; }
+  if (o.query) {
+    const int qrc = cfrk_host_read_fasta(o.query, 0, &g_qreads);
+    if (qrc) { fprintf(stderr, "cfrk: cannot read %s (error %d)\n", o.query, qrc); return 1; }
+  }
+  struct QFree { ~QFree() { if (g_qreads.data) cfrk_host_free_batch(&g_qreads); } } qfree;
+  if (o.query_db) return run_query_db(o);
   if (pos.size() < 3) {
     // src/main.cu:239-243
     printf("Usage: ./cfrk [dataset.fasta] [file_out.cfrk] [k] <number of threads: Default 12> <chunkSize: Default 8192>");

@@ -440,6 +440,29 @@ size_t cfrk_host_format_histo(const uint64_t *hist, uint64_t nbins, const uint32
   return buf ? (size_t)(p - buf) : s;
 }
 
+size_t cfrk_host_format_query(const uint32_t *counts, const int64_t *start, const int32_t *length, int64_t nS, int k,
+                              char *buf, size_t cap) {
+  size_t s = 0;
+  char *p = buf;
+  (void)cap;
+  for (int64_t i = 0; i < nS; ++i) {
+    const int64_t w = (int64_t)length[i] - k + 1;
+    for (int64_t j = 0; j < w; ++j) {
+      const uint32_t c = counts[start[i] + j];
+      if (buf) {
+        if (j) *p++ = ' ';
+        if (c == 0xFFFFFFFFu) *p++ = '-';
+        else p = put_u64(p, c);
+      } else {
+        s += (j ? 1 : 0) + (c == 0xFFFFFFFFu ? 1 : len_u64(c));
+      }
+    }
+    if (buf) *p++ = '\n';
+    else s += 1;
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
 static void put_le(char *p, uint64_t x, int bytes) { for (int i = 0; i < bytes; ++i) p[i] = (char)(x >> (8 * i)); }
 static uint64_t get_le(const char *p, int bytes) {
   uint64_t x = 0;

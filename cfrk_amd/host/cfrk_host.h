@@ -69,6 +69,13 @@ size_t cfrk_host_format_sparse_mt(const uint64_t *keys_lo, const uint64_t *keys_
 size_t cfrk_host_format_histo(const uint64_t *hist, uint64_t nbins, const uint32_t *tail_counts, uint64_t n_tail,
                               char *buf, size_t cap);
 
+/* Read-query answers as text (`cfrk --query`): one line per read i, the counts of its windows
+ * counts[start[i]], .. counts[start[i] + length[i] - k] separated by single spaces, "-" for 0xFFFFFFFF (CFRK_QUERY_NONE:
+ * the window holds an invalid base); a read shorter than k gives an empty line.  Returns bytes needed / written (buf
+ * may be NULL to size). */
+size_t cfrk_host_format_query(const uint32_t *counts, const int64_t *start, const int32_t *length, int64_t nS, int k,
+                              char *buf, size_t cap);
+
 /* Binary global form, little endian, everything in one file:
  *   header, 32 bytes:  char magic[8] = "CFRKGLB1"; uint32 k; uint32 flags (bit 0: canonical counting,
  *                      bit 1: two-word keys, i.e. k > 32); uint64 n (records); uint64 sum of counts

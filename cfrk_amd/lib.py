@@ -27,6 +27,7 @@ CFRK_DEBUG_NO_SMALL_LEAVES = 0x80
 CFRK_ERR_COUNT_OVERFLOW = -10        # finish / digest / export: some count was held at CFRK_COUNT_MAX
 CFRK_ERR_RUNS_REFUSED = -11          # a CFRK_RUNS_ONLY add that needs more than one pass
 CFRK_COUNT_MAX = 0xFFFFFFFE
+CFRK_QUERY_NONE = 0xFFFFFFFF         # read query: the window holds an invalid base or runs past nN
 CFRK_PARAM_MSP_CHUNKS, CFRK_PARAM_L2_SLACK_COMPLETE, CFRK_PARAM_L2_SLACK_TRUNCATED, CFRK_PARAM_MSP2_SUBVALUE_BITS = 0, 1, 2, 3   # cfrk_debug_set_param
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -87,6 +88,10 @@ def load_library():
         "cfrk_global_export": ([vp, vp, vp, vp, u64, C.POINTER(u64)], C.c_int),
         "cfrk_global_export_range": ([vp, C.c_uint32, C.c_uint32, vp, vp, vp, u64, C.POINTER(u64)], C.c_int),
         "cfrk_global_histogram": ([vp, vp, C.c_uint32], C.c_int),
+        "cfrk_global_query": ([vp, vp, vp, i64, vp], C.c_int),
+        "cfrk_global_query_device": ([vp, vp, vp, i64, vp], C.c_int),
+        "cfrk_global_query_reads": ([vp, vp, vp, vp, i64, i64, vp], C.c_int),
+        "cfrk_global_query_reads_device": ([vp, vp, i64, vp], C.c_int),
         "cfrk_global_export_device": ([vp, vp, vp, vp, u64, C.c_int, C.POINTER(u64)], C.c_int),
         "cfrk_global_digest": ([vp, C.POINTER(u64)], C.c_int),
         "cfrk_global_last_add_ms": ([vp, C.POINTER(C.c_float)], C.c_int),
@@ -383,6 +388,44 @@ class GlobalCounter:
         if not (allow_saturated and rc == CFRK_ERR_COUNT_OVERFLOW):
             self.ctx.check(rc, "cfrk_global_histogram")
         return h
+
+    def query(self, keys_lo, keys_hi=None):
+        """count of every key -> np.uint32[n] (0: absent; CFRK_COUNT_MAX: at least that); canonicalised in a
+        CFRK_CANONICAL job"""
+        lo = np.ascontiguousarray(keys_lo, np.uint64)
+        hi = None if keys_hi is None else np.ascontiguousarray(keys_hi, np.uint64)
+        if hi is not None and len(hi) != len(lo):
+            raise ValueError("keys_lo and keys_hi differ in length")
+        out = np.empty(len(lo), np.uint32)
+        self.ctx.check(self._L.cfrk_global_query(self.ctx._h, _ptr(lo), _ptr(hi), len(lo), _ptr(out)),
+                       "cfrk_global_query")
+        return out
+
+    def query_device(self, d_lo, d_hi, n, d_out):
+        """device form of query(): returns with the lookup kernel enqueued on the context stream"""
+        self.ctx.check(self._L.cfrk_global_query_device(self.ctx._h, C.c_void_p(d_lo) if d_lo else None,
+                                                        C.c_void_p(d_hi) if d_hi else None, n,
+                                                        C.c_void_p(d_out) if d_out else None),
+                       "cfrk_global_query_device")
+
+    def query_reads(self, data, start=None, length=None):
+        """count of the k-mer starting at every base -> np.uint32[nN]: CFRK_QUERY_NONE where the window holds an
+        invalid base or runs past the end, 0 where the k-mer is absent"""
+        data = np.ascontiguousarray(data, np.int8)
+        if start is not None:
+            start = np.ascontiguousarray(start, np.int64)
+            length = np.ascontiguousarray(length, np.int32)
+        nS = 0 if length is None else len(length)
+        out = np.empty(len(data), np.uint32)
+        self.ctx.check(self._L.cfrk_global_query_reads(self.ctx._h, _ptr(data), _ptr(start), _ptr(length),
+                                                       len(data), nS, _ptr(out)), "cfrk_global_query_reads")
+        return out
+
+    def query_reads_device(self, d_data, nN, d_out):
+        """device form of query_reads(): d_data 16-byte aligned, d_out nN uint32; returns with the kernel enqueued"""
+        self.ctx.check(self._L.cfrk_global_query_reads_device(self.ctx._h, C.c_void_p(d_data) if d_data else None,
+                                                              nN, C.c_void_p(d_out) if d_out else None),
+                       "cfrk_global_query_reads_device")
 
     def export_device(self, d_lo, d_hi, d_cnt, cap, parts=1):
         pc = (C.c_uint64 * parts)()

@@ -184,6 +184,27 @@ int cfrk_global_export_range(cfrk_ctx *ctx, uint32_t min_count, uint32_t max_cou
  * of times, before or after digest / export.  One read pass over the result on the device; synchronises. */
 int cfrk_global_histogram(cfrk_ctx *ctx, uint64_t *hist, uint32_t nbins);
 
+/* Point queries on the job's result: how often does a k-mer occur?  The first query after begin / add / merge builds a
+ * read-only lookup index from the result (one synchronisation: the resolve and a stats read); later queries use it
+ * until the result changes.  Digest, histogram and export read the same result afterwards.
+ *   keys: counts[i] = count of key i (keys_hi may be NULL for k <= 32); a key with bits set at or above 2k reads 0.
+ *   reads: counts[p] = count of the k-mer at bases p .. p+k-1 when all k codes are valid, 0 when it is absent,
+ *          CFRK_QUERY_NONE otherwise (terminators are invalid codes: no window crosses a read).  nN entries.
+ * In a CFRK_CANONICAL job the k-mer is canonicalised first: a k-mer and its reverse complement read the same count.
+ * A saturated key reads CFRK_COUNT_MAX ("at least"); queries never return CFRK_ERR_COUNT_OVERFLOW.  Errors:
+ * CFRK_ERR_STATE before begin and on a CFRK_RUNS_ONLY job, CFRK_ERR_TABLE_FULL as cfrk_global_digest, CFRK_ERR_ARG
+ * for NULL buffers and negative sizes (n = 0 is fine), CFRK_ERR_NOMEM when the index does not fit (the job is kept).
+ * The host forms synchronise; cfrk_global_query_reads checks start / length like cfrk_global_add (CFRK_ERR_LAYOUT;
+ * both may be NULL) and stages through buffers of its own.  The _device forms return with the lookup kernel enqueued
+ * on the context stream; d_data must be 16-byte aligned (CFRK_ERR_ALIGN). */
+#define CFRK_QUERY_NONE 0xFFFFFFFF   /* read query: the window holds an invalid base or runs past nN (unsigned, as CFRK_COUNT_MAX) */
+int cfrk_global_query(cfrk_ctx *ctx, const uint64_t *keys_lo, const uint64_t *keys_hi, int64_t n, uint32_t *counts);
+int cfrk_global_query_device(cfrk_ctx *ctx, const uint64_t *d_keys_lo, const uint64_t *d_keys_hi, int64_t n,
+                             uint32_t *d_counts);
+int cfrk_global_query_reads(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
+                            int64_t nN, int64_t nS, uint32_t *counts /* nN entries */);
+int cfrk_global_query_reads_device(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, uint32_t *d_counts);
+
 /* Unsorted export into device buffers, grouped into `parts` contiguous segments by
  * owner(key) = (mix(key) >> 32) % parts (key-owner partition for the multi-GPU
  * merge).  part_counts (host, `parts` entries) receives the segment sizes.  Synchronises. */
