@@ -43,6 +43,7 @@
 #include <algorithm>
 #include <cmath>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -133,6 +134,7 @@ __device__ __forceinline__ void l1_put(const MspView &v, uint32_t reg, uint32_t 
 // so that every record is expanded once (msp2.hip does the same).  2 KB more staging per wave: two
 // workgroups per CU instead of three.
 constexpr int SUB_BITS = 5;
+#define P1_MARK(text) asm volatile("; " text)
 template <int P1B_TR, bool SUB = false>
 struct P1Lds {
   static constexpr int STAGE = 4096 + 3 * 512 + P1B_TR * 128 + (SUB ? 2048 : 0);     // bytes of staging per wave
@@ -169,21 +171,28 @@ __device__ __forceinline__ void p1_tile(uint4 *pool, const int8_t *__restrict__ 
   const int nkmax = min(48 - k + 1, 32);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   uint8_t *const stage = reinterpret_cast<uint8_t *>(arena) + wave * P1B_STAGE;
-  uint16_t *const s_leaf = reinterpret_cast<uint16_t *>(stage);               // [64 lanes][32 positions]
-  uint32_t *const s_str = reinterpret_cast<uint32_t *>(stage + 4096);         // 128 dwords of bases
-  uint64_t *const s_E = reinterpret_cast<uint64_t *>(stage + 4096 + 512);     // run terminators
-  uint64_t *const s_W = reinterpret_cast<uint64_t *>(stage + 4096 + 1024);    // validity of position p-1
+  // (the base string first: the four dwords of a record's bases are read with small immediate offsets from one
+  // address; terminators and validity side by side: one 16-byte read per record)
+  uint32_t *const s_str = reinterpret_cast<uint32_t *>(stage);                // 128 dwords of bases
+  uint4 *const s_EW = reinterpret_cast<uint4 *>(stage + 512);                 // per lane {E low, E high, W low, W high}:
+                                                                              // run terminators, validity of position p-1
+  uint16_t *const s_leaf = reinterpret_cast<uint16_t *>(stage + 1536);        // [64 lanes][32 positions]
   uint16_t *const s_dsc = reinterpret_cast<uint16_t *>(stage + 4096 + 1536);  // (lane << 5) | position
   uint8_t *const s_sub = stage + 4096 + 1536 + P1B_TR * 128;                  // [64 lanes][32 positions] (SUB only)
   if (tid < B1) hist[tid] = 0;
   lds_barrier();
 
+  // (P1_PHASE_* / P1_COLD: assembly comments, no instructions; tools/p1_isa_account.py counts between them)
+  P1_MARK("P1_PHASE_A");
   // ---- A: this lane's chunk, packed 2 bits per base; neighbours' chunks by shuffle ----
   const int64_t wave_g = tile * P1_WAVES + wave;
   const int64_t chunk = wave_g * P1_OWN + lane - 1;
   const int64_t off = chunk * 32;
   uint32_t b0 = 0, b1 = 0, bad = 0xFFFFFFFFu;
-  if (chunk >= 0) dev_load_chunk32(data, off, nN, b0, b1, bad);
+  if (chunk >= 0) {
+    if (off + 32 > nN) P1_MARK("P1_COLD byte-wise tail chunk");
+    dev_load_chunk32(data, off, nN, b0, b1, bad);
+  }
   const uint32_t n0 = dev_lane_next(b0), n1 = dev_lane_next(b1);
   const uint32_t nbad = dev_lane_next(bad), nnbad = dev_lane_next(dev_lane_next(bad));
   const uint64_t hi = ((uint64_t)b0 << 32) | b1;
@@ -217,6 +226,7 @@ __device__ __forceinline__ void p1_tile(uint4 *pool, const int8_t *__restrict__ 
   if (!owner) S = 0;
 
   // ---- B1: stage what records are made of; list the run starts ----
+  P1_MARK("P1_PHASE_B1");
   {
     const LeafPack LP = leaf_pack(H);
     uint4 *lp = reinterpret_cast<uint4 *>(s_leaf + lane * 32);
@@ -225,8 +235,7 @@ __device__ __forceinline__ void p1_tile(uint4 *pool, const int8_t *__restrict__ 
     lp[2] = make_uint4(LP.w[8], LP.w[9], LP.w[10], LP.w[11]);
     lp[3] = make_uint4(LP.w[12], LP.w[13], LP.w[14], LP.w[15]);
     reinterpret_cast<uint2 *>(s_str)[lane] = make_uint2(b0, b1);
-    s_E[lane] = E;
-    s_W[lane] = (Vx >> 1) | ((uint64_t)prevV << 63);
+    s_EW[lane] = make_uint4((uint32_t)E, (uint32_t)(E >> 32), ((uint32_t)Vx >> 1) | (V << 31), Vprev);
     if (SUB) {
       // bits 24..27 and 7 of the packed minimum: hash bits, equal for every occurrence of a k-mer, that
       // neither the leaf id (bits 8..23) nor the position tag (bits 0..4) uses; bit 7 -- the uniform one -- lowest
@@ -260,48 +269,68 @@ __device__ __forceinline__ void p1_tile(uint4 *pool, const int8_t *__restrict__ 
     cnt_w = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     uint32_t widx = incl - mine;
     const uint32_t tag = (uint32_t)lane << 5;
-    while (S) {
-      const int a = __clz(S);
-      const uint32_t bit = 0x80000000u >> a;
-      S &= ~bit;
-      if (widx < wcap) s_dsc[widx] = (uint16_t)(tag | (uint32_t)a);
-      else S2 |= bit;
-      ++widx;
+    if (incl <= wcap) {                          // all of this lane's runs fit: nothing to test per run
+      uint16_t *dp = s_dsc + widx - 1;           // (pre-increment: the address register is updated in place)
+      while (S) {
+        const int a = __clz(S);
+        S &= ~(0x80000000u >> a);
+        *++dp = (uint16_t)(tag | (uint32_t)a);
+      }
+    } else {
+      P1_MARK("P1_COLD wave over capacity");
+      while (S) {
+        const int a = __clz(S);
+        const uint32_t bit = 0x80000000u >> a;
+        S &= ~bit;
+        if (widx < wcap) s_dsc[widx] = (uint16_t)(tag | (uint32_t)a);
+        else S2 |= bit;
+        ++widx;
+      }
     }
   }
   lds_wave_sync();                               // the wave's staging is written: lanes read each other's
 
   // record of the run that starts at position d & 31 of lane d >> 5 (d is also the index of its leaf id)
+  // (32-bit work where the ranges allow: a <= 31 and n <= 32, so the terminators that decide n are one
+  // 32-bit window of E from the run start, and alignbit / shifts take the low five bits of ~d = 31 - a)
+  const uint32_t nkm1 = (uint32_t)(nkmax - 1);
+  const int zc = 2 * (48 - k);                   // cleared tail bits of a run of one k-mer
   auto build = [&](uint32_t d) {
-    const uint32_t L = d >> 5, a = d & 31u;
-    const uint64_t Es = s_E[L], Ws = s_W[L];
+    const uint4 ew = s_EW[d >> 5];
     const uint32_t leaf = s_leaf[d];
-    // 96 bits of the wave's base string from bit 2d: dwords idx0..idx0+3, funnel-shifted
-    const uint32_t P = 2u * d - 2u, idx0 = P >> 5, sh = 30u - (P & 31u);
+    // 96 bits of the wave's base string from bit 2d - 2: dwords idx0..idx0+3, funnel-shifted by
+    // 30 - ((2d - 2) & 31) = -2d (mod 32)
+    const uint32_t idx0 = (d - 1u) >> 4, sh = 0u - 2u * d;
     const uint32_t D0 = s_str[idx0], D1 = s_str[idx0 + 1], D2 = s_str[idx0 + 2], D3 = s_str[idx0 + 3];
-    const uint64_t rest = Es << (a + 1);
-    const int n = min(__clzll(rest) + 1, nkmax);
+    const uint32_t a = d & 31u, na = ~d;
+    // terminators of positions a+1 .. a+32, the first in the top bit (none set: clz = 32, the min catches it)
+    const uint32_t e32 = __builtin_amdgcn_alignbit(ew.y, ew.x, na);
+    const uint32_t nm1 = min((uint32_t)__clz(e32), nkm1);        // n - 1
     // An end of the run is "closed" when it is a minimizer change between valid k-mers (header
     // bit 6: left end, bit 7: right end) and open when the read or an invalid base cut it.  Both
     // closed = a complete run: every read covering this locus emits the same record.  One end
     // open = a prefix (suffix) of the complete run of its locus, with which it shares its first
     // (last) k-mer.
-    const uint32_t flags = (((uint32_t)(Ws >> (63 - a)) & 1u) << 6) | (((uint32_t)(Ws >> (62 - a - n)) & 1u) << 7);
+    // left: bit 63 - a of W; right: bit 62 - a - n, brought to the top
+    const uint32_t lf = (ew.w >> (na & 31u)) & 1u;
+    const uint64_t Ws = ((uint64_t)ew.w << 32) | ew.z;
+    const uint32_t rf = (uint32_t)((Ws << (a + nm1 + 2u)) >> 63);
     uint4 rec;
     rec.x = __builtin_amdgcn_alignbit(D0, D1, sh);
     // bases after the run's last k-mer are cleared: equal runs -> byte-identical records
-    const int z = 2 * (48 - (n + k - 1));        // < 64 for k >= 17
+    const int z = zc - 2 * (int)nm1;             // 2 * (48 - (n + k - 1)), < 64 for k >= 17
     uint64_t r12 = ((uint64_t)__builtin_amdgcn_alignbit(D1, D2, sh) << 32) | __builtin_amdgcn_alignbit(D2, D3, sh);
-    r12 = (W < 8 && z >= 64) ? 0ull : ((r12 >> z) << z);
+    r12 = (W < 8 && z >= 64) ? 0ull : (r12 & (~0ull << z));
     rec.y = (uint32_t)(r12 >> 32);
     rec.z = (uint32_t)r12;
-    rec.w = (leaf << 8) | flags | (uint32_t)(n - 1);
+    rec.w = (leaf << 8) | (rf << 7) | (lf << 6) | nm1;
     if (SUB) rec.w |= (uint32_t)s_sub[d] << 24;
     return rec;
   };
 
   // more runs in this wave than the balanced phase holds (pathological input): append directly
   while (S2) {
+    P1_MARK("P1_COLD direct append");
     const int a = __clz(S2);
     S2 &= ~(0x80000000u >> a);
     const uint4 rec = build(((uint32_t)lane << 5) | (uint32_t)a);
@@ -312,23 +341,31 @@ __device__ __forceinline__ void p1_tile(uint4 *pool, const int8_t *__restrict__ 
   }
 
   // ---- B2: lane i builds the wave's i-th record ----
+  P1_MARK("P1_PHASE_B2");
   uint4 rc[P1B_TR];
   uint32_t rk[P1B_TR];                           // rank inside the record's bin; ~0: no record
   cnt_w = min(cnt_w, wcap);
+  // (rc[tr] is only ever read where rk[tr] says there is a record: no filler values to move around;
+  // the leaf selection of a multi-pass batch is tested per record only in such a batch)
+  auto emit = [&](auto sel) {
+    if (decltype(sel)::value) P1_MARK("P1_COLD multi-pass selection");
 #pragma unroll
-  for (int tr = 0; tr < P1B_TR; ++tr) {
-    rk[tr] = 0xFFFFFFFFu;
-    rc[tr] = make_uint4(0, 0, 0, 0);
-    const uint32_t i = (uint32_t)(tr * 64 + lane);
-    if (i < cnt_w) {
-      rc[tr] = build(s_dsc[i]);
-      if (((rc[tr].w >> 8) & v.sel_mask) == v.sel_val)       // (all leaves, unless the batch takes several passes)
-        rk[tr] = atomicAdd(&hist[bin_of<SUB>(rc[tr].w)], 1u);
+    for (int tr = 0; tr < P1B_TR; ++tr) {
+      rk[tr] = 0xFFFFFFFFu;
+      const uint32_t i = (uint32_t)(tr * 64 + lane);
+      if (i < cnt_w) {
+        rc[tr] = build(s_dsc[i]);
+        if (!decltype(sel)::value || ((rc[tr].w >> 8) & v.sel_mask) == v.sel_val)
+          rk[tr] = atomicAdd(&hist[bin_of<SUB>(rc[tr].w)], 1u);
+      }
     }
-  }
+  };
+  if (v.sel_mask == 0 && v.sel_val == 0) emit(std::false_type{});     // every leaf: all one-pass jobs
+  else emit(std::true_type{});
   lds_barrier();
 
   // ---- C: one global reservation per non-empty bin; bin offsets ----
+  P1_MARK("P1_PHASE_C");
   uint32_t my_base = 0;
   if (tid < B1) {
     const uint32_t c = hist[tid];
@@ -358,15 +395,21 @@ __device__ __forceinline__ void p1_tile(uint4 *pool, const int8_t *__restrict__ 
   lds_barrier();
 
   // ---- D: copy out in bin order ----
+  P1_MARK("P1_PHASE_D");
   const uint32_t nrec_s = *nrec_p;
   const uint32_t nrec = min(nrec_s, (uint32_t)P1B_RCAP);
   for (uint32_t p = tid; p < nrec; p += P1_THREADS) {
     const uint4 rec = arena[p];
     const uint32_t b = bin_of<SUB>(rec.w);
-    if (p < (uint32_t)plim[b]) v.rec1[dabs[b] + p] = rec;
-    else l1_put<EX>(v, l1_reg(b, subreg), gbase[b] + (p - loff[b]), rec, k, canon != 0, t);   // region full: park / flag
+    if (p < (uint32_t)plim[b]) {
+      v.rec1[dabs[b] + p] = rec;
+    } else {                                     // region full: park / flag
+      P1_MARK("P1_COLD region full");
+      l1_put<EX>(v, l1_reg(b, subreg), gbase[b] + (p - loff[b]), rec, k, canon != 0, t);
+    }
   }
   if (nrec_s > (uint32_t)P1B_RCAP) {             // records beyond the LDS arena go to their reserved places
+    P1_MARK("P1_COLD arena overflow");
 #pragma unroll
     for (int tr = 0; tr < P1B_TR; ++tr) {
       if (rk[tr] != 0xFFFFFFFFu) {
