@@ -645,6 +645,91 @@ int cfrk_global_last_add_ms(cfrk_ctx *ctx, float *ms) {
   return CFRK_OK;
 }
 
+/* ------------------------------------------------------------------ per-read sparse */
+
+static int sparse_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, int k, int flags, const void *row_ptr, const void *keys,
+                        const void *counts, uint64_t cap, const uint64_t *nnz_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  if (k < 1 || k > 32) return cfrk_fail(ctx, CFRK_ERR_ARG, "k=%d outside 1..32 (per-read sparse keys are one word)", k);
+  if (flags & ~CFRK_CANONICAL) return cfrk_fail(ctx, CFRK_ERR_ARG, "flags 0x%x: per-read sparse takes CFRK_CANONICAL only", flags);
+  if (nN < 0 || nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (!row_ptr || !nnz_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (cap > 0 && (!keys || !counts)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL keys / counts with cap > 0");
+  return CFRK_OK;
+}
+
+int cfrk_per_read_sparse_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                int64_t nN, int64_t nS, int k, int flags, int64_t *d_row_ptr, uint64_t *d_keys,
+                                uint32_t *d_counts, uint64_t cap, uint64_t *nnz_out) {
+  int rc = sparse_check(ctx, nN, nS, k, flags, d_row_ptr, d_keys, d_counts, cap, nnz_out);
+  if (rc) return rc;
+  *nnz_out = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (nS == 0) {
+    HIP_TRY(ctx, hipMemsetAsync(d_row_ptr, 0, 8, ctx->stream));
+    return CFRK_OK;
+  }
+  if (!d_start || !d_length || (nN > 0 && !d_data)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if ((rc = cfrk_sparse_count(ctx, d_data, d_start, d_length, nN, nS, k, flags, d_row_ptr))) return rc;
+  int64_t nnz = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&nnz, d_row_ptr + nS, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *nnz_out = (uint64_t)nnz;
+  if ((uint64_t)nnz > cap)
+    return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "%lld distinct (read, k-mer) pairs, room for %llu", (long long)nnz, (unsigned long long)cap);
+  if (nnz == 0) return CFRK_OK;
+  return cfrk_sparse_compact(ctx, d_start, d_row_ptr, nS, d_keys, d_counts);
+}
+
+int cfrk_per_read_sparse(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                         int64_t nS, int k, int flags, int64_t *row_ptr, uint64_t *keys, uint32_t *counts, uint64_t cap,
+                         uint64_t *nnz_out) {
+  int rc = sparse_check(ctx, nN, nS, k, flags, row_ptr, keys, counts, cap, nnz_out);
+  if (rc) return rc;
+  *nnz_out = 0;
+  row_ptr[0] = 0;
+  if (nS == 0) return CFRK_OK;
+  if (!start || !length || (nN > 0 && !data)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  LayoutCheck lc;      // (the add's check of the struct-read layout, beside the copies)
+  lc.begin(data, start, length, nN, nS);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // staged through slots of their own (BUF_DATA may still be read by an open job's last add):
+  // [data | start | length | row_ptr], each part 256-byte aligned
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_start = up((size_t)nN + 64), o_length = o_start + up((size_t)nS * 8), o_row = o_length + up((size_t)nS * 4);
+  void *p_in;
+  if ((rc = cfrk_pool_get(ctx, BUF_SPARSE_IN, o_row + (size_t)(nS + 1) * 8, &p_in))) return rc;
+  int8_t *d_data = (int8_t *)p_in;
+  int64_t *d_start = (int64_t *)((char *)p_in + o_start);
+  int32_t *d_length = (int32_t *)((char *)p_in + o_length);
+  int64_t *d_row = (int64_t *)((char *)p_in + o_row);
+  if (nN) HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_start, start, (size_t)nS * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_length, length, (size_t)nS * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (lc.failed(ctx)) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
+    return CFRK_ERR_LAYOUT;
+  }
+  if ((rc = cfrk_sparse_count(ctx, d_data, d_start, d_length, nN, nS, k, flags, d_row))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(row_ptr, d_row, (size_t)(nS + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const uint64_t nnz = (uint64_t)row_ptr[nS];
+  *nnz_out = nnz;
+  if (nnz > cap)
+    return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "%llu distinct (read, k-mer) pairs, room for %llu", (unsigned long long)nnz, (unsigned long long)cap);
+  if (nnz == 0) return CFRK_OK;
+  void *p_out;
+  const size_t o_cnt = up((size_t)nnz * 8);
+  if ((rc = cfrk_pool_get(ctx, BUF_SPARSE_OUT, o_cnt + (size_t)nnz * 4, &p_out))) return rc;
+  uint64_t *d_keys = (uint64_t *)p_out;
+  uint32_t *d_cnt = (uint32_t *)((char *)p_out + o_cnt);
+  if ((rc = cfrk_sparse_compact(ctx, d_start, d_row, nS, d_keys, d_cnt))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(keys, d_keys, (size_t)nnz * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(counts, d_cnt, (size_t)nnz * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CFRK_OK;
+}
+
 /* ------------------------------------------------------------------ synthetic reads */
 
 int cfrk_synth_reads_device(cfrk_ctx *ctx, int64_t r0, int64_t R, int L, int64_t Glen,

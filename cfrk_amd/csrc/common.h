@@ -26,6 +26,9 @@ enum {  // pool slots
   BUF_RUNS_AUX,                               // pipelined runs exchange: segment cursors, used rows per group
   BUF_QUERY_INDEX,                            // read-only lookup index of the result (query.hip)
   BUF_QUERY_IN, BUF_QUERY_OUT,                // staging of the host query calls (keys or reads in, counts out)
+  BUF_SPARSE_KEYS, BUF_SPARSE_CNT,            // per-read sparse (sparse.hip): the rows at their reads' offsets, nN entries
+  BUF_SPARSE_AUX,                             // block sums of the row-pointer scan
+  BUF_SPARSE_IN, BUF_SPARSE_OUT,              // staging of the host call (data, start, length, row_ptr in; keys, counts out)
   BUF_NSLOTS
 };
 
@@ -98,6 +101,11 @@ int cfrk_pool_get(cfrk_ctx *ctx, int slot, size_t bytes, void **out);
 int cfrk_launch_dense(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start,
                       const int32_t *d_length, int64_t nN, int64_t nS, int k, int flags,
                       int32_t *d_freq);
+// sparse.hip: count (row_ptr complete on the stream, rows parked in BUF_SPARSE_KEYS / _CNT), then the move to the caller's arrays
+int cfrk_sparse_count(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+                      int64_t nS, int k, int flags, int64_t *d_row_ptr);
+int cfrk_sparse_compact(cfrk_ctx *ctx, const int64_t *d_start, const int64_t *d_row_ptr, int64_t nS, uint64_t *d_keys,
+                        uint32_t *d_counts);
 int cfrk_launch_synth(cfrk_ctx *ctx, int64_t r0, int64_t R, int L, int64_t Glen, uint64_t seedG,
                       uint64_t seedR, uint64_t seedS, int uniform, int8_t *d_data, int64_t *d_start,
                       int32_t *d_length);

@@ -18,7 +18,13 @@
 //                    "hi:lo:count" lines (k > 32: key = hi * 2^64 + lo), ascending by key
 //   --binary         (global) the CFRKGLB1 binary form instead of text (cfrk_host.h: 32-byte header,
 //                    then 12-byte (k <= 32) or 20-byte records, ascending)
-//   --canonical      (global) count min(kmer, reverse complement)
+//   --canonical      (global, sparse) count min(kmer, reverse complement)
+//   --sparse         per-read counting in sparse form, 1 <= k <= 32 (cfrk_per_read_sparse): one line per read, in read
+//                    order, its distinct k-mers as "key:count" tokens separated by single spaces, ascending by key (keys
+//                    in decimal, as PrintFreq prints indices); a read without a valid window gives an empty line.  Clean
+//                    FASTA parsing and guarded semantics as --native, every chunk is written; runs through the per-read
+//                    chunk pipeline (--gpus, --batch, --timing).  Not with --global, --binary, --histo, --query* or
+//                    --min/--max-count
 //   --device N       first GPU ordinal (the reference picks the GPU with most memory, src/main.cu:83-108)
 //   --gpus N         chunks (per-read modes) or files (--batch) are dealt round-robin to N devices,
 //                    one cfrk_ctx pair per device; replaces the reference's pthread fan-out, whose
@@ -72,7 +78,7 @@ namespace {
 struct Options {
   int k = 0, threads = 12;
   long chunk_size = 8192;
-  bool all_chunks = false, native = false, global = false, canonical = false, same_device = false, binary = false, timing = false;
+  bool all_chunks = false, native = false, global = false, canonical = false, same_device = false, binary = false, timing = false, sparse = false;
   int device = 0, gpus = 1;
   const char *histo = nullptr;       // --histo FILE
   bool histo_only = false;
@@ -149,6 +155,7 @@ int run_per_read(const Options &o, const cfrk_batch &batch, std::vector<Worker> 
   const size_t n = chunks.size();
   std::vector<std::string> text(n);
   std::vector<char> ready(n, 0);
+  const char *call = o.sparse ? "cfrk_per_read_sparse" : "cfrk_per_read_dense";
   std::mutex mu;
   std::condition_variable cv;
   std::atomic<size_t> next{0};
@@ -158,8 +165,10 @@ int run_per_read(const Options &o, const cfrk_batch &batch, std::vector<Worker> 
   const int fmt_threads = std::max(1, o.threads / (int)workers.size());
 
   auto work = [&](Worker &w) {
-    std::vector<int64_t> start;
+    std::vector<int64_t> start, row_ptr;
     std::vector<int32_t> freq;
+    std::vector<uint64_t> keys;
+    std::vector<uint32_t> counts;
     for (;;) {
       const size_t c = next.fetch_add(1);
       if (c >= n) return;
@@ -171,15 +180,31 @@ int run_per_read(const Options &o, const cfrk_batch &batch, std::vector<Worker> 
       const int8_t *data; const int32_t *length; int64_t nN;
       start.resize((size_t)chunks[c].count);
       cfrk_host_chunk(&batch, chunks[c].first, chunks[c].count, &data, start.data(), &length, &nN);
-      freq.resize((size_t)chunks[c].count * fourk);
-      const int rc = cfrk_per_read_dense(w.ctx, data, start.data(), length, nN, chunks[c].count, o.k, flags, freq.data());
+      int rc;
       std::string t;
-      if (!rc) {
-        t.resize(cfrk_host_format_dense_mt(freq.data(), chunks[c].count, o.k, nullptr, 0, fmt_threads));
-        cfrk_host_format_dense_mt(freq.data(), chunks[c].count, o.k, &t[0], t.size(), fmt_threads);
+      if (o.sparse) {
+        // room for every window of the chunk: always enough (cfrk_abi.h)
+        uint64_t room = 0, nnz = 0;
+        for (int64_t r = 0; r < chunks[c].count; ++r) room += (uint64_t)std::max<int64_t>((int64_t)length[r] - o.k + 1, 0);
+        row_ptr.resize((size_t)chunks[c].count + 1);
+        keys.resize(room);
+        counts.resize(room);
+        rc = cfrk_per_read_sparse(w.ctx, data, start.data(), length, nN, chunks[c].count, o.k, o.canonical ? CFRK_CANONICAL : 0,
+                                  row_ptr.data(), keys.data(), counts.data(), room, &nnz);
+        if (!rc) {
+          t.resize(cfrk_host_format_sparse_rows_mt(row_ptr.data(), keys.data(), counts.data(), chunks[c].count, nullptr, 0, fmt_threads));
+          cfrk_host_format_sparse_rows_mt(row_ptr.data(), keys.data(), counts.data(), chunks[c].count, &t[0], t.size(), fmt_threads);
+        }
+      } else {
+        freq.resize((size_t)chunks[c].count * fourk);
+        rc = cfrk_per_read_dense(w.ctx, data, start.data(), length, nN, chunks[c].count, o.k, flags, freq.data());
+        if (!rc) {
+          t.resize(cfrk_host_format_dense_mt(freq.data(), chunks[c].count, o.k, nullptr, 0, fmt_threads));
+          cfrk_host_format_dense_mt(freq.data(), chunks[c].count, o.k, &t[0], t.size(), fmt_threads);
+        }
       }
       std::lock_guard<std::mutex> lk(mu);
-      if (rc && !failed) failed = die(w.ctx, rc, "cfrk_per_read_dense");
+      if (rc && !failed) failed = die(w.ctx, rc, call);
       text[c].swap(t);
       ready[c] = 1;
       cv.notify_all();
@@ -196,7 +221,7 @@ int run_per_read(const Options &o, const cfrk_batch &batch, std::vector<Worker> 
     std::string t;
     t.swap(text[c]);
     lk.unlock();
-    if (c) fputc('\n', out);
+    if (c && !o.sparse) fputc('\n', out);           // (dense rows are separated, sparse rows terminated by '\n')
     fwrite(t.data(), 1, t.size(), out);
     lk.lock();
     written = c + 1;
@@ -521,7 +546,7 @@ struct Parsed {
   std::thread th;
   void start(const Options &o, const char *in) {
     t0 = now_s();
-    const unsigned flags = (o.native || o.global) ? 0 : CFRK_INGEST_COMPAT;
+    const unsigned flags = (o.native || o.global || o.sparse) ? 0 : CFRK_INGEST_COMPAT;
     th = std::thread([this, in, flags] { rc = cfrk_host_read_fasta(in, flags, &batch); seconds = now_s() - t0; });
   }
 };
@@ -537,7 +562,7 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
     g_wait_parse = now_s() - w0;
     rc = pre->rc; batch = pre->batch; t0 = pre->t0;
   } else {
-    rc = cfrk_host_read_fasta(in, (o.native || o.global) ? 0 : CFRK_INGEST_COMPAT, &batch);
+    rc = cfrk_host_read_fasta(in, (o.native || o.global || o.sparse) ? 0 : CFRK_INGEST_COMPAT, &batch);
   }
   if (rc) { fprintf(stderr, "cfrk: cannot read %s (error %d)\n", in, rc); return 1; }
   const double t1 = pre ? t0 + pre->seconds : now_s();
@@ -633,6 +658,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--native")) o.native = true;
     else if (!strcmp(argv[i], "--global")) o.global = true;
     else if (!strcmp(argv[i], "--canonical")) o.canonical = true;
+    else if (!strcmp(argv[i], "--sparse")) o.sparse = true;
     else if (!strcmp(argv[i], "--binary")) o.binary = true;
     else if (!strcmp(argv[i], "--timing")) o.timing = true;
     else if (!strcmp(argv[i], "--parse-threads") && i + 1 < argc) cfrk_host_set_parse_threads(atoi(argv[++i]));
@@ -662,6 +688,11 @@ int main(int argc, char **argv) {
     else pos.push_back(argv[i]);
   }
   // (refused here: before the input is parsed or a device is opened)
+  if (o.sparse && (o.global || o.binary || o.histo || o.histo_only || range_set || o.query || o.query_out || o.query_only ||
+                   o.query_db)) {
+    fprintf(stderr, "cfrk: --sparse is a per-read mode: not with --global, --binary, --histo, --query or --min-count / --max-count\n");
+    return 1;
+  }
   if ((o.histo || o.histo_only || range_set) && !o.global) {
     fprintf(stderr, "cfrk: --histo, --histo-only, --min-count and --max-count need --global\n");
     return 1;
@@ -692,6 +723,8 @@ int main(int argc, char **argv) {
     return 1;
   }
   o.k = atoi(pos[2]);
+  if (o.sparse && (o.k < 1 || o.k > 32)) { fprintf(stderr, "cfrk: --sparse needs 1 <= k <= 32 (one-word keys), not %d\n", o.k); return 1; }
+  if (o.sparse) { o.native = true; o.all_chunks = true; }   // clean parse, guarded semantics, every chunk
   if (pos.size() >= 4) o.threads = atoi(pos[3]);
   if (o.threads < 1) o.threads = 1;
   { const unsigned hw = std::thread::hardware_concurrency(); if (hw && (unsigned)o.threads > hw) o.threads = (int)hw; }

@@ -412,6 +412,54 @@ size_t cfrk_host_format_sparse_mt(const uint64_t *keys_lo, const uint64_t *keys_
   return total;
 }
 
+size_t cfrk_host_format_sparse_rows(const int64_t *row_ptr, const uint64_t *keys, const uint32_t *counts, int64_t nS,
+                                    char *buf, size_t cap) {
+  size_t s = 0;
+  char *p = buf;
+  (void)cap;
+  for (int64_t i = 0; i < nS; ++i) {
+    for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
+      if (buf) {
+        if (e != row_ptr[i]) *p++ = ' ';
+        p = put_u64(p, keys[e]); *p++ = ':';
+        p = put_u64(p, counts[e]);
+      } else {
+        s += (e != row_ptr[i] ? 1 : 0) + len_u64(keys[e]) + 1 + len_u64(counts[e]);
+      }
+    }
+    if (buf) *p++ = '\n';
+    else s += 1;
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
+size_t cfrk_host_format_sparse_rows_mt(const int64_t *row_ptr, const uint64_t *keys, const uint32_t *counts, int64_t nS,
+                                       char *buf, size_t cap, int threads) {
+  int T = threads < 1 ? 1 : threads;
+  if ((int64_t)T > nS / 1024 + 1) T = (int)(nS / 1024 + 1);       // (a thread per 1024 rows at least)
+  if (T == 1) return cfrk_host_format_sparse_rows(row_ptr, keys, counts, nS, buf, cap);
+  // row ranges per thread: sizes first (the text of a range starts where the previous one ends)
+  auto r_of = [&](int t) { return nS * t / T; };
+  auto part = [&](int t, char *dst) {
+    const int64_t r0 = r_of(t), r1 = r_of(t + 1);
+    return cfrk_host_format_sparse_rows(row_ptr + r0, keys, counts, r1 - r0, dst, dst ? (size_t)-1 : 0);
+  };
+  std::vector<size_t> sz((size_t)T), off((size_t)T);
+  {
+    std::vector<std::thread> th;
+    for (int t = 0; t < T; ++t) th.emplace_back([&, t] { sz[(size_t)t] = part(t, nullptr); });
+    for (auto &x : th) x.join();
+  }
+  size_t total = 0;
+  for (int t = 0; t < T; ++t) { off[(size_t)t] = total; total += sz[(size_t)t]; }
+  if (!buf) return total;
+  if (cap < total) return 0;
+  std::vector<std::thread> th;
+  for (int t = 0; t < T; ++t) th.emplace_back([&, t] { part(t, buf + off[(size_t)t]); });
+  for (auto &x : th) x.join();
+  return total;
+}
+
 size_t cfrk_host_format_histo(const uint64_t *hist, uint64_t nbins, const uint32_t *tail_counts, uint64_t n_tail,
                               char *buf, size_t cap) {
   // the tail: one count per key, binned here (sorted, then runs of equal counts)

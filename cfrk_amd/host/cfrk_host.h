@@ -62,6 +62,15 @@ size_t cfrk_host_format_sparse2(const uint64_t *keys_lo, const uint64_t *keys_hi
 size_t cfrk_host_format_sparse_mt(const uint64_t *keys_lo, const uint64_t *keys_hi, const uint32_t *counts,
                                   uint64_t n, char *buf, size_t cap, int threads);
 
+/* Per-read sparse rows (cfrk_per_read_sparse: CSR row_ptr[nS+1], keys, counts) as text (`cfrk --sparse`): one line per
+ * read, in read order, its "<key>:<count>" tokens separated by single spaces, ascending by key as the rows are, keys
+ * in decimal; a read without a valid window gives an empty line.  Returns bytes needed / written (buf may be NULL to
+ * size).  _mt: the same text, formatted by `threads` host threads (row ranges). */
+size_t cfrk_host_format_sparse_rows(const int64_t *row_ptr, const uint64_t *keys, const uint32_t *counts, int64_t nS,
+                                    char *buf, size_t cap);
+size_t cfrk_host_format_sparse_rows_mt(const int64_t *row_ptr, const uint64_t *keys, const uint32_t *counts, int64_t nS,
+                                       char *buf, size_t cap, int threads);
+
 /* Abundance histogram (k-mer spectrum) as text: "<c>\t<n_c>\n" for every c >= 1 with n_c > 0, ascending in c (the shape
  * of `jellyfish histo`).  n_c = hist[c] for c < nbins (hist[0] is ignored; hist may be NULL with nbins 0) plus the keys of
  * tail_counts (one count per key, any order; those below nbins are added to their bin).  Returns bytes needed /

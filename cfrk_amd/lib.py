@@ -28,6 +28,8 @@ CFRK_ERR_COUNT_OVERFLOW = -10        # finish / digest / export: some count was 
 CFRK_ERR_RUNS_REFUSED = -11          # a CFRK_RUNS_ONLY add that needs more than one pass
 CFRK_COUNT_MAX = 0xFFFFFFFE
 CFRK_QUERY_NONE = 0xFFFFFFFF         # read query: the window holds an invalid base or runs past nN
+CFRK_ERR_SMALL_BUF = -9
+CFRK_SPARSE_FAST_WINDOWS = 2048      # per-read sparse: windows per read the LDS path holds (longer reads: slower, exact)
 CFRK_PARAM_MSP_CHUNKS, CFRK_PARAM_L2_SLACK_COMPLETE, CFRK_PARAM_L2_SLACK_TRUNCATED, CFRK_PARAM_MSP2_SUBVALUE_BITS = 0, 1, 2, 3   # cfrk_debug_set_param
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -80,6 +82,8 @@ def load_library():
         "cfrk_memcpy_peer": ([vp, vp, vp, vp, C.c_size_t], C.c_int),
         "cfrk_per_read_dense": ([vp, vp, vp, vp, i64, i64, i32, i32, vp], C.c_int),
         "cfrk_per_read_dense_device": ([vp, vp, vp, vp, i64, i64, i32, i32, vp], C.c_int),
+        "cfrk_per_read_sparse": ([vp, vp, vp, vp, i64, i64, i32, i32, vp, vp, vp, u64, C.POINTER(u64)], C.c_int),
+        "cfrk_per_read_sparse_device": ([vp, vp, vp, vp, i64, i64, i32, i32, vp, vp, vp, u64, C.POINTER(u64)], C.c_int),
         "cfrk_global_begin": ([vp, i32, i32, u64], C.c_int),
         "cfrk_global_add": ([vp, vp, vp, vp, i64, i64], C.c_int),
         "cfrk_global_add_device": ([vp, vp, i64], C.c_int),
@@ -204,6 +208,44 @@ class Context:
                                                len(data), nS, k, flags, _ptr(freq)),
                    "cfrk_per_read_dense")
         return freq.reshape(nS, -1) if nS else freq.reshape(0, 4 ** k)
+
+    # -- per-read sparse (CSR rows of distinct k-mers, 1 <= k <= 32) -----------------------
+    def per_read_sparse(self, data, start, length, k, flags=0):
+        """-> (row_ptr int64[nS+1], keys uint64[nnz], counts uint32[nnz]): row i = the distinct k-mers of read i,
+        ascending, with their multiplicities.  Sized by a sizes-only call, then filled by a second one."""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        nS = len(length)
+        if len(start) != nS:
+            raise ValueError("start and length differ in size")
+        row_ptr = np.zeros(nS + 1, np.int64)
+        nnz = C.c_uint64()
+        args = (self._h, _ptr(data), _ptr(start), _ptr(length), len(data), nS, k, flags, _ptr(row_ptr))
+        rc = self._L.cfrk_per_read_sparse(*args, None, None, 0, C.byref(nnz))
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.check(rc, "cfrk_per_read_sparse")
+            return row_ptr, np.empty(0, np.uint64), np.empty(0, np.uint32)
+        keys = np.empty(nnz.value, np.uint64)
+        counts = np.empty(nnz.value, np.uint32)
+        self.check(self._L.cfrk_per_read_sparse(*args, _ptr(keys), _ptr(counts), len(keys), C.byref(nnz)),
+                   "cfrk_per_read_sparse")
+        return row_ptr, keys, counts
+
+    def per_read_sparse_device(self, d_data, d_start, d_length, nN, nS, k, flags, d_row_ptr, d_keys, d_counts, cap):
+        """device form -> nnz; d_keys / d_counts may be 0 with cap 0 (sizes only).  Raises CfrkError (code
+        CFRK_ERR_SMALL_BUF, with .nnz set; d_row_ptr is complete) when nnz > cap.  Synchronises once, returns with
+        the move of the rows enqueued on the context stream."""
+        nnz = C.c_uint64()
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_per_read_sparse_device(self._h, vp(d_data), vp(d_start), vp(d_length), nN, nS, k, flags,
+                                                 vp(d_row_ptr), vp(d_keys), vp(d_counts), cap, C.byref(nnz))
+        try:
+            self.check(rc, "cfrk_per_read_sparse_device")
+        except CfrkError as e:
+            e.nnz = nnz.value
+            raise
+        return nnz.value
 
     def synth_reads_device(self, r0, R, L, Glen, d_data, d_start=None, d_length=None,
                            seedG=1, seedR=2, seedS=3, uniform=False):

@@ -61,7 +61,7 @@ extern "C" {
                                 spill into the previous row's last bin, bound length-1, 1024-window
                                 cap; src/kmer_kernel.cu:73-90, src/kmer_main.cu:82-83).  Without it:
                                 the guarded ComputeFreq semantics (src/kmer_kernel.cu:52-70).        */
-#define CFRK_CANONICAL  0x2  /* global only: key = min(kmer, reverse complement)                     */
+#define CFRK_CANONICAL  0x2  /* global and per-read sparse: key = min(kmer, reverse complement)      */
 #define CFRK_FORCE_HASH 0x4  /* global only: count with one HBM atomic per occurrence (the general
                                 path) even where the minimizer-partitioned LDS path applies          */
 #define CFRK_RUNS_ONLY  0x8  /* global only, 16 <= k <= 64: the job partitions and deduplicates ONE add
@@ -126,6 +126,44 @@ int cfrk_per_read_dense(cfrk_ctx *ctx, const int8_t *data, const int64_t *start,
 int cfrk_per_read_dense_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start,
                                const int32_t *d_length, int64_t nN, int64_t nS, int k, int flags,
                                int32_t *d_freq_out);
+
+/* ---- per-read sparse counting: the rows of the dense form without their zeros, 1 <= k <= 32 ---- */
+
+/* For every read its DISTINCT k-mers in ascending order with their multiplicities, as CSR:
+ *   row_ptr[0] = 0, row_ptr[i+1] - row_ptr[i] = distinct k-mers of read i, *nnz_out = row_ptr[nS];
+ *   keys / counts [row_ptr[i], row_ptr[i+1]) = read i's keys, strictly ascending, and how often each occurs in it.
+ * Semantics: the guarded ComputeFreq (src/kmer_kernel.cu:52-70), i.e. cfrk_per_read_dense without CFRK_COMPAT: a
+ * window of read i counts iff it starts inside the read and all its k codes are 0..3 (the terminator is an invalid
+ * code: no window crosses a read); key = sum code[j] * 4^(k-1-j).  For k <= 15 without flags row i is exactly the
+ * non-zero bins of row i of the native dense result -- at 12 bytes per distinct k-mer instead of 4^k * 4 per read, so
+ * k = 21 or 31 and chunks of millions of reads are ordinary.  With CFRK_CANONICAL the key is min(key, reverse
+ * complement), as in global mode.  Counts are uint32 and cannot saturate (a count never exceeds the read's length).
+ * The compat quirks of the dense form (spill into the previous row, length-1 bound, 1024-window cap) and
+ * CFRK_FLOAT_INDEX have no sparse form: any flag other than CFRK_CANONICAL is CFRK_ERR_ARG, and so are k < 1, k > 32
+ * (two-word keys, k > 32, are out of scope of these calls), negative sizes, a NULL row_ptr / nnz_out and NULL keys or
+ * counts with cap > 0.  nS = 0 is fine (row_ptr[0] = 0, nnz 0).
+ * cap = entries available in keys and counts.  cap = sum over reads of max(length[i] - k + 1, 0) -- the number of
+ * windows -- is always enough.  When nnz > cap the call returns CFRK_ERR_SMALL_BUF: row_ptr and *nnz_out are complete
+ * all the same and nothing is written to keys or counts, so a caller can size exactly and call again; keys or counts
+ * NULL with cap = 0 is that "sizes only" call.
+ * Device form: every buffer on the context's device, no alignment requirement on d_data.  It synchronises ONCE, to
+ * read nnz back; it returns with the last kernel (the move of the rows into d_keys / d_counts) enqueued on the context
+ * stream.  start / length are not checked: a read whose range does not lie inside [0, nN) gets an empty row; ranges
+ * that overlap give undefined rows (never an access outside the buffers).  Temporary device memory: 12 bytes per byte
+ * of data, kept in the context's pool.
+ * Host form: checks start and length against the terminators in data like cfrk_global_add (CFRK_ERR_LAYOUT), stages
+ * through the pool and is synchronous.
+ * Neither call touches a global job that is open on the same context.
+ * Reads of up to CFRK_SPARSE_FAST_WINDOWS windows are counted in LDS by a group of lanes; longer reads are exact too,
+ * on a slower path (one workgroup per read, sorting in device memory). */
+#define CFRK_SPARSE_FAST_WINDOWS 2048
+int cfrk_per_read_sparse_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                int64_t nN, int64_t nS, int k, int flags,
+                                int64_t *d_row_ptr /* nS+1 */, uint64_t *d_keys, uint32_t *d_counts,
+                                uint64_t cap, uint64_t *nnz_out);
+int cfrk_per_read_sparse(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
+                         int64_t nN, int64_t nS, int k, int flags,
+                         int64_t *row_ptr, uint64_t *keys, uint32_t *counts, uint64_t cap, uint64_t *nnz_out);
 
 /* ---- global counting: sum over reads of the per-read rows, any 1 <= k <= 64 ------------ */
 
