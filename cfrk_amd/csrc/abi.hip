@@ -637,6 +637,56 @@ int cfrk_global_query_reads(cfrk_ctx *ctx, const int8_t *data, const int64_t *st
   return CFRK_OK;
 }
 
+static_assert(sizeof(cfrk_read_stats) == 32, "cfrk_read_stats is 32 bytes without padding");
+
+static int read_stats_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, const void *data, const void *start,
+                            const void *length, const void *out) {
+  int rc = query_check(ctx, nN);
+  if (rc) return rc;
+  if (nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (nS > 0 && (!data || !start || !length || !out)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  return CFRK_OK;
+}
+
+int cfrk_global_read_stats_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                  int64_t nN, int64_t nS, uint32_t threshold, cfrk_read_stats *d_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = read_stats_check(ctx, nN, nS, d_data, d_start, d_length, d_out);
+  if (rc || nS == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_read_stats_launch(ctx, d_data, d_start, d_length, nN, nS, threshold, d_out);
+}
+
+int cfrk_global_read_stats(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                           int64_t nS, uint32_t threshold, cfrk_read_stats *out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = read_stats_check(ctx, nN, nS, data, start, length, out);
+  if (rc || nS == 0) return rc;
+  LayoutCheck lc;      // (the add's check of the struct-read layout, beside the copies)
+  lc.begin(data, start, length, nN, nS);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // staged through the query calls' slots: [data | start | length] in, the rows out; each part 256-byte aligned
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_start = up((size_t)nN + 64), o_length = o_start + up((size_t)nS * 8);
+  void *p_in, *p_out;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_IN, o_length + (size_t)nS * 4, &p_in))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, (size_t)nS * sizeof(cfrk_read_stats), &p_out))) return rc;
+  int8_t *d_data = (int8_t *)p_in;
+  int64_t *d_start = (int64_t *)((char *)p_in + o_start);
+  int32_t *d_length = (int32_t *)((char *)p_in + o_length);
+  if (nN) HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_start, start, (size_t)nS * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_length, length, (size_t)nS * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (lc.failed(ctx)) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
+    return CFRK_ERR_LAYOUT;
+  }
+  if ((rc = cfrk_read_stats_launch(ctx, d_data, d_start, d_length, nN, nS, threshold, (cfrk_read_stats *)p_out))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(out, p_out, (size_t)nS * sizeof(cfrk_read_stats), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CFRK_OK;
+}
+
 int cfrk_global_last_add_ms(cfrk_ctx *ctx, float *ms) {
   if (!ctx || !ms) return CFRK_ERR_ARG;
   if (!ctx->ev_valid) return cfrk_fail(ctx, CFRK_ERR_STATE, "no add recorded");

@@ -25,7 +25,7 @@ enum {  // pool slots
   BUF_MSP_OVF1, BUF_MSP_LAYOUT1,              // the same for the level-1 regions
   BUF_RUNS_AUX,                               // pipelined runs exchange: segment cursors, used rows per group
   BUF_QUERY_INDEX,                            // read-only lookup index of the result (query.hip)
-  BUF_QUERY_IN, BUF_QUERY_OUT,                // staging of the host query calls (keys or reads in, counts out)
+  BUF_QUERY_IN, BUF_QUERY_OUT,                // staging of the host query / read-stats calls (keys or reads in, counts or rows out)
   BUF_SPARSE_KEYS, BUF_SPARSE_CNT,            // per-read sparse (sparse.hip): the rows at their reads' offsets, nN entries
   BUF_SPARSE_AUX,                             // block sums of the row-pointer scan
   BUF_SPARSE_IN, BUF_SPARSE_OUT,              // staging of the host call (data, start, length, row_ptr in; keys, counts out)
@@ -130,6 +130,9 @@ int cfrk_result_histogram(cfrk_ctx *ctx, const ResultSrc *src, uint32_t nbins, u
 // the lookup kernel is left enqueued.  Arguments are checked by the callers (abi.hip).
 int cfrk_query_keys(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t *d_hi, int64_t n, uint32_t *d_out);
 int cfrk_query_reads(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, uint32_t *d_out);
+// read_stats.hip: one cfrk_read_stats row per read from the same index; the kernels are left enqueued.  nS >= 1.
+int cfrk_read_stats_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                           int64_t nN, int64_t nS, uint32_t threshold, cfrk_read_stats *d_out);
 
 // ---- device helpers -----------------------------------------------------------------------
 #ifdef __HIPCC__

@@ -19,57 +19,15 @@
 // and the wave's 2048 answers staged in LDS so that they leave as coalesced 16-B stores.  k > 32 rolls byte-wise like
 // hash_count2_kernel, its answers staged the same way.
 #include "msp.h"
+#include "query_dev.h"
 #include "table.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int QB = 8;                 // windows per lane whose first-slot loads are in flight together
 constexpr int QROW = 33;              // a lane's 32 staged answers, rows padded by one word: conflict-free LDS access
 constexpr int QSTAGE = 64 * QROW;     // one wave's staged answers (words)
-
-struct QIndex {
-  const void *p;
-  uint64_t mask;
-  int shift;                          // 64 - log2(slots)
-  int k;
-};
-
-__device__ __forceinline__ uint64_t q_slot1(uint64_t lo, int shift) { return dev_mix64(lo) >> shift; }
-__device__ __forceinline__ uint64_t q_slot2(uint64_t lo, uint64_t hi, int shift) { return dev_mix64(lo ^ dev_mix64(hi)) >> shift; }
-__device__ __forceinline__ uint64_t q_lo(uint4 v) { return ((uint64_t)v.y << 32) | v.x; }
-__device__ __forceinline__ uint64_t q_hi(uint4 v) { return ((uint64_t)v.w << 32) | v.z; }
-
-// probe from slot h on; 0 when the key is absent (load <= 0.5: an empty slot ends every probe sequence)
-__device__ __forceinline__ uint32_t q_find1(const uint4 *__restrict__ s, uint64_t mask, uint64_t h, uint64_t key) {
-  for (uint64_t probe = 0; probe <= mask; ++probe) {
-    const uint4 v = s[h];
-    if (v.z == 0) return 0;
-    if (q_lo(v) == key) return v.z;
-    h = (h + 1) & mask;
-  }
-  return 0;
-}
-__device__ __forceinline__ uint32_t q_find2(const uint4 *__restrict__ s, uint64_t mask, uint64_t h, uint64_t lo,
-                                            uint64_t hi) {
-  for (uint64_t probe = 0; probe <= mask; ++probe) {
-    const uint4 a = s[2 * h], b = s[2 * h + 1];
-    if (b.x == 0) return 0;
-    if (q_lo(a) == lo && q_hi(a) == hi) return b.x;
-    h = (h + 1) & mask;
-  }
-  return 0;
-}
-
-// canonical form of a two-word key (2k bits, first base most significant): min with its 128-bit reverse complement
-__device__ __forceinline__ void q_canon2(uint64_t &lo, uint64_t &hi, int k) {
-  const uint64_t rhi = dev_revcomp64(lo, 32), rlo = dev_revcomp64(hi, 32);   // all 64 bases, reversed + complemented
-  const int s = 128 - 2 * k;                                                  // 0 .. 62: the k-mer's complement on top
-  const uint64_t clo = s ? (rlo >> s) | (rhi << (64 - s)) : rlo;
-  const uint64_t chi = s ? rhi >> s : rhi;
-  if (chi < hi || (chi == hi && clo < lo)) { lo = clo; hi = chi; }
-}
 
 // ---- index build -----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void qidx_dense_kernel(ResultSrc r, uint32_t *__restrict__ dense, uint64_t nkeys) {
@@ -122,21 +80,7 @@ __global__ void qidx_ones_kernel(uint4 *__restrict__ slots, uint64_t mask, int s
 }
 
 // ---- lookups ---------------------------------------------------------------------------------------------------
-// MODE 0: dense (k <= 12), 1: one-word hash (k <= 32), 2: two-word hash (k > 32)
-template <int MODE, bool CANON>
-__device__ __forceinline__ uint32_t q_key(const QIndex &q, uint64_t lo, uint64_t hi) {
-  const int k = q.k;
-  if (MODE < 2) {
-    if (hi != 0 || (k < 32 && (lo >> (2 * k)) != 0)) return 0;      // bits at or above 2k: no such k-mer
-    if (CANON) { const uint64_t rc = dev_revcomp64(lo, k); lo = rc < lo ? rc : lo; }
-    if (MODE == 0) return static_cast<const uint32_t *>(q.p)[lo];
-    return q_find1(static_cast<const uint4 *>(q.p), q.mask, q_slot1(lo, q.shift), lo);
-  }
-  if (k < 64 && (hi >> (2 * k - 64)) != 0) return 0;
-  if (CANON) q_canon2(lo, hi, k);
-  return q_find2(static_cast<const uint4 *>(q.p), q.mask, q_slot2(lo, hi, q.shift), lo, hi);
-}
-
+// MODE 0: dense (k <= 12), 1: one-word hash (k <= 32), 2: two-word hash (k > 32): q_key, query_dev.h
 template <int MODE, bool CANON>
 __global__ __launch_bounds__(256) void query_keys_kernel(QIndex q, const uint64_t *__restrict__ keys_lo,
                                                          const uint64_t *__restrict__ keys_hi, int64_t n,
@@ -285,8 +229,10 @@ int q_grid(const cfrk_ctx *ctx, int64_t items_per_block, int64_t items) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)ctx->num_cus * 8));
 }
 
+}  // namespace
+
 // the index of the job's current result, built when it is not valid
-int q_index(cfrk_ctx *ctx, QIndex *q) {
+int cfrk_query_index(cfrk_ctx *ctx, QIndex *q) {
   const int k = ctx->g_k;
   const bool two = ctx->g_two;
   if (!ctx->q_valid) {
@@ -336,11 +282,9 @@ int q_index(cfrk_ctx *ctx, QIndex *q) {
   return CFRK_OK;
 }
 
-}  // namespace
-
 int cfrk_query_keys(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t *d_hi, int64_t n, uint32_t *d_out) {
   QIndex q;
-  int rc = q_index(ctx, &q);
+  int rc = cfrk_query_index(ctx, &q);
   if (rc || n == 0) return rc;
   const bool canon = (ctx->g_flags & CFRK_CANONICAL) != 0;
   const int grid = q_grid(ctx, 256 * 4, n);
@@ -359,7 +303,7 @@ int cfrk_query_keys(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t *d_hi, i
 
 int cfrk_query_reads(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, uint32_t *d_out) {
   QIndex q;
-  int rc = q_index(ctx, &q);
+  int rc = cfrk_query_index(ctx, &q);
   if (rc || nN == 0) return rc;
   const bool canon = (ctx->g_flags & CFRK_CANONICAL) != 0;
   const bool vec = ((uintptr_t)d_out & 15) == 0;

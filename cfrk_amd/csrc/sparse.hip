@@ -21,6 +21,7 @@
 // Scan: three small kernels turn the counts into offsets in place (reduce per block, scan of the block sums, apply).
 // Compaction pass, sparse_compact_kernel: every row moves from its temporary place to row_ptr[i].
 #include "common.h"
+#include "lane_group.h"
 
 #include <algorithm>
 
@@ -33,53 +34,6 @@ constexpr int SP_STAGE_SLACK = 48;                     // k - 1 <= 31 bytes + sk
 constexpr int SP_BIG_ROW = 4096;                       // compaction: rows above this are copied by the whole workgroup
 constexpr int SP_SCAN_ITEMS = 16;                      // scan: items per thread (256 threads: 4096 per block)
 
-// the lanes of one wave run in lock step and LDS is in order per wave: this only keeps the compiler from moving LDS
-// accesses across a phase boundary
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-struct WaveSync { __device__ __forceinline__ void operator()() const { wave_sync(); } };
-struct BlockSync { __device__ __forceinline__ void operator()() const { __syncthreads(); } };
-
-template <int G>
-__device__ __forceinline__ int group_sum(int v) {
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__device__ __forceinline__ void cmp_exchange(uint64_t *a, int lo, int hi) {
-  const uint64_t x = a[lo], y = a[hi];
-  if (x > y) { a[lo] = y; a[hi] = x; }
-}
-
-// a[0 .. n) ascending, by nt cooperating threads (tid = 0 .. nt-1; all of them call with the same n).  Bitonic network
-// in the form whose merges begin with a "flip" step: every compare-exchange puts the smaller key at the lower index,
-// so with +infinity imagined at the indices >= n an exchange that reaches there never swaps and is skipped.
-template <class Sync>
-__device__ __forceinline__ void sort_keys(uint64_t *a, int n, int tid, int nt, Sync sync) {
-  if (n < 2) return;
-  const int P = 1 << (32 - __clz(n - 1));
-  const int half = P >> 1;
-  for (int span = 2; span <= P; span <<= 1) {
-    const int h = span >> 1;
-    for (int t = tid; t < half; t += nt) {
-      const int blk = (t & ~(h - 1)) << 1, off = t & (h - 1);
-      const int hi = blk + span - 1 - off;
-      if (hi < n) cmp_exchange(a, blk + off, hi);
-    }
-    sync();
-    for (int j = h >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < half; t += nt) {
-        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        if (lo + j < n) cmp_exchange(a, lo, lo + j);
-      }
-      sync();
-    }
-  }
-}
-
 // first index in (idx, n) whose key differs from a[idx] (n when there is none); a is sorted
 __device__ __forceinline__ int run_end(const uint64_t *a, int idx, int n, uint64_t key) {
   int lo = idx + 1, hi = n;
@@ -88,12 +42,6 @@ __device__ __forceinline__ int run_end(const uint64_t *a, int idx, int n, uint64
     if (a[mid] == key) lo = mid + 1; else hi = mid;
   }
   return lo;
-}
-
-// windows of a read that can count: those that end inside it.  A read whose range does not lie in [0, nN) (the device
-// form does not check the layout) has none, so nothing is ever read or written outside the buffers.
-__device__ __forceinline__ int read_windows(int64_t st, int L, int64_t nN, int k) {
-  return (st >= 0 && L >= k && st <= nN - (int64_t)L) ? L - k + 1 : 0;
 }
 
 // one base into the rolling forward / reverse-complement keys; run = valid bases in a row
@@ -114,28 +62,7 @@ __device__ __forceinline__ void count_read(const int8_t *__restrict__ data, int6
                                            int64_t *__restrict__ row_ptr) {
   const uint64_t mask = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1);
   const int rcshift = 2 * (k - 1);
-  // bytes [st, st + L) as the aligned dwords that cover them; a dword that is not wholly inside [data, data + nN) is
-  // assembled from guarded byte loads
-  const int nbytes = nwin + k - 1;
-  const int skew = (int)((reinterpret_cast<uintptr_t>(data) + (uintptr_t)st) & 3u);
-  const int ndw = (skew + nbytes + 3) >> 2;
-  for (int d = lane; d < ndw; d += G) {
-    const int64_t off = st - skew + 4 * (int64_t)d;
-    int32_t w;
-    if (off >= 0 && off + 4 <= nN) {
-      w = *reinterpret_cast<const int32_t *>(data + off);
-    } else {
-      uint32_t u = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int64_t g = off + j;
-        const uint32_t c = (g >= 0 && g < nN) ? (uint32_t)(uint8_t)data[g] : 0xFFu;
-        u |= c << (8 * j);
-      }
-      w = (int32_t)u;
-    }
-    stage_dw[d] = w;
-  }
+  const int skew = stage_read<G>(data, nN, st, nwin + k - 1, stage_dw, lane);
   wave_sync();
   const int8_t *stage = reinterpret_cast<const int8_t *>(stage_dw) + skew;
   const int per = (nwin + G - 1) / G;

@@ -46,7 +46,14 @@
 //                    in the whole result (whatever --min-count / --max-count keep)?  OFILE: one line per query record, in
 //                    record order, the counts of its windows separated by single spaces, "-" for a window that holds a
 //                    non-ACGT base; a record shorter than k gives an empty line
-//   --query-only     (with --query) write OFILE only: the counts are not exported and the output path is left untouched
+//   --query-stats SFILE  (with --query; --query-out becomes optional) per-read abundance statistics of the reads of QFILE
+//                    against the whole result (cfrk_global_read_stats): one line per query record, in record order, seven
+//                    tab-separated decimal fields -- valid windows, present (count >= 1), below (count < T), min, lower
+//                    median, max and sum of the windows' counts; a record without a valid window gives zeros.  One device
+//                    (not with --gpus above 1), not with --batch or --sparse
+//   --stats-below T  (with --query-stats) the threshold of the `below` field, 0 .. 4294967295 (default 0: below is 0)
+//   --query-only     (with --query) write OFILE / SFILE only: the counts are not exported and the output path is left
+//                    untouched
 //   --query-db DB.bin  (with --query, no positional arguments) query a saved --binary count file without recounting; k and
 //                    the canonical bit come from its header
 //   --batch N        the Swift/T workflow's loop (swift/cfrk.swf:15-20) in one process: for i < N
@@ -85,12 +92,14 @@ struct Options {
   uint32_t min_count = 1, max_count = CFRK_COUNT_MAX;
   const char *query = nullptr, *query_out = nullptr, *query_db = nullptr;   // --query QFILE --query-out OFILE --query-db DB
   bool query_only = false;
+  const char *query_stats = nullptr;   // --query-stats SFILE
+  uint32_t stats_below = 0;            // --stats-below T
 };
 
 // --timing: wall-clock seconds by phase (one file; with --batch the last file's)
 struct Timing {
   double parse = 0, add_call = 0, finish_wait = 0, export_ = 0, format = 0, write = 0, per_read = 0, total = 0, histo = 0;
-  double query = 0;
+  double query = 0, stats = 0;
   double close = 0, free_batch = 0, open = 0;
   double contexts = 0, begin = 0, wait_parse = 0;   // context creation (beside the parse), cfrk_global_begin, the main thread's wait for the parser
   float count_kernels_ms = 0;
@@ -297,6 +306,24 @@ int write_query(const Options &o, int k, const uint32_t *ans) {
   return 0;
 }
 
+// --query-stats: the query reads' abundance statistics against one result, written to SFILE
+int write_query_stats(const Options &o, cfrk_ctx *ctx) {
+  const cfrk_batch &q = g_qreads;
+  std::vector<cfrk_read_stats> st((size_t)q.nS);
+  if (q.nS) {
+    const int rc = cfrk_global_read_stats(ctx, q.data, q.start, q.length, q.nN, q.nS, o.stats_below, st.data());
+    if (rc) return die(ctx, rc, "cfrk_global_read_stats");
+  }
+  std::string buf;
+  buf.resize(cfrk_host_format_read_stats(st.data(), q.nS, nullptr, 0));
+  cfrk_host_format_read_stats(st.data(), q.nS, &buf[0], buf.size());
+  FILE *f = fopen(o.query_stats, "wb");
+  if (!f) { fprintf(stderr, "cfrk: cannot write %s\n", o.query_stats); return 1; }
+  const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+  if (fclose(f) != 0 || !ok) { fprintf(stderr, "cfrk: cannot write %s\n", o.query_stats); return 1; }
+  return 0;
+}
+
 // the global result (ascending keys) as sparse text or in the binary form
 void write_global(const Options &o, const uint64_t *lo, const uint64_t *hi, const uint32_t *cnt, uint64_t n, FILE *out) {
   const uint64_t *hi2 = (o.k > 32) ? hi : nullptr;
@@ -352,9 +379,16 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
   g_timing.histo = now_s() - t2;
   if (o.query) {
     const double q0 = now_s();
-    std::vector<uint32_t> ans;
-    if ((rc = query_answers(ctx, ans)) || (rc = write_query(o, o.k, ans.data()))) return rc;
+    if (o.query_out) {
+      std::vector<uint32_t> ans;
+      if ((rc = query_answers(ctx, ans)) || (rc = write_query(o, o.k, ans.data()))) return rc;
+    }
     g_timing.query = now_s() - q0;
+    if (o.query_stats) {
+      const double s0 = now_s();
+      if ((rc = write_query_stats(o, ctx))) return rc;
+      g_timing.stats = now_s() - s0;
+    }
   }
   if (early_free && owned) *early_free = std::thread([owned] { cfrk_host_free_batch(owned); });
   cfrk_global_last_add_ms(ctx, &g_timing.count_kernels_ms);
@@ -587,8 +621,9 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
   else cfrk_host_free_batch(&batch);
   g_timing.total = now_s() - t0;
   g_timing.close = tf1 - tf0; g_timing.free_batch = now_s() - tf1; g_timing.open = t_open;
-  char query_field[64] = "";     // (only with --query: the line is unchanged otherwise)
-  if (o.query) snprintf(query_field, sizeof query_field, "\"query_s\": %.4f, ", g_timing.query);
+  char query_field[96] = "";     // (only with --query: the line is unchanged otherwise)
+  if (o.query_stats) snprintf(query_field, sizeof query_field, "\"query_s\": %.4f, \"stats_s\": %.4f, ", g_timing.query, g_timing.stats);
+  else if (o.query) snprintf(query_field, sizeof query_field, "\"query_s\": %.4f, ", g_timing.query);
   if (o.timing)
     fprintf(stderr, "cfrk-timing {\"fasta_bytes\": %lld, \"reads\": %lld, \"code_bytes\": %lld, \"parse_s\": %.4f, \"add_call_s\": %.4f, "
             "\"finish_wait_s\": %.4f, \"count_kernels_ms\": %.3f, \"export_s\": %.4f, \"format_s\": %.4f, \"write_s\": %.4f, "
@@ -640,9 +675,15 @@ int run_query_db(const Options &o) {
     for (void *d : {d_lo, d_hi, d_cnt}) if (d) cfrk_device_free(ctx, d);
     if (rc) return die(ctx, rc, "loading the count file");
   }
-  std::vector<uint32_t> ans;
-  if ((rc = query_answers(ctx, ans)) || (rc = write_query(o, k, ans.data()))) return rc;
-  if (o.timing) fprintf(stderr, "cfrk-timing {\"entries\": %llu, \"query_s\": %.4f}\n", (unsigned long long)n, now_s() - q0);
+  if (o.query_out) {
+    std::vector<uint32_t> ans;
+    if ((rc = query_answers(ctx, ans)) || (rc = write_query(o, k, ans.data()))) return rc;
+  }
+  const double s0 = now_s();
+  if (o.query_stats && (rc = write_query_stats(o, ctx))) return rc;
+  if (o.timing && o.query_stats)
+    fprintf(stderr, "cfrk-timing {\"entries\": %llu, \"query_s\": %.4f, \"stats_s\": %.4f}\n", (unsigned long long)n, s0 - q0, now_s() - s0);
+  else if (o.timing) fprintf(stderr, "cfrk-timing {\"entries\": %llu, \"query_s\": %.4f}\n", (unsigned long long)n, now_s() - q0);
   return 0;
 }
 
@@ -652,7 +693,7 @@ int main(int argc, char **argv) {
   std::vector<const char *> pos;
   Options o;
   int batch_n = -1;
-  bool range_set = false;
+  bool range_set = false, stats_below_set = false;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--all-chunks")) o.all_chunks = true;
     else if (!strcmp(argv[i], "--native")) o.native = true;
@@ -675,6 +716,13 @@ int main(int argc, char **argv) {
       else if (!strcmp(opt, "--query-out")) o.query_out = v;
       else o.query_db = v;
     }
+    else if (!strcmp(argv[i], "--query-stats") || !strcmp(argv[i], "--stats-below")) {
+      if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
+      const char *opt = argv[i], *v = argv[++i];
+      if (!strcmp(opt, "--query-stats")) { o.query_stats = v; continue; }
+      if (!parse_count(v, &o.stats_below)) { fprintf(stderr, "cfrk: %s needs a count (an integer from 0 to 4294967295), not '%s'\n", opt, v); return 1; }
+      stats_below_set = true;
+    }
     else if (!strcmp(argv[i], "--histo") || !strcmp(argv[i], "--min-count") || !strcmp(argv[i], "--max-count")) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
       const char *opt = argv[i], *v = argv[++i];
@@ -689,7 +737,7 @@ int main(int argc, char **argv) {
   }
   // (refused here: before the input is parsed or a device is opened)
   if (o.sparse && (o.global || o.binary || o.histo || o.histo_only || range_set || o.query || o.query_out || o.query_only ||
-                   o.query_db)) {
+                   o.query_db || o.query_stats || stats_below_set)) {
     fprintf(stderr, "cfrk: --sparse is a per-read mode: not with --global, --binary, --histo, --query or --min-count / --max-count\n");
     return 1;
   }
@@ -708,7 +756,10 @@ int main(int argc, char **argv) {
     fprintf(stderr, "cfrk: --query-out, --query-only and --query-db need --query QFILE\n");
     return 1;
   }
-  if (o.query && !o.query_out) { fprintf(stderr, "cfrk: --query needs --query-out OFILE\n"); return 1; }
+  if ((o.query_stats || stats_below_set) && !o.query) { fprintf(stderr, "cfrk: --query-stats and --stats-below need --query QFILE\n"); return 1; }
+  if (stats_below_set && !o.query_stats) { fprintf(stderr, "cfrk: --stats-below needs --query-stats SFILE\n"); return 1; }
+  if (o.query && !o.query_out && !o.query_stats) { fprintf(stderr, "cfrk: --query needs --query-out OFILE or --query-stats SFILE\n"); return 1; }
+  if (o.query_stats && o.gpus > 1) { fprintf(stderr, "cfrk: --query-stats runs on one device: not with --gpus above 1\n"); return 1; }
   if (o.query && batch_n >= 0) { fprintf(stderr, "cfrk: --query writes one file: not with --batch\n"); return 1; }
   if (o.query_db && !pos.empty()) { fprintf(stderr, "cfrk: --query-db takes no positional arguments\n"); return 1; }
   if (o.query) {

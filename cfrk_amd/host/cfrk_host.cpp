@@ -511,6 +511,26 @@ size_t cfrk_host_format_query(const uint32_t *counts, const int64_t *start, cons
   return buf ? (size_t)(p - buf) : s;
 }
 
+size_t cfrk_host_format_read_stats(const void *stats, int64_t nS, char *buf, size_t cap) {
+  size_t s = 0;
+  char *p = buf;
+  (void)cap;
+  const char *row = static_cast<const char *>(stats);
+  for (int64_t i = 0; i < nS; ++i, row += 32) {
+    uint32_t w[6];
+    uint64_t sum;
+    memcpy(w, row, 24);
+    memcpy(&sum, row + 24, 8);
+    for (int j = 0; j < 6; ++j) {
+      if (buf) { p = put_u64(p, w[j]); *p++ = '\t'; }
+      else s += len_u64(w[j]) + 1;
+    }
+    if (buf) { p = put_u64(p, sum); *p++ = '\n'; }
+    else s += len_u64(sum) + 1;
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
 static void put_le(char *p, uint64_t x, int bytes) { for (int i = 0; i < bytes; ++i) p[i] = (char)(x >> (8 * i)); }
 static uint64_t get_le(const char *p, int bytes) {
   uint64_t x = 0;

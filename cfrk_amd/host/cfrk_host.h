@@ -85,6 +85,12 @@ size_t cfrk_host_format_histo(const uint64_t *hist, uint64_t nbins, const uint32
 size_t cfrk_host_format_query(const uint32_t *counts, const int64_t *start, const int32_t *length, int64_t nS, int k,
                               char *buf, size_t cap);
 
+/* Per-read abundance statistics as text (`cfrk --query-stats`): stats = nS rows of cfrk_read_stats (cfrk_abi.h: 32
+ * bytes -- windows, present, below, min, median, max as uint32, sum as uint64).  One line per record, in record order,
+ * the seven fields in struct order, in decimal, separated by tabs.  Returns bytes needed / written (buf may be NULL to
+ * size). */
+size_t cfrk_host_format_read_stats(const void *stats, int64_t nS, char *buf, size_t cap);
+
 /* Binary global form, little endian, everything in one file:
  *   header, 32 bytes:  char magic[8] = "CFRKGLB1"; uint32 k; uint32 flags (bit 0: canonical counting,
  *                      bit 1: two-word keys, i.e. k > 32); uint64 n (records); uint64 sum of counts

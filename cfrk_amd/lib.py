@@ -30,6 +30,10 @@ CFRK_COUNT_MAX = 0xFFFFFFFE
 CFRK_QUERY_NONE = 0xFFFFFFFF         # read query: the window holds an invalid base or runs past nN
 CFRK_ERR_SMALL_BUF = -9
 CFRK_SPARSE_FAST_WINDOWS = 2048      # per-read sparse: windows per read the LDS path holds (longer reads: slower, exact)
+CFRK_STATS_FAST_WINDOWS = 2048       # read stats: windows per read a lane group holds (longer reads: slower, exact)
+# cfrk_read_stats: one row per read of GlobalCounter.read_stats()
+READ_STATS_DTYPE = np.dtype([("windows", "<u4"), ("present", "<u4"), ("below", "<u4"), ("min", "<u4"),
+                             ("median", "<u4"), ("max", "<u4"), ("sum", "<u8")])
 CFRK_PARAM_MSP_CHUNKS, CFRK_PARAM_L2_SLACK_COMPLETE, CFRK_PARAM_L2_SLACK_TRUNCATED, CFRK_PARAM_MSP2_SUBVALUE_BITS = 0, 1, 2, 3   # cfrk_debug_set_param
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -96,6 +100,8 @@ def load_library():
         "cfrk_global_query_device": ([vp, vp, vp, i64, vp], C.c_int),
         "cfrk_global_query_reads": ([vp, vp, vp, vp, i64, i64, vp], C.c_int),
         "cfrk_global_query_reads_device": ([vp, vp, i64, vp], C.c_int),
+        "cfrk_global_read_stats": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
+        "cfrk_global_read_stats_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
         "cfrk_global_export_device": ([vp, vp, vp, vp, u64, C.c_int, C.POINTER(u64)], C.c_int),
         "cfrk_global_digest": ([vp, C.POINTER(u64)], C.c_int),
         "cfrk_global_last_add_ms": ([vp, C.POINTER(C.c_float)], C.c_int),
@@ -468,6 +474,31 @@ class GlobalCounter:
         self.ctx.check(self._L.cfrk_global_query_reads_device(self.ctx._h, C.c_void_p(d_data) if d_data else None,
                                                               nN, C.c_void_p(d_out) if d_out else None),
                        "cfrk_global_query_reads_device")
+
+    def read_stats(self, data, start, length, threshold=0):
+        """per-read abundance statistics against the job's result -> np.ndarray[nS] of READ_STATS_DTYPE: valid
+        windows, how many of their k-mers are present / counted below `threshold`, and min, lower median, max and sum
+        of their counts; a read without a valid window gives an all-zero row"""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        nS = len(length)
+        if len(start) != nS:
+            raise ValueError("start and length differ in size")
+        if not 0 <= int(threshold) <= 0xFFFFFFFF:
+            raise ValueError("threshold outside 0 .. 2^32 - 1")
+        out = np.zeros(nS, READ_STATS_DTYPE)
+        self.ctx.check(self._L.cfrk_global_read_stats(self.ctx._h, _ptr(data), _ptr(start), _ptr(length), len(data), nS,
+                                                      int(threshold), _ptr(out)), "cfrk_global_read_stats")
+        return out
+
+    def read_stats_device(self, d_data, d_start, d_length, nN, nS, threshold, d_out):
+        """device form of read_stats(): d_out nS rows of 32 bytes; no alignment requirement on d_data; returns with
+        the last kernel enqueued on the context stream"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self.ctx.check(self._L.cfrk_global_read_stats_device(self.ctx._h, vp(d_data), vp(d_start), vp(d_length), nN, nS,
+                                                             int(threshold), vp(d_out)),
+                       "cfrk_global_read_stats_device")
 
     def export_device(self, d_lo, d_hi, d_cnt, cap, parts=1):
         pc = (C.c_uint64 * parts)()

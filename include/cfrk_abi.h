@@ -243,6 +243,35 @@ int cfrk_global_query_reads(cfrk_ctx *ctx, const int8_t *data, const int64_t *st
                             int64_t nN, int64_t nS, uint32_t *counts /* nN entries */);
 int cfrk_global_query_reads_device(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, uint32_t *d_counts);
 
+/* Per-read abundance statistics against the job's result: what cfrk_global_query_reads answers for the windows of a
+ * read, reduced on the device to one 32-byte row per read (digital normalisation by the median, error / contamination
+ * screening by `below` and `present`, per-read coverage by sum / windows).  Same job, same lookup index, same
+ * canonicalisation in a CFRK_CANONICAL job; a saturated key reads CFRK_COUNT_MAX; never CFRK_ERR_COUNT_OVERFLOW.
+ * The windows of read i are the starts p in [start[i], start[i] + length[i] - k] whose k codes are all 0..3; a read
+ * without one gets an all-zero row.  threshold = 0 gives below = 0 everywhere.  1 <= k <= 64, reads of any length:
+ * reads of up to CFRK_STATS_FAST_WINDOWS windows are looked up and reduced by a group of lanes in LDS, longer ones by a
+ * workgroup on a slower, exact path.
+ * start and length are required.  Errors: CFRK_ERR_STATE before begin and on a CFRK_RUNS_ONLY job, CFRK_ERR_TABLE_FULL
+ * and CFRK_ERR_NOMEM as the query calls, CFRK_ERR_ARG for NULL buffers with nS > 0 and negative sizes (nS = 0 is fine).
+ * The job stays usable for digest, histogram, export and queries.
+ * Device form: no alignment requirement on d_data; start / length are not checked: a read whose range does not lie
+ * inside [0, nN) gets a zero row (never an access outside the buffers).  Returns with the last kernel enqueued on the
+ * context stream (the index build of a job's first query synchronises).
+ * Host form: checks start and length like cfrk_global_add (CFRK_ERR_LAYOUT), stages through the pool, synchronous. */
+typedef struct cfrk_read_stats {   /* 32 bytes, no padding */
+  uint32_t windows;   /* windows of the read whose k codes are all valid                       */
+  uint32_t present;   /* of those: count >= 1                                                  */
+  uint32_t below;     /* of those: count < threshold (an absent k-mer counts 0)                */
+  uint32_t min, median, max;   /* over the `windows` counts; median = LOWER median:           */
+                               /* element (windows-1)/2 of the counts sorted ascending         */
+  uint64_t sum;       /* sum of the counts (saturated keys add CFRK_COUNT_MAX)                 */
+} cfrk_read_stats;
+#define CFRK_STATS_FAST_WINDOWS 2048
+int cfrk_global_read_stats_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                  int64_t nN, int64_t nS, uint32_t threshold, cfrk_read_stats *d_out);
+int cfrk_global_read_stats(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
+                           int64_t nN, int64_t nS, uint32_t threshold, cfrk_read_stats *out);
+
 /* Unsorted export into device buffers, grouped into `parts` contiguous segments by
  * owner(key) = (mix(key) >> 32) % parts (key-owner partition for the multi-GPU
  * merge).  part_counts (host, `parts` entries) receives the segment sizes.  Synchronises. */
