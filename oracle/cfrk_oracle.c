@@ -2,7 +2,8 @@
  * cfrk_oracle.c -- CPU restatement of the reference k-mer counting path.
  *
  * TEST INFRASTRUCTURE ONLY (see cfrk_oracle.h).  Parity: pinned by the reference's k=2
- * goldens via golden-derived FASTA pre-images; no oracle/_ref build (reference is CUDA).
+ * goldens via golden-derived FASTA pre-images, and compared bit for bit with the reference's own
+ * kmer_main() built for the CPU (oracle/_ref/, tests/test_reference_cpu.py).
  * Citations are file:line under /root/reference/.
  */
 #include "cfrk_oracle.h"

@@ -9,9 +9,9 @@
  * Parity status: PINNED by the reference's own k=2 goldens
  * (tests/golden/out-seq{1,2}.cfrk, copied data files of
  * /root/reference/test/) through golden-derived FASTA pre-images
- * (tests/golden/derive_fasta.py).  The reference's sources are CUDA (.cu) and
- * cannot be built in this image without stand-ins for the CUDA toolkit, so no
- * oracle/_ref build exists; see DESIGN.md "Oracle".
+ * (tests/golden/derive_fasta.py), and HELD TO THE REFERENCE'S OWN SOURCES,
+ * built for the CPU into oracle/_ref/ (Makefile target `ref`, ref_shim/), by
+ * tests/test_reference_cpu.py; see DESIGN.md "Oracle".
  *
  * Every function cites the reference file:line it restates
  * (paths relative to /root/reference/).
