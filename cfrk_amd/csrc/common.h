@@ -176,8 +176,8 @@ __device__ __forceinline__ uint64_t dev_splitmix64(uint64_t x) {
   return x ^ (x >> 31);
 }
 
-// slot / owner hash of a key
-__device__ __forceinline__ uint64_t dev_mix64(uint64_t x) {
+// slot / owner hash of a key (host as well: cfrk_debug_hash_info evaluates this very function for the tests)
+__host__ __device__ __forceinline__ uint64_t dev_mix64(uint64_t x) {
   x ^= x >> 32; x *= 0xD6E8FEB86659FD93ull;
   x ^= x >> 32; x *= 0xD6E8FEB86659FD93ull;
   x ^= x >> 32;

@@ -282,6 +282,17 @@ int cfrk_query_index(cfrk_ctx *ctx, QIndex *q) {
   return CFRK_OK;
 }
 
+// Read-only: the geometry of the job's table and index and the slot hashes of one key, evaluated on the host by the
+// functions the kernels call (q_slot1 / q_slot2 -> dev_mix64, compiled for both sides).
+extern "C" int cfrk_debug_hash_info(const cfrk_ctx *ctx, uint64_t lo, uint64_t hi, uint64_t out[4]) {
+  if (!out) return CFRK_ERR_ARG;
+  out[0] = (ctx && ctx->g_active) ? (uint64_t)ctx->g_log2cap : 0;
+  out[1] = (ctx && ctx->g_active && ctx->q_valid && ctx->g_k > 12) ? (uint64_t)ctx->q_log2cap : 0;
+  out[2] = q_slot1(lo, 0);
+  out[3] = q_slot2(lo, hi, 0);
+  return CFRK_OK;
+}
+
 int cfrk_query_keys(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t *d_hi, int64_t n, uint32_t *d_out) {
   QIndex q;
   int rc = cfrk_query_index(ctx, &q);

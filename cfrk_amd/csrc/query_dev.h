@@ -20,8 +20,8 @@ namespace {
 
 constexpr int QB = 8;                 // windows per lane whose first-slot loads are in flight together
 
-__device__ __forceinline__ uint64_t q_slot1(uint64_t lo, int shift) { return dev_mix64(lo) >> shift; }
-__device__ __forceinline__ uint64_t q_slot2(uint64_t lo, uint64_t hi, int shift) { return dev_mix64(lo ^ dev_mix64(hi)) >> shift; }
+__host__ __device__ __forceinline__ uint64_t q_slot1(uint64_t lo, int shift) { return dev_mix64(lo) >> shift; }
+__host__ __device__ __forceinline__ uint64_t q_slot2(uint64_t lo, uint64_t hi, int shift) { return dev_mix64(lo ^ dev_mix64(hi)) >> shift; }
 __device__ __forceinline__ uint64_t q_lo(uint4 v) { return ((uint64_t)v.y << 32) | v.x; }
 __device__ __forceinline__ uint64_t q_hi(uint4 v) { return ((uint64_t)v.w << 32) | v.z; }
 

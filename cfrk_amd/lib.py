@@ -117,6 +117,7 @@ def load_library():
         "cfrk_debug_msp_info": ([vp, C.POINTER(u64)], C.c_int),
         "cfrk_debug_set_mem_budget": ([vp, u64], C.c_int),
         "cfrk_debug_device_bytes": ([vp, C.POINTER(u64)], C.c_int),
+        "cfrk_debug_hash_info": ([vp, u64, u64, C.POINTER(u64)], C.c_int),
         "cfrk_debug_set_flags": ([vp, C.c_uint32], C.c_int),
         "cfrk_debug_set_param": ([vp, C.c_int, C.c_double], C.c_int),
         "cfrk_debug_last_add_passes": ([vp, C.POINTER(C.c_int)], C.c_int),
@@ -144,6 +145,17 @@ def device_count():
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def hash_info(lo, hi=0, ctx=None):
+    """cfrk_debug_hash_info -> (log2 table slots, log2 index slots, hash of the one-word key lo, hash of the two-word
+    key (lo, hi)); the hashes are the kernels' own function evaluated on the host, a key's home slot in 2^n slots is the
+    hash's top n bits.  Without a Context (no device needed) both slot counts read 0."""
+    out = (C.c_uint64 * 4)()
+    rc = load_library().cfrk_debug_hash_info(ctx._h if ctx is not None else None, int(lo), int(hi), out)
+    if rc != 0:
+        raise CfrkError(rc, "cfrk_debug_hash_info")
+    return tuple(int(x) for x in out)
 
 
 class Context:
@@ -373,6 +385,10 @@ class GlobalCounter:
         names = ("l1_records", "l1_max_bin", "l1_cap", "l2_records", "l2_max_leaf", "l2_cap",
                  "spilled_records", "spilled_kmers", "list_entries")
         return dict(zip(names, (int(x) for x in out)))
+
+    def hash_geometry(self):
+        """(log2 slots of the HBM table, log2 slots of the query index or 0 while no hash index is valid)"""
+        return hash_info(0, 0, self.ctx)[:2]
 
     def set_mem_budget(self, nbytes):
         self.ctx.check(self._L.cfrk_debug_set_mem_budget(self.ctx._h, int(nbytes)), "cfrk_debug_set_mem_budget")

@@ -375,6 +375,15 @@ int cfrk_debug_set_mem_budget(cfrk_ctx *ctx, uint64_t bytes);
 int cfrk_debug_device_bytes(cfrk_ctx *ctx, uint64_t *out_bytes);
 int cfrk_debug_last_add_passes(cfrk_ctx *ctx, int *out_passes);
 
+/* Read-only introspection of the hashed structures, so that a test can craft keys that collide and notices when the
+ * hash or a sizing rule changes.  out[0] = log2 of the slots of the job's HBM table (0 before cfrk_global_begin);
+ * out[1] = log2 of the slots of the job's query index (0 while no hash index is valid: before the first query, after
+ * every call that changes the result, and for k <= 12, whose index is a dense array); out[2] = the 64-bit hash of the
+ * one-word key lo, out[3] = that of the two-word key (lo, hi) -- a key's home slot in a structure of 2^n slots is the
+ * hash's top n bits.  The hashes are evaluated on the host by the very function the kernels call, need no device and
+ * no context: ctx may be NULL (out[0] = out[1] = 0).  Touches nothing; never synchronises. */
+int cfrk_debug_hash_info(const cfrk_ctx *ctx, uint64_t lo, uint64_t hi, uint64_t out[4]);
+
 /* Test switches for rarely taken device paths (0 = normal operation).  Bit 0: every leaf of the
  * one-word partitioned path (16 <= k <= 32) is treated as if its complete runs had overflowed the
  * record table, i.e. takes the second-chance deduplication over the whole LDS pool. */
