@@ -780,6 +780,64 @@ int cfrk_per_read_sparse(cfrk_ctx *ctx, const int8_t *data, const int64_t *start
   return CFRK_OK;
 }
 
+/* ------------------------------------------------------------------ distinct sketch */
+
+static int sketch_check(cfrk_ctx *ctx, int64_t nN, int k, int flags) {
+  if (!ctx) return CFRK_ERR_ARG;
+  if (k < 1 || k > 64) return cfrk_fail(ctx, CFRK_ERR_ARG, "k=%d outside 1..64", k);
+  if (flags & ~CFRK_CANONICAL) return cfrk_fail(ctx, CFRK_ERR_ARG, "flags 0x%x: the distinct sketch takes CFRK_CANONICAL only", flags);
+  if (nN < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  return CFRK_OK;
+}
+
+int cfrk_distinct_sketch_device(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,
+                                uint64_t *windows_out) {
+  int rc = sketch_check(ctx, nN, k, flags);
+  if (rc) return rc;
+  if (windows_out) *windows_out = 0;
+  if (nN == 0) return CFRK_OK;
+  if (!d_data || !d_regs) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (((uintptr_t)d_data & 15) != 0) return cfrk_fail(ctx, CFRK_ERR_ALIGN, "d_data %p", (const void *)d_data);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint64_t *d_windows;
+  if ((rc = cfrk_sketch_launch(ctx, d_data, nN, k, flags, d_regs, &d_windows))) return rc;
+  if (windows_out) {
+    HIP_TRY(ctx, hipMemcpyAsync(windows_out, d_windows, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return CFRK_OK;
+}
+
+int cfrk_distinct_sketch(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                         int64_t nS, int k, int flags, uint8_t *regs, uint64_t *windows_out) {
+  int rc = sketch_check(ctx, nN, k, flags);
+  if (rc) return rc;
+  if (nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (windows_out) *windows_out = 0;
+  if (nN == 0) return CFRK_OK;
+  if (!data || !regs) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  LayoutCheck lc;      // (the add's check of the struct-read layout, beside the copy)
+  if (start && length) lc.begin(data, start, length, nN, nS);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // (staged through the query calls' slot: BUF_DATA may still be read by an open job's last add)
+  void *d_data;
+  uint8_t *d_regs;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_IN, (size_t)nN + 64, &d_data))) return rc;
+  if ((rc = cfrk_sketch_stage(ctx, &d_regs))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_regs, regs, CFRK_SKETCH_REGS, hipMemcpyHostToDevice, ctx->stream));
+  if (lc.failed(ctx)) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
+    return CFRK_ERR_LAYOUT;
+  }
+  const uint64_t *d_windows;
+  if ((rc = cfrk_sketch_launch(ctx, (const int8_t *)d_data, nN, k, flags, d_regs, &d_windows))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(regs, d_regs, CFRK_SKETCH_REGS, hipMemcpyDeviceToHost, ctx->stream));
+  if (windows_out) HIP_TRY(ctx, hipMemcpyAsync(windows_out, d_windows, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CFRK_OK;
+}
+
 /* ------------------------------------------------------------------ synthetic reads */
 
 int cfrk_synth_reads_device(cfrk_ctx *ctx, int64_t r0, int64_t R, int L, int64_t Glen,

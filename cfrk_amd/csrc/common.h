@@ -29,6 +29,7 @@ enum {  // pool slots
   BUF_SPARSE_KEYS, BUF_SPARSE_CNT,            // per-read sparse (sparse.hip): the rows at their reads' offsets, nN entries
   BUF_SPARSE_AUX,                             // block sums of the row-pointer scan
   BUF_SPARSE_IN, BUF_SPARSE_OUT,              // staging of the host call (data, start, length, row_ptr in; keys, counts out)
+  BUF_SKETCH,                                 // distinct sketch (sketch.hip): the workgroups' merged registers as words, the window count, the host form's registers
   BUF_NSLOTS
 };
 
@@ -133,6 +134,11 @@ int cfrk_query_reads(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, uint32_t *
 // read_stats.hip: one cfrk_read_stats row per read from the same index; the kernels are left enqueued.  nS >= 1.
 int cfrk_read_stats_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
                            int64_t nN, int64_t nS, uint32_t threshold, cfrk_read_stats *d_out);
+// sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
+// enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
+int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,
+                       const uint64_t **d_windows);
+int cfrk_sketch_stage(cfrk_ctx *ctx, uint8_t **d_stage);   // device room for the host form's registers
 
 // ---- device helpers -----------------------------------------------------------------------
 #ifdef __HIPCC__

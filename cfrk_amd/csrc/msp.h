@@ -27,9 +27,12 @@ struct TableView;
 #define CFRK_ABL_RX2_NO_OUT    CFRK_ABL_BIT(0x40000u)   // radix second-level kernel: the sorted tile is not written out
 #define CFRK_ABL_RX1_NO_OUT    CFRK_ABL_BIT(0x80000u)   // radix first-level kernel: the sorted tile is not written out
 #define CFRK_ABL_RX1_LINEAR    CFRK_ABL_BIT(0x100000u)  // radix first-level kernel: the sorted tile goes out back to back (no scatter into regions)
+// (these two count RIGHT: other LDS layouts of the distinct sketch, sketch.hip, for timing)
+#define CFRK_ABL_SK_WORDS      CFRK_ABL_BIT(0x200000u)  // sketch: one LDS word per register (64 KiB), read first, atomic max when larger
+#define CFRK_ABL_SK_ALWAYS     CFRK_ABL_BIT(0x400000u)  // sketch: one LDS word per register, atomic max for every window
 // every bit cfrk_debug_set_flags accepts: the documented test switches of include/cfrk_abi.h, plus the ablations of an ablation build
 #ifdef CFRK_ABLATIONS
-#define CFRK_DEBUG_KNOWN_BITS (0xFFu | 0x7F00u | 0x1F0000u)
+#define CFRK_DEBUG_KNOWN_BITS (0xFFu | 0x7F00u | 0x7F0000u)
 #else
 #define CFRK_DEBUG_KNOWN_BITS 0xFFu
 #endif

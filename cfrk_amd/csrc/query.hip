@@ -111,15 +111,6 @@ __device__ __forceinline__ void q_flush(const uint32_t *st, uint32_t *__restrict
   }
 }
 
-// window i (bases i .. i+k-1 of the 64-base string hi:lo) as a key, canonical when asked
-template <bool CANON>
-__device__ __forceinline__ uint64_t q_window(uint64_t hi, uint64_t lo, int i, int k) {
-  const uint64_t x = i ? ((hi << (2 * i)) | (lo >> (64 - 2 * i))) : hi;
-  uint64_t key = x >> (64 - 2 * k);
-  if (CANON) { const uint64_t rc = dev_revcomp64(key, k); key = rc < key ? rc : key; }
-  return key;
-}
-
 // k <= 32 (MODE 0 / 1).  The block's four waves take tiles t0 + wave: the loop's trip count is the block's, so the
 // barriers around the LDS staging are reached by every wave.
 template <int MODE, bool CANON>

@@ -1,6 +1,6 @@
 // query_dev.h -- the lookup index of a finished global result as the kernels see it: the index descriptor, the slot
-// hashes, the probe loops and the canonical form of a two-word key.  Shared by query.hip (which also builds the index)
-// and read_stats.hip; the index layout is described at the top of query.hip.
+// hashes, the probe loops and the canonical form of a two-word key.  Shared by query.hip (which also builds the index),
+// read_stats.hip and (the window extraction and the key hashes) sketch.hip; the index layout is described at the top of query.hip.
 #pragma once
 
 #include "common.h"
@@ -44,6 +44,15 @@ __device__ __forceinline__ uint32_t q_find2(const uint4 *__restrict__ s, uint64_
     h = (h + 1) & mask;
   }
   return 0;
+}
+
+// window i (bases i .. i+k-1 of the 64-base string hi:lo) as a key, canonical when asked
+template <bool CANON>
+__device__ __forceinline__ uint64_t q_window(uint64_t hi, uint64_t lo, int i, int k) {
+  const uint64_t x = i ? ((hi << (2 * i)) | (lo >> (64 - 2 * i))) : hi;
+  uint64_t key = x >> (64 - 2 * k);
+  if (CANON) { const uint64_t rc = dev_revcomp64(key, k); key = rc < key ? rc : key; }
+  return key;
 }
 
 // canonical form of a two-word key (2k bits, first base most significant): min with its 128-bit reverse complement

@@ -56,6 +56,15 @@
 //                    untouched
 //   --query-db DB.bin  (with --query, no positional arguments) query a saved --binary count file without recounting; k and
 //                    the canonical bit come from its header
+//   --estimate       (global) sketch the batch before it is counted (cfrk_distinct_sketch: one streaming pass, HyperLogLog
+//                    with 2^14 registers, standard error 0.81 %) and print one line on stderr,
+//                    `cfrk-estimate distinct=<n> windows=<n> hint=<n>`: the estimated distinct k-mers, the exact number of
+//                    valid windows, and the capacity hint cfrk_sketch_hint derives (estimate + 3.25 %, at least 2^20)
+//   --estimate-only  (global) print that line and stop: nothing is counted, the output path is left untouched
+//   --auto-hint      (global) the first cfrk_global_begin announces that hint instead of nN / 16 keys, so that input with
+//                    few repeats (low coverage, metagenomes) is counted once instead of up to three times; the retry with
+//                    eight times the room stays behind it.  With --gpus N every device sketches its shard and the
+//                    registers are merged on the host before the owners begin
 //   --batch N        the Swift/T workflow's loop (swift/cfrk.swf:15-20) in one process: for i < N
 //                    count <dataset_prefix>_<i>.fasta into <out_prefix>_<i>.cfrk
 // Chunk pipeline: every device runs two contexts (two HIP streams), each on a host thread of its
@@ -94,6 +103,7 @@ struct Options {
   bool query_only = false;
   const char *query_stats = nullptr;   // --query-stats SFILE
   uint32_t stats_below = 0;            // --stats-below T
+  bool estimate = false, estimate_only = false, auto_hint = false;   // --estimate, --estimate-only, --auto-hint
 };
 
 // --timing: wall-clock seconds by phase (one file; with --batch the last file's)
@@ -105,6 +115,9 @@ struct Timing {
   float count_kernels_ms = 0;
   int64_t fasta_bytes = 0, nN = 0, nS = 0;
   uint64_t entries = 0, out_bytes = 0;
+  int attempts = 0;                    // begin / add / finish passes of the global job (above 1: the hint was too small)
+  double estimate = 0, distinct_estimate = 0;   // the sketch before the count: seconds, estimated distinct k-mers
+  uint64_t hint = 0;                   // capacity hint of the LAST attempt
 } g_timing;
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -342,28 +355,74 @@ void write_global(const Options &o, const uint64_t *lo, const uint64_t *hi, cons
   g_timing.format = t1 - t0; g_timing.write = now_s() - t1; g_timing.entries = n; g_timing.out_bytes = buf.size();
 }
 
+// --estimate / --estimate-only / --auto-hint: the batch's distinct sketch.  Context i sketches shard i of the reads (the
+// shards of run_global_multi); the registers are merged on the host.
+struct Estimate {
+  bool have = false;
+  double distinct = 0;
+  uint64_t windows = 0, hint = 0;
+};
+
+// 0, or the exit status (the error reported)
+int sketch_batch(const Options &o, const cfrk_batch &batch, const std::vector<cfrk_ctx *> &ctxs, Estimate &e) {
+  const double t0 = now_s();
+  const int N = (int)ctxs.size();
+  std::vector<std::vector<uint8_t>> regs((size_t)N, std::vector<uint8_t>(CFRK_SKETCH_REGS, 0));
+  std::vector<uint64_t> windows((size_t)N, 0);
+  std::vector<int> status((size_t)N, 0);
+  auto shard = [&](int sh) {
+    const int64_t r0 = batch.nS * sh / N, r1 = batch.nS * (sh + 1) / N;
+    const int64_t b0 = (r0 < batch.nS) ? batch.start[r0] : batch.nN, b1 = (r1 < batch.nS) ? batch.start[r1] : batch.nN;
+    if (b1 <= b0) return;
+    const int rc = cfrk_distinct_sketch(ctxs[(size_t)sh], batch.data + b0, nullptr, nullptr, b1 - b0, 0, o.k,
+                                        o.canonical ? CFRK_CANONICAL : 0, regs[(size_t)sh].data(), &windows[(size_t)sh]);
+    if (rc) status[(size_t)sh] = die(ctxs[(size_t)sh], rc, "cfrk_distinct_sketch");
+  };
+  if (N == 1) shard(0);
+  else {
+    std::vector<std::thread> th;
+    for (int sh = 0; sh < N; ++sh) th.emplace_back(shard, sh);
+    for (auto &t : th) t.join();
+  }
+  for (int r : status) if (r) return r;
+  for (int sh = 1; sh < N; ++sh) { cfrk_sketch_merge(regs[0].data(), regs[(size_t)sh].data()); windows[0] += windows[(size_t)sh]; }
+  cfrk_sketch_estimate(regs[0].data(), &e.distinct);
+  cfrk_sketch_hint(regs[0].data(), &e.hint);
+  e.windows = windows[0];
+  e.have = true;
+  g_timing.estimate = now_s() - t0; g_timing.distinct_estimate = e.distinct;
+  fprintf(stderr, "cfrk-estimate distinct=%.0f windows=%llu hint=%llu\n", e.distinct, (unsigned long long)e.windows, (unsigned long long)e.hint);
+  return 0;
+}
+
 // early_free: the batch is no longer needed once it has been counted -- returning 1.6 GB of pages to the kernel takes
 // ~0.17 s, which then runs beside the export, the formatting and the write instead of behind them
-int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, std::thread *early_free = nullptr, cfrk_batch *owned = nullptr) {
+int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, const Estimate &est, std::thread *early_free = nullptr, cfrk_batch *owned = nullptr) {
   int rc;
   cfrk_ctx *ctx = w.ctx;
   // The capacity hint sizes the result list and the spill table (12 B per slot at load <= 0.5).  Distinct k-mers cannot
   // exceed the window starts (nN), but a table for nN keys is 25 - 50 GB for a 1.5 GB batch and allocating it took
   // 5 of the 6 seconds of a k = 31 run (round 5, profiles/r05/end_to_end.txt): the first attempt announces nN / 16 keys
   // (sequencing depth is rarely below that) and an overflowing result (CFRK_ERR_TABLE_FULL) is counted again with
-  // eight times the room, up to nN (capped at 2^31 keys).
+  // eight times the room, up to nN (capped at 2^31 keys).  --auto-hint: the first attempt announces the sketch's hint instead.
   const uint64_t hint_max = std::min<uint64_t>(std::max<uint64_t>((uint64_t)(batch.nN > 0 ? batch.nN : 1), 1ull << 20), 1ull << 31);
   uint64_t hint = std::min<uint64_t>(std::max<uint64_t>(hint_max / 16, 1ull << 20), hint_max);
+  if (o.auto_hint && est.have) hint = std::min<uint64_t>(est.hint, hint_max);
   uint64_t n = 0;
-  double t0 = 0, t1 = 0;
+  // (the phase times add up over the attempts: a batch counted three times shows three times the seconds)
+  double add_s = 0, finish_s = 0;
+  g_timing.begin = 0;
   for (;;) {
     const double tb = now_s();
+    ++g_timing.attempts;
+    g_timing.hint = hint;
     if ((rc = cfrk_global_begin(ctx, o.k, o.canonical ? CFRK_CANONICAL : 0, hint))) return die(ctx, rc, "cfrk_global_begin");
-    t0 = now_s();
-    g_timing.begin = t0 - tb;
+    const double t0 = now_s();
+    g_timing.begin += t0 - tb;
     if ((rc = cfrk_global_add(ctx, batch.data, batch.start, batch.length, batch.nN, batch.nS))) return die(ctx, rc, "cfrk_global_add");
-    t1 = now_s();
+    const double t1 = now_s();
     rc = cfrk_global_finish(ctx, &n);
+    add_s += t1 - t0; finish_s += now_s() - t1;
     if (rc == CFRK_ERR_TABLE_FULL && hint < hint_max) { hint = std::min<uint64_t>(hint * 8, hint_max); continue; }
     break;
   }
@@ -392,7 +451,7 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
   }
   if (early_free && owned) *early_free = std::thread([owned] { cfrk_host_free_batch(owned); });
   cfrk_global_last_add_ms(ctx, &g_timing.count_kernels_ms);
-  g_timing.add_call = t1 - t0; g_timing.finish_wait = t2 - t1;
+  g_timing.add_call = add_s; g_timing.finish_wait = finish_s;
   if (o.histo_only || o.query_only) return 0;
   const double t3 = now_s();
   std::vector<uint64_t> keys(n), hi(n);
@@ -408,12 +467,15 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
 // device s then owns the leaves s, s + N, ...: it receives its segment of every shard's packed runs
 // and counts them on its second context.  The owners' key sets are disjoint; their sorted lists are
 // merged into one ascending output.
-int run_global_multi(const Options &o, const cfrk_batch &batch, std::vector<std::vector<Worker>> &per_dev, FILE *out) {
+int run_global_multi(const Options &o, const cfrk_batch &batch, std::vector<std::vector<Worker>> &per_dev, FILE *out, const Estimate &est) {
   const int N = (int)per_dev.size();
   const int flags = o.canonical ? CFRK_CANONICAL : 0;
   // (as in run_global: nN / 16 keys announced first; an owner whose result overflows makes the job count on one device,
   //  where the hint grows)
   uint64_t hint = std::min<uint64_t>(std::max<uint64_t>((uint64_t)(batch.nN > 0 ? batch.nN : 1) / 16, 1ull << 20), 1ull << 31);
+  // --auto-hint: the merged sketch's hint; the owners' shares of the leaves are close to even, not even: an eighth on top
+  if (o.auto_hint && est.have) hint = std::min<uint64_t>(est.hint + est.hint / 8, 1ull << 31);
+  g_timing.attempts = 1; g_timing.hint = hint;
   // shard s: packed rows stay ON ITS DEVICE (16 bytes per row), rows[s][o] = rows of owner o's segment
   std::vector<void *> d_packed((size_t)N, nullptr);
   std::vector<std::vector<uint64_t>> rows((size_t)N, std::vector<uint64_t>((size_t)N, 0));
@@ -463,7 +525,7 @@ int run_global_multi(const Options &o, const cfrk_batch &batch, std::vector<std:
       if (r) {
         free_packed();
         fprintf(stderr, "cfrk: a shard could not export its runs; counting on one device\n");
-        return run_global(o, batch, per_dev[0][0], out);
+        return run_global(o, batch, per_dev[0][0], out, est);
       }
   }
   std::vector<std::vector<uint64_t>> keys((size_t)N), his((size_t)N);
@@ -525,7 +587,7 @@ int run_global_multi(const Options &o, const cfrk_batch &batch, std::vector<std:
     for (char r : refused)
       if (r) {
         fprintf(stderr, "cfrk: more distinct k-mers than announced; counting on one device\n");
-        return run_global(o, batch, per_dev[0][0], out);
+        return run_global(o, batch, per_dev[0][0], out, est);
       }
   }
   g_timing.export_ = *std::max_element(export_s.begin(), export_s.end());
@@ -606,14 +668,25 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
   { FILE *f = fopen(in, "rb"); if (f) { fseek(f, 0, SEEK_END); g_timing.fasta_bytes = (int64_t)ftell(f); fclose(f); } }
   std::thread freer;                                  // (global mode: frees the batch beside the export)
   const double to0 = now_s();
-  const bool no_out = o.histo_only || o.query_only;
+  const bool no_out = o.histo_only || o.query_only || o.estimate_only;
   FILE *out = no_out ? nullptr : fopen(outp, "wb");   // PrintFreq opens with "w" even when empty
   const double t_open = now_s() - to0;
   if (!out && !no_out) { fprintf(stderr, "cfrk: cannot write %s\n", outp); cfrk_host_free_batch(&batch); return 1; }
-  if (o.global && per_dev && per_dev->size() > 1 && o.k >= 16 && o.k <= 64 && batch.nS >= (int64_t)per_dev->size()) rc = run_global_multi(o, batch, *per_dev, out);
-  else if (o.global) rc = run_global(o, batch, workers[0], out, &freer, &batch);
-  else { const double p0 = now_s(); rc = run_per_read(o, batch, workers, out); g_timing.per_read = now_s() - p0; }
-  if (!o.global) { fflush(out); g_timing.out_bytes = (uint64_t)ftell(out); }
+  const bool multi = o.global && per_dev && per_dev->size() > 1 && o.k >= 16 && o.k <= 64 && batch.nS >= (int64_t)per_dev->size();
+  Estimate est;
+  rc = 0;
+  if (o.estimate || o.estimate_only || o.auto_hint) {
+    std::vector<cfrk_ctx *> ctxs;
+    if (multi) for (auto &d : *per_dev) ctxs.push_back(d[0].ctx);
+    else ctxs.push_back(workers[0].ctx);
+    rc = sketch_batch(o, batch, ctxs, est);
+  }
+  if (!rc && !o.estimate_only) {
+    if (multi) rc = run_global_multi(o, batch, *per_dev, out, est);
+    else if (o.global) rc = run_global(o, batch, workers[0], out, est, &freer, &batch);
+    else { const double p0 = now_s(); rc = run_per_read(o, batch, workers, out); g_timing.per_read = now_s() - p0; }
+  }
+  if (!o.global && out) { fflush(out); g_timing.out_bytes = (uint64_t)ftell(out); }
   const double tf0 = now_s();
   if (out) fclose(out);
   const double tf1 = now_s();
@@ -628,11 +701,13 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
     fprintf(stderr, "cfrk-timing {\"fasta_bytes\": %lld, \"reads\": %lld, \"code_bytes\": %lld, \"parse_s\": %.4f, \"add_call_s\": %.4f, "
             "\"finish_wait_s\": %.4f, \"count_kernels_ms\": %.3f, \"export_s\": %.4f, \"format_s\": %.4f, \"write_s\": %.4f, "
             "\"per_read_pipeline_s\": %.4f, \"entries\": %llu, \"out_bytes\": %llu, \"contexts_s\": %.4f, \"wait_for_parser_s\": %.4f, "
-            "\"begin_s\": %.4f, \"open_out_s\": %.4f, \"close_out_s\": %.4f, \"free_batch_s\": %.4f, \"histo_s\": %.4f, %s\"wall_s\": %.4f}\n",
+            "\"begin_s\": %.4f, \"open_out_s\": %.4f, \"close_out_s\": %.4f, \"free_batch_s\": %.4f, \"histo_s\": %.4f, %s\"attempts\": %d, "
+            "\"estimate_s\": %.4f, \"distinct_estimate\": %.0f, \"hint\": %llu, \"wall_s\": %.4f}\n",
             (long long)g_timing.fasta_bytes, (long long)g_timing.nS, (long long)g_timing.nN, g_timing.parse, g_timing.add_call,
             g_timing.finish_wait, (double)g_timing.count_kernels_ms, g_timing.export_, g_timing.format, g_timing.write,
             g_timing.per_read, (unsigned long long)g_timing.entries, (unsigned long long)g_timing.out_bytes, g_timing.contexts,
-            g_timing.wait_parse, g_timing.begin, g_timing.open, g_timing.close, g_timing.free_batch, g_timing.histo, query_field, g_timing.total);
+            g_timing.wait_parse, g_timing.begin, g_timing.open, g_timing.close, g_timing.free_batch, g_timing.histo, query_field, g_timing.attempts,
+            g_timing.estimate, g_timing.distinct_estimate, (unsigned long long)g_timing.hint, g_timing.total);
   return rc;
 }
 
@@ -708,6 +783,9 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) o.gpus = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--batch") && i + 1 < argc) batch_n = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--histo-only")) o.histo_only = true;
+    else if (!strcmp(argv[i], "--estimate")) o.estimate = true;
+    else if (!strcmp(argv[i], "--estimate-only")) o.estimate_only = true;
+    else if (!strcmp(argv[i], "--auto-hint")) o.auto_hint = true;
     else if (!strcmp(argv[i], "--query-only")) o.query_only = true;
     else if (!strcmp(argv[i], "--query") || !strcmp(argv[i], "--query-out") || !strcmp(argv[i], "--query-db")) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
@@ -745,6 +823,11 @@ int main(int argc, char **argv) {
     fprintf(stderr, "cfrk: --histo, --histo-only, --min-count and --max-count need --global\n");
     return 1;
   }
+  if ((o.estimate || o.estimate_only || o.auto_hint) && !o.global) {
+    fprintf(stderr, "cfrk: --estimate, --estimate-only and --auto-hint need --global\n");
+    return 1;
+  }
+  if (o.estimate_only && batch_n >= 0) { fprintf(stderr, "cfrk: --estimate-only prints one estimate: not with --batch\n"); return 1; }
   if (o.histo_only && !o.histo) { fprintf(stderr, "cfrk: --histo-only needs --histo FILE\n"); return 1; }
   if (o.min_count > o.max_count) {
     fprintf(stderr, "cfrk: --min-count %u is above --max-count %u\n", o.min_count, o.max_count);

@@ -34,6 +34,8 @@ CFRK_STATS_FAST_WINDOWS = 2048       # read stats: windows per read a lane group
 # cfrk_read_stats: one row per read of GlobalCounter.read_stats()
 READ_STATS_DTYPE = np.dtype([("windows", "<u4"), ("present", "<u4"), ("below", "<u4"), ("min", "<u4"),
                              ("median", "<u4"), ("max", "<u4"), ("sum", "<u8")])
+CFRK_SKETCH_LOG2M = 14               # distinct sketch: log2 of its registers
+CFRK_SKETCH_REGS = 16384             # one uint8 register per bucket
 CFRK_PARAM_MSP_CHUNKS, CFRK_PARAM_L2_SLACK_COMPLETE, CFRK_PARAM_L2_SLACK_TRUNCATED, CFRK_PARAM_MSP2_SUBVALUE_BITS = 0, 1, 2, 3   # cfrk_debug_set_param
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -121,6 +123,11 @@ def load_library():
         "cfrk_debug_set_flags": ([vp, C.c_uint32], C.c_int),
         "cfrk_debug_set_param": ([vp, C.c_int, C.c_double], C.c_int),
         "cfrk_debug_last_add_passes": ([vp, C.POINTER(C.c_int)], C.c_int),
+        "cfrk_distinct_sketch_device": ([vp, vp, i64, i32, i32, vp, C.POINTER(u64)], C.c_int),
+        "cfrk_distinct_sketch": ([vp, vp, vp, vp, i64, i64, i32, i32, vp, C.POINTER(u64)], C.c_int),
+        "cfrk_sketch_estimate": ([vp, C.POINTER(C.c_double)], C.c_int),
+        "cfrk_sketch_merge": ([vp, vp], C.c_int),
+        "cfrk_sketch_hint": ([vp, C.POINTER(u64)], C.c_int),
         "cfrk_synth_reads_device": ([vp, i64, i64, i32, i64, u64, u64, u64, i32, vp, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
@@ -156,6 +163,42 @@ def hash_info(lo, hi=0, ctx=None):
     if rc != 0:
         raise CfrkError(rc, "cfrk_debug_hash_info")
     return tuple(int(x) for x in out)
+
+
+def _sketch_regs(regs):
+    regs = np.ascontiguousarray(regs, np.uint8)
+    if regs.shape != (CFRK_SKETCH_REGS,):
+        raise ValueError(f"a sketch is {CFRK_SKETCH_REGS} uint8 registers")
+    return regs
+
+
+def _sketch_call(name, rc):
+    if rc != 0:
+        raise CfrkError(rc, name, load_library().cfrk_strerror(rc).decode())
+
+
+def sketch_estimate(regs):
+    """distinct k-mers a sketch (Context.distinct_sketch) stands for: HyperLogLog with 2^14 registers, standard error
+    0.81 %; all-zero registers give 0.0.  A host function: no device needed."""
+    out = C.c_double()
+    _sketch_call("cfrk_sketch_estimate", load_library().cfrk_sketch_estimate(_ptr(_sketch_regs(regs)), C.byref(out)))
+    return out.value
+
+
+def sketch_merge(dst, src):
+    """dst = element-wise maximum of dst and src, in place: the sketch of the union of the two read sets -> dst"""
+    if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.flags.writeable):
+        raise ValueError("dst must be a writable contiguous uint8 array")
+    _sketch_call("cfrk_sketch_merge", load_library().cfrk_sketch_merge(_ptr(_sketch_regs(dst)), _ptr(_sketch_regs(src))))
+    return dst
+
+
+def sketch_hint(regs):
+    """a capacity_hint for GlobalCounter from a sketch: the estimate plus four standard errors (3.25 %), clamped to
+    [2^20, 2^31]"""
+    out = C.c_uint64()
+    _sketch_call("cfrk_sketch_hint", load_library().cfrk_sketch_hint(_ptr(_sketch_regs(regs)), C.byref(out)))
+    return out.value
 
 
 class Context:
@@ -264,6 +307,33 @@ class Context:
             e.nnz = nnz.value
             raise
         return nnz.value
+
+    # -- distinct k-mer estimate (HyperLogLog sketch, 1 <= k <= 64) ---------------------------
+    def distinct_sketch(self, data, k, flags=0, start=None, length=None, regs=None):
+        """-> (regs uint8[CFRK_SKETCH_REGS], valid windows of this call).  regs: a sketch to accumulate into (merged by
+        maximum, in place when it is a contiguous uint8 array); None starts a fresh one.  sketch_estimate(regs) is the
+        number of distinct k-mers, sketch_hint(regs) a capacity_hint for GlobalCounter."""
+        data = np.ascontiguousarray(data, np.int8)
+        if start is not None:
+            start = np.ascontiguousarray(start, np.int64)
+            length = np.ascontiguousarray(length, np.int32)
+        nS = 0 if length is None else len(length)
+        regs = np.zeros(CFRK_SKETCH_REGS, np.uint8) if regs is None else _sketch_regs(regs)
+        windows = C.c_uint64()
+        self.check(self._L.cfrk_distinct_sketch(self._h, _ptr(data), _ptr(start), _ptr(length), len(data), nS, k, flags,
+                                                _ptr(regs), C.byref(windows)), "cfrk_distinct_sketch")
+        return regs, windows.value
+
+    def distinct_sketch_device(self, d_data, nN, k, flags, d_regs, want_windows=True):
+        """device form: d_data 16-byte aligned, d_regs CFRK_SKETCH_REGS bytes on the device, merged by maximum (zero
+        them for a fresh sketch) -> the call's valid windows (synchronises), or None with want_windows=False (returns
+        with the kernels enqueued on the context stream)"""
+        windows = C.c_uint64()
+        self.check(self._L.cfrk_distinct_sketch_device(self._h, C.c_void_p(d_data) if d_data else None, nN, k, flags,
+                                                       C.c_void_p(d_regs) if d_regs else None,
+                                                       C.byref(windows) if want_windows else None),
+                   "cfrk_distinct_sketch_device")
+        return windows.value if want_windows else None
 
     def synth_reads_device(self, r0, R, L, Glen, d_data, d_start=None, d_length=None,
                            seedG=1, seedR=2, seedS=3, uniform=False):

@@ -238,6 +238,21 @@ def merge_digests(local, device):
     return (d, s, w, x)
 
 
+def merge_sketch(regs, wire_device=None):
+    """The distinct sketch (Context.distinct_sketch) of ALL ranks' reads from every rank's own: the registers are
+    maxima, so one all_reduce(MAX) merges them.  regs: uint8 registers as a numpy array or a torch tensor (CPU over
+    gloo, GPU over RCCL; wire_device moves them for the collective) -> the merged registers, same kind as given.
+    cfrk_amd.sketch_estimate / sketch_hint of the result size the job of the whole process group."""
+    is_np = not torch.is_tensor(regs)
+    t = torch.from_numpy(regs.copy()) if is_np else regs.clone()
+    home = t.device
+    if wire_device is not None:
+        t = t.to(torch.device(wire_device))
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    t = t.to(home)
+    return t.numpy() if is_np else t
+
+
 def _to_i64(u):
     u &= 0xFFFFFFFFFFFFFFFF
     return u - (1 << 64) if u >= (1 << 63) else u

@@ -272,6 +272,47 @@ int cfrk_global_read_stats_device(cfrk_ctx *ctx, const int8_t *d_data, const int
 int cfrk_global_read_stats(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
                            int64_t nN, int64_t nS, uint32_t threshold, cfrk_read_stats *out);
 
+/* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
+
+/* How many DISTINCT k-mers will a job hold?  One streaming pass over the reads answers it to about 1 % before anything
+ * is counted, so that cfrk_global_begin can be given a capacity_hint that fits (cfrk_sketch_hint) instead of a guess
+ * that ends in CFRK_ERR_TABLE_FULL and a second pass.
+ * The sketch is CFRK_SKETCH_REGS registers of one byte, in a fixed format:
+ *   key      the window's k-mer as in global mode (canonicalised first under CFRK_CANONICAL); the k = 32 all-T key is
+ *            an ordinary key here
+ *   hash     h = mix(lo) for k <= 32, h = mix(lo ^ mix(hi)) for k > 32: cfrk_debug_hash_info's out[2] / out[3]
+ *   bucket   h >> (64 - CFRK_SKETCH_LOG2M)
+ *   rank     w = h << CFRK_SKETCH_LOG2M; rank = clz64(w) + 1 when w != 0, otherwise 64 - CFRK_SKETCH_LOG2M + 1 (51)
+ *   register the largest rank seen in its bucket (0: none)
+ * A window counts by the guarded ComputeFreq rule of global mode: all k codes 0..3, inside [0, nN); terminators are
+ * invalid codes, so no window crosses a read.  Two sketches of two read sets merge into the sketch of their union by
+ * the element-wise maximum (cfrk_sketch_merge; across processes an all-reduce with MAX).
+ * Estimate (cfrk_sketch_estimate): m = CFRK_SKETCH_REGS, alpha = 0.7213 / (1 + 1.079 / m),
+ * E = alpha * m^2 / sum(2^-register); when E <= 2.5 m and V > 0 registers are zero, E = m * ln(m / V) (linear
+ * counting).  No large-range correction: the hash has 64 bits.  All-zero registers give 0.  The standard error is
+ * 1.04 / sqrt(m) = 0.81 %.
+ * Hint (cfrk_sketch_hint): ceil(E * (1 + 4 * 1.04 / sqrt(m))) -- four standard errors, 3.25 % -- clamped to
+ * [2^20, 2^31]: a capacity_hint that the job's distinct k-mers exceed with negligible probability.
+ *
+ * cfrk_distinct_sketch_device: d_data 16-byte aligned (CFRK_ERR_ALIGN), flags 0 or CFRK_CANONICAL (anything else, k
+ * outside 1..64, negative nN, a NULL d_data or d_regs with nN > 0: CFRK_ERR_ARG).  d_regs = CFRK_SKETCH_REGS bytes on
+ * the device, MERGED BY MAXIMUM, not overwritten: the caller zeroes it for a fresh sketch, several calls accumulate
+ * into one.  windows_out (may be NULL) receives the exact number of valid windows of THIS call; asking for it
+ * synchronises, without it the call returns with the kernels enqueued on the context stream.  nN = 0 is fine.
+ * cfrk_distinct_sketch: host buffers, regs on the host (merged by maximum as well); start / length may be NULL and are
+ * checked like cfrk_global_add (CFRK_ERR_LAYOUT); stages through the pool; synchronous.
+ * Neither call touches a global job that is open on the same context.
+ * cfrk_sketch_estimate / _merge / _hint are pure host functions: no context, no device (NULL: CFRK_ERR_ARG). */
+#define CFRK_SKETCH_LOG2M 14
+#define CFRK_SKETCH_REGS 16384
+int cfrk_distinct_sketch_device(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,
+                                uint64_t *windows_out);
+int cfrk_distinct_sketch(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                         int64_t nS, int k, int flags, uint8_t *regs, uint64_t *windows_out);
+int cfrk_sketch_estimate(const uint8_t *regs, double *distinct);
+int cfrk_sketch_merge(uint8_t *dst, const uint8_t *src);
+int cfrk_sketch_hint(const uint8_t *regs, uint64_t *hint);
+
 /* Unsorted export into device buffers, grouped into `parts` contiguous segments by
  * owner(key) = (mix(key) >> 32) % parts (key-owner partition for the multi-GPU
  * merge).  part_counts (host, `parts` entries) receives the segment sizes.  Synchronises. */

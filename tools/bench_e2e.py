@@ -15,6 +15,12 @@ Writes a configs[1]-sized FASTA (10 M x 150 bp from the SURVEY 8d generator, 1.6
   cfrk first-1M-reads.fasta out4all.cfrk 4 T 8192 --all-chunks --timing   (every chunk written)
 and prints one JSON object: per run the phases `cfrk --timing` reports, as seconds and GB/s.
 `measure(reads, ...)` is what `bench.py --full` calls for the `end_to_end` object of its line.
+
+  python tools/bench_e2e.py --auto-hint-ab [--reads R] [--k 31] [--uniform]
+
+runs `cfrk ... --global --canonical --histo FILE --histo-only` (parse + count + spectrum: no export, whose size would
+drown the difference) with and without --auto-hint, alternating, three times each, and prints the medians: on uniform
+random reads (all-distinct: nN / 16 is too small a hint) what the sketch saves, on reads of a genome what it costs.
 """
 import json
 import os
@@ -27,7 +33,7 @@ sys.path.insert(0, ROOT)
 CFRK = os.path.join(ROOT, "cfrk_amd", "cfrk")
 
 
-def write_fasta(path, R, L, glen, ctx=None, r0=0):
+def write_fasta(path, R, L, glen, ctx=None, r0=0, uniform=False):
     """reads [r0, r0 + R) of the generator as `>rNNNNNNNNN\\n<bases>\\n` records (fixed width: numpy only)"""
     import numpy as np
     import cfrk_amd
@@ -36,7 +42,7 @@ def write_fasta(path, R, L, glen, ctx=None, r0=0):
         ctx = cfrk_amd.Context(0)
     nN = R * (L + 1)
     d = ctx.alloc(nN + 64)
-    ctx.synth_reads_device(r0, R, L, glen, d)
+    ctx.synth_reads_device(r0, R, L, glen, d, uniform=uniform)
     codes = np.empty(nN, np.int8)
     ctx.d2h(codes, d)
     ctx.free(d)
@@ -122,6 +128,43 @@ def measure(reads=10_000_000, L=150, k=15, glen=0, tmpdir=None, threads=0, ctx=N
     return res
 
 
+def measure_auto_hint(reads, L, k, tmpdir=None, threads=0, uniform=False, reps=3):
+    import statistics
+    tmpdir = tmpdir or os.environ.get("TMPDIR") or "/tmp"
+    threads = threads or min(64, os.cpu_count() or 1)
+    fa = os.path.join(tmpdir, f"cfrk_e2e_{os.getpid()}.fasta")
+    outp = os.path.join(tmpdir, f"cfrk_e2e_{os.getpid()}.cfrk")
+    histo = os.path.join(tmpdir, f"cfrk_e2e_{os.getpid()}.histo")
+    res = {"tool": "bench_e2e --auto-hint-ab", "reads": reads, "read_len": L, "k": k, "uniform": uniform,
+           "genome": None if uniform else reads, "reps": reps}
+    try:
+        res["fasta_bytes"] = write_fasta(fa, reads, L, reads, uniform=uniform)
+        base = [fa, outp, str(k), str(threads), "--global", "--canonical", "--histo", histo, "--histo-only"]
+        runs = {"plain": [], "auto_hint": []}
+        for _ in range(reps):
+            runs["plain"].append(run_cfrk(base))
+            runs["auto_hint"].append(run_cfrk(base + ["--auto-hint"]))
+        for name, rs in runs.items():
+            bad = [r for r in rs if "error" in r]
+            if bad:
+                res[name] = bad[0]
+                continue
+            res[name] = {"wall_s": statistics.median(r["wall_s"] for r in rs),
+                         "process_wall_s": statistics.median(r["process_wall_s"] for r in rs),
+                         "all_wall_s": [r["wall_s"] for r in rs],
+                         **{f: rs[-1][f] for f in ("attempts", "estimate_s", "distinct_estimate", "hint", "begin_s",
+                                                   "add_call_s", "finish_wait_s", "count_kernels_ms", "parse_s")}}
+        if "error" not in res["plain"] and "error" not in res["auto_hint"]:
+            res["auto_hint_over_plain_wall"] = round(res["auto_hint"]["wall_s"] / res["plain"]["wall_s"], 3)
+    finally:
+        for p in (fa, outp, histo):
+            try:
+                os.remove(p)
+            except OSError:
+                pass
+    return res
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
@@ -131,5 +174,10 @@ if __name__ == "__main__":
     ap.add_argument("--dir", default=None)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--auto-hint-ab", action="store_true")
+    ap.add_argument("--uniform", action="store_true")
     a = ap.parse_args()
+    if a.auto_hint_ab:
+        print(json.dumps(measure_auto_hint(a.reads, a.L, a.k, a.dir, a.threads, a.uniform)))
+        sys.exit(0)
     print(json.dumps(measure(a.reads, a.L, a.k, 0, a.dir, a.threads, quick=a.quick), indent=1))
