@@ -161,6 +161,62 @@ int cfrk_memcpy_h2d(cfrk_ctx *ctx, void *dst, const void *src, size_t bytes) {
   return CFRK_OK;
 }
 
+// Host memory the runtime cannot pin piece by piece at full rate (a mapped file) goes through a ring of pinned
+// buffers of the context's own: eight threads, two 4 MB buffers each; a thread copies its next piece into a buffer
+// while the device reads the other one.  All pieces are enqueued on the context stream.
+int cfrk_memcpy_h2d_staged(cfrk_ctx *ctx, void *dst, const void *src, size_t bytes) {
+  if (!ctx || (bytes && (!dst || !src))) return CFRK_ERR_ARG;
+  constexpr size_t CH = (size_t)4 << 20;
+  constexpr int NT = 8;
+  if (bytes < 2 * CH) return cfrk_memcpy_h2d(ctx, dst, src, bytes);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (ctx->pinned_cap < NT * 2 * CH) {
+    if (ctx->pinned) { HIP_TRY(ctx, hipHostFree(ctx->pinned)); ctx->pinned = nullptr; ctx->pinned_cap = 0; }
+    HIP_TRY(ctx, hipHostMalloc(&ctx->pinned, NT * 2 * CH, hipHostMallocDefault));
+    ctx->pinned_cap = NT * 2 * CH;
+  }
+  hipEvent_t ev[NT][2] = {};
+  auto drop_events = [&] {
+    for (int t = 0; t < NT; ++t)
+      for (int b = 0; b < 2; ++b) if (ev[t][b]) (void)hipEventDestroy(ev[t][b]);
+  };
+  for (int t = 0; t < NT; ++t)
+    for (int b = 0; b < 2; ++b) {
+      const hipError_t e = hipEventCreateWithFlags(&ev[t][b], hipEventDisableTiming);
+      if (e != hipSuccess) { ev[t][b] = nullptr; drop_events(); HIP_TRY(ctx, e); }
+    }
+  const size_t nchunks = (bytes + CH - 1) / CH;
+  hipError_t err[NT];
+  auto work = [&](int t) {
+    err[t] = hipSetDevice(ctx->device);
+    size_t round = 0;
+    for (size_t c = (size_t)t; c < nchunks && err[t] == hipSuccess; c += NT, ++round) {
+      const int b = (int)(round & 1);
+      char *stage = (char *)ctx->pinned + ((size_t)t * 2 + (size_t)b) * CH;
+      const size_t off = c * CH, len = std::min(CH, bytes - off);
+      if (round >= 2 && (err[t] = hipEventSynchronize(ev[t][b])) != hipSuccess) break;
+      memcpy(stage, (const char *)src + off, len);
+      if ((err[t] = hipMemcpyAsync((char *)dst + off, stage, len, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
+      err[t] = hipEventRecord(ev[t][b], ctx->stream);
+    }
+  };
+  {
+    std::vector<std::thread> th;
+    int started = 0;
+    try {
+      for (; started < NT; ++started) th.emplace_back(work, started);
+    } catch (...) {
+    }
+    for (int t = started; t < NT; ++t) work(t);        // (threads that could not be started: their pieces, here)
+    for (auto &x : th) x.join();
+  }
+  const hipError_t se = hipStreamSynchronize(ctx->stream);
+  drop_events();
+  for (int t = 0; t < NT; ++t) HIP_TRY(ctx, err[t]);
+  HIP_TRY(ctx, se);
+  return CFRK_OK;
+}
+
 int cfrk_memcpy_d2h(cfrk_ctx *ctx, void *dst, const void *src, size_t bytes) {
   if (!ctx || (bytes && (!dst || !src))) return CFRK_ERR_ARG;
   HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));

@@ -30,6 +30,8 @@ enum {  // pool slots
   BUF_SPARSE_AUX,                             // block sums of the row-pointer scan
   BUF_SPARSE_IN, BUF_SPARSE_OUT,              // staging of the host call (data, start, length, row_ptr in; keys, counts out)
   BUF_SKETCH,                                 // distinct sketch (sketch.hip): the workgroups' merged registers as words, the window count, the host form's registers
+  BUF_FASTA,                                  // FASTA parser (ingest.hip): size / error words, tile aggregates, their scan
+  BUF_FASTA_IN, BUF_FASTA_OUT,                // staging of the host form (text in; data, start, length out)
   BUF_NSLOTS
 };
 

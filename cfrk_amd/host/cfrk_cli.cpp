@@ -65,6 +65,14 @@
 //                    few repeats (low coverage, metagenomes) is counted once instead of up to three times; the retry with
 //                    eight times the room stays behind it.  With --gpus N every device sketches its shard and the
 //                    registers are merged on the host before the owners begin
+//   --device-parse   (global, one device) the file is copied to the device as text and parsed there
+//                    (cfrk_fasta_parse_device), then counted with the _device calls on that buffer: no host batch; same
+//                    output files, same messages for a file the parser refuses.  Not with --gpus above 1 or --batch.
+//                    Query files keep the host parser.  --timing then reports text_map_s (mapping the file), text_h2d_s
+//                    and device_parse_ms (parse_s 0)
+//   --text-copy plain|staged   (with --device-parse) how the mapped text goes to the device: by one copy from the mapping
+//                    (plain, the default: measured the faster one) or through the context's ring of pinned staging
+//                    buffers (staged, cfrk_memcpy_h2d_staged)
 //   --batch N        the Swift/T workflow's loop (swift/cfrk.swf:15-20) in one process: for i < N
 //                    count <dataset_prefix>_<i>.fasta into <out_prefix>_<i>.cfrk
 // Chunk pipeline: every device runs two contexts (two HIP streams), each on a host thread of its
@@ -73,9 +81,13 @@
 // The threads argument is the number of host threads that format the .cfrk text (the reference
 // uses it for host memcpy only, src/main.cu:137,186); like the reference, with 5 positional
 // arguments the 5th is chunkSize and the 4th is not parsed (src/main.cu:246-249).
+#include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
@@ -104,6 +116,8 @@ struct Options {
   const char *query_stats = nullptr;   // --query-stats SFILE
   uint32_t stats_below = 0;            // --stats-below T
   bool estimate = false, estimate_only = false, auto_hint = false;   // --estimate, --estimate-only, --auto-hint
+  bool device_parse = false;                                        // --device-parse
+  bool text_copy_plain = true;                                      // --text-copy plain (the default) | staged
 };
 
 // --timing: wall-clock seconds by phase (one file; with --batch the last file's)
@@ -117,6 +131,8 @@ struct Timing {
   uint64_t entries = 0, out_bytes = 0;
   int attempts = 0;                    // begin / add / finish passes of the global job (above 1: the hint was too small)
   double estimate = 0, distinct_estimate = 0;   // the sketch before the count: seconds, estimated distinct k-mers
+  double text_map = 0, text_h2d = 0, device_parse_ms = 0;    // --device-parse: the text's copy to the device (s), the parse there (ms)
+  bool device_parse = false;
   uint64_t hint = 0;                   // capacity hint of the LAST attempt
 } g_timing;
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -397,7 +413,9 @@ int sketch_batch(const Options &o, const cfrk_batch &batch, const std::vector<cf
 
 // early_free: the batch is no longer needed once it has been counted -- returning 1.6 GB of pages to the kernel takes
 // ~0.17 s, which then runs beside the export, the formatting and the write instead of behind them
-int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, const Estimate &est, std::thread *early_free = nullptr, cfrk_batch *owned = nullptr) {
+// d_data: the batch's codes already on the device (--device-parse: batch then carries nN and nS only)
+int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, const Estimate &est, std::thread *early_free = nullptr, cfrk_batch *owned = nullptr,
+               bool on_device = false, const int8_t *d_data = nullptr) {
   int rc;
   cfrk_ctx *ctx = w.ctx;
   // The capacity hint sizes the result list and the spill table (12 B per slot at load <= 0.5).  Distinct k-mers cannot
@@ -419,7 +437,8 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
     if ((rc = cfrk_global_begin(ctx, o.k, o.canonical ? CFRK_CANONICAL : 0, hint))) return die(ctx, rc, "cfrk_global_begin");
     const double t0 = now_s();
     g_timing.begin += t0 - tb;
-    if ((rc = cfrk_global_add(ctx, batch.data, batch.start, batch.length, batch.nN, batch.nS))) return die(ctx, rc, "cfrk_global_add");
+    if (on_device) { if (batch.nN > 0 && (rc = cfrk_global_add_device(ctx, d_data, batch.nN))) return die(ctx, rc, "cfrk_global_add_device"); }
+    else if ((rc = cfrk_global_add(ctx, batch.data, batch.start, batch.length, batch.nN, batch.nS))) return die(ctx, rc, "cfrk_global_add");
     const double t1 = now_s();
     rc = cfrk_global_finish(ctx, &n);
     add_s += t1 - t0; finish_s += now_s() - t1;
@@ -631,6 +650,81 @@ int run_global_multi(const Options &o, const cfrk_batch &batch, std::vector<std:
   return 0;
 }
 
+// --device-parse: the file goes to the device as text and is parsed there (cfrk_fasta_parse_device); no host batch
+struct DeviceText {
+  cfrk_ctx *ctx = nullptr;
+  void *d_text = nullptr, *d_start = nullptr, *d_length = nullptr, *d_regs = nullptr;
+  int8_t *d_data = nullptr;
+  ~DeviceText() { for (void *d : {d_text, (void *)d_data, d_start, d_length, d_regs}) if (d) cfrk_device_free(ctx, d); }
+  // 0, a negative code of the host parser (the caller prints its message), or the exit status of a reported device error
+  int load(const char *in, bool plain_copy, int64_t *nN, int64_t *nS, double *map_s, double *h2d_s, double *parse_ms) {
+    const int fd = open(in, O_RDONLY);
+    if (fd < 0) return -1;
+    struct stat st;
+    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { close(fd); return -1; }
+    const size_t n = (size_t)st.st_size;
+    *nN = *nS = 0;
+    if (n == 0) { close(fd); return 0; }
+    int rc;
+    if ((rc = cfrk_device_alloc(ctx, n + 16, &d_text))) { close(fd); return die(ctx, rc, "cfrk_device_alloc"); }
+    // One copy from the mapping by default.  The ring of pinned staging buffers (--text-copy staged) was built for this
+    // and measured: for a mapped, populated file it is no faster than the runtime's own pageable path.
+    const double tm = now_s();
+    void *m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
+    close(fd);
+    if (m == MAP_FAILED) return -1;
+    const double t0 = now_s();
+    *map_s = t0 - tm;
+    rc = plain_copy ? cfrk_memcpy_h2d(ctx, d_text, m, n) : cfrk_memcpy_h2d_staged(ctx, d_text, m, n);
+    munmap(m, n);
+    if (rc) return die(ctx, rc, plain_copy ? "cfrk_memcpy_h2d" : "cfrk_memcpy_h2d_staged");
+    *h2d_s = now_s() - t0;
+    const double t1 = now_s();
+    rc = cfrk_fasta_parse_device(ctx, (const uint8_t *)d_text, n, 0, nullptr, 0, nullptr, nullptr, 0, nN, nS);
+    if (rc == CFRK_ERR_SMALL_BUF) {
+      void *dd = nullptr;
+      if ((rc = cfrk_device_alloc(ctx, (size_t)*nN + 64, &dd))) return die(ctx, rc, "cfrk_device_alloc");
+      d_data = (int8_t *)dd;
+      if ((rc = cfrk_device_alloc(ctx, (size_t)*nS * 8, &d_start)) || (rc = cfrk_device_alloc(ctx, (size_t)*nS * 4, &d_length)))
+        return die(ctx, rc, "cfrk_device_alloc");
+      rc = cfrk_fasta_parse_device(ctx, (const uint8_t *)d_text, n, 0, d_data, (uint64_t)*nN, (int64_t *)d_start, (int32_t *)d_length,
+                                   (uint64_t)*nS, nN, nS);
+      if (!rc) rc = cfrk_ctx_sync(ctx);
+    }
+    // What the host parser refuses with -2 (a sequence line before the first header: the only text it can refuse in native
+    // mode short of a record of 2^31 bases) is reported in its words; the wording looked for is pinned at its cfrk_fail in
+    // ingest.hip and by tests/test_gpu_ingest.py.  Anything else the device parser refuses is reported in the library's.
+    if (rc == CFRK_ERR_LAYOUT) {
+      if (strstr(cfrk_last_error(ctx), "before the first header")) return -2;
+      fprintf(stderr, "cfrk: cannot read %s (%s)\n", in, cfrk_last_error(ctx));
+      return 1;
+    }
+    if (rc) return die(ctx, rc, "cfrk_fasta_parse_device");
+    *parse_ms = (now_s() - t1) * 1e3;
+    cfrk_device_free(ctx, d_text);                      // (the codes are what is counted)
+    d_text = nullptr;
+    return 0;
+  }
+  int sketch(const Options &o, int64_t nN, Estimate &e) {
+    const double t0 = now_s();
+    std::vector<uint8_t> regs(CFRK_SKETCH_REGS, 0);
+    int rc;
+    if (nN > 0) {
+      if ((rc = cfrk_device_alloc(ctx, CFRK_SKETCH_REGS, &d_regs)) || (rc = cfrk_memcpy_h2d(ctx, d_regs, regs.data(), regs.size())))
+        return die(ctx, rc, "cfrk_device_alloc");
+      if ((rc = cfrk_distinct_sketch_device(ctx, d_data, nN, o.k, o.canonical ? CFRK_CANONICAL : 0, (uint8_t *)d_regs, &e.windows)))
+        return die(ctx, rc, "cfrk_distinct_sketch_device");
+      if ((rc = cfrk_memcpy_d2h(ctx, regs.data(), d_regs, regs.size()))) return die(ctx, rc, "cfrk_memcpy_d2h");
+    }
+    cfrk_sketch_estimate(regs.data(), &e.distinct);
+    cfrk_sketch_hint(regs.data(), &e.hint);
+    e.have = true;
+    g_timing.estimate = now_s() - t0; g_timing.distinct_estimate = e.distinct;
+    fprintf(stderr, "cfrk-estimate distinct=%.0f windows=%llu hint=%llu\n", e.distinct, (unsigned long long)e.windows, (unsigned long long)e.hint);
+    return 0;
+  }
+};
+
 // one FASTA file -> one .cfrk file on the given workers
 // a FASTA file being parsed on a thread of its own while the caller creates the device contexts (single-file mode: HIP
 // start-up and two contexts are ~0.15 s, the parse of a 1.6 GB file ~0.28 s -- they need nothing from each other)
@@ -652,7 +746,14 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
   cfrk_batch batch;
   double t0 = now_s();
   int rc;
-  if (pre) {
+  DeviceText dt;
+  dt.ctx = workers[0].ctx;
+  double text_map = 0, text_h2d = 0, device_parse_ms = 0;
+  if (o.device_parse) {
+    memset(&batch, 0, sizeof batch);
+    rc = dt.load(in, o.text_copy_plain, &batch.nN, &batch.nS, &text_map, &text_h2d, &device_parse_ms);
+    if (rc > 0) return rc;                              // (a device error, reported)
+  } else if (pre) {
     const double w0 = now_s();
     pre->th.join();
     g_wait_parse = now_s() - w0;
@@ -665,6 +766,7 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
   g_timing = Timing();
   g_timing.contexts = g_contexts_s; g_timing.wait_parse = g_wait_parse;
   g_timing.parse = t1 - t0; g_timing.nN = batch.nN; g_timing.nS = batch.nS;
+  if (o.device_parse) { g_timing.parse = 0; g_timing.device_parse = true; g_timing.text_map = text_map; g_timing.text_h2d = text_h2d; g_timing.device_parse_ms = device_parse_ms; }
   { FILE *f = fopen(in, "rb"); if (f) { fseek(f, 0, SEEK_END); g_timing.fasta_bytes = (int64_t)ftell(f); fclose(f); } }
   std::thread freer;                                  // (global mode: frees the batch beside the export)
   const double to0 = now_s();
@@ -679,10 +781,11 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
     std::vector<cfrk_ctx *> ctxs;
     if (multi) for (auto &d : *per_dev) ctxs.push_back(d[0].ctx);
     else ctxs.push_back(workers[0].ctx);
-    rc = sketch_batch(o, batch, ctxs, est);
+    rc = o.device_parse ? dt.sketch(o, batch.nN, est) : sketch_batch(o, batch, ctxs, est);
   }
   if (!rc && !o.estimate_only) {
     if (multi) rc = run_global_multi(o, batch, *per_dev, out, est);
+    else if (o.device_parse) rc = run_global(o, batch, workers[0], out, est, nullptr, nullptr, true, dt.d_data);
     else if (o.global) rc = run_global(o, batch, workers[0], out, est, &freer, &batch);
     else { const double p0 = now_s(); rc = run_per_read(o, batch, workers, out); g_timing.per_read = now_s() - p0; }
   }
@@ -694,9 +797,11 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
   else cfrk_host_free_batch(&batch);
   g_timing.total = now_s() - t0;
   g_timing.close = tf1 - tf0; g_timing.free_batch = now_s() - tf1; g_timing.open = t_open;
-  char query_field[96] = "";     // (only with --query: the line is unchanged otherwise)
-  if (o.query_stats) snprintf(query_field, sizeof query_field, "\"query_s\": %.4f, \"stats_s\": %.4f, ", g_timing.query, g_timing.stats);
-  else if (o.query) snprintf(query_field, sizeof query_field, "\"query_s\": %.4f, ", g_timing.query);
+  char query_field[192] = "";     // (only with --query / --device-parse: the line is unchanged otherwise)
+  if (g_timing.device_parse) snprintf(query_field, sizeof query_field, "\"text_map_s\": %.4f, \"text_h2d_s\": %.4f, \"device_parse_ms\": %.3f, ", g_timing.text_map, g_timing.text_h2d, g_timing.device_parse_ms);
+  const size_t qf = strlen(query_field);
+  if (o.query_stats) snprintf(query_field + qf, sizeof query_field - qf, "\"query_s\": %.4f, \"stats_s\": %.4f, ", g_timing.query, g_timing.stats);
+  else if (o.query) snprintf(query_field + qf, sizeof query_field - qf, "\"query_s\": %.4f, ", g_timing.query);
   if (o.timing)
     fprintf(stderr, "cfrk-timing {\"fasta_bytes\": %lld, \"reads\": %lld, \"code_bytes\": %lld, \"parse_s\": %.4f, \"add_call_s\": %.4f, "
             "\"finish_wait_s\": %.4f, \"count_kernels_ms\": %.3f, \"export_s\": %.4f, \"format_s\": %.4f, \"write_s\": %.4f, "
@@ -786,6 +891,12 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--estimate")) o.estimate = true;
     else if (!strcmp(argv[i], "--estimate-only")) o.estimate_only = true;
     else if (!strcmp(argv[i], "--auto-hint")) o.auto_hint = true;
+    else if (!strcmp(argv[i], "--device-parse")) o.device_parse = true;
+    else if (!strcmp(argv[i], "--text-copy") && i + 1 < argc) {
+      const char *v = argv[++i];
+      if (strcmp(v, "plain") && strcmp(v, "staged")) { fprintf(stderr, "cfrk: --text-copy takes plain or staged, not '%s'\n", v); return 1; }
+      o.text_copy_plain = !strcmp(v, "plain");
+    }
     else if (!strcmp(argv[i], "--query-only")) o.query_only = true;
     else if (!strcmp(argv[i], "--query") || !strcmp(argv[i], "--query-out") || !strcmp(argv[i], "--query-db")) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
@@ -825,6 +936,10 @@ int main(int argc, char **argv) {
   }
   if ((o.estimate || o.estimate_only || o.auto_hint) && !o.global) {
     fprintf(stderr, "cfrk: --estimate, --estimate-only and --auto-hint need --global\n");
+    return 1;
+  }
+  if (o.device_parse && (!o.global || o.gpus > 1 || batch_n >= 0)) {
+    fprintf(stderr, "cfrk: --device-parse needs --global on one device: not with --gpus above 1 or --batch\n");
     return 1;
   }
   if (o.estimate_only && batch_n >= 0) { fprintf(stderr, "cfrk: --estimate-only prints one estimate: not with --batch\n"); return 1; }
@@ -869,7 +984,7 @@ int main(int argc, char **argv) {
 
   // single-file mode: the parse starts now, beside the creation of the contexts
   Parsed pre;
-  if (batch_n < 0) pre.start(o, pos[0]);
+  if (batch_n < 0 && !o.device_parse) pre.start(o, pos[0]);
   struct Joiner { Parsed &p; ~Joiner() { if (p.th.joinable()) { p.th.join(); if (!p.rc) cfrk_host_free_batch(&p.batch); } } } joiner{pre};   // (early returns)
   const double tc0 = now_s();                          // (runtime start-up + the contexts)
   int ndev = 0, rc;
@@ -894,7 +1009,7 @@ int main(int argc, char **argv) {
     std::vector<Worker> all;
     for (int s = 0; s < 2; ++s)                       // device-major would put both streams of a device first
       for (int g = 0; g < o.gpus; ++g) all.push_back(per_dev[(size_t)g][(size_t)s]);
-    status = run_file(o, pos[0], pos[1], all, &per_dev, &pre);
+    status = run_file(o, pos[0], pos[1], all, &per_dev, o.device_parse ? nullptr : &pre);
   } else {
     // file i goes to device i % gpus (swift/cfrk.swf:15-20 starts one cfrk process per file)
     std::vector<int> st((size_t)o.gpus, 0);

@@ -36,6 +36,9 @@ READ_STATS_DTYPE = np.dtype([("windows", "<u4"), ("present", "<u4"), ("below", "
                              ("median", "<u4"), ("max", "<u4"), ("sum", "<u8")])
 CFRK_SKETCH_LOG2M = 14               # distinct sketch: log2 of its registers
 CFRK_SKETCH_REGS = 16384             # one uint8 register per bucket
+CFRK_FASTA_TILE_BYTES = 16384        # device FASTA parser: text bytes per workgroup
+CFRK_FASTA_SCAN_TILES = 1024         # tiles per block of its tile scan
+CFRK_FASTA_MAX_CR_RUN = 4096         # native mode: carriage returns in a row it follows to the line's end
 CFRK_PARAM_MSP_CHUNKS, CFRK_PARAM_L2_SLACK_COMPLETE, CFRK_PARAM_L2_SLACK_TRUNCATED, CFRK_PARAM_MSP2_SUBVALUE_BITS = 0, 1, 2, 3   # cfrk_debug_set_param
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -85,6 +88,7 @@ def load_library():
         "cfrk_device_free": ([vp, vp], C.c_int),
         "cfrk_memcpy_h2d": ([vp, vp, vp, C.c_size_t], C.c_int),
         "cfrk_memcpy_d2h": ([vp, vp, vp, C.c_size_t], C.c_int),
+        "cfrk_memcpy_h2d_staged": ([vp, vp, vp, C.c_size_t], C.c_int),
         "cfrk_memcpy_peer": ([vp, vp, vp, vp, C.c_size_t], C.c_int),
         "cfrk_per_read_dense": ([vp, vp, vp, vp, i64, i64, i32, i32, vp], C.c_int),
         "cfrk_per_read_dense_device": ([vp, vp, vp, vp, i64, i64, i32, i32, vp], C.c_int),
@@ -128,6 +132,8 @@ def load_library():
         "cfrk_sketch_estimate": ([vp, C.POINTER(C.c_double)], C.c_int),
         "cfrk_sketch_merge": ([vp, vp], C.c_int),
         "cfrk_sketch_hint": ([vp, C.POINTER(u64)], C.c_int),
+        "cfrk_fasta_parse_device": ([vp, vp, u64, i32, vp, u64, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "cfrk_fasta_parse": ([vp, vp, u64, i32, vp, u64, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_synth_reads_device": ([vp, i64, i64, i32, i64, u64, u64, u64, i32, vp, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
@@ -253,6 +259,11 @@ class Context:
         arr = np.ascontiguousarray(arr)
         self.check(self._L.cfrk_memcpy_h2d(self._h, C.c_void_p(dptr), _ptr(arr), arr.nbytes), "cfrk_memcpy_h2d")
 
+    def h2d_staged(self, dptr, arr):
+        """h2d through the context's ring of pinned staging buffers (for memory the runtime copies slowly: a mapped file)"""
+        arr = np.ascontiguousarray(arr)
+        self.check(self._L.cfrk_memcpy_h2d_staged(self._h, C.c_void_p(dptr), _ptr(arr), arr.nbytes), "cfrk_memcpy_h2d_staged")
+
     def d2h(self, arr, dptr):
         self.check(self._L.cfrk_memcpy_d2h(self._h, _ptr(arr), C.c_void_p(dptr), arr.nbytes), "cfrk_memcpy_d2h")
 
@@ -334,6 +345,37 @@ class Context:
                                                        C.byref(windows) if want_windows else None),
                    "cfrk_distinct_sketch_device")
         return windows.value if want_windows else None
+
+    # -- FASTA text parsed on the device -------------------------------------------------------
+    def parse_fasta_device(self, d_text, nbytes, flags, d_data, cap_data, d_start, d_length, cap_reads):
+        """device form: d_text 16-byte aligned -> (nN, nS); d_data / d_start / d_length may be 0 with zero capacities
+        (sizes only).  Raises CfrkError (code CFRK_ERR_SMALL_BUF, with .nN and .nS set, nothing written) when the
+        arrays are too small.  Synchronises once, returns with the last kernel enqueued on the context stream."""
+        nN, nS = C.c_int64(), C.c_int64()
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_fasta_parse_device(self._h, vp(d_text), nbytes, flags, vp(d_data), cap_data, vp(d_start),
+                                             vp(d_length), cap_reads, C.byref(nN), C.byref(nS))
+        try:
+            self.check(rc, "cfrk_fasta_parse_device")
+        except CfrkError as e:
+            e.nN, e.nS = nN.value, nS.value
+            raise
+        return nN.value, nS.value
+
+    def parse_fasta(self, text, flags=0):
+        """FASTA text (bytes or a uint8 array) -> host (data int8[nN], start int64[nS], length int32[nS]), what the
+        host parser makes of it: flags 0 = native, CFRK_COMPAT = the reference's reader.  A sizes-only call, then
+        the parse into arrays of exactly that size."""
+        text = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+        nN, nS = C.c_int64(), C.c_int64()
+        rc = self._L.cfrk_fasta_parse(self._h, _ptr(text), text.size, flags, None, 0, None, None, 0, C.byref(nN), C.byref(nS))
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.check(rc, "cfrk_fasta_parse")
+        data, start, length = np.empty(nN.value, np.int8), np.empty(nS.value, np.int64), np.empty(nS.value, np.int32)
+        if rc == CFRK_ERR_SMALL_BUF:
+            self.check(self._L.cfrk_fasta_parse(self._h, _ptr(text), text.size, flags, _ptr(data), data.size, _ptr(start),
+                                                _ptr(length), start.size, C.byref(nN), C.byref(nS)), "cfrk_fasta_parse")
+        return data, start, length
 
     def synth_reads_device(self, r0, R, L, Glen, d_data, d_start=None, d_length=None,
                            seedG=1, seedR=2, seedS=3, uniform=False):

@@ -101,6 +101,12 @@ int  cfrk_device_alloc(cfrk_ctx *ctx, size_t bytes, void **dptr);
 int  cfrk_device_free(cfrk_ctx *ctx, void *dptr);
 int  cfrk_memcpy_h2d(cfrk_ctx *ctx, void *dst_device, const void *src_host, size_t bytes);
 int  cfrk_memcpy_d2h(cfrk_ctx *ctx, void *dst_host, const void *src_device, size_t bytes);
+/* cfrk_memcpy_h2d through a ring of pinned staging buffers (64 MB, allocated on the first call and kept by the context),
+ * filled by eight host threads.  Synchronous; copies of less than 8 MB take cfrk_memcpy_h2d.  Prefer cfrk_memcpy_h2d: on
+ * the MI355X hosts measured the runtime copies ordinary and mapped-file memory at 56 GB/s by itself and
+ * this ring reaches 43-46 GB/s.  It is for a host where the runtime's pageable path is the slow one -- measure both
+ * (tools/bench_ingest.py, `cfrk --device-parse --text-copy plain|staged`) before choosing it. */
+int  cfrk_memcpy_h2d_staged(cfrk_ctx *ctx, void *dst_device, const void *src_host, size_t bytes);
 /* Device-to-device copy between two contexts, possibly on different GPUs of the node: over xGMI
  * peer-to-peer (hipMemcpyPeerAsync; peer access is enabled on first use where the topology allows it),
  * enqueued on dst_ctx's stream.  src_ctx's stream is drained first, so whatever src_ctx was asked to
@@ -312,6 +318,52 @@ int cfrk_distinct_sketch(cfrk_ctx *ctx, const int8_t *data, const int64_t *start
 int cfrk_sketch_estimate(const uint8_t *regs, double *distinct);
 int cfrk_sketch_merge(uint8_t *dst, const uint8_t *src);
 int cfrk_sketch_hint(const uint8_t *regs, uint64_t *hint);
+
+/* ---- FASTA text parsed on the device: text in, struct-read buffers out --------------------------------------- */
+
+/* nbytes of FASTA text -> data (codes, one -1 terminator behind every read), start, length, nN, nS: byte for byte what
+ * the host parser (cfrk_host_parse_fasta, cfrk_amd/host/cfrk_host.h) makes of the same bytes and flags.
+ * Grammar: a line ends at '\n' or at the end of the text; a line whose first byte is '>' is a header and starts a
+ * record, every other line is a sequence line of the current record; a '>' elsewhere is an ordinary invalid base.
+ * aA cC gG tT -> 0 1 2 3, anything else -> -1.
+ *   flags 0 (native): a sequence line contributes its bytes without its trailing run of '\n' / '\r' (an interior '\r'
+ *     stays and encodes as -1, an empty line contributes nothing); a record may be empty (length 0) and still gets
+ *     its terminator; start[r] = kept bytes before record r + r; nN = kept bytes + nS.
+ *   CFRK_COMPAT (the reference's ReadFasta, src/fastaIO.h:60-102): a sequence line contributes all its bytes, newline
+ *     included (-1); length[r] = contributed bytes - 1, the record's last contributed byte holds the terminator;
+ *     start[r] = contributed bytes before record r; nN = contributed bytes.
+ * CFRK_ERR_LAYOUT (cfrk_last_error names the cause and the byte offset or the record): non-empty text that does not
+ * begin with '>' (a sequence line before the first header), in compat mode a record without a contributed byte, a
+ * record of more than 2^31 - 1 bases, and -- the one thing the host parser accepts and this one refuses -- in native
+ * mode a SEQUENCE line that holds more than CFRK_FASTA_MAX_CR_RUN carriage returns in a row (the look ahead from a
+ * '\r' to its line's end is bounded, so that no text can keep a kernel busy without end).  The bound is exact: a run of
+ * CFRK_FASTA_MAX_CR_RUN is parsed as the host parser parses it, a run of one more is refused, wherever it lies; the
+ * error names the run's first byte (the first such run's).  Header lines and compat mode have no bound.
+ * Empty text: nS = nN = 0.
+ * Any flag other than CFRK_COMPAT, a NULL text with nbytes > 0, NULL size outputs and a NULL array with a capacity
+ * above 0 are CFRK_ERR_ARG; d_text must be 16-byte aligned (CFRK_ERR_ALIGN), d_data need not be.
+ * Capacities: cap_data = nbytes and cap_reads = (nbytes + 1) / 2 always suffice.  A record needs its '>' and, unless
+ * it is the text's last line, the '\n' behind it: nS records take at least 2 nS - 1 bytes, so nS <= (nbytes + 1) / 2.
+ * A '>' contributes no code, so a record's terminator takes the place of its header's '>' (native: nN = kept + nS <=
+ * nbytes; compat: nN = contributed bytes < nbytes).  When nN > cap_data or nS > cap_reads the call returns
+ * CFRK_ERR_SMALL_BUF with *nN_out / *nS_out complete and nothing written to the arrays; NULL arrays with zero
+ * capacities are that "sizes only" call (as in cfrk_per_read_sparse).
+ * Device form: reduce, scan, scatter and a length pass as separate launches on the context stream (no workgroup waits
+ * for another one).  It synchronises ONCE, to read the sizes and error words back, and returns with the last kernel
+ * enqueued; only a text of 2^31 bytes or more, which alone can hold an over-long record, is waited for at the end as
+ * well.  Temporary device memory, kept in the context's pool: 64 bytes + 32 bytes per tile of CFRK_FASTA_TILE_BYTES
+ * (an aggregate and its scan: 2 MB per GB of text); the scan walks the tiles in blocks of CFRK_FASTA_SCAN_TILES.
+ * Host form: host text in, host arrays out; stages through the pool (the text, then data / start / length); synchronous.
+ * Neither call touches a global job that is open on the same context. */
+#define CFRK_FASTA_TILE_BYTES 16384
+#define CFRK_FASTA_SCAN_TILES 1024
+#define CFRK_FASTA_MAX_CR_RUN 4096
+int cfrk_fasta_parse_device(cfrk_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, int flags,
+                            int8_t *d_data, uint64_t cap_data, int64_t *d_start, int32_t *d_length, uint64_t cap_reads,
+                            int64_t *nN_out, int64_t *nS_out);
+int cfrk_fasta_parse(cfrk_ctx *ctx, const char *text, uint64_t nbytes, int flags,
+                     int8_t *data, uint64_t cap_data, int64_t *start, int32_t *length, uint64_t cap_reads,
+                     int64_t *nN_out, int64_t *nS_out);
 
 /* Unsorted export into device buffers, grouped into `parts` contiguous segments by
  * owner(key) = (mix(key) >> 32) % parts (key-owner partition for the multi-GPU
