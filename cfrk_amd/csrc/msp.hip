@@ -34,6 +34,10 @@
 // table) is counted with table_add1() into the global HBM table instead ("64-bit HBM atomics
 // only on spill") and ST_SPILLED is raised; the host then folds the list into the table.
 //
+// msp_shared.h holds what this file shares with msp2.hip (33 <= k <= 64) and that does not depend on the record
+// format -- the layout and sum kernels, the sizing rules, the index buffers, the exact level-1 layout, the passes
+// of a batch that does not fit -- and msp_runs.h the exchange by runs, host side included.
+//
 // Semantics are those of global_hash.hip (the guarded ComputeFreq of
 // /root/reference/src/kmer_kernel.cu:52-70 summed over reads).
 #include "msp.h"
@@ -47,6 +51,7 @@
 #include <vector>
 
 namespace {
+#include "msp_shared.h"
 #include "msp_runs.h"
 
 constexpr int P1_THREADS = 512;
@@ -85,11 +90,6 @@ __device__ __noinline__ void spill_record(uint4 rec, int k, bool canon, TableVie
 constexpr int P1_OWN = 61;                       // owner lanes per wave
 constexpr int P1_WAVES = P1_THREADS / 64;
 
-// Level-1 region (and cursor) of bin `bin`, sub-region `xg`: sub-region major.  Global atomics
-// execute at the memory side, one 64-byte request per touched 64 bytes: with the cursors of the
-// 256 bins of one sub-region side by side, a workgroup's 256 reservations are 16 requests instead
-// of 256.
-__host__ __device__ __forceinline__ uint32_t l1_reg(uint32_t bin, uint32_t xg) { return xg * (uint32_t)B1 + bin; }
 // level-1 bin of a record: the leaf id's high byte (header bits 16..23; the top byte may hold sub-value bits)
 template <bool SUB>
 __device__ __forceinline__ uint32_t bin_of(uint32_t w) { return SUB ? ((w >> 16) & (uint32_t)(B1 - 1)) : (w >> 16); }
@@ -131,9 +131,8 @@ __device__ __forceinline__ void l1_put(const MspView &v, uint32_t reg, uint32_t 
 // SUB: a job with far more distinct k-mers than the leaf tables hold (capacity hint > ~2.7e8) also stages
 // five bits of every position's minimizer hash that the leaf id does not use and writes them to the top
 // byte of the record's header word: the leaf kernel then splits an overfull leaf by RECORD, not by key,
-// so that every record is expanded once (msp2.hip does the same).  2 KB more staging per wave: two
-// workgroups per CU instead of three.
-constexpr int SUB_BITS = 5;
+// so that every record is expanded once (msp2.hip does the same; SUB_BITS: msp_shared.h).  2 KB more staging per
+// wave: two workgroups per CU instead of three.
 #define P1_MARK(text) asm volatile("; " text)
 template <int P1B_TR, bool SUB = false>
 struct P1Lds {
@@ -443,6 +442,7 @@ __global__ __launch_bounds__(P1_THREADS, ((P1B_TR <= 6 && !SUB) ? 6 : 4)) void m
 // Two streams per leaf: truncated runs (class 0) and complete runs (class 1).  The leaf kernel
 // sorts records by length itself, so finer classes would only shorten P2's write segments.
 constexpr int NCLS = 2;
+static_assert(NCLS <= SUM_CLASSES, "msp_sum_kernel clears a word per class");
 constexpr int NSUB = NCLS * B2;                           // 512 sub-bins of a level-1 bin
 __device__ __forceinline__ uint32_t sub_of(uint32_t w) { return (((w >> 8) & (B2 - 1)) << 1) | ((((w >> 6) & 3u) == 3u) ? 1u : 0u); }
 
@@ -2189,31 +2189,6 @@ __global__ __launch_bounds__(256) void msp_runs_scatter_kernel(const uint4 *__re
   }
 }
 
-// exact layout of a level from the demand the first attempt counted: base = exclusive prefix sum
-// of the n cursors, cap = the cursors themselves (single workgroup, 1024 threads)
-// (slack: room beyond the counted demand per region -- the chunked path runs P1 again, and which records its
-//  first level PARKED last time depended on the order of atomics: a stream's demand may differ by a few)
-__global__ __launch_bounds__(1024) void msp_layout_kernel(const uint32_t *__restrict__ cnt, uint32_t n,
-                                                          uint64_t *__restrict__ base, uint32_t *__restrict__ cap, uint32_t slack = 0u) {
-  __shared__ unsigned long long part[1024];
-  const uint32_t per = (n + 1023u) / 1024u;
-  const uint32_t tid = threadIdx.x;
-  unsigned long long s = 0;
-  for (uint32_t i = 0; i < per; ++i) { const uint32_t l = tid * per + i; if (l < n) s += (unsigned long long)cnt[l] + slack; }
-  part[tid] = s;
-  __syncthreads();
-  if (tid == 0) {
-    unsigned long long run = 0;
-    for (int i = 0; i < 1024; ++i) { const unsigned long long x = part[i]; part[i] = run; run += x; }
-  }
-  __syncthreads();
-  unsigned long long run = part[tid];
-  for (uint32_t i = 0; i < per; ++i) {
-    const uint32_t l = tid * per + i;
-    if (l < n) { const uint32_t c = cnt[l] + slack; base[l] = run; cap[l] = c; run += c; }
-  }
-}
-
 // the few records that did not fit their leaf stream: counted k-mer by k-mer in the HBM table
 __global__ __launch_bounds__(256) void msp_spill_list_kernel(const uint4 *__restrict__ recs, uint32_t n, int k,
                                                              int canon, TableView t) {
@@ -2221,20 +2196,9 @@ __global__ __launch_bounds__(256) void msp_spill_list_kernel(const uint4 *__rest
   if (i < n) spill_record(recs[i], k, canon != 0, t);
 }
 
-// sum of n cursors (one workgroup): how many records the first chunk of a batch made
-__global__ __launch_bounds__(1024) void msp_sum_kernel(const uint32_t *__restrict__ cnt, uint32_t n, uint64_t *out) {
-  __shared__ unsigned long long tot;
-  if (threadIdx.x == 0) tot = 0;
-  __syncthreads();
-  unsigned long long mine = 0;
-  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) mine += cnt[i];
-  atomicAdd(&tot, mine);
-  __syncthreads();
-  if (threadIdx.x == 0) { out[0] = tot; out[1] = 0; out[2] = 0; }
-}
-
-// ... and what share of them are truncated runs: the records of sub-region 0 of every level-1 bin (1/64
-// of the chunk, every bin in it) -- out[1] += records looked at, out[2] += truncated ones among them
+// the first chunk of a batch (behind msp_sum_kernel): what share of its records are truncated runs -- the records
+// of sub-region 0 of every level-1 bin (1/64 of the chunk, every bin in it): out[1] += records looked at,
+// out[2] += truncated ones among them
 __global__ __launch_bounds__(256) void msp_class_sample_kernel(MspView v, unsigned long long *out) {
   const uint32_t reg = l1_reg(blockIdx.x, 0u);
   const uint32_t n = (uint32_t)min((uint64_t)v.cnt1[reg], v.cap1);
@@ -2387,20 +2351,13 @@ static int msp_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, in
   // (a chunked batch sizes its leaf streams after the first chunk: whatever the pool already holds will do until then)
   if ((rc = cfrk_pool_get(ctx, BUF_MSP_L2, (pipelined && !small_pipe) ? 16 : (size_t)(NLEAF >> sel_bits) * (cap2c + cap2t) * sizeof(uint4), &p))) return rc;
   v.rec2 = (uint4 *)p; v.cap2c = cap2c; v.cap2t = cap2t;
-  // far more distinct k-mers expected than the leaf tables hold (65536 x ~2500): records carry extra
-  // minimizer-hash bits and 2^sub_bits workgroups share a leaf (~2000 distinct k-mers each; msp2.hip)
-  uint32_t sub_bits = 0;
-  while (sub_bits < (uint32_t)SUB_BITS && ((ctx->g_cap / NLEAF) >> sub_bits) > 2048u) ++sub_bits;
-  if (ctx->g_cap / NLEAF <= 4096u) sub_bits = 0;
-  if ((ctx->dbg_flags & CFRK_DEBUG_RECORD_SUBSETS) && sub_bits < 2u) sub_bits = 2u;
+  uint32_t sub_bits = msp_sub_bits(ctx, ctx->g_cap / NLEAF);
   if (ctx->g_flags & CFRK_RUNS_ONLY) sub_bits = 0;       // (the exchange by runs has no room for the bits in a distinct run's header)
   const bool sub = sub_bits != 0u;
   v.sub_bits = sub_bits; v.seg_bits = sub_bits;
   // (leaf index: one entry per leaf, or per (leaf, sub-value) when leaves are shared)
   const size_t nseg = (size_t)NLEAF << sub_bits;
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_AUX, nseg * 8 + ((size_t)B1 * nxg + (size_t)NCLS * NLEAF + nseg) * sizeof(uint32_t), &p))) return rc;
-  v.leaf_off = (uint64_t *)p;
-  v.cnt1 = (uint32_t *)(v.leaf_off + nseg); v.cnt2 = v.cnt1 + B1 * nxg; v.leaf_n = v.cnt2 + NCLS * NLEAF;
+  if ((rc = msp_aux_buffers(ctx, v, nseg, nxg, (size_t)NCLS * NLEAF))) return rc;
   if ((rc = cfrk_pool_get(ctx, BUF_MSP_OUTK, (size_t)ctx->g_cap * 8, &p))) return rc;
   v.out_keys = (uint64_t *)p;
   if ((rc = cfrk_pool_get(ctx, BUF_MSP_OUTC, (size_t)ctx->g_cap * 4, &p))) return rc;
@@ -2408,9 +2365,7 @@ static int msp_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, in
   v.stats = ctx->g_stats;
   TableView t = cfrk_table_view(ctx);
 
-  // (cnt1, cnt2 and -- first pass only -- the leaf index and the list cursor)
-  HIP_TRY(ctx, hipMemsetAsync(v.cnt1, 0, ((size_t)B1 * nxg + (size_t)NCLS * NLEAF + (first ? nseg : 0)) * sizeof(uint32_t), ctx->stream));
-  if (first) HIP_TRY(ctx, hipMemsetAsync(ctx->g_stats + ST_CURSOR, 0, sizeof(uint64_t), ctx->stream));
+  if ((rc = msp_aux_clear(ctx, v, nseg, nxg, (size_t)NCLS * NLEAF, first))) return rc;
 
   // Both levels are laid out for an input that spreads evenly over the minimizer space.  One that
   // does not -- deep coverage of a small genome puts tens of thousands of records into a handful of
@@ -2510,18 +2465,8 @@ static int msp_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, in
           // bases -- 16 % of a deep batch of 150-base reads, half of the records of 50-base reads at
           // k = 31); the heaviest complete stream of a uniform batch is ~1.35 x the mean one
           const double ft = made[1] >= 4096 ? std::min(1.0, (double)made[2] / (double)made[1] + 0.01) : 0.5;
-          // (measured on C3: with 1.3 x a few leaves' complete streams overflow and their records are parked --
-          //  counted through the HBM table, +0.5 ms and a merge at finish; 1.4 x has none)
-          double fc_slack = 1.45, ft_slack = 1.6;
-          {
-            // ... and a leaf's load scatters with the number of distinct runs it holds (the copies of a run come
-            // and go together): lambda = distinct k-mers per leaf x 4 / (W + 1) -- 320 for C3, 64 for 20 M reads
-            // of a 20 Mb genome, whose heaviest complete stream is 2.0 x the mean one (5448 records parked at 1.45 x)
-            // (the table holds 2 .. 4 x the announced distinct k-mers: a third of it stands for the hint)
-            const double lambda = std::max(4.0, (double)ctx->g_cap / 3.0 / (double)NLEAF * 4.0 / (double)(W + 1));
-            fc_slack = std::min(4.0, std::max(fc_slack, 1.2 + 6.5 / std::sqrt(lambda)));
-            ft_slack = std::min(4.0, std::max(ft_slack, 1.3 + 6.5 / std::sqrt(lambda)));
-          }
+          double fc_slack, ft_slack;
+          msp_leaf_slack(ctx, W, &fc_slack, &ft_slack);
           if (ctx->dbg_param[CFRK_PARAM_L2_SLACK_COMPLETE] > 0) fc_slack = ctx->dbg_param[CFRK_PARAM_L2_SLACK_COMPLETE];   // (experiments)
           if (ctx->dbg_param[CFRK_PARAM_L2_SLACK_TRUNCATED] > 0) ft_slack = ctx->dbg_param[CFRK_PARAM_L2_SLACK_TRUNCATED];
           const uint64_t m2c = (uint64_t)(per_leaf * (1.0 - ft) * fc_slack + per_leaf * 0.02) + 512, m2t = (uint64_t)(per_leaf * ft * ft_slack) + 256;
@@ -2546,8 +2491,7 @@ static int msp_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, in
     // (the group epilogue of the pipelined one folds the flags into what the host waits for anyway)
     if (defer) { settled = true; break; }
     uint64_t st[ST_NWORDS];
-    HIP_TRY(ctx, hipMemcpyAsync(st, ctx->g_stats, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = cfrk_msp_sync_stats(ctx, st))) return rc;
     if (st[ST_CWRAP]) return CFRK_INTERNAL_FLOOD;      // (nothing of this pass has been counted yet)
     // (level-1 records PARKED in a chunked attempt whose leaf streams overflowed: which records are parked depends on
     //  the order of atomics, so the exact stream sizes counted now need not hold when P1 runs again -- same remedy)
@@ -2577,31 +2521,9 @@ static int msp_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, in
     }
     if (st[ST_L1OVF]) {
       // exact level-1 layout; P2 ran on an incomplete level 1 and is redone as well
-      if ((rc = cfrk_pool_get(ctx, BUF_MSP_LAYOUT1, nreg * (sizeof(uint64_t) + sizeof(uint32_t)), &p))) return rc;
-      uint64_t *rbase = (uint64_t *)p;
-      uint32_t *rcap = (uint32_t *)(rbase + nreg);
-      hipLaunchKernelGGL(msp_layout_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t *)v.cnt1, (uint32_t)nreg, rbase, rcap);
-      HIP_TRY(ctx, hipGetLastError());
-      {
-        // all records of the batch: the buffer must hold them back to back
-        std::vector<uint32_t> c1(nreg);
-        HIP_TRY(ctx, hipMemcpyAsync(c1.data(), v.cnt1, nreg * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        uint64_t maxbin = 0, all = 0;
-        for (int b = 0; b < B1; ++b) {
-          uint64_t sum = 0;
-          for (int r = 0; r < nxg; ++r) sum += c1[l1_reg((uint32_t)b, (uint32_t)r)];
-          maxbin = std::max(maxbin, sum);
-          all += sum;
-        }
-        if (all > (uint64_t)B1 * nxg * cap1) {           // more records than the density estimate allowed for
-          if ((rc = cfrk_pool_get(ctx, BUF_MSP_L1, (size_t)all * sizeof(uint4), &p))) return rc;
-          v.rec1 = (uint4 *)p;
-        }
-        (void)maxbin;                                  // (P2 is persistent: it sizes its work from the cursors)
-      }
-      HIP_TRY(ctx, hipMemsetAsync(v.cnt1, 0, (nreg + (size_t)NCLS * NLEAF) * sizeof(uint32_t), ctx->stream));   // cnt1 and cnt2
-      v.exact1 = 1; v.rbase = rbase; v.rcap = rcap;
+      uint64_t maxbin;                                 // (unused: P2 is persistent and sizes its work from the cursors)
+      if ((rc = msp_layout_level1(ctx, v.cnt1, nxg, (size_t)NCLS * NLEAF, cap1, &v.rec1, &v.rbase, &v.rcap, &maxbin))) return rc;
+      v.exact1 = 1;
       run_p1 = true;
       continue;
     }
@@ -2649,12 +2571,9 @@ static int msp_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, in
   return CFRK_OK;
 }
 
-// How many passes does a batch of `ntiles` tiles (tile_span base positions each) take so that one
-// pass's buffers fit the memory the pool may use?  0 = not even a minimal pass fits.
-int cfrk_msp_plan_groups(cfrk_ctx *ctx, int64_t nN, int64_t ntiles, int64_t tile_span,
-                         size_t (*need_fn)(const cfrk_ctx *, int64_t), size_t acc_bytes, size_t have,
-                         int *groups) {
-  (void)ntiles; (void)tile_span; (void)acc_bytes;
+// How many passes does a batch of nN base positions take so that one pass's buffers (need_fn) fit
+// the memory the pool may use (have: what it holds already)?  0 = not even a minimal pass fits.
+int cfrk_msp_plan_groups(cfrk_ctx *ctx, int64_t nN, size_t (*need_fn)(const cfrk_ctx *, int64_t), size_t have, int *groups) {
   *groups = 1;
   if (need_fn(ctx, nN) <= have && !ctx->mem_budget) return CFRK_OK;   // fits what the pool already holds
   size_t free_b = 0, total_b = 0;
@@ -2688,8 +2607,7 @@ int cfrk_msp_count(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN) {
   const size_t have = ctx->pool[BUF_MSP_L1].cap + ctx->pool[BUF_MSP_L2].cap + ctx->pool[BUF_MSP_OUTK].cap +
                       ctx->pool[BUF_MSP_OUTC].cap;
   int groups = 1;
-  if ((rc = cfrk_msp_plan_groups(ctx, nN, ntiles, (int64_t)P1_WAVES * P1_OWN * 32, msp_need, (size_t)ctx->g_cap * 12,
-                                 have, &groups))) return rc;
+  if ((rc = cfrk_msp_plan_groups(ctx, nN, msp_need, have, &groups))) return rc;
   if (groups == 0) return cfrk_fail(ctx, CFRK_ERR_NOMEM, "partitioned path does not fit device memory");
   const int passes = groups;
   ctx->last_passes = passes;
@@ -2698,38 +2616,12 @@ int cfrk_msp_count(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN) {
     if (passes != 1) return cfrk_fail(ctx, CFRK_ERR_RUNS_REFUSED, "a CFRK_RUNS_ONLY job must fit device memory in one pass");
   }
   if (ms->pending && (rc = cfrk_msp_flush_to_table(ctx))) return rc;
-  if (passes == 1) {
-    // Leaves are lumpy when the genome is small (few distinct runs per leaf, each repeated by
-    // every read over it): with memory to spare the leaf streams get up to twice the room, so
-    // that an ordinary imbalance does not end in the spill path.
-    double slack = 1.0;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      int W0, m0;
-      msp_params(ctx->g_k, &W0, &m0);
-      const double l2 = (double)nN * (2.0 / (W0 + 1) + 1.0 / 64.0) * 2.7 * 16;
-      size_t budget = have + free_b;
-      if (ctx->mem_budget) budget = std::min(budget, ctx->mem_budget);
-      const double room = 0.5 * (double)budget - (double)msp_need(ctx, nN);
-      if (room > 0 && l2 > 0) slack = std::min(2.0, 1.0 + room / l2);
-    }
-    return msp_count_tiles(ctx, ms, d_data, nN, 0, ntiles, slack);
-  }
-  // A batch whose records do not fit beside the caller's data is counted in `passes` passes over
-  // the WHOLE input, each emitting only the runs of 1/passes of the leaves (leaf id low bits): the
-  // partition kernel's front end runs again every pass, but every pass produces the FINAL counts
-  // of its leaves -- nothing to merge afterwards, and the result stays in per-leaf list form.
-  int sel_bits = 0;
-  while ((1 << sel_bits) < passes) ++sel_bits;
-  for (int pass = 0; pass < passes; ++pass) {
-    if ((rc = msp_count_tiles(ctx, ms, d_data, nN, 0, ntiles, 1.0, sel_bits, (uint32_t)pass, pass == 0))) {
-      // a refusal after the first pass must not reach the caller's fallback (it would count
-      // the finished passes twice)
-      if (pass > 0 && (rc == CFRK_ERR_NOMEM || rc == CFRK_INTERNAL_FLOOD)) return cfrk_fail(ctx, CFRK_ERR_STATE, "out of device memory in pass %d of a multi-pass add", pass);
-      return rc;
-    }
-  }
-  return CFRK_OK;
+  int W0, m0;
+  msp_params(ctx->g_k, &W0, &m0);
+  const double l2 = (double)nN * (2.0 / (W0 + 1) + 1.0 / 64.0) * 2.7 * 16;      // bytes of the leaf streams
+  return msp_for_each_pass(ctx, passes, true, have, msp_need(ctx, nN), l2, [&](double slack, int sel_bits, uint32_t sel_val, bool first) {
+    return msp_count_tiles(ctx, ms, d_data, nN, 0, ntiles, slack, sel_bits, sel_val, first);
+  });
 }
 
 int cfrk_msp_sync_stats(cfrk_ctx *ctx, uint64_t st[ST_NWORDS]) {
@@ -2969,50 +2861,20 @@ extern "C" int cfrk_global_export_runs_device(cfrk_ctx *ctx, void *d_packed, uin
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (ctx->g_two) return cfrk_msp2_export_runs(ctx, d_packed, cap_rows, parts, part_rows);
   const MspView &v = ms->view;
-  if (ms->runs_unchecked) {
-    // a CFRK_RUNS_DEFER add: did its regions hold?  (an add without the flag lays an overflowing level out again)
-    uint64_t st0[ST_NWORDS];
-    int rc0 = cfrk_msp_sync_stats(ctx, st0);
-    if (rc0) return rc0;
-    if (st0[ST_L1OVF] || st0[ST_L2OVF] || st0[ST_OVFN] || st0[ST_OVFN1] || st0[ST_CWRAP])
-      return cfrk_fail(ctx, CFRK_ERR_STATE, "the CFRK_RUNS_DEFER add overflowed a record region: add again without the flag");
-    ms->runs_unchecked = false;
-  }
+  int rc;
+  if ((rc = runs_check_deferred(ctx, ms))) return rc;
   if (!ms->runs_deduped) {
     hipLaunchKernelGGL(msp_dedupe_export_kernel, dim3(NLEAF), dim3(DX_THREADS), 0, ctx->stream, ctx->g_k, (ctx->g_flags & CFRK_CANONICAL) ? 1 : 0, v);
     HIP_TRY(ctx, hipGetLastError());
     ms->runs_deduped = true;
   }
-  const int lpp = (NLEAF + parts - 1) / parts;           // leaves per part (owner p: leaves p, p+parts, ...)
-  const int hrows = runs_header_rows(lpp);
-  int rc;
-  void *p;
-  // offsets, headers and segment sizes are worked out on the device (one workgroup); the host
-  // only learns the segment sizes -- together with the job's flags, in ONE copy
-  if ((rc = cfrk_pool_get(ctx, BUF_SCRATCH, (NLEAF + 65 + ST_NWORDS + 1 + 64 + 72) * sizeof(uint64_t) + (size_t)NLEAF * sizeof(uint4), &p))) return rc;
-  uint64_t *d_off = (uint64_t *)p, *d_rows = d_off + NLEAF;
-  uint64_t *d_seg = d_rows + 65 + ST_NWORDS + 1;
-  unsigned long long *d_sync = (unsigned long long *)(d_seg + 64);
-  uint4 *d_sz = (uint4 *)(d_sync + 72);      // (16-byte aligned: the pool is, and NLEAF + 65 + ST_NWORDS + 1 is even)
-  static_assert((NLEAF + 65 + ST_NWORDS + 1 + 64 + 72) % 2 == 0, "d_sz is 16-byte aligned");
-  hipLaunchKernelGGL(msp_runs_sizes_kernel, dim3(NLEAF / 256), dim3(256), 0, ctx->stream, v, d_sz, d_sync);
-  HIP_TRY(ctx, hipGetLastError());
-  hipLaunchKernelGGL(msp_runs_plan_kernel, dim3(runs_plan_grid(parts, lpp)), dim3(1024), 0, ctx->stream, (const uint4 *)d_sz, parts, lpp, hrows, d_off,
-                     d_rows + parts, d_seg, d_sync);
-  HIP_TRY(ctx, hipGetLastError());
-  hipLaunchKernelGGL(msp_runs_gather_kernel, dim3(NLEAF), dim3(256), 0, ctx->stream, v, (const uint64_t *)d_off, (uint4 *)d_packed,
-                     (const uint64_t *)d_rows, (const uint64_t *)d_seg, parts, cap_rows);
-  HIP_TRY(ctx, hipGetLastError());
-  // [0, 65): all rows at [parts]; then the job's flags; then the segment starts -- ONE copy
-  uint64_t h[65 + ST_NWORDS + 1 + 64];
-  HIP_TRY(ctx, hipMemcpyAsync(d_rows + 65, ctx->g_stats, ST_NWORDS * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(h, d_rows, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const uint64_t *st = h + 65, *seg = h + 65 + ST_NWORDS + 1;
-  if (st[ST_SPILLED] || st[ST_ONES]) return cfrk_fail(ctx, CFRK_ERR_STATE, "part of the batch was counted in the HBM table");
-  if (h[parts] > cap_rows) return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "%llu rows, room for %llu", (unsigned long long)h[parts], (unsigned long long)cap_rows);
-  for (int q = 0; q < parts; ++q) part_rows[q] = (q + 1 < parts ? seg[q + 1] : h[parts]) - seg[q];
-  return CFRK_OK;
+  return runs_export_host(ctx, cap_rows, parts, part_rows,
+    [&](uint4 *d_sz, unsigned long long *d_sync) {
+      hipLaunchKernelGGL(msp_runs_sizes_kernel, dim3(NLEAF / 256), dim3(256), 0, ctx->stream, v, d_sz, d_sync);
+    },
+    [&](const uint64_t *d_off, const uint64_t *d_rows, const uint64_t *d_seg) {
+      hipLaunchKernelGGL(msp_runs_gather_kernel, dim3(NLEAF), dim3(256), 0, ctx->stream, v, d_off, (uint4 *)d_packed, d_rows, d_seg, parts, cap_rows);
+    });
 }
 
 extern "C" int cfrk_global_merge_runs_device(cfrk_ctx *ctx, const void *d_packed, const uint64_t *recv_rows, int parts) {
@@ -3028,58 +2890,31 @@ extern "C" int cfrk_global_merge_runs_device(cfrk_ctx *ctx, const void *d_packed
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   const int k = ctx->g_k;
   const int canon = (ctx->g_flags & CFRK_CANONICAL) ? 1 : 0;
-  const int lpp = (NLEAF + parts - 1) / parts;
-  const int hrows = runs_header_rows(lpp);
-  const size_t nseg = (size_t)parts * lpp;
   int rc;
-  void *p;
-  RunsRecv rr;
-  memset(&rr, 0, sizeof rr);
-  uint64_t rows_all = 0;
-  for (int r = 0; r < parts; ++r) {
-    if (recv_rows[r] < (uint64_t)hrows) return cfrk_fail(ctx, CFRK_ERR_ARG, "rank %d sent %llu rows, fewer than its header", r, (unsigned long long)recv_rows[r]);
-    rr.rstart[r] = rows_all; rr.rows[r] = recv_rows[r];
-    rows_all += recv_rows[r];
-  }
   MspView &v = ms->view;
-  memset(&v, 0, sizeof v);
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_AUX, (size_t)NLEAF * 8 + (size_t)(B1 * NXG + (NCLS + 1) * NLEAF) * sizeof(uint32_t), &p))) return rc;
-  v.leaf_off = (uint64_t *)p;
-  v.cnt1 = (uint32_t *)(v.leaf_off + NLEAF); v.nxg = NXG; v.cnt2 = v.cnt1 + B1 * NXG; v.leaf_n = v.cnt2 + NCLS * NLEAF;
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_LAYOUT, (size_t)NCLS * NLEAF * (sizeof(uint64_t) + sizeof(uint32_t)), &p))) return rc;
-  uint64_t *d_lbase = (uint64_t *)p;
-  uint32_t *d_lcap = (uint32_t *)(d_lbase + NCLS * NLEAF);
-  v.exact = 1; v.lbase = d_lbase; v.lcap = d_lcap;
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_OUTK, (size_t)ctx->g_cap * 8, &p))) return rc;
-  v.out_keys = (uint64_t *)p;
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_OUTC, (size_t)ctx->g_cap * 4, &p))) return rc;
-  v.out_cnt = (uint32_t *)p; v.out_cap = ctx->g_cap;
-  v.stats = ctx->g_stats; v.dbg = ctx->dbg_flags;
-  if ((rc = cfrk_pool_get(ctx, BUF_SCRATCH, (nseg * 3 + 2) * sizeof(uint64_t) + nseg * sizeof(uint32_t), &p))) return rc;
-  uint64_t *d_src = (uint64_t *)p, *d_d1 = d_src + nseg, *d_d0 = d_d1 + nseg, *d_out = d_d0 + nseg;
-  uint32_t *d_segrows = (uint32_t *)(d_out + 2);
-  HIP_TRY(ctx, hipMemsetAsync(d_out, 0, 2 * sizeof(uint64_t), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->g_stats + ST_CURSOR, 0, sizeof(uint64_t), ctx->stream));
+  RunsPlan pl;
+  // (one stream of complete and one of truncated runs per leaf, a record a row)
+  if ((rc = runs_merge_plan_host<NCLS, 1, 0, 1>(ctx, d_packed, recv_rows, parts, [&](uint64_t **lbase, uint32_t **lcap, uint32_t **cnt2) -> int {
+        int rc2;
+        void *p;
+        memset(&v, 0, sizeof v);
+        v.nxg = NXG;
+        if ((rc2 = msp_aux_buffers(ctx, v, (size_t)NLEAF, NXG, (size_t)NCLS * NLEAF))) return rc2;
+        if ((rc2 = cfrk_pool_get(ctx, BUF_MSP_LAYOUT, (size_t)NCLS * NLEAF * (sizeof(uint64_t) + sizeof(uint32_t)), &p))) return rc2;
+        *lbase = (uint64_t *)p; *lcap = (uint32_t *)(*lbase + NCLS * NLEAF);
+        v.exact = 1; v.lbase = *lbase; v.lcap = *lcap;
+        if ((rc2 = cfrk_pool_get(ctx, BUF_MSP_OUTK, (size_t)ctx->g_cap * 8, &p))) return rc2;
+        v.out_keys = (uint64_t *)p;
+        if ((rc2 = cfrk_pool_get(ctx, BUF_MSP_OUTC, (size_t)ctx->g_cap * 4, &p))) return rc2;
+        v.out_cnt = (uint32_t *)p; v.out_cap = ctx->g_cap;
+        v.stats = ctx->g_stats; v.dbg = ctx->dbg_flags;
+        *cnt2 = v.cnt2;
+        return CFRK_OK;
+      }, &pl, &v.rec2))) return rc;
+  const int lpp = pl.lpp;
   TableView t = cfrk_table_view(ctx);
-  // segment (source rank, local leaf): the ranks' headers say how large; all offsets on the device
-  hipLaunchKernelGGL((msp_runs_layout1_kernel<NCLS, 1, 0, 1>), dim3((unsigned)(lpp + 255) / 256), dim3(256), 0, ctx->stream, (const uint4 *)d_packed, rr, parts, lpp,
-                     d_segrows, d_d1, d_d0, d_lcap, d_out);
-  HIP_TRY(ctx, hipGetLastError());
-  hipLaunchKernelGGL((msp_runs_layout_kernel<NCLS, 1, 0>), dim3((unsigned)parts + 1u), dim3(1024), 0, ctx->stream, rr, parts, lpp, hrows, (const uint32_t *)d_segrows,
-                     d_src, d_d1, d_d0, d_lbase, (const uint32_t *)d_lcap, v.cnt2, d_out);
-  HIP_TRY(ctx, hipGetLastError());
-  // the headers are checked before anything is copied by them: sizes that add up to the rows each
-  // rank sent keep every segment inside its rank's part of the buffer and every stream inside rec2
-  uint64_t h[2];
-  HIP_TRY(ctx, hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (h[1]) return cfrk_fail(ctx, CFRK_ERR_ARG, "a rank's header does not add up to the rows it sent");
-  // the leaf streams: what arrived, every note a record again (h[0] records; at most eight per row)
-  if (h[0] > rows_all * NOTES_PER_ROW) return cfrk_fail(ctx, CFRK_ERR_ARG, "the headers announce more records than the rows can hold");
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_L2, (size_t)(h[0] ? h[0] : 1) * sizeof(uint4), &p))) return rc;
-  v.rec2 = (uint4 *)p;
-  hipLaunchKernelGGL(msp_runs_scatter_kernel, dim3((unsigned)nseg), dim3(256), 0, ctx->stream, (const uint4 *)d_packed, rr, lpp, k,
-                     (const uint64_t *)d_src, (const uint64_t *)d_d1, (const uint64_t *)d_d0, v.rec2);
+  hipLaunchKernelGGL(msp_runs_scatter_kernel, dim3((unsigned)pl.nseg), dim3(256), 0, ctx->stream, (const uint4 *)d_packed, pl.rr, lpp, k,
+                     pl.src, pl.d1, pl.d0, v.rec2);
   HIP_TRY(ctx, hipGetLastError());
   if (canon) hipLaunchKernelGGL((msp_p3_kernel<true, false>), dim3(lpp), dim3(P3_THREADS), 0, ctx->stream, k, P3_WEIGHTED, v, t);
   else hipLaunchKernelGGL((msp_p3_kernel<false, false>), dim3(lpp), dim3(P3_THREADS), 0, ctx->stream, k, P3_WEIGHTED, v, t);
@@ -3154,14 +2989,7 @@ extern "C" int cfrk_global_merge_runs_group_device(cfrk_ctx *ctx, const void *d_
     v.stats = ctx->g_stats; v.dbg = ctx->dbg_flags;
     HIP_TRY(ctx, hipMemsetAsync(ctx->g_stats + ST_CURSOR, 0, sizeof(uint64_t), ctx->stream));
   }
-  P3ListsT<true> lx;
-  memset(&lx, 0, sizeof lx);
-  lx.packed = (const uint4 *)d_recv;
-  uint64_t at = 0;
-  for (int r = 0; r < parts; ++r) { lx.rr.rstart[r] = at; lx.rr.rows[r] = recv_rows[r]; at += recv_rows[r]; }
-  lx.parts = parts;
-  lx.ll0 = runs_ll0(lpp, group, ngroups);
-  lx.lcount = runs_ll0(lpp, group + 1, ngroups) - lx.ll0;
+  const P3ListsT<true> lx = runs_group_lists(d_recv, recv_rows, parts, group, ngroups);
   TableView t = cfrk_table_view(ctx);
   if (lx.lcount) {
     if (ctx->g_flags & CFRK_CANONICAL) hipLaunchKernelGGL((msp_p3_lists_kernel<true>), dim3(lx.lcount), dim3(P3_THREADS), 0, ctx->stream, ctx->g_k, v, t, lx);

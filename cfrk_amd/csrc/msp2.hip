@@ -12,6 +12,10 @@
 //     first, as in msp.hip; results go to a two-word list.
 // Anything that does not fit is counted in the two-word HBM table (table_add2).
 //
+// msp_shared.h holds what the two files share and that does not depend on the record format (layout and sum
+// kernels, sizing rules, index buffers, the exact level-1 layout, the passes of a batch that does not fit),
+// msp_runs.h the exchange by runs, host side included.
+//
 // Semantics: the guarded ComputeFreq of /root/reference/src/kmer_kernel.cu:52-70 summed over
 // reads, like global_hash.hip.
 #include "msp.h"
@@ -23,6 +27,7 @@
 #include <vector>
 
 namespace {
+#include "msp_shared.h"
 #include "msp_runs.h"
 
 // Window (m-mers per k-mer the minimizer is taken over = longest run): all but a margin of c = 1 on
@@ -53,11 +58,11 @@ struct View2 {
   uint64_t *out_lo, *out_hi; uint32_t *out_cnt; uint64_t out_cap;
   uint64_t *leaf_off; uint32_t *leaf_n;                  // where each leaf's entries sit in the result list (shared leaves: one
                                                          // segment per sub-value, entry (leaf << sub_bits) | sub-value)
-  // exact layout after leaf streams overflowed the fixed stride (see msp.hip): stream (leaf, class)
+  // exact layout after leaf streams overflowed the fixed stride (msp_count_tiles of either file): stream (leaf, class)
   // starts at record lbase[NCLS * leaf + class] and holds exactly lcap[...] records
   const uint64_t *lbase; const uint32_t *lcap; uint32_t exact;
   Rec2 *ovf; uint32_t ovf_cap;                           // parking for a few overflowing records
-  // the same for the level-1 regions (msp.hip): region reg starts at record rbase[reg], holds rcap[reg]
+  // the same for the level-1 regions (msp_shared.h: msp_layout_level1): region reg starts at record rbase[reg], holds rcap[reg]
   const uint64_t *rbase; const uint32_t *rcap; uint32_t exact1;
   Rec2 *ovf1; uint32_t ovf1_cap;
   uint32_t count_only;                                   // second-level kernel: count the streams' records, write nothing
@@ -71,6 +76,7 @@ struct View2 {
 // Truncated runs are split by length class as well, so that in the leaf kernel the lanes of a
 // wave expand records of similar length.
 constexpr int NCLS = 4;                                   // 0..2 truncated (n<=4, <=10, >10), 3 complete
+static_assert(NCLS <= SUM_CLASSES, "msp_sum_kernel clears a word per class");
 constexpr int NSUB = NCLS * B2;
 __device__ __forceinline__ uint32_t cls_of(uint32_t w) {
   const uint32_t n = (w & 63u) + 1u;
@@ -138,9 +144,7 @@ __device__ __noinline__ void spill_record2(uint4 ra, uint4 rb, int k, bool canon
 }
 
 // ---------------------------------------------------------------------------------------- Q1
-// level-1 region / cursor of (bin, sub-region): sub-region major, so that a workgroup's 256
-// reservations (memory-side atomics, one request per touched 64 bytes) are 16 requests (msp.hip: l1_reg)
-__host__ __device__ __forceinline__ uint32_t q1_reg(uint32_t bin, uint32_t xg) { return xg * (uint32_t)B1 + bin; }
+// (level-1 region / cursor of (bin, sub-region): l1_reg, msp_shared.h)
 __device__ __forceinline__ uint64_t q1_cap(const View2 &v, uint32_t reg) { return v.exact1 ? (uint64_t)v.rcap[reg] : v.cap1; }
 __device__ __forceinline__ uint64_t q1_at(const View2 &v, uint32_t reg) { return v.exact1 ? v.rbase[reg] : (uint64_t)reg * v.cap1; }
 // a record that found its level-1 region full: a few are parked (and counted through the HBM table
@@ -203,7 +207,6 @@ __device__ __forceinline__ Rec2 q1_build(const Stage2 &st, uint32_t d, int k, in
 // and 7 of the packed minimum: hash bits, equal for every occurrence of a k-mer) and writes them to
 // the record's spare word: the leaf kernel then splits an overfull leaf by RECORD, not by key, so
 // that every record is expanded once.  2 KB more staging per wave: two workgroups per CU.
-constexpr int SUB_BITS = 5;
 template <int W2, bool SUB>
 __global__ __launch_bounds__(Q1_THREADS, (SUB ? 4 : 6)) void msp2_p1_kernel(const int8_t *__restrict__ data, int64_t nN,
                                                              int k, int m, int c, int canon, int64_t tile0,
@@ -327,7 +330,7 @@ __global__ __launch_bounds__(Q1_THREADS, (SUB ? 4 : 6)) void msp2_p1_kernel(cons
     S2 &= ~(0x80000000u >> a);
     const Rec2 rec = q1_build(st, ((uint32_t)lane << 5) | (uint32_t)a, k, c, W2);
     if (((rec.b.w >> 8) & v.sel_mask) != v.sel_val) continue;    // not a leaf of this pass
-    const uint32_t reg = q1_reg(rec.b.w >> 16, blockIdx.x & (NXG - 1));
+    const uint32_t reg = l1_reg(rec.b.w >> 16, blockIdx.x & (NXG - 1));
     const uint32_t dst = atomicAdd(&v.cnt1[reg], 1u);
     if (dst < q1_cap(v, reg)) v.rec1[q1_at(v, reg) + dst] = rec;
     else q1_overflow(v, rec.a, rec.b, k, canon != 0, t);
@@ -356,7 +359,7 @@ __global__ __launch_bounds__(Q1_THREADS, (SUB ? 4 : 6)) void msp2_p1_kernel(cons
   uint32_t my_base = 0;
   if (tid < B1) {
     const uint32_t cnum = hist[tid];
-    if (cnum) my_base = atomicAdd(&v.cnt1[q1_reg(tid, blockIdx.x & (NXG - 1))], cnum);
+    if (cnum) my_base = atomicAdd(&v.cnt1[l1_reg(tid, blockIdx.x & (NXG - 1))], cnum);
   }
   block_scan<B1, true>(hist, loff, wtot);                // ends with a barrier: the staging area is dead
   if (tid == B1 - 1) nrec_s = loff[tid] + hist[tid];
@@ -372,7 +375,7 @@ __global__ __launch_bounds__(Q1_THREADS, (SUB ? 4 : 6)) void msp2_p1_kernel(cons
 
   // ---- D: copy out in bin order ----
   auto put = [&](uint32_t b, uint32_t dst, const Rec2 &rec) {
-    const uint32_t reg = q1_reg(b, blockIdx.x & (NXG - 1));
+    const uint32_t reg = l1_reg(b, blockIdx.x & (NXG - 1));
     if (dst < q1_cap(v, reg)) v.rec1[q1_at(v, reg) + dst] = rec;
     else q1_overflow(v, rec.a, rec.b, k, canon != 0, t);
   };
@@ -395,7 +398,7 @@ __global__ __launch_bounds__(Q1_THREADS, (SUB ? 4 : 6)) void msp2_p1_kernel(cons
     const uint32_t p = q >> 1;
     const uint32_t b = arena[p].b.w >> 16;
     const uint32_t dst = gbase[b] + (p - loff[b]);
-    const uint32_t reg = q1_reg(b, blockIdx.x & (NXG - 1));
+    const uint32_t reg = l1_reg(b, blockIdx.x & (NXG - 1));
     if (dst < q1_cap(v, reg)) out4[(q1_at(v, reg) + dst) * 2 + (q & 1u)] = arena4[q];
     else if (!(q & 1u)) q1_overflow(v, arena[p].a, arena[p].b, k, canon != 0, t);
   }
@@ -418,9 +421,9 @@ __global__ __launch_bounds__(Q2_THREADS) void msp2_p2_kernel(int groups_per_bin,
   const uint32_t grp = seq % (uint32_t)groups_per_bin;
   // the bin's sub-regions are read as one stream (as in msp.hip's P2)
   if (tid < 64) {
-    const uint32_t c = (tid < NXG) ? (uint32_t)min((uint64_t)v.cnt1[q1_reg(b1, tid)], q1_cap(v, q1_reg(b1, tid))) : 0u;
+    const uint32_t c = (tid < NXG) ? (uint32_t)min((uint64_t)v.cnt1[l1_reg(b1, tid)], q1_cap(v, l1_reg(b1, tid))) : 0u;
     const uint32_t incl = dev_wave_scan_incl(c);
-    if (tid < NXG) { rpre[tid] = incl - c; rfirst[tid] = q1_at(v, q1_reg(b1, tid)); }
+    if (tid < NXG) { rpre[tid] = incl - c; rfirst[tid] = q1_at(v, l1_reg(b1, tid)); }
     if (tid == 63) rpre[NXG] = incl;
   }
   lds_barrier();
@@ -1362,7 +1365,6 @@ __global__ __launch_bounds__(256) void msp2_huge_leaves_kernel(int k, int canon,
   }
 }
 
-// exact layout of the second level from the demand the first attempt counted (see msp.hip)
 // bytes that are not a base (read terminators, N): one 64-bit sum (a batch that does not fit is looked
 // at before it is planned again: every such byte ends up to k k-mers)
 __global__ __launch_bounds__(256) void msp2_count_invalid_kernel(const int8_t *__restrict__ data, int64_t nN,
@@ -1388,52 +1390,18 @@ __global__ __launch_bounds__(256) void msp2_count_invalid_kernel(const int8_t *_
   if ((threadIdx.x & 63) == 0 && mine) atomicAdd(out, mine);
 }
 
-// (either level: base = exclusive prefix sum of the n cursors, cap = the cursors themselves)
-// sum of n cursors (one workgroup): how many records the first chunk of a batch made
-__global__ __launch_bounds__(1024) void msp2_sum_kernel(const uint32_t *__restrict__ cnt, uint32_t n, uint64_t *out) {
-  __shared__ unsigned long long tot;
-  if (threadIdx.x == 0) tot = 0;
-  __syncthreads();
-  unsigned long long mine = 0;
-  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) mine += cnt[i];
-  atomicAdd(&tot, mine);
-  __syncthreads();
-  if (threadIdx.x == 0) { out[0] = tot; out[1] = out[2] = out[3] = out[4] = 0; }
-}
-
-// ... and how they split into the four classes of streams: the records of sub-region 0 of every level-1
-// bin (1/64 of the chunk, every bin in it) -- out[1 + class] += records of that class (msp.hip)
+// the first chunk of a batch (behind msp_sum_kernel): how its records split into the four classes of streams -- the
+// records of sub-region 0 of every level-1 bin (1/64 of the chunk, every bin in it): out[1 + class] += records of that class
 __global__ __launch_bounds__(256) void msp2_class_sample_kernel(View2 v, unsigned long long *out) {
   __shared__ uint32_t c[NCLS];
   if (threadIdx.x < NCLS) c[threadIdx.x] = 0;
   __syncthreads();
-  const uint32_t reg = q1_reg(blockIdx.x, 0u);
+  const uint32_t reg = l1_reg(blockIdx.x, 0u);
   const uint32_t n = (uint32_t)min((uint64_t)v.cnt1[reg], v.cap1);
   const uint32_t *w = reinterpret_cast<const uint32_t *>(v.rec1 + (uint64_t)reg * v.cap1) + 7;
   for (uint32_t i = threadIdx.x; i < n; i += 256u) atomicAdd(&c[cls_of(w[8 * (size_t)i])], 1u);
   __syncthreads();
   if (threadIdx.x < NCLS && c[threadIdx.x]) atomicAdd(&out[1 + threadIdx.x], (unsigned long long)c[threadIdx.x]);
-}
-
-__global__ __launch_bounds__(1024) void msp2_layout_kernel(const uint32_t *__restrict__ cnt, uint32_t n, uint64_t *__restrict__ base,
-                                                           uint32_t *__restrict__ cap) {
-  __shared__ unsigned long long part[1024];
-  const uint32_t per = (n + 1023u) / 1024u;
-  const uint32_t tid = threadIdx.x;
-  unsigned long long s = 0;
-  for (uint32_t i = 0; i < per; ++i) { const uint32_t l = tid * per + i; if (l < n) s += cnt[l]; }
-  part[tid] = s;
-  __syncthreads();
-  if (tid == 0) {
-    unsigned long long run = 0;
-    for (int i = 0; i < 1024; ++i) { const unsigned long long x = part[i]; part[i] = run; run += x; }
-  }
-  __syncthreads();
-  unsigned long long run = part[tid];
-  for (uint32_t i = 0; i < per; ++i) {
-    const uint32_t l = tid * per + i;
-    if (l < n) { const uint32_t c = cnt[l]; base[l] = run; cap[l] = c; run += c; }
-  }
 }
 
 // the few records that did not fit their leaf stream: counted k-mer by k-mer in the HBM table
@@ -1984,6 +1952,15 @@ static uint32_t msp2_hbits(const cfrk_ctx *ctx, uint32_t sub_bits, uint64_t per_
 // lean: the leaf streams get no room up front; the second-level kernel first only COUNTS them, they are
 // laid out back to back with exactly that room, and the kernel runs again (a batch that would need
 // more passes over the input otherwise: one more read of the level-1 records is cheaper than a pass)
+// the result list of a View2, and -- where the leaf kernel wrote one -- its leaf index, to the view that the
+// code common to all key widths reads (msp.h: MspView; no record levels)
+static void msp2_publish_view(cfrk_msp *ms, const View2 &v, bool leaf_index) {
+  ms->view.out_keys = v.out_lo; ms->view.out_hi = v.out_hi; ms->view.out_cnt = v.out_cnt;
+  ms->view.out_cap = v.out_cap; ms->view.stats = v.stats; ms->view.cnt1 = nullptr;
+  ms->view.leaf_off = leaf_index ? v.leaf_off : nullptr; ms->view.leaf_n = leaf_index ? v.leaf_n : nullptr;
+  ms->view.seg_bits = leaf_index ? v.sub_bits : 0u;
+}
+
 // deduplicate every leaf's complete stream where it lies (the one-shot runs export reads the result)
 static int msp2_dedupe_in_place(cfrk_ctx *ctx, const View2 &v) {
   const int k = ctx->g_k, canon = (ctx->g_flags & CFRK_CANONICAL) ? 1 : 0;
@@ -2037,20 +2014,13 @@ static int msp2_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, i
   }
   v.cap2c = cap2c; v.cap2t = cap2t; v.count_only = lean ? 1u : 0u;
   v.sel_mask = (1u << sel_bits) - 1u; v.sel_val = sel_val; v.sel_bits = (uint32_t)sel_bits;
-  // far more distinct k-mers expected than the leaf tables hold (65536 x ~2500): records carry extra
-  // minimizer-hash bits and 2^sub_bits workgroups share a leaf (~2000 distinct k-mers each)
-  uint32_t sub_bits = 0;
-  while (sub_bits < (uint32_t)SUB_BITS && ((ctx->g_cap / NLEAF) >> sub_bits) > 2048u) ++sub_bits;
-  if (ctx->g_cap / NLEAF <= 4096u) sub_bits = 0;
-  if ((ctx->dbg_flags & CFRK_DEBUG_RECORD_SUBSETS) && sub_bits < 2u) sub_bits = 2u;
+  const uint32_t sub_bits = msp_sub_bits(ctx, ctx->g_cap / NLEAF);
   const bool sub = sub_bits != 0u;
   v.sub_bits = sub_bits;
   v.hbits = msp2_hbits(ctx, sub_bits, ctx->g_cap / NLEAF);
   // (leaf index: one entry per leaf, or per (leaf, sub-value) when leaves are shared)
   const size_t nseg = (size_t)NLEAF << sub_bits;
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_AUX, nseg * 8 + ((size_t)B1 * NXG + (size_t)NCLS * NLEAF + nseg) * sizeof(uint32_t), &p))) return rc;
-  v.leaf_off = (uint64_t *)p;
-  v.cnt1 = (uint32_t *)(v.leaf_off + nseg); v.cnt2 = v.cnt1 + B1 * NXG; v.leaf_n = v.cnt2 + NCLS * NLEAF;
+  if ((rc = msp_aux_buffers(ctx, v, nseg, NXG, (size_t)NCLS * NLEAF))) return rc;
   if ((rc = cfrk_pool_get(ctx, BUF_MSP_OUTK, (size_t)ctx->g_cap * 8, &p))) return rc;
   v.out_lo = (uint64_t *)p;
   if ((rc = cfrk_pool_get(ctx, BUF_MSP_OUTH, (size_t)ctx->g_cap * 8, &p))) return rc;
@@ -2060,14 +2030,12 @@ static int msp2_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, i
   v.stats = ctx->g_stats; v.dbg = ctx->dbg_flags;
   TableView t = cfrk_table_view(ctx);
 
-  // (cnt1, cnt2 and -- first pass only -- the leaf index and the list cursor)
-  HIP_TRY(ctx, hipMemsetAsync(v.cnt1, 0, ((size_t)B1 * NXG + (size_t)NCLS * NLEAF + (first ? nseg : 0)) * sizeof(uint32_t), ctx->stream));
-  if (first) HIP_TRY(ctx, hipMemsetAsync(ctx->g_stats + ST_CURSOR, 0, sizeof(uint64_t), ctx->stream));
+  if ((rc = msp_aux_clear(ctx, v, nseg, NXG, (size_t)NCLS * NLEAF, first))) return rc;
   // Both levels are laid out for an input that spreads evenly over the minimizer space; one that does
   // not overflows its regions.  The cursors keep counting past the capacity, so after Q2 the host
   // knows the exact demand of both levels (one D2H + stream sync per add): a few overflowing records
   // were parked and are counted through the HBM table, more than that and the level is laid out again
-  // back to back with exactly the room each region needs, and its kernel runs again (msp.hip).
+  // back to back with exactly the room each region needs, and its kernel runs again (msp.hip: msp_count_tiles).
   constexpr uint32_t OVF_CAP = 1u << 19;
   if ((rc = cfrk_pool_get(ctx, BUF_MSP_OVF, (size_t)OVF_CAP * sizeof(Rec2), &p))) return rc;
   v.ovf = (Rec2 *)p; v.ovf_cap = (uint32_t)std::min<double>((double)OVF_CAP, expect / 256.0);
@@ -2116,7 +2084,7 @@ static int msp2_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, i
         if (cc == 0) {
           void *sp;
           if ((rc = cfrk_pool_get(ctx, BUF_SCRATCH, 64 * sizeof(uint64_t), &sp))) return rc;
-          hipLaunchKernelGGL(msp2_sum_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t *)v.cnt1, (uint32_t)nreg, (uint64_t *)sp);
+          hipLaunchKernelGGL(msp_sum_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t *)v.cnt1, (uint32_t)nreg, (uint64_t *)sp);
           HIP_TRY(ctx, hipGetLastError());
           hipLaunchKernelGGL(msp2_class_sample_kernel, dim3(B1), dim3(256), 0, ctx->stream, v, (unsigned long long *)sp);
           HIP_TRY(ctx, hipGetLastError());
@@ -2124,7 +2092,7 @@ static int msp2_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, i
           HIP_TRY(ctx, hipMemcpyAsync(made, sp, sizeof made, hipMemcpyDeviceToHost, ctx->stream));
           HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
           // records of this pass's leaves in the whole batch (+3 %), per leaf, split by the sample: complete
-          // runs up to 1.45 x their share of the mean leaf (1.3 x parks records of a few leaves, msp.hip), the largest class of truncated runs up to 1.6 x its share
+          // runs and the largest class of truncated runs with the room of msp_leaf_slack over their share of the mean leaf
           const double per_leaf = (double)made[0] * ((double)ntiles / (double)(t1 - t0)) * 1.03 / (double)(NLEAF >> sel_bits);
           const uint64_t sampled = made[1] + made[2] + made[3] + made[4];
           double fc = 0.75, ft = 0.3;
@@ -2132,10 +2100,8 @@ static int msp2_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, i
             fc = (double)made[4] / (double)sampled + 0.02;
             ft = (double)std::max(made[1], std::max(made[2], made[3])) / (double)sampled + 0.01;
           }
-          // (the slack grows with how few distinct runs a leaf holds, msp.hip)
-          const double lambda = std::max(4.0, (double)ctx->g_cap / 3.0 / (double)NLEAF * 4.0 / (double)(W2 + 1));
-          const double fc_slack = std::min(4.0, std::max(1.45, 1.2 + 6.5 / std::sqrt(lambda)));
-          const double ft_slack = std::min(4.0, std::max(1.6, 1.3 + 6.5 / std::sqrt(lambda)));
+          double fc_slack, ft_slack;
+          msp_leaf_slack(ctx, W2, &fc_slack, &ft_slack);
           v.cap2c = (uint64_t)(per_leaf * std::min(1.0, fc) * fc_slack) + 512; v.cap2t = (uint64_t)(per_leaf * std::min(1.0, ft) * ft_slack) + 256;
           if ((rc = cfrk_pool_get(ctx, BUF_MSP_L2, (size_t)(NLEAF >> sel_bits) * (v.cap2c + 3 * v.cap2t) * sizeof(Rec2), &p))) return rc;
           v.rec2 = (Rec2 *)p;
@@ -2144,9 +2110,8 @@ static int msp2_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, i
         HIP_TRY(ctx, hipGetLastError());
       }
       uint64_t stc[ST_NWORDS];
-      HIP_TRY(ctx, hipMemcpyAsync(stc, ctx->g_stats, sizeof stc, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      if (stc[ST_CWRAP]) return CFRK_INTERNAL_FLOOD;                     // (msp.hip: nothing of this pass has been counted yet)
+      if ((rc = cfrk_msp_sync_stats(ctx, stc))) return rc;
+      if (stc[ST_CWRAP]) return CFRK_INTERNAL_FLOOD;                     // (nothing of this pass has been counted yet)
       if (stc[ST_L1OVF] || stc[ST_L2OVF]) return CFRK_ERR_SMALL_BUF;   // (no error text: the caller starts over, the old way)
       parked1 = stc[ST_OVFN1]; parked2 = stc[ST_OVFN];
       settled = true;
@@ -2162,37 +2127,16 @@ static int msp2_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, i
     HIP_TRY(ctx, hipGetLastError());
     if (defer) { settled = true; break; }             // (whether a region overflowed is looked at by the export)
     uint64_t st[ST_NWORDS];
-    HIP_TRY(ctx, hipMemcpyAsync(st, ctx->g_stats, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = cfrk_msp_sync_stats(ctx, st))) return rc;
     if (st[ST_CWRAP]) return CFRK_INTERNAL_FLOOD;
     if (st[ST_L1OVF]) {
       // exact level-1 layout; Q2 ran on an incomplete level 1 and is redone as well
-      if ((rc = cfrk_pool_get(ctx, BUF_MSP_LAYOUT1, nreg * (sizeof(uint64_t) + sizeof(uint32_t)), &p))) return rc;
-      uint64_t *rbase = (uint64_t *)p;
-      uint32_t *rcap = (uint32_t *)(rbase + nreg);
-      hipLaunchKernelGGL(msp2_layout_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t *)v.cnt1, (uint32_t)nreg, rbase, rcap);
-      HIP_TRY(ctx, hipGetLastError());
-      {
-        // the heaviest bin decides how many tile groups per bin Q2 needs from now on
-        std::vector<uint32_t> c1(nreg);
-        HIP_TRY(ctx, hipMemcpyAsync(c1.data(), v.cnt1, nreg * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        uint64_t maxbin = 0, all = 0;
-        for (int b = 0; b < B1; ++b) {
-          uint64_t sum = 0;
-          for (int r = 0; r < NXG; ++r) sum += c1[q1_reg((uint32_t)b, (uint32_t)r)];
-          maxbin = std::max(maxbin, sum);
-          all += sum;
-        }
-        if (all > (uint64_t)B1 * NXG * cap1) {           // (more records than the density estimate allowed for)
-          if ((rc = cfrk_pool_get(ctx, BUF_MSP_L1, (size_t)all * sizeof(Rec2), &p))) return rc;
-          v.rec1 = (Rec2 *)p;
-        }
-        q2_groups = (int64_t)((maxbin + (uint64_t)Q2_TILE * Q2_GROUP - 1) / ((uint64_t)Q2_TILE * Q2_GROUP)) + 1;
-        if (q2_groups * B1 > 0x7FFFFFFF) return cfrk_fail(ctx, CFRK_ERR_ARG, "batch too large for one add");
-      }
-      HIP_TRY(ctx, hipMemsetAsync(v.cnt1, 0, (nreg + (size_t)NCLS * NLEAF) * sizeof(uint32_t), ctx->stream));   // cnt1 and cnt2
-      v.exact1 = 1; v.rbase = rbase; v.rcap = rcap;
+      // (the heaviest bin decides how many tile groups per bin Q2 needs from now on)
+      uint64_t maxbin;
+      if ((rc = msp_layout_level1(ctx, v.cnt1, NXG, (size_t)NCLS * NLEAF, cap1, &v.rec1, &v.rbase, &v.rcap, &maxbin))) return rc;
+      v.exact1 = 1;
+      q2_groups = (int64_t)((maxbin + (uint64_t)Q2_TILE * Q2_GROUP - 1) / ((uint64_t)Q2_TILE * Q2_GROUP)) + 1;
+      if (q2_groups * B1 > 0x7FFFFFFF) return cfrk_fail(ctx, CFRK_ERR_ARG, "batch too large for one add");
       run_q1 = true;
       continue;
     }
@@ -2201,7 +2145,7 @@ static int msp2_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, i
       if ((rc = cfrk_pool_get(ctx, BUF_MSP_LAYOUT, (size_t)NCLS * NLEAF * (sizeof(uint64_t) + 2 * sizeof(uint32_t)), &p))) return rc;
       uint64_t *lbase = (uint64_t *)p;
       uint32_t *lcap = (uint32_t *)(lbase + NCLS * NLEAF);
-      hipLaunchKernelGGL(msp2_layout_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t *)v.cnt2, (uint32_t)(NCLS * NLEAF), lbase, lcap);
+      hipLaunchKernelGGL(msp_layout_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t *)v.cnt2, (uint32_t)(NCLS * NLEAF), lbase, lcap, 0u);
       HIP_TRY(ctx, hipGetLastError());
       if (v.count_only) {
         // the streams' buffer: exactly what was counted (last stream's start + size)
@@ -2269,9 +2213,7 @@ static int msp2_count_tiles(cfrk_ctx *ctx, cfrk_msp *ms, const int8_t *d_data, i
     hipLaunchKernelGGL(msp2_huge_leaves_kernel, dim3((((unsigned)NLEAF >> sel_bits) + 255u) / 256u), dim3(256), 0, ctx->stream, k, canon, 0, (uint32_t)NLEAF >> sel_bits, v, t);
   }
   HIP_TRY(ctx, hipGetLastError());
-  ms->view.out_keys = v.out_lo; ms->view.out_hi = v.out_hi; ms->view.out_cnt = v.out_cnt;
-  ms->view.out_cap = v.out_cap; ms->view.stats = v.stats; ms->view.cnt1 = nullptr;
-  ms->view.leaf_off = v.leaf_off; ms->view.leaf_n = v.leaf_n; ms->view.seg_bits = v.sub_bits;
+  msp2_publish_view(ms, v, true);
   ms->pending = true;
   ms->leaf_form = true;
   ms->list_n_valid = false;
@@ -2296,54 +2238,25 @@ int cfrk_msp2_merge_lists(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t *d
 }
 
 // ------------------------------------------------------------------ multi-GPU exchange by runs
-// (cfrk_global_export_runs_device / cfrk_global_merge_runs_device of msp.hip for two-word keys;
-// the callers have checked the arguments and the job's state)
+// (cfrk_global_export_runs_device / cfrk_global_merge_runs_device of msp.hip for two-word keys: the callers have
+// checked the arguments and the job's state; the call sequence itself is msp_runs.h's)
 int cfrk_msp2_export_runs(cfrk_ctx *ctx, void *d_packed, uint64_t cap_rows, int parts, uint64_t *part_rows) {
   cfrk_msp *ms = ctx->msp;
   View2 v;
   memcpy(&v, ms->view2, sizeof v);
-  if (ms->runs_unchecked) {
-    // a CFRK_RUNS_DEFER add: did its regions hold?  (an add without the flag lays an overflowing level out again)
-    uint64_t st0[ST_NWORDS];
-    int rc0 = cfrk_msp_sync_stats(ctx, st0);
-    if (rc0) return rc0;
-    if (st0[ST_L1OVF] || st0[ST_L2OVF] || st0[ST_OVFN] || st0[ST_OVFN1] || st0[ST_CWRAP])
-      return cfrk_fail(ctx, CFRK_ERR_STATE, "the CFRK_RUNS_DEFER add overflowed a record region: add again without the flag");
-    ms->runs_unchecked = false;
-  }
+  int rc;
+  if ((rc = runs_check_deferred(ctx, ms))) return rc;
   if (!ms->runs_deduped) {
-    int rc0 = msp2_dedupe_in_place(ctx, v);
-    if (rc0) return rc0;
+    if ((rc = msp2_dedupe_in_place(ctx, v))) return rc;
     ms->runs_deduped = true;
   }
-  const int lpp = (NLEAF + parts - 1) / parts;           // leaves per part (owner p: leaves p, p+parts, ...)
-  const int hrows = runs_header_rows(lpp);
-  int rc;
-  void *p;
-  if ((rc = cfrk_pool_get(ctx, BUF_SCRATCH, (NLEAF + 65 + ST_NWORDS + 1 + 64 + 72) * sizeof(uint64_t) + (size_t)NLEAF * sizeof(uint4), &p))) return rc;
-  uint64_t *d_off = (uint64_t *)p, *d_rows = d_off + NLEAF;
-  uint64_t *d_seg = d_rows + 65 + ST_NWORDS + 1;
-  unsigned long long *d_sync = (unsigned long long *)(d_seg + 64);
-  uint4 *d_sz = (uint4 *)(d_sync + 72);      // (16-byte aligned: the pool is, and NLEAF + 65 + ST_NWORDS + 1 is even)
-  static_assert((NLEAF + 65 + ST_NWORDS + 1 + 64 + 72) % 2 == 0, "d_sz is 16-byte aligned");
-  hipLaunchKernelGGL(msp2_runs_sizes_kernel, dim3(NLEAF / 256), dim3(256), 0, ctx->stream, v, d_sz, d_sync);
-  HIP_TRY(ctx, hipGetLastError());
-  hipLaunchKernelGGL(msp_runs_plan_kernel, dim3(runs_plan_grid(parts, lpp)), dim3(1024), 0, ctx->stream, (const uint4 *)d_sz, parts, lpp, hrows, d_off,
-                     d_rows + parts, d_seg, d_sync);
-  HIP_TRY(ctx, hipGetLastError());
-  hipLaunchKernelGGL(msp2_runs_gather_kernel, dim3(NLEAF), dim3(256), 0, ctx->stream, v, (const uint64_t *)d_off, (uint4 *)d_packed,
-                     (const uint64_t *)d_rows, (const uint64_t *)d_seg, parts, cap_rows);
-  HIP_TRY(ctx, hipGetLastError());
-  // [0, 65): all rows at [parts]; then the job's flags; then the segment starts -- ONE copy
-  uint64_t h[65 + ST_NWORDS + 1 + 64];
-  HIP_TRY(ctx, hipMemcpyAsync(d_rows + 65, ctx->g_stats, ST_NWORDS * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(h, d_rows, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const uint64_t *st = h + 65, *seg = h + 65 + ST_NWORDS + 1;
-  if (st[ST_SPILLED] || st[ST_ONES]) return cfrk_fail(ctx, CFRK_ERR_STATE, "part of the batch was counted in the HBM table");
-  if (h[parts] > cap_rows) return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "%llu rows, room for %llu", (unsigned long long)h[parts], (unsigned long long)cap_rows);
-  for (int q = 0; q < parts; ++q) part_rows[q] = (q + 1 < parts ? seg[q + 1] : h[parts]) - seg[q];
-  return CFRK_OK;
+  return runs_export_host(ctx, cap_rows, parts, part_rows,
+    [&](uint4 *d_sz, unsigned long long *d_sync) {
+      hipLaunchKernelGGL(msp2_runs_sizes_kernel, dim3(NLEAF / 256), dim3(256), 0, ctx->stream, v, d_sz, d_sync);
+    },
+    [&](const uint64_t *d_off, const uint64_t *d_rows, const uint64_t *d_seg) {
+      hipLaunchKernelGGL(msp2_runs_gather_kernel, dim3(NLEAF), dim3(256), 0, ctx->stream, v, d_off, (uint4 *)d_packed, d_rows, d_seg, parts, cap_rows);
+    });
 }
 
 int cfrk_msp2_merge_runs(cfrk_ctx *ctx, const void *d_packed, const uint64_t *recv_rows, int parts) {
@@ -2354,72 +2267,43 @@ int cfrk_msp2_merge_runs(cfrk_ctx *ctx, const void *d_packed, const uint64_t *re
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   const int k = ctx->g_k;
   const int canon = (ctx->g_flags & CFRK_CANONICAL) ? 1 : 0;
-  const int lpp = (NLEAF + parts - 1) / parts;
-  const int hrows = runs_header_rows(lpp);
-  const size_t nseg = (size_t)parts * lpp;
   int rc;
-  void *p;
-  RunsRecv rr;
-  memset(&rr, 0, sizeof rr);
-  uint64_t rows_all = 0;
-  for (int r = 0; r < parts; ++r) {
-    if (recv_rows[r] < (uint64_t)hrows) return cfrk_fail(ctx, CFRK_ERR_ARG, "rank %d sent %llu rows, fewer than its header", r, (unsigned long long)recv_rows[r]);
-    rr.rstart[r] = rows_all; rr.rows[r] = recv_rows[r];
-    rows_all += recv_rows[r];
-  }
   View2 v;
-  memset(&v, 0, sizeof v);
-  // shared leaves (msp2_count_tiles): the owner holds 1 / parts of the leaves, each as heavy as it is in
-  // the whole job -- the capacity hint of an owner is its share of the job's distinct k-mers
-  const uint64_t per_leaf = ctx->g_cap / NLEAF * (uint64_t)parts;
   uint32_t sub_bits = 0;
-  while (sub_bits < (uint32_t)SUB_BITS && (per_leaf >> sub_bits) > 2048u) ++sub_bits;
-  if (per_leaf <= 4096u) sub_bits = 0;
-  if ((ctx->dbg_flags & CFRK_DEBUG_RECORD_SUBSETS) && sub_bits < 2u) sub_bits = 2u;
-  v.sub_bits = sub_bits;
-  v.hbits = msp2_hbits(ctx, sub_bits, per_leaf);
-  const size_t nsub = (size_t)NLEAF << sub_bits;
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_AUX, nsub * 8 + ((size_t)B1 * NXG + (size_t)NCLS * NLEAF + nsub) * sizeof(uint32_t), &p))) return rc;
-  v.leaf_off = (uint64_t *)p;
-  v.cnt1 = (uint32_t *)(v.leaf_off + nsub); v.cnt2 = v.cnt1 + B1 * NXG; v.leaf_n = v.cnt2 + NCLS * NLEAF;
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_LAYOUT, (size_t)NCLS * NLEAF * (sizeof(uint64_t) + 2 * sizeof(uint32_t)), &p))) return rc;
-  uint64_t *d_lbase = (uint64_t *)p;
-  uint32_t *d_lcap = (uint32_t *)(d_lbase + NCLS * NLEAF);
-  v.exact = 1; v.lbase = d_lbase; v.lcap = d_lcap;
-  // (streams nobody fills -- truncated classes 1 and 2, leaves of other owners -- hold nothing)
-  HIP_TRY(ctx, hipMemsetAsync(v.cnt2, 0, ((size_t)NCLS * NLEAF + nsub) * sizeof(uint32_t), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(d_lbase, 0, (size_t)NCLS * NLEAF * (sizeof(uint64_t) + sizeof(uint32_t)), ctx->stream));
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_OUTK, (size_t)ctx->g_cap * 8, &p))) return rc;
-  v.out_lo = (uint64_t *)p;
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_OUTH, (size_t)ctx->g_cap * 8, &p))) return rc;
-  v.out_hi = (uint64_t *)p;
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_OUTC, (size_t)ctx->g_cap * 4, &p))) return rc;
-  v.out_cnt = (uint32_t *)p; v.out_cap = ctx->g_cap;
-  v.stats = ctx->g_stats; v.dbg = ctx->dbg_flags;
-  if ((rc = cfrk_pool_get(ctx, BUF_SCRATCH, (nseg * 3 + 2) * sizeof(uint64_t) + nseg * sizeof(uint32_t), &p))) return rc;
-  uint64_t *d_src = (uint64_t *)p, *d_d1 = d_src + nseg, *d_d0 = d_d1 + nseg, *d_out = d_d0 + nseg;
-  uint32_t *d_segrows = (uint32_t *)(d_out + 2);
-  HIP_TRY(ctx, hipMemsetAsync(d_out, 0, 2 * sizeof(uint64_t), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->g_stats + ST_CURSOR, 0, sizeof(uint64_t), ctx->stream));
+  RunsPlan pl;
+  // Stream 3 of a leaf takes the ranks' distinct runs, stream 0 all their truncated runs; a record is two rows.
+  if ((rc = runs_merge_plan_host<NCLS, 3, 0, 2>(ctx, d_packed, recv_rows, parts, [&](uint64_t **lbase, uint32_t **lcap, uint32_t **cnt2) -> int {
+        int rc2;
+        void *p;
+        memset(&v, 0, sizeof v);
+        // shared leaves (msp2_count_tiles): the owner holds 1 / parts of the leaves, each as heavy as it is in
+        // the whole job -- the capacity hint of an owner is its share of the job's distinct k-mers
+        const uint64_t per_leaf = ctx->g_cap / NLEAF * (uint64_t)parts;
+        sub_bits = msp_sub_bits(ctx, per_leaf);
+        v.sub_bits = sub_bits;
+        v.hbits = msp2_hbits(ctx, sub_bits, per_leaf);
+        const size_t nsub = (size_t)NLEAF << sub_bits;
+        if ((rc2 = msp_aux_buffers(ctx, v, nsub, NXG, (size_t)NCLS * NLEAF))) return rc2;
+        if ((rc2 = cfrk_pool_get(ctx, BUF_MSP_LAYOUT, (size_t)NCLS * NLEAF * (sizeof(uint64_t) + 2 * sizeof(uint32_t)), &p))) return rc2;
+        *lbase = (uint64_t *)p; *lcap = (uint32_t *)(*lbase + NCLS * NLEAF);
+        v.exact = 1; v.lbase = *lbase; v.lcap = *lcap;
+        // (streams nobody fills -- truncated classes 1 and 2, leaves of other owners -- hold nothing)
+        HIP_TRY(ctx, hipMemsetAsync(v.cnt2, 0, ((size_t)NCLS * NLEAF + nsub) * sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(*lbase, 0, (size_t)NCLS * NLEAF * (sizeof(uint64_t) + sizeof(uint32_t)), ctx->stream));
+        if ((rc2 = cfrk_pool_get(ctx, BUF_MSP_OUTK, (size_t)ctx->g_cap * 8, &p))) return rc2;
+        v.out_lo = (uint64_t *)p;
+        if ((rc2 = cfrk_pool_get(ctx, BUF_MSP_OUTH, (size_t)ctx->g_cap * 8, &p))) return rc2;
+        v.out_hi = (uint64_t *)p;
+        if ((rc2 = cfrk_pool_get(ctx, BUF_MSP_OUTC, (size_t)ctx->g_cap * 4, &p))) return rc2;
+        v.out_cnt = (uint32_t *)p; v.out_cap = ctx->g_cap;
+        v.stats = ctx->g_stats; v.dbg = ctx->dbg_flags;
+        *cnt2 = v.cnt2;
+        return CFRK_OK;
+      }, &pl, &v.rec2))) return rc;
+  const int lpp = pl.lpp;
   TableView t = cfrk_table_view(ctx);
-  // segment (source rank, local leaf): the ranks' headers say how large; all offsets on the device.
-  // Stream 3 of a leaf takes the ranks' distinct runs, stream 0 all their truncated runs.
-  hipLaunchKernelGGL((msp_runs_layout1_kernel<NCLS, 3, 0, 2>), dim3((unsigned)(lpp + 255) / 256), dim3(256), 0, ctx->stream, (const uint4 *)d_packed, rr, parts, lpp,
-                     d_segrows, d_d1, d_d0, d_lcap, d_out);
-  HIP_TRY(ctx, hipGetLastError());
-  hipLaunchKernelGGL((msp_runs_layout_kernel<NCLS, 3, 0>), dim3((unsigned)parts + 1u), dim3(1024), 0, ctx->stream, rr, parts, lpp, hrows, (const uint32_t *)d_segrows,
-                     d_src, d_d1, d_d0, d_lbase, (const uint32_t *)d_lcap, v.cnt2, d_out);
-  HIP_TRY(ctx, hipGetLastError());
-  // the headers are checked before anything is copied by them (msp.hip)
-  uint64_t h[2];
-  HIP_TRY(ctx, hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (h[1]) return cfrk_fail(ctx, CFRK_ERR_ARG, "a rank's header does not add up to the rows it sent");
-  if (h[0] > rows_all * NOTES_PER_ROW) return cfrk_fail(ctx, CFRK_ERR_ARG, "the headers announce more records than the rows can hold");
-  if ((rc = cfrk_pool_get(ctx, BUF_MSP_L2, (size_t)(h[0] ? h[0] : 1) * sizeof(Rec2), &p))) return rc;
-  v.rec2 = (Rec2 *)p;
-  hipLaunchKernelGGL(msp2_runs_scatter_kernel, dim3((unsigned)nseg), dim3(256), 0, ctx->stream, (const uint4 *)d_packed, rr, lpp, k,
-                     (const uint64_t *)d_src, (const uint64_t *)d_d1, (const uint64_t *)d_d0, v.rec2);
+  hipLaunchKernelGGL(msp2_runs_scatter_kernel, dim3((unsigned)pl.nseg), dim3(256), 0, ctx->stream, (const uint4 *)d_packed, pl.rr, lpp, k,
+                     pl.src, pl.d1, pl.d0, v.rec2);
   HIP_TRY(ctx, hipGetLastError());
   {
     // the owner's leaves are local indices 0 .. lpp-1 (a shared leaf: one workgroup per four sub-values,
@@ -2441,16 +2325,14 @@ int cfrk_msp2_merge_runs(cfrk_ctx *ctx, const void *d_packed, const uint64_t *re
   ctx->ev_valid = true;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->h_stats_valid = false;                          // the leaf kernel may have spilled into the table
-  ms->view.out_keys = v.out_lo; ms->view.out_hi = v.out_hi; ms->view.out_cnt = v.out_cnt;
-  ms->view.out_cap = v.out_cap; ms->view.stats = v.stats; ms->view.cnt1 = nullptr;
-  ms->view.leaf_off = v.leaf_off; ms->view.leaf_n = v.leaf_n; ms->view.seg_bits = v.sub_bits;
+  msp2_publish_view(ms, v, true);
   ms->pending = true;
   ms->leaf_form = false;
   ms->list_n_valid = false;
   return CFRK_OK;
 }
 
-// ------------------------------------------------------------------ multi-GPU exchange by runs, pipelined (msp.hip)
+// ------------------------------------------------------------------ multi-GPU exchange by runs, pipelined (host side: msp_runs.h)
 int cfrk_msp2_export_runs_async(cfrk_ctx *ctx, void *d_packed, uint64_t seg_cap_rows, int parts, int ngroups) {
   cfrk_msp *ms = ctx->msp;
   View2 v;
@@ -2483,12 +2365,8 @@ int cfrk_msp2_merge_runs_group(cfrk_ctx *ctx, const void *d_recv, const uint64_t
     memset(&v, 0, sizeof v);
     // shared leaves (cfrk_msp2_merge_runs): the owner holds 1 / parts of the leaves, each as heavy as it is in the whole job
     const uint64_t per_leaf = ctx->g_cap / NLEAF * (uint64_t)parts;
-    uint32_t sub_bits = 0;
-    while (sub_bits < (uint32_t)SUB_BITS && (per_leaf >> sub_bits) > 2048u) ++sub_bits;
-    if (per_leaf <= 4096u) sub_bits = 0;
-    if ((ctx->dbg_flags & CFRK_DEBUG_RECORD_SUBSETS) && sub_bits < 2u) sub_bits = 2u;
-    v.sub_bits = sub_bits;
-    v.hbits = msp2_hbits(ctx, sub_bits, per_leaf);
+    v.sub_bits = msp_sub_bits(ctx, per_leaf);
+    v.hbits = msp2_hbits(ctx, v.sub_bits, per_leaf);
     if ((rc = cfrk_pool_get(ctx, BUF_MSP_OUTK, (size_t)ctx->g_cap * 8, &p))) return rc;
     v.out_lo = (uint64_t *)p;
     if ((rc = cfrk_pool_get(ctx, BUF_MSP_OUTH, (size_t)ctx->g_cap * 8, &p))) return rc;
@@ -2501,14 +2379,7 @@ int cfrk_msp2_merge_runs_group(cfrk_ctx *ctx, const void *d_recv, const uint64_t
   } else {
     memcpy(&v, ms->view2, sizeof v);
   }
-  P3ListsT<true> lx;
-  memset(&lx, 0, sizeof lx);
-  lx.packed = (const uint4 *)d_recv;
-  uint64_t at = 0;
-  for (int r = 0; r < parts; ++r) { lx.rr.rstart[r] = at; lx.rr.rows[r] = recv_rows[r]; at += recv_rows[r]; }
-  lx.parts = parts;
-  lx.ll0 = runs_ll0(lpp, group, ngroups);
-  lx.lcount = runs_ll0(lpp, group + 1, ngroups) - lx.ll0;
+  const P3ListsT<true> lx = runs_group_lists(d_recv, recv_rows, parts, group, ngroups);
   TableView t = cfrk_table_view(ctx);
   if (lx.lcount) {
     const bool canon = (ctx->g_flags & CFRK_CANONICAL) != 0;
@@ -2526,9 +2397,7 @@ int cfrk_msp2_merge_runs_group(cfrk_ctx *ctx, const void *d_recv, const uint64_t
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   ctx->ev_valid = true;
   ctx->h_stats_valid = false;                          // the leaf kernel may have spilled into the table
-  ms->view.out_keys = v.out_lo; ms->view.out_hi = v.out_hi; ms->view.out_cnt = v.out_cnt;
-  ms->view.out_cap = v.out_cap; ms->view.stats = v.stats; ms->view.cnt1 = nullptr;
-  ms->view.leaf_off = nullptr; ms->view.leaf_n = nullptr; ms->view.seg_bits = 0;
+  msp2_publish_view(ms, v, false);
   ms->lists_group = group + 1;
   ms->pending = true;
   ms->leaf_form = false;
@@ -2549,8 +2418,7 @@ int cfrk_msp2_count(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN) {
   const bool runs_only = (ctx->g_flags & CFRK_RUNS_ONLY) != 0;
   if (runs_only && ms->runs_ready) return cfrk_fail(ctx, CFRK_ERR_STATE, "a CFRK_RUNS_ONLY job takes one add");
   int groups = 1;
-  if ((rc = cfrk_msp_plan_groups(ctx, nN + 32, ntiles, (int64_t)Q1_WAVES * Q1_OWN * 32, msp2_need,
-                                 (size_t)ctx->g_cap * 20, have, &groups))) return rc;
+  if ((rc = cfrk_msp_plan_groups(ctx, nN + 32, msp2_need, have, &groups))) return rc;
   // a batch that does not fit in one pass with the generous fixed-stride streams: would it with streams
   // sized from a counting pass?  (fewer passes over the input for one more read of the level-1 records)
   bool lean = false;
@@ -2564,7 +2432,7 @@ int cfrk_msp2_count(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN) {
     //  a chunked add sizes its streams from a read-back)
     const bool want_defer = runs_only && (ctx->g_flags & CFRK_RUNS_DEFER) && groups == 1;
     if (big && !want_defer && !(ctx->dbg_flags & CFRK_DEBUG_NO_PIPELINE) && !ctx->mem_budget &&
-        !(rc = cfrk_msp_plan_groups(ctx, nN + 32, ntiles, (int64_t)Q1_WAVES * Q1_OWN * 32, msp2_need_chunked, (size_t)ctx->g_cap * 20, have, &cg)) &&
+        !(rc = cfrk_msp_plan_groups(ctx, nN + 32, msp2_need_chunked, have, &cg)) &&
         cg == 1) {
       if (ms->pending && (rc = cfrk_msp_flush_to_table(ctx))) return rc;
       ctx->last_passes = 1;
@@ -2588,13 +2456,11 @@ int cfrk_msp2_count(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const double starts = std::max(0.0, (double)nN - (double)ninv * (double)ctx->g_k);
     ms->dens_scale = std::min(1.0, std::max(0.05, starts / (double)std::max<int64_t>(nN, 1)));
-    if ((rc = cfrk_msp_plan_groups(ctx, nN + 32, ntiles, (int64_t)Q1_WAVES * Q1_OWN * 32, msp2_need,
-                                   (size_t)ctx->g_cap * 20, have, &groups))) return rc;
+    if ((rc = cfrk_msp_plan_groups(ctx, nN + 32, msp2_need, have, &groups))) return rc;
   }
   if (groups != 1) {
     int lg = 1;
-    if ((rc = cfrk_msp_plan_groups(ctx, nN + 32, ntiles, (int64_t)Q1_WAVES * Q1_OWN * 32, msp2_need_lean,
-                                   (size_t)ctx->g_cap * 20, have, &lg))) return rc;
+    if ((rc = cfrk_msp_plan_groups(ctx, nN + 32, msp2_need_lean, have, &lg))) return rc;
     if (lg != 0 && (groups == 0 || lg < groups)) { groups = lg; lean = true; }
   }
   if (groups == 0) return cfrk_fail(ctx, CFRK_ERR_NOMEM, "partitioned path does not fit device memory");
@@ -2602,31 +2468,9 @@ int cfrk_msp2_count(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN) {
   ctx->last_passes = passes;
   if (runs_only && passes != 1) return cfrk_fail(ctx, CFRK_ERR_RUNS_REFUSED, "a CFRK_RUNS_ONLY job must fit device memory in one pass");
   if (ms->pending && (rc = cfrk_msp_flush_to_table(ctx))) return rc;
-  if (passes == 1 && lean) return msp2_count_tiles(ctx, ms, d_data, nN, 0, ntiles, 1.0, 0, 0, true, true);
-  if (passes == 1) {
-    // lumpy leaves (small genomes): up to twice the stream room when memory is plentiful (msp.hip)
-    double slack = 1.0;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      const double l2 = (double)(nN + 32) * msp2_density(ctx) * 3.3 * 32;
-      size_t budget = have + free_b;
-      if (ctx->mem_budget) budget = std::min(budget, ctx->mem_budget);
-      const double room = 0.5 * (double)budget - (double)msp2_need(ctx, nN + 32);
-      if (room > 0 && l2 > 0) slack = std::min(2.0, 1.0 + room / l2);
-    }
-    return msp2_count_tiles(ctx, ms, d_data, nN, 0, ntiles, slack);
-  }
-
-  // several passes over the WHOLE input, each emitting and counting 1/passes of the leaves (msp.hip)
-  int sel_bits = 0;
-  while ((1 << sel_bits) < passes) ++sel_bits;
-  for (int pass = 0; pass < passes; ++pass) {
-    if ((rc = msp2_count_tiles(ctx, ms, d_data, nN, 0, ntiles, 1.0, sel_bits, (uint32_t)pass, pass == 0, lean))) {
-      // a refusal after the first pass must not reach the caller's fallback (it would count
-      // the finished passes twice)
-      if (pass > 0 && (rc == CFRK_ERR_NOMEM || rc == CFRK_INTERNAL_FLOOD)) return cfrk_fail(ctx, CFRK_ERR_STATE, "out of device memory in pass %d of a multi-pass add", pass);
-      return rc;
-    }
-  }
-  return CFRK_OK;
+  // (a count-first add gets exactly the stream room it counted: nothing to widen)
+  const double l2 = (double)(nN + 32) * msp2_density(ctx) * 3.3 * 32;           // bytes of the leaf streams
+  return msp_for_each_pass(ctx, passes, !lean, have, msp2_need(ctx, nN + 32), l2, [&](double slack, int sel_bits, uint32_t sel_val, bool first) {
+    return msp2_count_tiles(ctx, ms, d_data, nN, 0, ntiles, slack, sel_bits, sel_val, first, lean);
+  });
 }

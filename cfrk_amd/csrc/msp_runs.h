@@ -1,7 +1,9 @@
-// msp_runs.h -- the parts of the multi-GPU exchange by runs (msp.hip: "multi-GPU by runs") that do not
-// depend on the record format: where every leaf's rows go in the packed buffer (sender) and where
-// every received segment goes in the owner's leaf streams.  Included by msp.hip (16-byte records,
-// one row each) and msp2.hip (32-byte records, two rows each) inside their anonymous namespaces.
+// msp_runs.h -- the parts of the multi-GPU exchange by runs that do not depend on the record format.  Device side:
+// where every leaf's rows go in the packed buffer (sender) and where every received segment goes in the owner's
+// leaf streams.  Host side: the whole call sequence of the one-shot and the pipelined exchange -- scratch buffers,
+// plan and layout kernels, read-backs and the checks of what arrived -- with the kernels that read or write records
+// handed in as launch lambdas.  Included by msp.hip (16-byte records, one row each) and msp2.hip (32-byte records,
+// two rows each) inside their anonymous namespaces; msp_shared.h holds what the two share outside the exchange.
 #pragma once
 
 constexpr uint32_t RUN_NOTED = 0xFFFFFFFFu;        // (a record's header word has the top 8 bits clear)
@@ -258,4 +260,117 @@ static int runs_export_async_host(cfrk_ctx *ctx, void *d_packed, uint64_t seg_ca
   }
   ctx->runs_groups = ngroups; ctx->runs_parts = parts; ctx->runs_seg_cap = seg_cap_rows;
   return CFRK_OK;
+}
+
+// ------------------------------------------------------------------- host side of the one-shot exchange, both key widths
+// a CFRK_RUNS_DEFER add ended unsynchronised: did its regions hold?  (an add without the flag lays an overflowing level out again)
+static int runs_check_deferred(cfrk_ctx *ctx, cfrk_msp *ms) {
+  if (!ms->runs_unchecked) return CFRK_OK;
+  uint64_t st[ST_NWORDS];
+  const int rc = cfrk_msp_sync_stats(ctx, st);
+  if (rc) return rc;
+  if (st[ST_L1OVF] || st[ST_L2OVF] || st[ST_OVFN] || st[ST_OVFN1] || st[ST_CWRAP])
+    return cfrk_fail(ctx, CFRK_ERR_STATE, "the CFRK_RUNS_DEFER add overflowed a record region: add again without the flag");
+  ms->runs_unchecked = false;
+  return CFRK_OK;
+}
+
+// sender: offsets, headers and segment sizes are worked out on the device; the host only learns the segment
+// sizes -- together with the job's flags, in ONE copy.  launch_sizes(d_sz, d_sync): every leaf's sizes;
+// launch_gather(d_off, d_rows, d_seg): the leaves' rows to where the plan put them
+template <class Sizes, class Gather>
+static int runs_export_host(cfrk_ctx *ctx, uint64_t cap_rows, int parts, uint64_t *part_rows, Sizes launch_sizes, Gather launch_gather) {
+  const int lpp = (NLEAF + parts - 1) / parts;           // leaves per part (owner p: leaves p, p+parts, ...)
+  const int hrows = runs_header_rows(lpp);
+  int rc;
+  void *p;
+  if ((rc = cfrk_pool_get(ctx, BUF_SCRATCH, (NLEAF + 65 + ST_NWORDS + 1 + 64 + 72) * sizeof(uint64_t) + (size_t)NLEAF * sizeof(uint4), &p))) return rc;
+  uint64_t *d_off = (uint64_t *)p, *d_rows = d_off + NLEAF;
+  uint64_t *d_seg = d_rows + 65 + ST_NWORDS + 1;
+  unsigned long long *d_sync = (unsigned long long *)(d_seg + 64);
+  uint4 *d_sz = (uint4 *)(d_sync + 72);      // (16-byte aligned: the pool is, and NLEAF + 65 + ST_NWORDS + 1 is even)
+  static_assert((NLEAF + 65 + ST_NWORDS + 1 + 64 + 72) % 2 == 0, "d_sz is 16-byte aligned");
+  launch_sizes(d_sz, d_sync);
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(msp_runs_plan_kernel, dim3(runs_plan_grid(parts, lpp)), dim3(1024), 0, ctx->stream, (const uint4 *)d_sz, parts, lpp, hrows, d_off,
+                     d_rows + parts, d_seg, d_sync);
+  HIP_TRY(ctx, hipGetLastError());
+  launch_gather((const uint64_t *)d_off, (const uint64_t *)d_rows, (const uint64_t *)d_seg);
+  HIP_TRY(ctx, hipGetLastError());
+  // [0, 65): all rows at [parts]; then the job's flags; then the segment starts -- ONE copy
+  uint64_t h[65 + ST_NWORDS + 1 + 64];
+  HIP_TRY(ctx, hipMemcpyAsync(d_rows + 65, ctx->g_stats, ST_NWORDS * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(h, d_rows, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const uint64_t *st = h + 65, *seg = h + 65 + ST_NWORDS + 1;
+  if (st[ST_SPILLED] || st[ST_ONES]) return cfrk_fail(ctx, CFRK_ERR_STATE, "part of the batch was counted in the HBM table");
+  if (h[parts] > cap_rows) return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "%llu rows, room for %llu", (unsigned long long)h[parts], (unsigned long long)cap_rows);
+  for (int q = 0; q < parts; ++q) part_rows[q] = (q + 1 < parts ? seg[q + 1] : h[parts]) - seg[q];
+  return CFRK_OK;
+}
+
+// rank r's rows start where rank r - 1's end; returns the rows of all ranks
+static uint64_t runs_recv(RunsRecv *rr, const uint64_t *recv_rows, int parts) {
+  memset(rr, 0, sizeof *rr);
+  uint64_t at = 0;
+  for (int r = 0; r < parts; ++r) { rr->rstart[r] = at; rr->rows[r] = recv_rows[r]; at += recv_rows[r]; }
+  return at;
+}
+
+// owner: what the scatter kernel needs to copy segment (source rank, local leaf) into the leaf's streams
+struct RunsPlan { RunsRecv rr; int lpp; size_t nseg; const uint64_t *src, *d1, *d0; };
+// owner: the ranks' headers say how large every segment is; all offsets on the device (msp_runs_layout1_kernel,
+// msp_runs_layout_kernel) into the exact layout of the leaf streams.  The headers are checked before anything is
+// copied by them: sizes that add up to the rows each rank sent keep every segment inside its rank's part of the
+// buffer and every stream inside rec2, which is sized here to what arrived, every note a record again.
+// view(&lbase, &lcap, &cnt2): the caller sets up its view once the messages are long enough for their headers and
+// hands back the streams' layout arrays (BUF_MSP_LAYOUT) and cursors
+template <int NC, int CI1, int CI0, int RMUL, class Rec, class ViewSetup>
+static int runs_merge_plan_host(cfrk_ctx *ctx, const void *d_packed, const uint64_t *recv_rows, int parts, ViewSetup view,
+                                RunsPlan *pl, Rec **rec2) {
+  const int lpp = (NLEAF + parts - 1) / parts;
+  const int hrows = runs_header_rows(lpp);
+  const size_t nseg = (size_t)parts * lpp;
+  for (int r = 0; r < parts; ++r)
+    if (recv_rows[r] < (uint64_t)hrows) return cfrk_fail(ctx, CFRK_ERR_ARG, "rank %d sent %llu rows, fewer than its header", r, (unsigned long long)recv_rows[r]);
+  const uint64_t rows_all = runs_recv(&pl->rr, recv_rows, parts);
+  int rc;
+  void *p;
+  uint64_t *d_lbase;
+  uint32_t *d_lcap, *d_cnt2;
+  if ((rc = view(&d_lbase, &d_lcap, &d_cnt2))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_SCRATCH, (nseg * 3 + 2) * sizeof(uint64_t) + nseg * sizeof(uint32_t), &p))) return rc;
+  uint64_t *d_src = (uint64_t *)p, *d_d1 = d_src + nseg, *d_d0 = d_d1 + nseg, *d_out = d_d0 + nseg;
+  uint32_t *d_segrows = (uint32_t *)(d_out + 2);
+  HIP_TRY(ctx, hipMemsetAsync(d_out, 0, 2 * sizeof(uint64_t), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->g_stats + ST_CURSOR, 0, sizeof(uint64_t), ctx->stream));   // (the result list starts empty)
+  hipLaunchKernelGGL((msp_runs_layout1_kernel<NC, CI1, CI0, RMUL>), dim3((unsigned)(lpp + 255) / 256), dim3(256), 0, ctx->stream, (const uint4 *)d_packed, pl->rr, parts, lpp,
+                     d_segrows, d_d1, d_d0, d_lcap, d_out);
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL((msp_runs_layout_kernel<NC, CI1, CI0>), dim3((unsigned)parts + 1u), dim3(1024), 0, ctx->stream, pl->rr, parts, lpp, hrows, (const uint32_t *)d_segrows,
+                     d_src, d_d1, d_d0, d_lbase, (const uint32_t *)d_lcap, d_cnt2, d_out);
+  HIP_TRY(ctx, hipGetLastError());
+  uint64_t h[2];
+  HIP_TRY(ctx, hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (h[1]) return cfrk_fail(ctx, CFRK_ERR_ARG, "a rank's header does not add up to the rows it sent");
+  // (h[0] records; at most eight per row)
+  if (h[0] > rows_all * NOTES_PER_ROW) return cfrk_fail(ctx, CFRK_ERR_ARG, "the headers announce more records than the rows can hold");
+  if ((rc = cfrk_pool_get(ctx, BUF_MSP_L2, (size_t)(h[0] ? h[0] : 1) * sizeof(Rec), &p))) return rc;
+  *rec2 = (Rec *)p;
+  pl->lpp = lpp; pl->nseg = nseg; pl->src = d_src; pl->d1 = d_d1; pl->d0 = d_d0;
+  return CFRK_OK;
+}
+
+// owner, pipelined: the lists of group `group` of `ngroups` in the receive buffer
+static P3ListsT<true> runs_group_lists(const void *d_recv, const uint64_t *recv_rows, int parts, int group, int ngroups) {
+  const int lpp = (NLEAF + parts - 1) / parts;
+  P3ListsT<true> lx;
+  memset(&lx, 0, sizeof lx);
+  lx.packed = (const uint4 *)d_recv;
+  runs_recv(&lx.rr, recv_rows, parts);
+  lx.parts = parts;
+  lx.ll0 = runs_ll0(lpp, group, ngroups);
+  lx.lcount = runs_ll0(lpp, group + 1, ngroups) - lx.ll0;
+  return lx;
 }

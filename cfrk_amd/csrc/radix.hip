@@ -61,7 +61,7 @@ struct RxView {
 };
 
 // level-1 region / cursor of (bin, sub-region): sub-region major -- the cursors a workgroup reserves
-// from lie side by side (memory-side atomics: one request per touched 64 bytes, see msp.hip l1_reg)
+// from lie side by side (memory-side atomics: one request per touched 64 bytes, see msp_shared.h l1_reg)
 __device__ __forceinline__ uint32_t rx_reg(const RxView &v, uint32_t bin, uint32_t sub) { return (sub << v.b1) | bin; }
 // The scramble is one odd multiply mod 4^k (a bijection): the level-1 bin is the product's TOP bits, which
 // mix every bit of the key -- canonical k-mers are skewed low, the product's top bits are not.  (Until round 4

@@ -652,6 +652,30 @@ def test_two_word_single_amplicon_overflows_its_level1_regions_and_is_laid_out_a
     assert info["spilled_records"] == 0 and info["spilled_kmers"] == 0
 
 
+@pytest.mark.parametrize("k", [21, 31])
+def test_one_word_single_amplicon_overflows_its_level1_regions_and_is_laid_out_again(ctx, k):
+    """the same for 17 <= k <= 32 (msp.hip, through the exact level-1 layout both key widths share): 100 k
+    copies of one read make 1.5 - 2.5 M records in at most ~25 level-1 bins, over 10 k per sub-region where the
+    density estimate gave each 3 - 4 k, and the excess is a hundred times what the parking buffer takes.  That the level
+    really was laid out again shows in its cursors: a region holds more records than the fixed stride, and yet
+    none went through the HBM table."""
+    import cfrk_amd
+    rng = np.random.default_rng(5)
+    read = np.append(rng.integers(0, 4, 150).astype(np.int8), np.int8(-1))
+    R = 100_000
+    data = np.tile(read, R)
+    want = orc.global_count(data, k, orc.ORC_CANONICAL, threads=8)
+    assert len(want[0]) == 150 - k + 1 and int(want[2].min()) == R
+    g = cfrk_amd.GlobalCounter(ctx, k, cfrk_amd.CFRK_CANONICAL, 100_000)
+    g.add(data)
+    lo, hi, cnt = g.export()
+    assert (lo == want[0]).all() and (cnt.astype(np.uint64) == want[2]).all()
+    info = g.msp_info()
+    assert g.last_add_passes() == 1 and info["l1_records"] > 0
+    assert info["l1_max_bin"] > info["l1_cap"], "no level-1 region outgrew its fixed stride: the exact layout did not run"
+    assert info["spilled_records"] == 0 and info["spilled_kmers"] == 0
+
+
 @pytest.mark.parametrize("k", [9, 13, 14, 15, 16])
 def test_radix_single_amplicon_overflows_its_level1_regions_and_is_laid_out_again(ctx, k):
     """the same for 8 <= k <= 16 (radix.hip): 800 000 copies of one read put every key into ~140 of
@@ -1974,6 +1998,39 @@ def test_pipelined_runs_exchange_emulated_ranks_equal_the_oracle(ctx, k, canonic
         assert all(merged[int(a)] == int(b) for a, b in zip(wlo, wcnt))
     else:
         assert all(merged[(int(h) << 64) | int(a)] == int(b) for a, h, b in zip(wlo, whi, wcnt))
+
+
+def test_two_word_deferred_add_is_checked_by_the_one_shot_export(ctx):
+    """k = 63, one rank: a CFRK_RUNS_DEFER add ends unsynchronised, so the ONE-SHOT export is what looks at the add's
+    overflow flags (the check both key widths share).  (1) an add that held: the export deduplicates, packs, and the
+    owner's merge gives the oracle's counts; (2) deep coverage of a 1200-base genome, ~2400 records per leaf where the
+    fixed stride holds ~120: the export refuses with CFRK_ERR_STATE and names the flag -- that it was the deferred
+    add's check that refused shows in the same batch settling without the flag."""
+    import cfrk_amd
+    R, L, k = 24_000, 150, 63
+    flags = cfrk_amd.CFRK_CANONICAL
+    data, _, _ = orc.synth_reads(0, R, L, 300_000)
+    g = cfrk_amd.GlobalCounter(ctx, k, flags | cfrk_amd.CFRK_RUNS_ONLY | cfrk_amd.CFRK_RUNS_DEFER, 600_000)
+    g.add(data)
+    d = ctx.alloc((1 << 20) * 16)
+    rows = g.export_runs_device(d, 1 << 20, 1)
+    assert len(rows) == 1 and rows[0] > 0
+    og = cfrk_amd.GlobalCounter(ctx, k, flags, 600_000)
+    og.merge_runs_device(d, rows)
+    lo, hi, cnt = og.export()
+    wlo, whi, wcnt = orc.global_count(data, k, orc.ORC_CANONICAL)
+    assert len(lo) == len(wlo) and (lo == wlo).all() and (hi == whi).all() and (cnt.astype(np.uint64) == wcnt).all()
+    # (2)
+    tiny, _, _ = orc.synth_reads(0, R, L, 1_200)
+    g = cfrk_amd.GlobalCounter(ctx, k, flags | cfrk_amd.CFRK_RUNS_ONLY | cfrk_amd.CFRK_RUNS_DEFER, 60_000)
+    g.add(tiny)
+    with pytest.raises(cfrk_amd.CfrkError) as e:
+        g.export_runs_device(d, 1 << 20, 1)
+    assert e.value.code == -4 and "CFRK_RUNS_DEFER" in str(e.value)
+    g = cfrk_amd.GlobalCounter(ctx, k, flags | cfrk_amd.CFRK_RUNS_ONLY, 60_000)     # without the flag the add settles
+    g.add(tiny)
+    assert sum(g.export_runs_device(d, 1 << 20, 1)) > 0
+    ctx.free(d)
 
 
 def test_pipelined_runs_exchange_refuses_what_it_cannot_carry_and_the_classic_export_follows(ctx):
