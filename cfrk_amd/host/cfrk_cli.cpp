@@ -73,6 +73,13 @@
 //   --text-copy plain|staged   (with --device-parse) how the mapped text goes to the device: by one copy from the mapping
 //                    (plain, the default: measured the faster one) or through the context's ring of pinned staging
 //                    buffers (staged, cfrk_memcpy_h2d_staged)
+//   --format fasta|fastq|auto   the format of the input and of the --query file.  auto (the default) goes by each file's
+//                    first byte: '@' is FASTQ, anything else FASTA.  FASTQ is strict four-line FASTQ (the grammar of
+//                    cfrk_fastq_parse_device, cfrk_abi.h) and is taken by --native, --global (with --device-parse too:
+//                    cfrk_fastq_parse_device) and --sparse, and as the --query file; the default per-read mode is the
+//                    reference's drop-in, which reads FASTA only, and refuses a FASTQ file
+//   --min-qual Q     (FASTQ input, 0 .. 93) a base whose Phred+33 quality is below Q counts as an invalid base: it breaks
+//                    its k-mer windows, as an N does.  An error with FASTA input.  The --query file is read unmasked
 //   --batch N        the Swift/T workflow's loop (swift/cfrk.swf:15-20) in one process: for i < N
 //                    count <dataset_prefix>_<i>.fasta into <out_prefix>_<i>.cfrk
 // Chunk pipeline: every device runs two contexts (two HIP streams), each on a host thread of its
@@ -118,6 +125,9 @@ struct Options {
   bool estimate = false, estimate_only = false, auto_hint = false;   // --estimate, --estimate-only, --auto-hint
   bool device_parse = false;                                        // --device-parse
   bool text_copy_plain = true;                                      // --text-copy plain (the default) | staged
+  int format = -1;                                                  // --format: CFRK_FORMAT_FASTA / _FASTQ, -1 = by the first byte
+  int min_qual = 0;                                                 // --min-qual
+  bool min_qual_set = false;
 };
 
 // --timing: wall-clock seconds by phase (one file; with --batch the last file's)
@@ -133,6 +143,7 @@ struct Timing {
   double estimate = 0, distinct_estimate = 0;   // the sketch before the count: seconds, estimated distinct k-mers
   double text_map = 0, text_h2d = 0, device_parse_ms = 0;    // --device-parse: the text's copy to the device (s), the parse there (ms)
   bool device_parse = false;
+  int in_format = CFRK_FORMAT_FASTA;   // what the input was read as
   uint64_t hint = 0;                   // capacity hint of the LAST attempt
 } g_timing;
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -141,6 +152,41 @@ struct Worker {            // one context (= one HIP stream + buffer pool) on on
   cfrk_ctx *ctx = nullptr;
   int device = 0;
 };
+
+// the format a file is read as: --format, or its first byte (a file that cannot be opened reads as FASTA: the reader says so)
+int file_format(const Options &o, const char *path) {
+  if (o.format >= 0) return o.format;
+  char c = 0;
+  size_t n = 0;
+  if (FILE *f = fopen(path, "rb")) { n = fread(&c, 1, 1, f); fclose(f); }
+  return cfrk_host_sniff_format(&c, n);
+}
+// may this run read `path` as `fmt`?  Says why not, before anything is parsed or a device is opened.
+bool format_allowed(const Options &o, const char *path, int fmt) {
+  if (fmt == CFRK_FORMAT_FASTQ && !(o.native || o.global || o.sparse)) {
+    fprintf(stderr, "cfrk: %s is FASTQ: the default per-read mode is the reference's, which reads FASTA only; FASTQ is taken by --native, --global and --sparse (and as --query)\n", path);
+    return false;
+  }
+  if (fmt == CFRK_FORMAT_FASTA && o.min_qual_set) {
+    fprintf(stderr, "cfrk: --min-qual applies to FASTQ input: %s is read as FASTA\n", path);
+    return false;
+  }
+  return true;
+}
+// host parse of either format; a refusal is printed here (1), 0 otherwise
+int read_reads(const char *path, int fmt, int fasta_flags, int min_qual, cfrk_batch *b) {
+  if (fmt == CFRK_FORMAT_FASTQ) {
+    uint64_t where = 0;
+    const int rc = cfrk_host_read_fastq(path, min_qual, b, &where);
+    char msg[160];
+    if (rc && cfrk_host_fastq_message(rc, where, msg, sizeof msg)) { fprintf(stderr, "cfrk: cannot read %s (%s)\n", path, msg); return 1; }
+    if (rc) { fprintf(stderr, "cfrk: cannot read %s (error %d)\n", path, rc); return 1; }
+    return 0;
+  }
+  const int rc = cfrk_host_read_fasta(path, fasta_flags, b);
+  if (rc) { fprintf(stderr, "cfrk: cannot read %s (error %d)\n", path, rc); return 1; }
+  return 0;
+}
 
 int die(cfrk_ctx *ctx, int rc, const char *what) {
   fprintf(stderr, "cfrk: %s: %s (%s)\n", what, cfrk_strerror(rc), ctx ? cfrk_last_error(ctx) : "");
@@ -650,19 +696,27 @@ int run_global_multi(const Options &o, const cfrk_batch &batch, std::vector<std:
   return 0;
 }
 
-// --device-parse: the file goes to the device as text and is parsed there (cfrk_fasta_parse_device); no host batch
+// --device-parse: the file goes to the device as text and is parsed there (cfrk_fasta_parse_device, or for FASTQ
+// cfrk_fastq_parse_device); no host batch
 struct DeviceText {
   cfrk_ctx *ctx = nullptr;
   void *d_text = nullptr, *d_start = nullptr, *d_length = nullptr, *d_regs = nullptr;
   int8_t *d_data = nullptr;
+  size_t n_text = 0;
   ~DeviceText() { for (void *d : {d_text, (void *)d_data, d_start, d_length, d_regs}) if (d) cfrk_device_free(ctx, d); }
   // 0, a negative code of the host parser (the caller prints its message), or the exit status of a reported device error
-  int load(const char *in, bool plain_copy, int64_t *nN, int64_t *nS, double *map_s, double *h2d_s, double *parse_ms) {
+  int load(const char *in, bool plain_copy, int fmt, int min_qual, int64_t *nN, int64_t *nS, double *map_s, double *h2d_s, double *parse_ms) {
+    const bool fq = fmt == CFRK_FORMAT_FASTQ;
+    auto parse = [&](int8_t *data, uint64_t cap_data, int64_t *start, int32_t *length, uint64_t cap_reads) {
+      return fq ? cfrk_fastq_parse_device(ctx, (const uint8_t *)d_text, n_text, min_qual, data, cap_data, start, length, cap_reads, nN, nS)
+                : cfrk_fasta_parse_device(ctx, (const uint8_t *)d_text, n_text, 0, data, cap_data, start, length, cap_reads, nN, nS);
+    };
     const int fd = open(in, O_RDONLY);
     if (fd < 0) return -1;
     struct stat st;
     if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { close(fd); return -1; }
     const size_t n = (size_t)st.st_size;
+    n_text = n;
     *nN = *nS = 0;
     if (n == 0) { close(fd); return 0; }
     int rc;
@@ -680,15 +734,14 @@ struct DeviceText {
     if (rc) return die(ctx, rc, plain_copy ? "cfrk_memcpy_h2d" : "cfrk_memcpy_h2d_staged");
     *h2d_s = now_s() - t0;
     const double t1 = now_s();
-    rc = cfrk_fasta_parse_device(ctx, (const uint8_t *)d_text, n, 0, nullptr, 0, nullptr, nullptr, 0, nN, nS);
+    rc = parse(nullptr, 0, nullptr, nullptr, 0);
     if (rc == CFRK_ERR_SMALL_BUF) {
       void *dd = nullptr;
       if ((rc = cfrk_device_alloc(ctx, (size_t)*nN + 64, &dd))) return die(ctx, rc, "cfrk_device_alloc");
       d_data = (int8_t *)dd;
       if ((rc = cfrk_device_alloc(ctx, (size_t)*nS * 8, &d_start)) || (rc = cfrk_device_alloc(ctx, (size_t)*nS * 4, &d_length)))
         return die(ctx, rc, "cfrk_device_alloc");
-      rc = cfrk_fasta_parse_device(ctx, (const uint8_t *)d_text, n, 0, d_data, (uint64_t)*nN, (int64_t *)d_start, (int32_t *)d_length,
-                                   (uint64_t)*nS, nN, nS);
+      rc = parse(d_data, (uint64_t)*nN, (int64_t *)d_start, (int32_t *)d_length, (uint64_t)*nS);
       if (!rc) rc = cfrk_ctx_sync(ctx);
     }
     // What the host parser refuses with -2 (a sequence line before the first header: the only text it can refuse in native
@@ -699,7 +752,7 @@ struct DeviceText {
       fprintf(stderr, "cfrk: cannot read %s (%s)\n", in, cfrk_last_error(ctx));
       return 1;
     }
-    if (rc) return die(ctx, rc, "cfrk_fasta_parse_device");
+    if (rc) return die(ctx, rc, fq ? "cfrk_fastq_parse_device" : "cfrk_fasta_parse_device");
     *parse_ms = (now_s() - t1) * 1e3;
     cfrk_device_free(ctx, d_text);                      // (the codes are what is counted)
     d_text = nullptr;
@@ -734,16 +787,20 @@ struct Parsed {
   int rc = 0;
   double t0 = 0, seconds = 0;
   std::thread th;
-  void start(const Options &o, const char *in) {
+  void start(const Options &o, const char *in, int fmt) {
     t0 = now_s();
-    const unsigned flags = (o.native || o.global || o.sparse) ? 0 : CFRK_INGEST_COMPAT;
-    th = std::thread([this, in, flags] { rc = cfrk_host_read_fasta(in, flags, &batch); seconds = now_s() - t0; });
+    const int flags = (o.native || o.global || o.sparse) ? 0 : CFRK_INGEST_COMPAT, min_qual = o.min_qual;
+    th = std::thread([this, in, fmt, flags, min_qual] { rc = read_reads(in, fmt, flags, min_qual, &batch); seconds = now_s() - t0; });
   }
 };
 
 int run_file(const Options &o, const char *in, const char *outp, std::vector<Worker> &workers,
-             std::vector<std::vector<Worker>> *per_dev = nullptr, Parsed *pre = nullptr) {
+             std::vector<std::vector<Worker>> *per_dev = nullptr, Parsed *pre = nullptr, int fmt = -1) {
   cfrk_batch batch;
+  if (fmt < 0) {                                        // (--batch: every file is looked at on its own)
+    fmt = file_format(o, in);
+    if (!format_allowed(o, in, fmt)) return 1;
+  }
   double t0 = now_s();
   int rc;
   DeviceText dt;
@@ -751,21 +808,23 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
   double text_map = 0, text_h2d = 0, device_parse_ms = 0;
   if (o.device_parse) {
     memset(&batch, 0, sizeof batch);
-    rc = dt.load(in, o.text_copy_plain, &batch.nN, &batch.nS, &text_map, &text_h2d, &device_parse_ms);
+    rc = dt.load(in, o.text_copy_plain, fmt, o.min_qual, &batch.nN, &batch.nS, &text_map, &text_h2d, &device_parse_ms);
     if (rc > 0) return rc;                              // (a device error, reported)
   } else if (pre) {
     const double w0 = now_s();
     pre->th.join();
     g_wait_parse = now_s() - w0;
     rc = pre->rc; batch = pre->batch; t0 = pre->t0;
+    if (rc) return 1;                                   // (read_reads has said why)
   } else {
-    rc = cfrk_host_read_fasta(in, (o.native || o.global || o.sparse) ? 0 : CFRK_INGEST_COMPAT, &batch);
+    if (read_reads(in, fmt, (o.native || o.global || o.sparse) ? 0 : CFRK_INGEST_COMPAT, o.min_qual, &batch)) return 1;
+    rc = 0;
   }
   if (rc) { fprintf(stderr, "cfrk: cannot read %s (error %d)\n", in, rc); return 1; }
   const double t1 = pre ? t0 + pre->seconds : now_s();
   g_timing = Timing();
   g_timing.contexts = g_contexts_s; g_timing.wait_parse = g_wait_parse;
-  g_timing.parse = t1 - t0; g_timing.nN = batch.nN; g_timing.nS = batch.nS;
+  g_timing.parse = t1 - t0; g_timing.nN = batch.nN; g_timing.nS = batch.nS; g_timing.in_format = fmt;
   if (o.device_parse) { g_timing.parse = 0; g_timing.device_parse = true; g_timing.text_map = text_map; g_timing.text_h2d = text_h2d; g_timing.device_parse_ms = device_parse_ms; }
   { FILE *f = fopen(in, "rb"); if (f) { fseek(f, 0, SEEK_END); g_timing.fasta_bytes = (int64_t)ftell(f); fclose(f); } }
   std::thread freer;                                  // (global mode: frees the batch beside the export)
@@ -807,12 +866,12 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
             "\"finish_wait_s\": %.4f, \"count_kernels_ms\": %.3f, \"export_s\": %.4f, \"format_s\": %.4f, \"write_s\": %.4f, "
             "\"per_read_pipeline_s\": %.4f, \"entries\": %llu, \"out_bytes\": %llu, \"contexts_s\": %.4f, \"wait_for_parser_s\": %.4f, "
             "\"begin_s\": %.4f, \"open_out_s\": %.4f, \"close_out_s\": %.4f, \"free_batch_s\": %.4f, \"histo_s\": %.4f, %s\"attempts\": %d, "
-            "\"estimate_s\": %.4f, \"distinct_estimate\": %.0f, \"hint\": %llu, \"wall_s\": %.4f}\n",
+            "\"estimate_s\": %.4f, \"distinct_estimate\": %.0f, \"hint\": %llu, \"format\": \"%s\", \"wall_s\": %.4f}\n",
             (long long)g_timing.fasta_bytes, (long long)g_timing.nS, (long long)g_timing.nN, g_timing.parse, g_timing.add_call,
             g_timing.finish_wait, (double)g_timing.count_kernels_ms, g_timing.export_, g_timing.format, g_timing.write,
             g_timing.per_read, (unsigned long long)g_timing.entries, (unsigned long long)g_timing.out_bytes, g_timing.contexts,
             g_timing.wait_parse, g_timing.begin, g_timing.open, g_timing.close, g_timing.free_batch, g_timing.histo, query_field, g_timing.attempts,
-            g_timing.estimate, g_timing.distinct_estimate, (unsigned long long)g_timing.hint, g_timing.total);
+            g_timing.estimate, g_timing.distinct_estimate, (unsigned long long)g_timing.hint, g_timing.in_format == CFRK_FORMAT_FASTQ ? "fastq" : "fasta", g_timing.total);
   return rc;
 }
 
@@ -897,6 +956,20 @@ int main(int argc, char **argv) {
       if (strcmp(v, "plain") && strcmp(v, "staged")) { fprintf(stderr, "cfrk: --text-copy takes plain or staged, not '%s'\n", v); return 1; }
       o.text_copy_plain = !strcmp(v, "plain");
     }
+    else if (!strcmp(argv[i], "--format") && i + 1 < argc) {
+      const char *v = argv[++i];
+      if (!strcmp(v, "fasta")) o.format = CFRK_FORMAT_FASTA;
+      else if (!strcmp(v, "fastq")) o.format = CFRK_FORMAT_FASTQ;
+      else if (!strcmp(v, "auto")) o.format = -1;
+      else { fprintf(stderr, "cfrk: --format takes fasta, fastq or auto, not '%s'\n", v); return 1; }
+    }
+    else if (!strcmp(argv[i], "--min-qual") && i + 1 < argc) {
+      const char *v = argv[++i];
+      char *end = nullptr;
+      const long q = strtol(v, &end, 10);
+      if (!*v || *end || q < 0 || q > CFRK_FASTQ_MAX_QUAL) { fprintf(stderr, "cfrk: --min-qual needs an integer from 0 to %d, not '%s'\n", CFRK_FASTQ_MAX_QUAL, v); return 1; }
+      o.min_qual = (int)q; o.min_qual_set = true;
+    }
     else if (!strcmp(argv[i], "--query-only")) o.query_only = true;
     else if (!strcmp(argv[i], "--query") || !strcmp(argv[i], "--query-out") || !strcmp(argv[i], "--query-db")) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
@@ -960,10 +1033,8 @@ int main(int argc, char **argv) {
   if (o.query_stats && o.gpus > 1) { fprintf(stderr, "cfrk: --query-stats runs on one device: not with --gpus above 1\n"); return 1; }
   if (o.query && batch_n >= 0) { fprintf(stderr, "cfrk: --query writes one file: not with --batch\n"); return 1; }
   if (o.query_db && !pos.empty()) { fprintf(stderr, "cfrk: --query-db takes no positional arguments\n"); return 1; }
-  if (o.query) {
-    const int qrc = cfrk_host_read_fasta(o.query, 0, &g_qreads);
-    if (qrc) { fprintf(stderr, "cfrk: cannot read %s (error %d)\n", o.query, qrc); return 1; }
-  }
+  if (o.query_db && o.min_qual_set) { fprintf(stderr, "cfrk: --min-qual applies to the FASTQ input that is counted: not with --query-db\n"); return 1; }
+  if (o.query && read_reads(o.query, file_format(o, o.query), 0, 0, &g_qreads)) return 1;
   struct QFree { ~QFree() { if (g_qreads.data) cfrk_host_free_batch(&g_qreads); } } qfree;
   if (o.query_db) return run_query_db(o);
   if (pos.size() < 3) {
@@ -983,8 +1054,13 @@ int main(int argc, char **argv) {
   if (batch_n == 0 || batch_n < -1) { fprintf(stderr, "cfrk: --batch needs a positive file count\n"); return 1; }
 
   // single-file mode: the parse starts now, beside the creation of the contexts
+  int fmt = -1;
+  if (batch_n < 0) {
+    fmt = file_format(o, pos[0]);
+    if (!format_allowed(o, pos[0], fmt)) return 1;
+  }
   Parsed pre;
-  if (batch_n < 0 && !o.device_parse) pre.start(o, pos[0]);
+  if (batch_n < 0 && !o.device_parse) pre.start(o, pos[0], fmt);
   struct Joiner { Parsed &p; ~Joiner() { if (p.th.joinable()) { p.th.join(); if (!p.rc) cfrk_host_free_batch(&p.batch); } } } joiner{pre};   // (early returns)
   const double tc0 = now_s();                          // (runtime start-up + the contexts)
   int ndev = 0, rc;
@@ -1009,7 +1085,7 @@ int main(int argc, char **argv) {
     std::vector<Worker> all;
     for (int s = 0; s < 2; ++s)                       // device-major would put both streams of a device first
       for (int g = 0; g < o.gpus; ++g) all.push_back(per_dev[(size_t)g][(size_t)s]);
-    status = run_file(o, pos[0], pos[1], all, &per_dev, o.device_parse ? nullptr : &pre);
+    status = run_file(o, pos[0], pos[1], all, &per_dev, o.device_parse ? nullptr : &pre, fmt);
   } else {
     // file i goes to device i % gpus (swift/cfrk.swf:15-20 starts one cfrk process per file)
     std::vector<int> st((size_t)o.gpus, 0);

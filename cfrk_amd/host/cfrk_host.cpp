@@ -1,4 +1,4 @@
-// cfrk_host.cpp -- FASTA ingest, chunk views and .cfrk formatting (see cfrk_host.h).
+// cfrk_host.cpp -- FASTA and FASTQ ingest, chunk views and .cfrk formatting (see cfrk_host.h).
 #include "cfrk_host.h"
 
 #include <fcntl.h>
@@ -277,6 +277,185 @@ int cfrk_host_read_fasta(const char *path, int flags, cfrk_batch *out) {
   while ((n = fread(tmp, 1, sizeof tmp, f)) > 0) buf.append(tmp, n);   // growing file / pipe
   fclose(f);
   return cfrk_host_parse_fasta(buf.data(), buf.size(), flags, out);
+}
+
+int cfrk_host_sniff_format(const char *buf, size_t len) {
+  return (buf && len > 0 && buf[0] == '@') ? CFRK_FORMAT_FASTQ : CFRK_FORMAT_FASTA;
+}
+
+size_t cfrk_host_fastq_message(int rc, uint64_t where, char *buf, size_t cap) {
+  char tmp[160];
+  int n = 0;
+  const unsigned long long w = (unsigned long long)where;
+  switch (rc) {
+    case CFRK_FASTQ_NO_AT: n = snprintf(tmp, sizeof tmp, "FASTQ: line %llu does not begin with '@'", w); break;
+    case CFRK_FASTQ_NO_PLUS: n = snprintf(tmp, sizeof tmp, "FASTQ: line %llu does not begin with '+'", w); break;
+    case CFRK_FASTQ_TRUNCATED: n = snprintf(tmp, sizeof tmp, "FASTQ: %llu lines, not a multiple of four", w); break;
+    case CFRK_FASTQ_LENGTHS: n = snprintf(tmp, sizeof tmp, "FASTQ: record %llu has sequence and quality lines of different lengths", w); break;
+    case CFRK_FASTQ_LONG: n = snprintf(tmp, sizeof tmp, "FASTQ: record %llu is longer than 2^31 - 1 bases", w); break;
+    case CFRK_FASTQ_MIN_QUAL: n = snprintf(tmp, sizeof tmp, "FASTQ: min_qual outside 0 .. 93"); break;
+    default: break;
+  }
+  if (n <= 0) return 0;
+  if (buf && cap > 0) {
+    const size_t m = std::min((size_t)n, cap - 1);
+    memcpy(buf, tmp, m);
+    buf[m] = 0;
+  }
+  return (size_t)n;
+}
+
+int cfrk_host_parse_fastq(const char *buf, size_t len, int min_qual, cfrk_batch *out, uint64_t *where) {
+  uint64_t where_unused;
+  if (!where) where = &where_unused;
+  *where = 0;
+  if (!out || (!buf && len)) return -4;
+  memset(out, 0, sizeof *out);
+  if (min_qual < 0 || min_qual > 93) return CFRK_FASTQ_MIN_QUAL;
+  // an explicit thread count holds for a text of any size (slices may be empty); the default threads large texts only
+  unsigned nthr;
+  if (g_parse_threads > 0) {
+    nthr = (unsigned)std::min(g_parse_threads, 256);
+  } else {
+    nthr = std::thread::hardware_concurrency();
+    if (nthr > 64) nthr = 64;
+    if (nthr < 2 || len < ((size_t)8 << 20)) nthr = 1;
+  }
+  auto run = [&](auto &&fn) {
+    if (nthr == 1) { fn(0u); return; }
+    std::vector<std::thread> pool;
+    for (unsigned t = 0; t < nthr; ++t) pool.emplace_back(fn, t);
+    for (auto &th : pool) th.join();
+  };
+  std::vector<size_t> cut(nthr + 1, len);
+  for (unsigned t = 0; t < nthr; ++t) cut[t] = len / nthr * t;
+  // pass 1: the newlines of every slice; the lines in front of a slice are the newlines in front of it
+  std::vector<uint64_t> lines_before(nthr + 1, 0);
+  run([&](unsigned t) {
+    uint64_t c = 0;
+    for (const char *p = buf + cut[t], *e = buf + cut[t + 1]; p < e;) {
+      const char *nl = (const char *)memchr(p, '\n', (size_t)(e - p));
+      if (!nl) break;
+      ++c; p = nl + 1;
+    }
+    lines_before[t + 1] = c;
+  });
+  for (unsigned t = 0; t < nthr; ++t) lines_before[t + 1] += lines_before[t];
+  // pass 2: a slice handles the lines that START in it, to their ends; the kind of a line is its number mod 4
+  struct Line { size_t pos, n; };
+  struct Part { std::vector<Line> seq, qual; uint64_t bad_line = ~(uint64_t)0; };
+  std::vector<Part> parts(nthr);
+  run([&](unsigned t) {
+    Part &pt = parts[t];
+    size_t pos = cut[t];
+    const size_t stop = cut[t + 1];
+    uint64_t line = lines_before[t];
+    if (pos >= stop) return;
+    if (pos > 0 && buf[pos - 1] != '\n') {                // in the middle of a line that an earlier slice handles
+      const char *nl = (const char *)memchr(buf + pos, '\n', stop - pos);
+      if (!nl) return;
+      pos = (size_t)(nl - buf) + 1; ++line;
+    }
+    while (pos < stop) {
+      const char *nl = (const char *)memchr(buf + pos, '\n', len - pos);
+      size_t e = nl ? (size_t)(nl - buf) : len;
+      const size_t next = nl ? e + 1 : len;
+      if (e > pos && buf[e - 1] == '\r') --e;               // in front of the '\n', or the text's last byte
+      switch (line & 3) {
+        case 0: if (buf[pos] != '@' && pt.bad_line == ~(uint64_t)0) pt.bad_line = line; break;
+        case 1: pt.seq.push_back(Line{pos, e - pos}); break;
+        case 2: if (buf[pos] != '+' && pt.bad_line == ~(uint64_t)0) pt.bad_line = line; break;
+        default: pt.qual.push_back(Line{pos, e - pos}); break;
+      }
+      pos = next; ++line;
+    }
+  });
+  for (const Part &pt : parts)
+    if (pt.bad_line != ~(uint64_t)0) { *where = pt.bad_line; return (pt.bad_line & 3) ? CFRK_FASTQ_NO_PLUS : CFRK_FASTQ_NO_AT; }
+  const uint64_t lines = lines_before[nthr] + ((len > 0 && buf[len - 1] != '\n') ? 1 : 0);
+  if (lines & 3) { *where = lines; return CFRK_FASTQ_TRUNCATED; }
+  const int64_t nS = (int64_t)(lines >> 2);
+  std::vector<Line> seq, qual;
+  seq.reserve((size_t)nS); qual.reserve((size_t)nS);
+  for (const Part &pt : parts) {
+    seq.insert(seq.end(), pt.seq.begin(), pt.seq.end());
+    qual.insert(qual.end(), pt.qual.begin(), pt.qual.end());
+  }
+  if (seq.size() != (size_t)nS || qual.size() != (size_t)nS) return -4;       // (cannot happen: every line has one owner)
+  for (int64_t r = 0; r < nS; ++r)
+    if (seq[(size_t)r].n != qual[(size_t)r].n) { *where = (uint64_t)r; return CFRK_FASTQ_LENGTHS; }
+  int64_t nN = 0;
+  for (int64_t r = 0; r < nS; ++r) {
+    if (seq[(size_t)r].n > 0x7FFFFFFF) { *where = (uint64_t)r; return CFRK_FASTQ_LONG; }
+    nN += (int64_t)seq[(size_t)r].n + 1;
+  }
+  out->data = (int8_t *)big_alloc((size_t)(nN > 0 ? nN : 1));
+  out->start = (int64_t *)big_alloc(sizeof(int64_t) * (size_t)(nS > 0 ? nS : 1));
+  out->length = (int32_t *)big_alloc(sizeof(int32_t) * (size_t)(nS > 0 ? nS : 1));
+  if (!out->data || !out->start || !out->length) { cfrk_host_free_batch(out); return -4; }
+  out->nN = nN; out->nS = nS;
+  {
+    int64_t w = 0;
+    for (int64_t r = 0; r < nS; ++r) {
+      out->start[r] = w;
+      out->length[r] = (int32_t)seq[(size_t)r].n;
+      w += (int64_t)seq[(size_t)r].n + 1;
+    }
+  }
+  // pass 3: encode and mask; records are independent, split by bytes
+  const int low = 33 + min_qual;
+  auto encode = [&](int64_t r0, int64_t r1) {
+    for (int64_t r = r0; r < r1; ++r) {
+      const Line s = seq[(size_t)r];
+      int8_t *d = out->data + out->start[r];
+      encode_bytes(reinterpret_cast<const unsigned char *>(buf) + s.pos, d, s.n);
+      if (min_qual > 0) {
+        const unsigned char *q = reinterpret_cast<const unsigned char *>(buf) + qual[(size_t)r].pos;
+        for (size_t j = 0; j < s.n; ++j)
+          if ((int)q[j] < low) d[j] = -1;
+      }
+      d[s.n] = -1;
+    }
+  };
+  if (nthr < 2) {
+    encode(0, nS);
+  } else {
+    std::vector<std::thread> pool;
+    int64_t r0 = 0;
+    for (unsigned t = 0; t < nthr; ++t) {
+      const int64_t target = nN / nthr * (t + 1);
+      int64_t r1 = r0;
+      if (t + 1 == nthr) r1 = nS;
+      else while (r1 < nS && out->start[r1] < target) ++r1;
+      if (r1 > r0) pool.emplace_back(encode, r0, r1);
+      r0 = r1;
+    }
+    for (auto &th : pool) th.join();
+  }
+  return 0;
+}
+
+int cfrk_host_read_fastq(const char *path, int min_qual, cfrk_batch *out, uint64_t *where) {
+  // as cfrk_host_read_fasta: a regular file is mapped, anything else (a pipe) is read chunk by chunk
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return -1;
+  struct stat st;
+  if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
+    void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
+    if (m != MAP_FAILED) {
+      (void)madvise(m, (size_t)st.st_size, MADV_SEQUENTIAL);
+      const int rc = cfrk_host_parse_fastq((const char *)m, (size_t)st.st_size, min_qual, out, where);
+      munmap(m, (size_t)st.st_size);
+      close(fd);
+      return rc;
+    }
+  }
+  std::string text;
+  char tmp[1 << 16];
+  ssize_t n;
+  while ((n = read(fd, tmp, sizeof tmp)) > 0) text.append(tmp, (size_t)n);
+  close(fd);
+  return cfrk_host_parse_fastq(text.data(), text.size(), min_qual, out, where);
 }
 
 int cfrk_host_chunk(const cfrk_batch *b, int64_t first, int64_t count, const int8_t **data,

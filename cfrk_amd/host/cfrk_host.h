@@ -1,4 +1,4 @@
-// cfrk_host.h -- host side of the cfrk drop-in: FASTA ingest, chunking, .cfrk output.
+// cfrk_host.h -- host side of the cfrk drop-in: FASTA / FASTQ ingest, chunking, .cfrk output.
 //
 // Mirrors the reference's host code around kmer_main() (paths under /root/reference/):
 //   ReadFasta / ReadFASTASequences / ProcessData   src/fastaIO.h:24-148
@@ -39,6 +39,36 @@ int  cfrk_host_parse_fasta(const char *buf, size_t len, int flags, cfrk_batch *o
 void cfrk_host_free_batch(cfrk_batch *b);
 /* threads the parser may use for large inputs (0 = the default, min(hardware threads, 64)) */
 void cfrk_host_set_parse_threads(int n);
+
+/* Parse strict four-line FASTQ (the grammar of cfrk_fastq_parse_device, include/cfrk_abi.h: records of an '@' line, a
+ * sequence line, a '+' line and a quality line; one '\r' in front of a '\n' or at the text's end dropped per line) into
+ * the native struct-read layout.  min_qual 0 .. 93: with min_qual >= 1 a base whose Phred+33 quality is below it
+ * becomes -1.  Threaded like the FASTA parser (cfrk_host_set_parse_threads; an explicit thread count is honoured for
+ * texts of any size); the result does not depend on the thread count.
+ * Returns 0, -1 (cannot open), -4 (out of memory, NULL argument), or, with the place in *where (may be NULL):
+ *   CFRK_FASTQ_NO_AT     line *where (a multiple of four, counted from 0) does not begin with '@'
+ *   CFRK_FASTQ_NO_PLUS   line *where does not begin with '+'
+ *   CFRK_FASTQ_TRUNCATED *where lines, not a multiple of four
+ *   CFRK_FASTQ_LENGTHS   record *where (from 0): sequence and quality lines differ in length
+ *   CFRK_FASTQ_LONG      record *where has more than 2^31 - 1 bases
+ *   CFRK_FASTQ_MIN_QUAL  min_qual outside 0 .. 93
+ * in the order of the device parser: the structural fault (the first three) on the earliest line, the truncated record
+ * behind every line; then the first record of differing lengths; then the first over-long one.
+ * cfrk_host_fastq_message writes the one-line text of such a code ("FASTQ: ..."), in the device parser's words, and
+ * returns its length (0 for a code that is none of these). */
+#define CFRK_FASTQ_NO_AT (-5)
+#define CFRK_FASTQ_NO_PLUS (-6)
+#define CFRK_FASTQ_TRUNCATED (-7)
+#define CFRK_FASTQ_LENGTHS (-8)
+#define CFRK_FASTQ_LONG (-9)
+#define CFRK_FASTQ_MIN_QUAL (-10)
+int  cfrk_host_parse_fastq(const char *buf, size_t len, int min_qual, cfrk_batch *out, uint64_t *where);
+int  cfrk_host_read_fastq(const char *path, int min_qual, cfrk_batch *out, uint64_t *where);
+size_t cfrk_host_fastq_message(int rc, uint64_t where, char *buf, size_t cap);
+/* the format of a text by its first byte: '@' is FASTQ, anything else, the empty text included, FASTA */
+#define CFRK_FORMAT_FASTA 0
+#define CFRK_FORMAT_FASTQ 1
+int  cfrk_host_sniff_format(const char *buf, size_t len);
 
 /* Chunk [first, first+count) of a batch with chunk-relative start[] (SelectChunk,
  * src/main.cu:160-206): views into the batch, nothing is copied; start_out needs count slots. */

@@ -39,6 +39,10 @@ CFRK_SKETCH_REGS = 16384             # one uint8 register per bucket
 CFRK_FASTA_TILE_BYTES = 16384        # device FASTA parser: text bytes per workgroup
 CFRK_FASTA_SCAN_TILES = 1024         # tiles per block of its tile scan
 CFRK_FASTA_MAX_CR_RUN = 4096         # native mode: carriage returns in a row it follows to the line's end
+CFRK_FASTQ_TILE_BYTES = 16384        # device FASTQ parser: text bytes per workgroup
+CFRK_FASTQ_SCAN_TILES = 1024         # tiles per block of its tile scan
+CFRK_FASTQ_QUAL_BASE = 33            # qualities are Phred+33
+CFRK_FASTQ_MAX_QUAL = 93             # min_qual is 0 .. this
 CFRK_PARAM_MSP_CHUNKS, CFRK_PARAM_L2_SLACK_COMPLETE, CFRK_PARAM_L2_SLACK_TRUNCATED, CFRK_PARAM_MSP2_SUBVALUE_BITS = 0, 1, 2, 3   # cfrk_debug_set_param
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -134,6 +138,8 @@ def load_library():
         "cfrk_sketch_hint": ([vp, C.POINTER(u64)], C.c_int),
         "cfrk_fasta_parse_device": ([vp, vp, u64, i32, vp, u64, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_fasta_parse": ([vp, vp, u64, i32, vp, u64, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "cfrk_fastq_parse_device": ([vp, vp, u64, i32, vp, u64, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "cfrk_fastq_parse": ([vp, vp, u64, i32, vp, u64, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_synth_reads_device": ([vp, i64, i64, i32, i64, u64, u64, u64, i32, vp, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
@@ -375,6 +381,38 @@ class Context:
         if rc == CFRK_ERR_SMALL_BUF:
             self.check(self._L.cfrk_fasta_parse(self._h, _ptr(text), text.size, flags, _ptr(data), data.size, _ptr(start),
                                                 _ptr(length), start.size, C.byref(nN), C.byref(nS)), "cfrk_fasta_parse")
+        return data, start, length
+
+    # -- FASTQ text parsed on the device, low-quality bases masked ------------------------------
+    def parse_fastq_device(self, d_text, nbytes, min_qual, d_data, cap_data, d_start, d_length, cap_reads):
+        """device form: strict four-line FASTQ, d_text 16-byte aligned -> (nN, nS) in the native layout; with
+        min_qual >= 1 a base whose Phred+33 quality is below it gets code -1.  d_data / d_start / d_length may be 0
+        with zero capacities (sizes only).  Raises CfrkError (code CFRK_ERR_SMALL_BUF, with .nN and .nS set, nothing
+        written) when the arrays are too small.  Synchronises twice; the arrays are complete when it returns."""
+        nN, nS = C.c_int64(), C.c_int64()
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_fastq_parse_device(self._h, vp(d_text), nbytes, min_qual, vp(d_data), cap_data, vp(d_start),
+                                             vp(d_length), cap_reads, C.byref(nN), C.byref(nS))
+        try:
+            self.check(rc, "cfrk_fastq_parse_device")
+        except CfrkError as e:
+            e.nN, e.nS = nN.value, nS.value
+            raise
+        return nN.value, nS.value
+
+    def parse_fastq(self, text, min_qual=0):
+        """FASTQ text (bytes or a uint8 array) -> host (data int8[nN], start int64[nS], length int32[nS]), what the
+        host parser (cfrk_host_parse_fastq) makes of it.  A sizes-only call, then the parse into arrays of exactly
+        that size."""
+        text = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+        nN, nS = C.c_int64(), C.c_int64()
+        rc = self._L.cfrk_fastq_parse(self._h, _ptr(text), text.size, min_qual, None, 0, None, None, 0, C.byref(nN), C.byref(nS))
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.check(rc, "cfrk_fastq_parse")
+        data, start, length = np.empty(nN.value, np.int8), np.empty(nS.value, np.int64), np.empty(nS.value, np.int32)
+        if rc == CFRK_ERR_SMALL_BUF:
+            self.check(self._L.cfrk_fastq_parse(self._h, _ptr(text), text.size, min_qual, _ptr(data), data.size, _ptr(start),
+                                                _ptr(length), start.size, C.byref(nN), C.byref(nS)), "cfrk_fastq_parse")
         return data, start, length
 
     def synth_reads_device(self, r0, R, L, Glen, d_data, d_start=None, d_length=None,

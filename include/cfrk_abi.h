@@ -365,6 +365,62 @@ int cfrk_fasta_parse(cfrk_ctx *ctx, const char *text, uint64_t nbytes, int flags
                      int8_t *data, uint64_t cap_data, int64_t *start, int32_t *length, uint64_t cap_reads,
                      int64_t *nN_out, int64_t *nS_out);
 
+/* ---- FASTQ text parsed on the device: text in, struct-read buffers out, low-quality bases masked -------------- */
+
+/* nbytes of strict four-line FASTQ text -> data, start, length, nN, nS in the native layout of the FASTA parser above:
+ * byte for byte what the host parser (cfrk_host_parse_fastq, cfrk_amd/host/cfrk_host.h) makes of the same bytes.
+ * Wrapped (multi-line) FASTQ is refused, not guessed at.  There is no compat mode: the reference reads no FASTQ.
+ * Lines: a line ends at '\n' or at the end of the text; the number of lines is the number of '\n', plus one if the
+ *   text is non-empty and does not end in '\n' (a trailing '\n' opens no further line; a final EMPTY quality line needs
+ *   its '\n').  Lines and records are numbered from 0.
+ * Carriage returns: a '\r' directly in front of a '\n', or as the text's last byte, is dropped from its line (one
+ *   only); every other '\r' is an ordinary byte of its line.
+ * Records: record r is lines 4r .. 4r+3: a line whose first byte is '@' (an empty line fails), the sequence line, a
+ *   line whose first byte is '+' (the rest of it is ignored), the quality line.  The kind of a line follows from its
+ *   number alone: a quality line that begins with '@', '+' or '>' is an ordinary quality line.
+ * Output: data = the codes of the sequence line (aA cC gG tT -> 0 1 2 3, anything else -> -1) and one -1 terminator;
+ *   length[r] = bytes of the sequence line; start[r] = bases before record r, plus r; nN = bases + nS; a record may be
+ *   empty (length 0).  Empty text: nS = nN = 0.
+ * Masking: qualities are Phred+33 (CFRK_FASTQ_QUAL_BASE); min_qual is 0 .. CFRK_FASTQ_MAX_QUAL, anything else is
+ *   CFRK_ERR_ARG.  With min_qual >= 1 base j of a record gets code -1 when (int)(unsigned char)qual[j] - 33 < min_qual
+ *   (a quality byte below 33 masks, a byte of 128 or more never does); length and start do not change.  With
+ *   min_qual = 0 the quality line is only measured and masks nothing, whatever bytes it holds.
+ * CFRK_ERR_LAYOUT (cfrk_last_error names the cause and the place; cfrk_host_parse_fastq reports the same cause and
+ * place), in this order:
+ *   1. structural faults, the one on the earliest line: line 4r does not begin with '@', line 4r+2 does not begin with
+ *      '+' (the message names the line and the byte offset of its first byte); a number of lines that is not a
+ *      multiple of four (names the number) -- this one counts as lying behind every line;
+ *   2. in a structurally sound text, the first record whose sequence and quality lines differ in length;
+ *   3. then a record of more than 2^31 - 1 bases.
+ * After an error the contents of the output arrays are unspecified; nothing outside the capacities is ever written.
+ * A NULL text with nbytes > 0, NULL size outputs and a NULL array with a capacity above 0 are CFRK_ERR_ARG; d_text
+ * must be 16-byte aligned (CFRK_ERR_ALIGN), d_data need not be.
+ * Capacities: cap_data = nbytes / 2 and cap_reads = (nbytes + 1) / 6 always suffice.  A record of L bases takes
+ * '@', '\n', L, '\n', '+', '\n', L and, unless it ends the text, '\n': nS records with B bases in all take at least
+ * 2 B + 6 nS - 1 bytes, so nS <= (nbytes + 1) / 6 and, for nS >= 1, nN = B + nS <= (nbytes + 1) / 2 - 2 nS <= nbytes / 2.
+ * When nN > cap_data or nS > cap_reads the call returns CFRK_ERR_SMALL_BUF with *nN_out / *nS_out complete and nothing
+ * written to the arrays; NULL arrays with zero capacities are that "sizes only" call.  The structural faults are found
+ * before the sizes are known and win over CFRK_ERR_SMALL_BUF; the length comparison (2.) and the over-long check (3.)
+ * run with the scatter pass, so a sizes-only call on such a text returns its sizes and the call with arrays refuses it.
+ * Device form: reduce, one-workgroup scan, scatter, (min_qual > 0) a masking pass and a length pass as separate
+ * launches on the context stream (no workgroup waits for another one).  It synchronises TWICE: once to read the sizes
+ * and the structural verdict back, and once at its end for the verdict of the length comparison, so the arrays are
+ * complete when it returns.  Temporary device memory, kept in the context's pool (the FASTA parser's slot): 128 bytes +
+ * 56 bytes per tile of CFRK_FASTQ_TILE_BYTES (3.5 MB per GB of text); the scan walks the tiles in blocks of
+ * CFRK_FASTQ_SCAN_TILES.
+ * Host form: host text in, host arrays out; stages through the pool (the text, then data / start / length); synchronous.
+ * Neither call touches a global job that is open on the same context. */
+#define CFRK_FASTQ_TILE_BYTES 16384
+#define CFRK_FASTQ_SCAN_TILES 1024
+#define CFRK_FASTQ_QUAL_BASE 33
+#define CFRK_FASTQ_MAX_QUAL 93
+int cfrk_fastq_parse_device(cfrk_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, int min_qual,
+                            int8_t *d_data, uint64_t cap_data, int64_t *d_start, int32_t *d_length, uint64_t cap_reads,
+                            int64_t *nN_out, int64_t *nS_out);
+int cfrk_fastq_parse(cfrk_ctx *ctx, const char *text, uint64_t nbytes, int min_qual,
+                     int8_t *data, uint64_t cap_data, int64_t *start, int32_t *length, uint64_t cap_reads,
+                     int64_t *nN_out, int64_t *nS_out);
+
 /* Unsorted export into device buffers, grouped into `parts` contiguous segments by
  * owner(key) = (mix(key) >> 32) % parts (key-owner partition for the multi-GPU
  * merge).  part_counts (host, `parts` entries) receives the segment sizes.  Synchronises. */
