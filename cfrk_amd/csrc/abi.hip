@@ -743,6 +743,161 @@ int cfrk_global_read_stats(cfrk_ctx *ctx, const int8_t *data, const int64_t *sta
   return CFRK_OK;
 }
 
+static_assert(sizeof(cfrk_read_span) == 8, "cfrk_read_span is 8 bytes without padding");
+
+static int read_spans_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, const void *data, const void *start,
+                            const void *length, const void *out, int mode) {
+  int rc = read_stats_check(ctx, nN, nS, data, start, length, out);
+  if (rc) return rc;
+  if (mode != CFRK_SPAN_PREFIX && mode != CFRK_SPAN_LONGEST)
+    return cfrk_fail(ctx, CFRK_ERR_ARG, "mode %d: CFRK_SPAN_PREFIX or CFRK_SPAN_LONGEST", mode);
+  return CFRK_OK;
+}
+
+int cfrk_global_read_spans_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                  int64_t nN, int64_t nS, uint32_t min_count, uint32_t max_count, int mode,
+                                  cfrk_read_span *d_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = read_spans_check(ctx, nN, nS, d_data, d_start, d_length, d_out, mode);
+  if (rc || nS == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_read_spans_launch(ctx, d_data, d_start, d_length, nN, nS, min_count, max_count, mode, d_out);
+}
+
+int cfrk_global_read_spans(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                           int64_t nS, uint32_t min_count, uint32_t max_count, int mode, cfrk_read_span *out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = read_spans_check(ctx, nN, nS, data, start, length, out, mode);
+  if (rc || nS == 0) return rc;
+  LayoutCheck lc;      // (the add's check of the struct-read layout, beside the copies)
+  lc.begin(data, start, length, nN, nS);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // staged through the query calls' slots: [data | start | length] in, the spans out; each part 256-byte aligned
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_start = up((size_t)nN + 64), o_length = o_start + up((size_t)nS * 8);
+  void *p_in, *p_out;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_IN, o_length + (size_t)nS * 4, &p_in))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, (size_t)nS * sizeof(cfrk_read_span), &p_out))) return rc;
+  int8_t *d_data = (int8_t *)p_in;
+  int64_t *d_start = (int64_t *)((char *)p_in + o_start);
+  int32_t *d_length = (int32_t *)((char *)p_in + o_length);
+  if (nN) HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_start, start, (size_t)nS * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_length, length, (size_t)nS * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (lc.failed(ctx)) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
+    return CFRK_ERR_LAYOUT;
+  }
+  if ((rc = cfrk_read_spans_launch(ctx, d_data, d_start, d_length, nN, nS, min_count, max_count, mode, (cfrk_read_span *)p_out))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(out, p_out, (size_t)nS * sizeof(cfrk_read_span), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CFRK_OK;
+}
+
+static int select_check(cfrk_ctx *ctx, const void *data, const void *start, const void *length, int64_t nN, int64_t nS,
+                        int32_t min_len, const void *data_out, uint64_t cap_data, const void *start_out,
+                        const void *length_out, uint64_t cap_reads, const int64_t *nN_out, const int64_t *nS_out) {
+  if (nN < 0 || nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (min_len < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "min_len %d is negative", (int)min_len);
+  if (!nN_out || !nS_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL size output");
+  if ((nS > 0 && (!start || !length)) || (nN > 0 && !data)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if ((cap_data > 0 && !data_out) || (cap_reads > 0 && (!start_out || !length_out)))
+    return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL array with a capacity above 0");
+  return CFRK_OK;
+}
+
+static int select_small(cfrk_ctx *ctx, int64_t nN, int64_t nS, uint64_t cap_data, uint64_t cap_reads) {
+  if ((uint64_t)nN > cap_data || (uint64_t)nS > cap_reads)
+    return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "select: %lld bytes of data and %lld reads, room for %llu and %llu", (long long)nN,
+                     (long long)nS, (unsigned long long)cap_data, (unsigned long long)cap_reads);
+  return CFRK_OK;
+}
+
+int cfrk_reads_select_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                             int64_t nN, int64_t nS, const cfrk_read_span *d_span, const uint8_t *d_keep,
+                             int32_t min_len, int8_t *d_data_out, uint64_t cap_data, int64_t *d_start_out,
+                             int32_t *d_length_out, int64_t *d_index_out, uint64_t cap_reads, int64_t *nN_out,
+                             int64_t *nS_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = select_check(ctx, d_data, d_start, d_length, nN, nS, min_len, d_data_out, cap_data, d_start_out, d_length_out,
+                        cap_reads, nN_out, nS_out);
+  if (rc) return rc;
+  *nN_out = *nS_out = 0;
+  if (nS == 0) return CFRK_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int64_t on = 0, os = 0;
+  if ((rc = cfrk_select_measure(ctx, d_start, d_length, nN, nS, d_span, d_keep, min_len, &on, &os))) return rc;
+  *nN_out = on; *nS_out = os;
+  if ((rc = select_small(ctx, on, os, cap_data, cap_reads))) return rc;
+  if (os == 0) return CFRK_OK;
+  return cfrk_select_emit(ctx, d_data, d_start, d_length, nN, nS, d_span, d_keep, min_len, d_data_out, d_start_out,
+                          d_length_out, d_index_out, on, os);
+}
+
+int cfrk_reads_select(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                      int64_t nS, const cfrk_read_span *span, const uint8_t *keep, int32_t min_len, int8_t *data_out,
+                      uint64_t cap_data, int64_t *start_out, int32_t *length_out, int64_t *index_out, uint64_t cap_reads,
+                      int64_t *nN_out, int64_t *nS_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = select_check(ctx, data, start, length, nN, nS, min_len, data_out, cap_data, start_out, length_out, cap_reads,
+                        nN_out, nS_out);
+  if (rc) return rc;
+  *nN_out = *nS_out = 0;
+  if (nS == 0) return CFRK_OK;
+  LayoutCheck lc;      // (the add's check of the struct-read layout, beside the copies)
+  lc.begin(data, start, length, nN, nS);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // [data | start | length | span | keep] in, each part 256-byte aligned
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_start = up((size_t)nN + 64), o_length = o_start + up((size_t)nS * 8), o_span = o_length + up((size_t)nS * 4);
+  const size_t o_keep = o_span + up(span ? (size_t)nS * sizeof(cfrk_read_span) : 0);
+  void *p_in;
+  if ((rc = cfrk_pool_get(ctx, BUF_SELECT_IN, o_keep + (keep ? (size_t)nS : 0), &p_in))) return rc;
+  int8_t *d_data = (int8_t *)p_in;
+  int64_t *d_start = (int64_t *)((char *)p_in + o_start);
+  int32_t *d_length = (int32_t *)((char *)p_in + o_length);
+  cfrk_read_span *d_span = span ? (cfrk_read_span *)((char *)p_in + o_span) : nullptr;
+  uint8_t *d_keep = keep ? (uint8_t *)((char *)p_in + o_keep) : nullptr;
+  if (nN) HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_start, start, (size_t)nS * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_length, length, (size_t)nS * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (span) HIP_TRY(ctx, hipMemcpyAsync(d_span, span, (size_t)nS * sizeof(cfrk_read_span), hipMemcpyHostToDevice, ctx->stream));
+  if (keep) HIP_TRY(ctx, hipMemcpyAsync(d_keep, keep, (size_t)nS, hipMemcpyHostToDevice, ctx->stream));
+  bool bad = lc.failed(ctx);
+  for (int64_t i = 0; !bad && span && i < nS; ++i) {
+    const cfrk_read_span s = span[i];
+    if (s.offset < 0 || s.length < 0 || (int64_t)s.offset + (int64_t)s.length > (int64_t)length[i]) {
+      cfrk_fail(ctx, CFRK_ERR_LAYOUT, "read %lld: span {%d, %d} does not lie inside its %d bases", (long long)i, (int)s.offset,
+                (int)s.length, (int)length[i]);
+      bad = true;
+    }
+  }
+  if (bad) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
+    return CFRK_ERR_LAYOUT;
+  }
+  int64_t on = 0, os = 0;
+  if ((rc = cfrk_select_measure(ctx, d_start, d_length, nN, nS, d_span, d_keep, min_len, &on, &os))) return rc;
+  *nN_out = on; *nS_out = os;
+  if ((rc = select_small(ctx, on, os, cap_data, cap_reads))) return rc;
+  if (os == 0) return CFRK_OK;
+  // [data | start | length | index] out
+  const size_t q_start = up((size_t)on + 16), q_length = q_start + up((size_t)os * 8), q_index = q_length + up((size_t)os * 4);
+  void *p_out;
+  if ((rc = cfrk_pool_get(ctx, BUF_SELECT_OUT, q_index + (size_t)os * 8, &p_out))) return rc;
+  int8_t *o_data = (int8_t *)p_out;
+  int64_t *o_st = (int64_t *)((char *)p_out + q_start);
+  int32_t *o_len = (int32_t *)((char *)p_out + q_length);
+  int64_t *o_idx = (int64_t *)((char *)p_out + q_index);
+  if ((rc = cfrk_select_emit(ctx, d_data, d_start, d_length, nN, nS, d_span, d_keep, min_len, o_data, o_st, o_len, o_idx, on, os))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(data_out, o_data, (size_t)on, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(start_out, o_st, (size_t)os * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(length_out, o_len, (size_t)os * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (index_out) HIP_TRY(ctx, hipMemcpyAsync(index_out, o_idx, (size_t)os * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CFRK_OK;
+}
+
 int cfrk_global_last_add_ms(cfrk_ctx *ctx, float *ms) {
   if (!ctx || !ms) return CFRK_ERR_ARG;
   if (!ctx->ev_valid) return cfrk_fail(ctx, CFRK_ERR_STATE, "no add recorded");

@@ -32,6 +32,9 @@ enum {  // pool slots
   BUF_SKETCH,                                 // distinct sketch (sketch.hip): the workgroups' merged registers as words, the window count, the host form's registers
   BUF_FASTA,                                  // FASTA parser (ingest.hip): size / error words, tile aggregates, their scan
   BUF_FASTA_IN, BUF_FASTA_OUT,                // staging of the host form (text in; data, start, length out)
+  BUF_SELECT,                                 // select (read_filter.hip): size words, the read tiles' aggregates, their scan
+  BUF_SELECT_SRC,                             // the kept reads' source offsets
+  BUF_SELECT_IN, BUF_SELECT_OUT,              // staging of the host form (reads, spans, keep in; the selected reads out)
   BUF_NSLOTS
 };
 
@@ -136,6 +139,15 @@ int cfrk_query_reads(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, uint32_t *
 // read_stats.hip: one cfrk_read_stats row per read from the same index; the kernels are left enqueued.  nS >= 1.
 int cfrk_read_stats_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
                            int64_t nN, int64_t nS, uint32_t threshold, cfrk_read_stats *d_out);
+// read_filter.hip: one cfrk_read_span per read from the same index; the kernels are left enqueued.  nS >= 1.
+int cfrk_read_spans_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                           int64_t nN, int64_t nS, uint32_t min_count, uint32_t max_count, int mode, cfrk_read_span *d_out);
+// read_filter.hip: the select in two steps: the sizes (synchronises), then the index pass and the copy, left enqueued
+int cfrk_select_measure(cfrk_ctx *ctx, const int64_t *d_start, const int32_t *d_length, int64_t nN, int64_t nS,
+                        const cfrk_read_span *d_span, const uint8_t *d_keep, int32_t min_len, int64_t *nN_out, int64_t *nS_out);
+int cfrk_select_emit(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+                     int64_t nS, const cfrk_read_span *d_span, const uint8_t *d_keep, int32_t min_len, int8_t *d_data_out,
+                     int64_t *d_start_out, int32_t *d_length_out, int64_t *d_index_out, int64_t nN_out, int64_t nS_out);
 // sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
 // enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
 int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,

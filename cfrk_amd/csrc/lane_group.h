@@ -1,6 +1,6 @@
 // lane_group.h -- what the kernels that give every read to a group of lanes (or to a workgroup) share: the phase
 // boundary of a wave, the sums over a group, the bitonic network that sorts a group's LDS array in place, and the
-// window count of a read that may lie anywhere (sparse.hip, read_stats.hip).
+// window count of a read that may lie anywhere (sparse.hip, read_stats.hip, read_filter.hip).
 #pragma once
 
 #include "common.h"

@@ -1,6 +1,6 @@
 // query_dev.h -- the lookup index of a finished global result as the kernels see it: the index descriptor, the slot
 // hashes, the probe loops and the canonical form of a two-word key.  Shared by query.hip (which also builds the index),
-// read_stats.hip and (the window extraction and the key hashes) sketch.hip; the index layout is described at the top of query.hip.
+// read_stats.hip, read_filter.hip and (the window extraction and the key hashes) sketch.hip; the index layout is described at the top of query.hip.
 #pragma once
 
 #include "common.h"

@@ -52,7 +52,17 @@
 //                    median, max and sum of the windows' counts; a record without a valid window gives zeros.  One device
 //                    (not with --gpus above 1), not with --batch or --sparse
 //   --stats-below T  (with --query-stats) the threshold of the `below` field, 0 .. 4294967295 (default 0: below is 0)
-//   --query-only     (with --query) write OFILE / SFILE only: the counts are not exported and the output path is left
+//   --filter-out FFILE  (with --query; --query-out becomes optional) the reads of QFILE trimmed to their solid spans and
+//                    filtered by abundance against the whole result, as FASTA: ">" + the record's number in QFILE, then
+//                    its kept bases on one line.  On the device: cfrk_global_read_spans_device, cfrk_reads_select_device,
+//                    one copy back, cfrk_host_format_fasta.  One device (not with --gpus above 1), not with --batch or --sparse
+//   --filter-min-count T / --filter-max-count U  a window is solid when T <= count <= U (defaults 2 and no upper bound)
+//   --filter-trim longest|prefix|none  keep the longest solid run (the default; the earliest on a tie), the run that
+//                    begins at the read's first window (khmer's filter-abund), or the whole read (no spans)
+//   --filter-min-len L  drop a read whose kept part is shorter than L bases (default k)
+//   --filter-min-median A / --filter-max-median B  keep only the reads whose median window count (cfrk_global_read_stats;
+//                    0 for a read without a valid window) is at least A / at most B
+//   --query-only     (with --query) write OFILE / SFILE / FFILE only: the counts are not exported and the output path is left
 //                    untouched
 //   --query-db DB.bin  (with --query, no positional arguments) query a saved --binary count file without recounting; k and
 //                    the canonical bit come from its header
@@ -122,6 +132,12 @@ struct Options {
   bool query_only = false;
   const char *query_stats = nullptr;   // --query-stats SFILE
   uint32_t stats_below = 0;            // --stats-below T
+  const char *filter_out = nullptr;    // --filter-out FFILE
+  uint32_t filter_min_count = 2, filter_max_count = CFRK_COUNT_MAX;   // --filter-min-count T, --filter-max-count U
+  int filter_trim = CFRK_SPAN_LONGEST; // --filter-trim: CFRK_SPAN_LONGEST / CFRK_SPAN_PREFIX, -1 = none
+  long filter_min_len = -1;            // --filter-min-len L (-1: k)
+  bool filter_median = false;          // --filter-min-median A / --filter-max-median B
+  uint32_t filter_min_median = 0, filter_max_median = 0xFFFFFFFFu;
   bool estimate = false, estimate_only = false, auto_hint = false;   // --estimate, --estimate-only, --auto-hint
   bool device_parse = false;                                        // --device-parse
   bool text_copy_plain = true;                                      // --text-copy plain (the default) | staged
@@ -399,6 +415,75 @@ int write_query_stats(const Options &o, cfrk_ctx *ctx) {
   return 0;
 }
 
+// --filter-out: the query reads trimmed to their solid spans and filtered, on the device, written to FFILE as FASTA
+int write_filter(const Options &o, cfrk_ctx *ctx, int k) {
+  const cfrk_batch &q = g_qreads;
+  const size_t nN = (size_t)q.nN, nS = (size_t)q.nS;
+  std::vector<int8_t> data;
+  std::vector<int64_t> start, index;
+  std::vector<int32_t> length;
+  int64_t onN = 0, onS = 0;
+  if (nS) {
+    void *d_data = nullptr, *d_start = nullptr, *d_length = nullptr, *d_span = nullptr, *d_keep = nullptr, *d_stats = nullptr;
+    void *o_data = nullptr, *o_start = nullptr, *o_length = nullptr, *o_index = nullptr;
+    const char *what = "cfrk_device_alloc";
+    int rc;
+    const bool trim = o.filter_trim >= 0;
+    if (!(rc = cfrk_device_alloc(ctx, nN + 16, &d_data)) && !(rc = cfrk_device_alloc(ctx, nS * 8, &d_start)) &&
+        !(rc = cfrk_device_alloc(ctx, nS * 4, &d_length)) && !(rc = cfrk_device_alloc(ctx, nN + 16, &o_data)) &&
+        !(rc = cfrk_device_alloc(ctx, nS * 8, &o_start)) && !(rc = cfrk_device_alloc(ctx, nS * 4, &o_length)) &&
+        !(rc = cfrk_device_alloc(ctx, nS * 8, &o_index)) && !(trim && (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_span), &d_span))) &&
+        !(o.filter_median && ((rc = cfrk_device_alloc(ctx, nS, &d_keep)) || (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_stats), &d_stats))))) {
+      what = "cfrk_memcpy_h2d";
+      if (!(rc = cfrk_memcpy_h2d(ctx, d_data, q.data, nN)) && !(rc = cfrk_memcpy_h2d(ctx, d_start, q.start, nS * 8)))
+        rc = cfrk_memcpy_h2d(ctx, d_length, q.length, nS * 4);
+      if (!rc && trim) {
+        what = "cfrk_global_read_spans_device";
+        rc = cfrk_global_read_spans_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS,
+                                           o.filter_min_count, o.filter_max_count, o.filter_trim, (cfrk_read_span *)d_span);
+      }
+      if (!rc && o.filter_median) {
+        // the rows come down (32 bytes per read), the keep bytes go up (1 byte per read)
+        what = "cfrk_global_read_stats_device";
+        std::vector<cfrk_read_stats> st(nS);
+        std::vector<uint8_t> keep(nS);
+        if (!(rc = cfrk_global_read_stats_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS, 0,
+                                                 (cfrk_read_stats *)d_stats)) &&
+            !(rc = cfrk_memcpy_d2h(ctx, st.data(), d_stats, nS * sizeof(cfrk_read_stats)))) {
+          for (size_t i = 0; i < nS; ++i) keep[i] = st[i].median >= o.filter_min_median && st[i].median <= o.filter_max_median;
+          rc = cfrk_memcpy_h2d(ctx, d_keep, keep.data(), nS);
+        }
+      }
+      if (!rc) {
+        what = "cfrk_reads_select_device";
+        const long min_len = o.filter_min_len >= 0 ? o.filter_min_len : (long)k;
+        rc = cfrk_reads_select_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS,
+                                      (const cfrk_read_span *)d_span, (const uint8_t *)d_keep, (int32_t)min_len, (int8_t *)o_data, nN,
+                                      (int64_t *)o_start, (int32_t *)o_length, (int64_t *)o_index, nS, &onN, &onS);
+      }
+      if (!rc) {
+        what = "cfrk_memcpy_d2h";
+        data.resize((size_t)onN); start.resize((size_t)onS); length.resize((size_t)onS); index.resize((size_t)onS);
+        if (onS && !(rc = cfrk_memcpy_d2h(ctx, data.data(), o_data, (size_t)onN)) && !(rc = cfrk_memcpy_d2h(ctx, start.data(), o_start, (size_t)onS * 8)) &&
+            !(rc = cfrk_memcpy_d2h(ctx, length.data(), o_length, (size_t)onS * 4)))
+          rc = cfrk_memcpy_d2h(ctx, index.data(), o_index, (size_t)onS * 8);
+      }
+    }
+    const int rc2 = cfrk_ctx_sync(ctx);
+    for (void *d : {d_data, d_start, d_length, d_span, d_keep, d_stats, o_data, o_start, o_length, o_index}) if (d) cfrk_device_free(ctx, d);
+    if (rc) return die(ctx, rc, what);
+    if (rc2) return die(ctx, rc2, "cfrk_ctx_sync");
+  }
+  std::string buf;
+  buf.resize(cfrk_host_format_fasta(data.data(), start.data(), length.data(), index.data(), onS, nullptr, 0));
+  cfrk_host_format_fasta(data.data(), start.data(), length.data(), index.data(), onS, &buf[0], buf.size());
+  FILE *f = fopen(o.filter_out, "wb");
+  if (!f) { fprintf(stderr, "cfrk: cannot write %s\n", o.filter_out); return 1; }
+  const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+  if (fclose(f) != 0 || !ok) { fprintf(stderr, "cfrk: cannot write %s\n", o.filter_out); return 1; }
+  return 0;
+}
+
 // the global result (ascending keys) as sparse text or in the binary form
 void write_global(const Options &o, const uint64_t *lo, const uint64_t *hi, const uint32_t *cnt, uint64_t n, FILE *out) {
   const uint64_t *hi2 = (o.k > 32) ? hi : nullptr;
@@ -513,6 +598,7 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
       if ((rc = write_query_stats(o, ctx))) return rc;
       g_timing.stats = now_s() - s0;
     }
+    if (o.filter_out && (rc = write_filter(o, ctx, o.k))) return rc;
   }
   if (early_free && owned) *early_free = std::thread([owned] { cfrk_host_free_batch(owned); });
   cfrk_global_last_add_ms(ctx, &g_timing.count_kernels_ms);
@@ -920,6 +1006,7 @@ int run_query_db(const Options &o) {
   }
   const double s0 = now_s();
   if (o.query_stats && (rc = write_query_stats(o, ctx))) return rc;
+  if (o.filter_out && (rc = write_filter(o, ctx, k))) return rc;
   if (o.timing && o.query_stats)
     fprintf(stderr, "cfrk-timing {\"entries\": %llu, \"query_s\": %.4f, \"stats_s\": %.4f}\n", (unsigned long long)n, s0 - q0, now_s() - s0);
   else if (o.timing) fprintf(stderr, "cfrk-timing {\"entries\": %llu, \"query_s\": %.4f}\n", (unsigned long long)n, now_s() - q0);
@@ -932,7 +1019,7 @@ int main(int argc, char **argv) {
   std::vector<const char *> pos;
   Options o;
   int batch_n = -1;
-  bool range_set = false, stats_below_set = false;
+  bool range_set = false, stats_below_set = false, filter_opt_set = false;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--all-chunks")) o.all_chunks = true;
     else if (!strcmp(argv[i], "--native")) o.native = true;
@@ -985,6 +1072,36 @@ int main(int argc, char **argv) {
       if (!parse_count(v, &o.stats_below)) { fprintf(stderr, "cfrk: %s needs a count (an integer from 0 to 4294967295), not '%s'\n", opt, v); return 1; }
       stats_below_set = true;
     }
+    else if (!strncmp(argv[i], "--filter-", 9)) {
+      const char *opt = argv[i];
+      static const char *const known[] = {"--filter-out", "--filter-min-count", "--filter-max-count", "--filter-trim", "--filter-min-len",
+                                          "--filter-min-median", "--filter-max-median"};
+      bool is_known = false;
+      for (const char *n : known) is_known = is_known || !strcmp(opt, n);
+      if (!is_known) { fprintf(stderr, "cfrk: unknown option %s\n", opt); return 1; }
+      if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", opt); return 1; }
+      const char *v = argv[++i];
+      if (!strcmp(opt, "--filter-out")) { o.filter_out = v; continue; }
+      filter_opt_set = true;
+      if (!strcmp(opt, "--filter-trim")) {
+        if (!strcmp(v, "longest")) o.filter_trim = CFRK_SPAN_LONGEST;
+        else if (!strcmp(v, "prefix")) o.filter_trim = CFRK_SPAN_PREFIX;
+        else if (!strcmp(v, "none")) o.filter_trim = -1;
+        else { fprintf(stderr, "cfrk: --filter-trim takes longest, prefix or none, not '%s'\n", v); return 1; }
+      } else if (!strcmp(opt, "--filter-min-len")) {
+        char *end = nullptr;
+        const long long L = strtoll(v, &end, 10);
+        if (!*v || *end || L < 0 || L > 0x7FFFFFFFll) { fprintf(stderr, "cfrk: --filter-min-len needs a length (an integer from 0 to 2147483647), not '%s'\n", v); return 1; }
+        o.filter_min_len = (long)L;
+      } else {
+        uint32_t x;
+        if (!parse_count(v, &x)) { fprintf(stderr, "cfrk: %s needs a count (an integer from 0 to 4294967295), not '%s'\n", opt, v); return 1; }
+        if (!strcmp(opt, "--filter-min-count")) o.filter_min_count = x;
+        else if (!strcmp(opt, "--filter-max-count")) o.filter_max_count = x;
+        else if (!strcmp(opt, "--filter-min-median")) { o.filter_min_median = x; o.filter_median = true; }
+        else { o.filter_max_median = x; o.filter_median = true; }
+      }
+    }
     else if (!strcmp(argv[i], "--histo") || !strcmp(argv[i], "--min-count") || !strcmp(argv[i], "--max-count")) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
       const char *opt = argv[i], *v = argv[++i];
@@ -999,7 +1116,7 @@ int main(int argc, char **argv) {
   }
   // (refused here: before the input is parsed or a device is opened)
   if (o.sparse && (o.global || o.binary || o.histo || o.histo_only || range_set || o.query || o.query_out || o.query_only ||
-                   o.query_db || o.query_stats || stats_below_set)) {
+                   o.query_db || o.query_stats || stats_below_set || o.filter_out || filter_opt_set)) {
     fprintf(stderr, "cfrk: --sparse is a per-read mode: not with --global, --binary, --histo, --query or --min-count / --max-count\n");
     return 1;
   }
@@ -1029,7 +1146,10 @@ int main(int argc, char **argv) {
   }
   if ((o.query_stats || stats_below_set) && !o.query) { fprintf(stderr, "cfrk: --query-stats and --stats-below need --query QFILE\n"); return 1; }
   if (stats_below_set && !o.query_stats) { fprintf(stderr, "cfrk: --stats-below needs --query-stats SFILE\n"); return 1; }
-  if (o.query && !o.query_out && !o.query_stats) { fprintf(stderr, "cfrk: --query needs --query-out OFILE or --query-stats SFILE\n"); return 1; }
+  if ((o.filter_out || filter_opt_set) && !o.query) { fprintf(stderr, "cfrk: --filter-out and the --filter- options need --query QFILE\n"); return 1; }
+  if (filter_opt_set && !o.filter_out) { fprintf(stderr, "cfrk: the --filter- options need --filter-out FFILE\n"); return 1; }
+  if (o.query && !o.query_out && !o.query_stats && !o.filter_out) { fprintf(stderr, "cfrk: --query needs --query-out OFILE, --query-stats SFILE or --filter-out FFILE\n"); return 1; }
+  if (o.filter_out && o.gpus > 1) { fprintf(stderr, "cfrk: --filter-out runs on one device: not with --gpus above 1\n"); return 1; }
   if (o.query_stats && o.gpus > 1) { fprintf(stderr, "cfrk: --query-stats runs on one device: not with --gpus above 1\n"); return 1; }
   if (o.query && batch_n >= 0) { fprintf(stderr, "cfrk: --query writes one file: not with --batch\n"); return 1; }
   if (o.query_db && !pos.empty()) { fprintf(stderr, "cfrk: --query-db takes no positional arguments\n"); return 1; }

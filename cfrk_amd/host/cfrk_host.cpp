@@ -710,6 +710,25 @@ size_t cfrk_host_format_read_stats(const void *stats, int64_t nS, char *buf, siz
   return buf ? (size_t)(p - buf) : s;
 }
 
+size_t cfrk_host_format_fasta(const int8_t *data, const int64_t *start, const int32_t *length, const int64_t *index,
+                              int64_t nS, char *buf, size_t cap) {
+  size_t s = 0;
+  char *p = buf;
+  (void)cap;
+  for (int64_t j = 0; j < nS; ++j) {
+    const uint64_t id = (uint64_t)(index ? index[j] : j);
+    const int64_t L = length[j] > 0 ? (int64_t)length[j] : 0;
+    if (!buf) { s += 1 + len_u64(id) + 1 + (size_t)L + 1; continue; }
+    *p++ = '>';
+    p = put_u64(p, id);
+    *p++ = '\n';
+    const int8_t *r = data + start[j];
+    for (int64_t x = 0; x < L; ++x) { const int c = r[x]; *p++ = (c >= 0 && c <= 3) ? "ACGT"[c] : 'N'; }
+    *p++ = '\n';
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
 static void put_le(char *p, uint64_t x, int bytes) { for (int i = 0; i < bytes; ++i) p[i] = (char)(x >> (8 * i)); }
 static uint64_t get_le(const char *p, int bytes) {
   uint64_t x = 0;

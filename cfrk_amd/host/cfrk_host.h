@@ -121,6 +121,13 @@ size_t cfrk_host_format_query(const uint32_t *counts, const int64_t *start, cons
  * size). */
 size_t cfrk_host_format_read_stats(const void *stats, int64_t nS, char *buf, size_t cap);
 
+/* Selected reads as FASTA text (`cfrk --filter-out`): one record per read j, ">" + index[j] in decimal (the input
+ * record number: the parsers keep no names; index NULL numbers the reads 0, 1, ..) + "\n" + the bases
+ * data[start[j]] .. data[start[j] + length[j] - 1] as ACGT, N for any other code, on one line + "\n" (an empty read
+ * gives an empty line).  Returns bytes needed / written (buf may be NULL to size). */
+size_t cfrk_host_format_fasta(const int8_t *data, const int64_t *start, const int32_t *length, const int64_t *index,
+                              int64_t nS, char *buf, size_t cap);
+
 /* Binary global form, little endian, everything in one file:
  *   header, 32 bytes:  char magic[8] = "CFRKGLB1"; uint32 k; uint32 flags (bit 0: canonical counting,
  *                      bit 1: two-word keys, i.e. k > 32); uint64 n (records); uint64 sum of counts

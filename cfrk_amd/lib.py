@@ -34,6 +34,14 @@ CFRK_STATS_FAST_WINDOWS = 2048       # read stats: windows per read a lane group
 # cfrk_read_stats: one row per read of GlobalCounter.read_stats()
 READ_STATS_DTYPE = np.dtype([("windows", "<u4"), ("present", "<u4"), ("below", "<u4"), ("min", "<u4"),
                              ("median", "<u4"), ("max", "<u4"), ("sum", "<u8")])
+CFRK_SPAN_PREFIX = 0                 # read spans: the solid run that begins at window 0 (the filter-abund rule)
+CFRK_SPAN_LONGEST = 1                # the longest solid run, the earliest one on a tie
+CFRK_SPANS_FAST_WINDOWS = 2048       # read spans: windows per read a lane group takes (longer reads: a workgroup each)
+# cfrk_read_span: bases [offset, offset + length) of a read
+READ_SPAN_DTYPE = np.dtype([("offset", "<i4"), ("length", "<i4")])
+CFRK_SELECT_TILE_BYTES = 16384       # select: bytes of data_out per workgroup of the copy
+CFRK_SELECT_TILE_READS = 256         # reads per workgroup of its per-read passes
+CFRK_SELECT_SCAN_TILES = 1024        # tiles of reads per block of its tile scan
 CFRK_SKETCH_LOG2M = 14               # distinct sketch: log2 of its registers
 CFRK_SKETCH_REGS = 16384             # one uint8 register per bucket
 CFRK_FASTA_TILE_BYTES = 16384        # device FASTA parser: text bytes per workgroup
@@ -112,6 +120,10 @@ def load_library():
         "cfrk_global_query_reads_device": ([vp, vp, i64, vp], C.c_int),
         "cfrk_global_read_stats": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
         "cfrk_global_read_stats_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
+        "cfrk_global_read_spans": ([vp, vp, vp, vp, i64, i64, C.c_uint32, C.c_uint32, i32, vp], C.c_int),
+        "cfrk_global_read_spans_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, C.c_uint32, i32, vp], C.c_int),
+        "cfrk_reads_select": ([vp, vp, vp, vp, i64, i64, vp, vp, C.c_int32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "cfrk_reads_select_device": ([vp, vp, vp, vp, i64, i64, vp, vp, C.c_int32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_global_export_device": ([vp, vp, vp, vp, u64, C.c_int, C.POINTER(u64)], C.c_int),
         "cfrk_global_digest": ([vp, C.POINTER(u64)], C.c_int),
         "cfrk_global_last_add_ms": ([vp, C.POINTER(C.c_float)], C.c_int),
@@ -415,6 +427,57 @@ class Context:
                                                 _ptr(length), start.size, C.byref(nN), C.byref(nS)), "cfrk_fastq_parse")
         return data, start, length
 
+    # -- select: the kept, trimmed reads compacted into new struct-read buffers ------------------
+    def select_reads(self, data, start, length, spans=None, keep=None, min_len=0):
+        """-> (data int8[nN'], start int64[nS'], length int32[nS'], index int64[nS']): the reads with keep[i] != 0
+        (None: all) whose span (READ_SPAN_DTYPE, None: the whole read) holds at least min_len bases, trimmed to their
+        spans, in input order in the native layout; index[j] = the input index of output read j.  A span that does not
+        lie inside its read raises CfrkError (CFRK_ERR_LAYOUT).  Needs no job."""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        nS = len(length)
+        if len(start) != nS:
+            raise ValueError("start and length differ in size")
+        if spans is not None:
+            spans = np.ascontiguousarray(spans, READ_SPAN_DTYPE)
+            if len(spans) != nS:
+                raise ValueError("one span per read")
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
+            if len(keep) != nS:
+                raise ValueError("one keep byte per read")
+        nN_o, nS_o = C.c_int64(), C.c_int64()
+        head = (self._h, _ptr(data), _ptr(start), _ptr(length), len(data), nS, _ptr(spans), _ptr(keep), int(min_len))
+        rc = self._L.cfrk_reads_select(*head, None, 0, None, None, None, 0, C.byref(nN_o), C.byref(nS_o))
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.check(rc, "cfrk_reads_select")
+        o_data, o_start = np.empty(nN_o.value, np.int8), np.empty(nS_o.value, np.int64)
+        o_length, o_index = np.empty(nS_o.value, np.int32), np.empty(nS_o.value, np.int64)
+        if rc == CFRK_ERR_SMALL_BUF:
+            self.check(self._L.cfrk_reads_select(*head, _ptr(o_data), o_data.size, _ptr(o_start), _ptr(o_length),
+                                                 _ptr(o_index), o_start.size, C.byref(nN_o), C.byref(nS_o)),
+                       "cfrk_reads_select")
+        return o_data, o_start, o_length, o_index
+
+    def select_reads_device(self, d_data, d_start, d_length, nN, nS, d_span, d_keep, min_len, d_data_out, cap_data,
+                            d_start_out, d_length_out, d_index_out, cap_reads):
+        """device form -> (nN', nS'); d_span 0: whole reads, d_keep 0: all, d_index_out may be 0; the output arrays may
+        be 0 with zero capacities (sizes only) and must not overlap the input.  Raises CfrkError (code
+        CFRK_ERR_SMALL_BUF, with .nN and .nS set, nothing written) when the arrays are too small.  Synchronises once,
+        returns with the copy enqueued on the context stream."""
+        nN_o, nS_o = C.c_int64(), C.c_int64()
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_reads_select_device(self._h, vp(d_data), vp(d_start), vp(d_length), nN, nS, vp(d_span),
+                                              vp(d_keep), int(min_len), vp(d_data_out), cap_data, vp(d_start_out),
+                                              vp(d_length_out), vp(d_index_out), cap_reads, C.byref(nN_o), C.byref(nS_o))
+        try:
+            self.check(rc, "cfrk_reads_select_device")
+        except CfrkError as e:
+            e.nN, e.nS = nN_o.value, nS_o.value
+            raise
+        return nN_o.value, nS_o.value
+
     def synth_reads_device(self, r0, R, L, Glen, d_data, d_start=None, d_length=None,
                            seedG=1, seedR=2, seedS=3, uniform=False):
         self.check(self._L.cfrk_synth_reads_device(self._h, r0, R, L, Glen, seedG, seedR, seedS,
@@ -665,6 +728,32 @@ class GlobalCounter:
         self.ctx.check(self._L.cfrk_global_read_stats_device(self.ctx._h, vp(d_data), vp(d_start), vp(d_length), nN, nS,
                                                              int(threshold), vp(d_out)),
                        "cfrk_global_read_stats_device")
+
+    def read_spans(self, data, start, length, min_count=1, max_count=CFRK_COUNT_MAX, mode=CFRK_SPAN_LONGEST):
+        """the solid span of every read against the job's result -> np.ndarray[nS] of READ_SPAN_DTYPE: the bases that
+        a run of windows with min_count <= count <= max_count covers -- the longest run (CFRK_SPAN_LONGEST, the
+        earliest on a tie) or the run that begins at window 0 (CFRK_SPAN_PREFIX); {0, 0} when there is none"""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        nS = len(length)
+        if len(start) != nS:
+            raise ValueError("start and length differ in size")
+        if not (0 <= int(min_count) <= 0xFFFFFFFF and 0 <= int(max_count) <= 0xFFFFFFFF):
+            raise ValueError("count bound outside 0 .. 2^32 - 1")
+        out = np.zeros(nS, READ_SPAN_DTYPE)
+        self.ctx.check(self._L.cfrk_global_read_spans(self.ctx._h, _ptr(data), _ptr(start), _ptr(length), len(data), nS,
+                                                      int(min_count), int(max_count), int(mode), _ptr(out)),
+                       "cfrk_global_read_spans")
+        return out
+
+    def read_spans_device(self, d_data, d_start, d_length, nN, nS, min_count, max_count, mode, d_out):
+        """device form of read_spans(): d_out nS spans of 8 bytes; no alignment requirement on d_data; returns with
+        the last kernel enqueued on the context stream"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self.ctx.check(self._L.cfrk_global_read_spans_device(self.ctx._h, vp(d_data), vp(d_start), vp(d_length), nN, nS,
+                                                             int(min_count), int(max_count), int(mode), vp(d_out)),
+                       "cfrk_global_read_spans_device")
 
     def export_device(self, d_lo, d_hi, d_cnt, cap, parts=1):
         pc = (C.c_uint64 * parts)()

@@ -278,6 +278,39 @@ int cfrk_global_read_stats_device(cfrk_ctx *ctx, const int8_t *d_data, const int
 int cfrk_global_read_stats(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
                            int64_t nN, int64_t nS, uint32_t threshold, cfrk_read_stats *out);
 
+/* Solid spans: which part of each read the job's counts support (the trim rule of filter-abund / trim-low-abund).
+ * The windows of read i are those of cfrk_global_read_stats: the starts p in [0, length[i] - k] relative to the read.
+ * A window is SOLID iff its k codes are all 0..3 and its count c satisfies min_count <= c <= max_count; the count comes
+ * from the same lookup index as the read query, canonicalised in a CFRK_CANONICAL job; an absent k-mer counts 0, a
+ * saturated key reads CFRK_COUNT_MAX.  There are no special cases: min_count = 0 makes every valid window solid,
+ * min_count > max_count makes none solid and is not an error.
+ * A run of solid windows a..b gives the span {a, (b - a + 1) + k - 1}: bases [offset, offset + length) of the read.
+ *   CFRK_SPAN_PREFIX   the run that begins at window 0 (empty when window 0 is not solid)
+ *   CFRK_SPAN_LONGEST  the longest run, the earliest one on a tie
+ * A read without a solid window -- every read shorter than k -- gets {0, 0}.  A span never holds an invalid code and
+ * holds at least k bases when it is not empty.  1 <= k <= 64, reads of any length: reads of up to
+ * CFRK_SPANS_FAST_WINDOWS windows are looked up and reduced by a group of lanes in LDS, longer ones by a workgroup.
+ * Errors and job state are those of cfrk_global_read_stats: CFRK_ERR_STATE before begin and on a CFRK_RUNS_ONLY job,
+ * CFRK_ERR_TABLE_FULL and CFRK_ERR_NOMEM as the query calls, CFRK_ERR_ARG for NULL buffers with nS > 0, negative sizes
+ * and a mode other than the two (nS = 0 is fine).  The job stays usable for digest, histogram, export and queries.
+ * Device form: no alignment requirement; start / length are not checked: a read whose range does not lie inside
+ * [0, nN) gets {0, 0} (never an access outside the buffers).  Returns with the last kernel enqueued on the context
+ * stream (the index build of a job's first query synchronises).
+ * Host form: checks start and length like cfrk_global_add (CFRK_ERR_LAYOUT), stages through the pool, synchronous. */
+typedef struct cfrk_read_span {   /* 8 bytes: bases [offset, offset + length) of the read */
+  int32_t offset;
+  int32_t length;
+} cfrk_read_span;
+#define CFRK_SPAN_PREFIX 0
+#define CFRK_SPAN_LONGEST 1
+#define CFRK_SPANS_FAST_WINDOWS 2048
+int cfrk_global_read_spans_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                  int64_t nN, int64_t nS, uint32_t min_count, uint32_t max_count, int mode,
+                                  cfrk_read_span *d_out);
+int cfrk_global_read_spans(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
+                           int64_t nN, int64_t nS, uint32_t min_count, uint32_t max_count, int mode,
+                           cfrk_read_span *out);
+
 /* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
 
 /* How many DISTINCT k-mers will a job hold?  One streaming pass over the reads answers it to about 1 % before anything
@@ -420,6 +453,44 @@ int cfrk_fastq_parse_device(cfrk_ctx *ctx, const uint8_t *d_text, uint64_t nbyte
 int cfrk_fastq_parse(cfrk_ctx *ctx, const char *text, uint64_t nbytes, int min_qual,
                      int8_t *data, uint64_t cap_data, int64_t *start, int32_t *length, uint64_t cap_reads,
                      int64_t *nN_out, int64_t *nS_out);
+
+/* ---- select: compact the kept (and trimmed) reads into new struct-read buffers -------------------------------- */
+
+/* Read i is KEPT iff keep is NULL or keep[i] != 0, its span lies inside the read (0 <= offset, 0 <= length,
+ * offset + length <= length[i]) and span.length >= min_len; span NULL stands for whole reads ({0, length[i]}).
+ * min_len = 0 keeps empty reads as well, which the native layout allows; a negative min_len is CFRK_ERR_ARG.
+ * Output: the kept reads in input order in the native layout of the parsers above: the span's bytes copied verbatim
+ * and one -1 terminator each; start_out[j] = bytes kept before read j, plus j; length_out[j] = the span's length;
+ * *nN_out = kept bytes + *nS_out; index_out[j] (may be NULL) = the input index of output read j.
+ * Capacities: cap_data = nN and cap_reads = nS always suffice.  When *nN_out > cap_data or *nS_out > cap_reads the call
+ * returns CFRK_ERR_SMALL_BUF with both sizes complete and nothing written to the arrays; NULL arrays with zero
+ * capacities are that "sizes only" call.  The output arrays MUST NOT OVERLAP the input arrays.
+ * CFRK_ERR_ARG: negative sizes or min_len, NULL size outputs, NULL start / length with nS > 0, NULL data with nN > 0,
+ * a NULL output array with a capacity above 0.  nS = 0 is fine.  No alignment requirement on any byte array.
+ * Device form: a per-read pass reduced per tile of CFRK_SELECT_TILE_READS reads, a one-workgroup scan of the tile
+ * aggregates in blocks of CFRK_SELECT_SCAN_TILES, a pass that writes start_out / length_out / index_out, and the copy,
+ * as separate launches on the context stream (no workgroup waits for another one).  The copy is balanced by OUTPUT
+ * bytes: one workgroup takes one tile of CFRK_SELECT_TILE_BYTES of data_out and finds the reads that intersect it by a
+ * search in start_out.  It synchronises ONCE, for the sizes, and returns with the copy enqueued.  start / length /
+ * span are not checked: a read whose range does not lie inside [0, nN), or whose span does not lie inside
+ * [0, length[i]] (a negative field included), is dropped silently; nothing outside the buffers is ever accessed.
+ * Temporary device memory, kept in the context's pool: 64 bytes, 32 bytes per tile of reads, 8 bytes per kept read.
+ * Host form: checks start and length like cfrk_global_add; a span outside its read is CFRK_ERR_LAYOUT as well
+ * (cfrk_last_error names the read); stages through the pool; synchronous.
+ * Neither call needs a global job or touches one that is open on the same context. */
+#define CFRK_SELECT_TILE_BYTES 16384
+#define CFRK_SELECT_TILE_READS 256
+#define CFRK_SELECT_SCAN_TILES 1024
+int cfrk_reads_select_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                             int64_t nN, int64_t nS, const cfrk_read_span *d_span, const uint8_t *d_keep,
+                             int32_t min_len, int8_t *d_data_out, uint64_t cap_data, int64_t *d_start_out,
+                             int32_t *d_length_out, int64_t *d_index_out, uint64_t cap_reads,
+                             int64_t *nN_out, int64_t *nS_out);
+int cfrk_reads_select(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
+                      int64_t nN, int64_t nS, const cfrk_read_span *span, const uint8_t *keep,
+                      int32_t min_len, int8_t *data_out, uint64_t cap_data, int64_t *start_out,
+                      int32_t *length_out, int64_t *index_out, uint64_t cap_reads,
+                      int64_t *nN_out, int64_t *nS_out);
 
 /* Unsorted export into device buffers, grouped into `parts` contiguous segments by
  * owner(key) = (mix(key) >> 32) % parts (key-owner partition for the multi-GPU
