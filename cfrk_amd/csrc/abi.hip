@@ -11,9 +11,9 @@
 #include <vector>
 #include <new>
 #include <numeric>
-#include <vector>
 
 #include "msp.h"
+#include "staging.h"
 #include "table.h"
 
 int cfrk_fail(cfrk_ctx *ctx, int code, const char *fmt, ...) {
@@ -295,9 +295,7 @@ int cfrk_per_read_dense(cfrk_ctx *ctx, const int8_t *data, const int64_t *start,
   rc = cfrk_launch_dense(ctx, (const int8_t *)d_data, (const int64_t *)d_start,
                          (const int32_t *)d_length, nN, nS, k, flags, (int32_t *)d_freq);
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(freq_out, d_freq, freq_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return CFRK_OK;
+  return cfrk_memcpy_d2h(ctx, freq_out, d_freq, freq_bytes);
 }
 
 /* ------------------------------------------------------------------ global counting */
@@ -417,70 +415,6 @@ int cfrk_global_add_device(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN) {
   return CFRK_OK;
 }
 
-// background check of the struct-read layout (joined by failed() or by the destructor: the function
-// below leaves early on HIP errors)
-struct LayoutCheck {
-  std::vector<std::thread> th;
-  std::vector<int64_t> bad;
-  std::vector<int> why;
-  const int8_t *data = nullptr; const int64_t *start = nullptr; const int32_t *length = nullptr;
-  int64_t nN = 0, nS = 0;
-  void begin(const int8_t *d, const int64_t *s, const int32_t *l, int64_t nn, int64_t ns) {
-    data = d; start = s; length = l; nN = nn; nS = ns;
-    const int64_t piece = 1 << 20;
-    unsigned nt = (unsigned)std::min<int64_t>((nS + piece - 1) / piece, 8);
-    const unsigned hw = std::thread::hardware_concurrency();
-    if (hw && nt > hw) nt = hw;
-    if (nt == 0) nt = 1;
-    bad.assign(nt, -1);
-    why.assign(nt, 0);
-    auto piece_fn = [this](unsigned t, unsigned nt) {
-      const int64_t i0 = nS * t / nt, i1 = nS * (t + 1) / nt;
-      for (int64_t i = i0; i < i1; ++i) {
-        // A thread's first read is compared with a predecessor another thread validates: every
-        // term is range-checked before it is used, so a corrupt table (negative starts, sums that
-        // overflow) never turns into an out-of-bounds read of data[].
-        int w = 0;
-        if (start[i] < 0 || start[i] > nN || length[i] < 0) w = 1;
-        else if (i && (start[i - 1] < 0 || start[i - 1] > nN || length[i - 1] < 0 ||
-                       start[i] != start[i - 1] + (int64_t)length[i - 1] + 1)) w = 1;
-        else if (!i && start[i] != 0) w = 1;
-        else if ((int64_t)length[i] + 1 > nN - start[i]) w = 2;
-        else { const int8_t term = data[start[i] + length[i]]; if (term >= 0 && term <= 3) w = 3; }
-        if (w) { bad[t] = i; why[t] = w; return; }
-      }
-    };
-    // std::thread may throw (resource exhaustion): nothing may cross the extern "C" boundary, so
-    // the pieces no thread could be started for are checked right here
-    unsigned started = 0;
-    try {
-      for (; started < nt; ++started) th.emplace_back(piece_fn, started, nt);
-    } catch (...) {
-      for (unsigned t = started; t < nt; ++t) piece_fn(t, nt);
-    }
-  }
-  void join() { for (auto &x : th) if (x.joinable()) x.join(); }
-  // true (and the context's error text set) when the layout is not the reference's
-  bool failed(cfrk_ctx *ctx) {
-    if (!start) return false;
-    join();
-    for (size_t t = 0; t < bad.size(); ++t) {
-      if (bad[t] < 0) continue;
-      const int64_t i = bad[t];
-      // (the predecessor's fields may themselves be garbage: wrap-around arithmetic, text only)
-      const int64_t want = i ? (int64_t)((uint64_t)start[i - 1] + (uint64_t)(int64_t)length[i - 1] + 1u) : 0;
-      if (why[t] == 1) cfrk_fail(ctx, CFRK_ERR_LAYOUT, "read %lld: start %lld, expected %lld", (long long)i, (long long)start[i], (long long)want);
-      else if (why[t] == 2) cfrk_fail(ctx, CFRK_ERR_LAYOUT, "read %lld runs past nN", (long long)i);
-      else cfrk_fail(ctx, CFRK_ERR_LAYOUT, "read %lld has no terminator", (long long)i);
-      return true;
-    }
-    const int64_t pos = nS ? start[nS - 1] + (int64_t)length[nS - 1] + 1 : 0;
-    if (pos != nN) { cfrk_fail(ctx, CFRK_ERR_LAYOUT, "sum(length)+nS = %lld but nN = %lld", (long long)pos, (long long)nN); return true; }
-    return false;
-  }
-  ~LayoutCheck() { join(); }
-};
-
 int cfrk_global_add(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
                     int64_t nN, int64_t nS) {
   if (!ctx) return CFRK_ERR_ARG;
@@ -488,24 +422,15 @@ int cfrk_global_add(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, con
   if (nN < 0 || nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
   if (nN == 0) return CFRK_OK;
   if (!data) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
-  // struct-read layout (src/fastaIO.h:74-102, src/main.cu:195-200): read i occupies
-  // [start[i], start[i]+length[i]) and is followed by one terminator byte.  Every read is checked
-  // against its predecessor, so ranges of reads are independent: up to eight threads check them
-  // WHILE the batch is staged and copied below (10^7 reads: 16 ms of cache misses that used to come
-  // first); nothing is counted before they have all passed.
-  LayoutCheck lc;
-  if (start && length) lc.begin(data, start, length, nN, nS);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  void *d_data;
-  int rc;
-  // the previous add may still be reading BUF_DATA
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if ((rc = cfrk_pool_get(ctx, BUF_DATA, (size_t)nN + 64, &d_data))) return rc;
+  // The layout check (staging.h) runs WHILE the previous add drains and the batch is copied; nothing is counted before
+  // it has passed.  STAGE_DRAIN_FIRST: the previous add may still be reading BUF_DATA.
   // The runtime's own path for pageable memory moves 46 GB/s here (it pins the caller's pages chunk
   // by chunk); a bounce buffer of our own, filled by one thread, made 26-32 GB/s, filled by eight 45.
-  HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
-  if (lc.failed(ctx)) return CFRK_ERR_LAYOUT;
-  return cfrk_global_add_device(ctx, (const int8_t *)d_data, nN);
+  StagedReads d;
+  const int rc = stage_reads(ctx, BUF_DATA, data, start, length, nN, nS, STAGE_DRAIN_FIRST, nullptr, 0, &d);
+  if (rc) return rc;
+  return stage_drain(ctx, cfrk_global_add_device(ctx, d.data, nN));
 }
 
 int cfrk_global_merge_device(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t *d_hi,
@@ -655,9 +580,7 @@ int cfrk_global_query(cfrk_ctx *ctx, const uint64_t *keys_lo, const uint64_t *ke
   HIP_TRY(ctx, hipMemcpyAsync(d_lo, keys_lo, bytes, hipMemcpyHostToDevice, ctx->stream));
   if (keys_hi) HIP_TRY(ctx, hipMemcpyAsync(d_hi, keys_hi, bytes, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = cfrk_query_keys(ctx, d_lo, d_hi, n, (uint32_t *)d_out))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(counts, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return CFRK_OK;
+  return cfrk_memcpy_d2h(ctx, counts, d_out, (size_t)n * 4);
 }
 
 int cfrk_global_query_reads_device(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, uint32_t *d_counts) {
@@ -678,19 +601,14 @@ int cfrk_global_query_reads(cfrk_ctx *ctx, const int8_t *data, const int64_t *st
   if (nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
   if (nN == 0) return CFRK_OK;
   if (!data || !counts) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
-  LayoutCheck lc;      // (the add's check of the struct-read layout, beside the copy)
-  if (start && length) lc.begin(data, start, length, nN, nS);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  void *d_data, *d_out;
   // (staged through slots of their own: BUF_DATA may still be read by the job's last add)
-  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_IN, (size_t)nN + 64, &d_data))) return rc;
+  void *d_out;
+  StagedReads d;
   if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, (size_t)nN * 4, &d_out))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
-  if (lc.failed(ctx)) return CFRK_ERR_LAYOUT;
-  if ((rc = cfrk_query_reads(ctx, (const int8_t *)d_data, nN, (uint32_t *)d_out))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(counts, d_out, (size_t)nN * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return CFRK_OK;
+  if ((rc = stage_reads(ctx, BUF_QUERY_IN, data, start, length, nN, nS, 0, nullptr, 0, &d))) return rc;
+  if ((rc = cfrk_query_reads(ctx, d.data, nN, (uint32_t *)d_out))) return stage_drain(ctx, rc);
+  return cfrk_memcpy_d2h(ctx, counts, d_out, (size_t)nN * 4);
 }
 
 static_assert(sizeof(cfrk_read_stats) == 32, "cfrk_read_stats is 32 bytes without padding");
@@ -718,29 +636,14 @@ int cfrk_global_read_stats(cfrk_ctx *ctx, const int8_t *data, const int64_t *sta
   if (!ctx) return CFRK_ERR_ARG;
   int rc = read_stats_check(ctx, nN, nS, data, start, length, out);
   if (rc || nS == 0) return rc;
-  LayoutCheck lc;      // (the add's check of the struct-read layout, beside the copies)
-  lc.begin(data, start, length, nN, nS);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // staged through the query calls' slots: [data | start | length] in, the rows out; each part 256-byte aligned
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_start = up((size_t)nN + 64), o_length = o_start + up((size_t)nS * 8);
-  void *p_in, *p_out;
-  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_IN, o_length + (size_t)nS * 4, &p_in))) return rc;
-  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, (size_t)nS * sizeof(cfrk_read_stats), &p_out))) return rc;
-  int8_t *d_data = (int8_t *)p_in;
-  int64_t *d_start = (int64_t *)((char *)p_in + o_start);
-  int32_t *d_length = (int32_t *)((char *)p_in + o_length);
-  if (nN) HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_start, start, (size_t)nS * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_length, length, (size_t)nS * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (lc.failed(ctx)) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
-    return CFRK_ERR_LAYOUT;
-  }
-  if ((rc = cfrk_read_stats_launch(ctx, d_data, d_start, d_length, nN, nS, threshold, (cfrk_read_stats *)p_out))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out, p_out, (size_t)nS * sizeof(cfrk_read_stats), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return CFRK_OK;
+  // staged through the query calls' slots: the reads in, the rows out
+  void *p_out;
+  StagedReads d;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, (size_t)nS * sizeof *out, &p_out))) return rc;
+  if ((rc = stage_reads(ctx, BUF_QUERY_IN, data, start, length, nN, nS, STAGE_TABLE, nullptr, 0, &d))) return rc;
+  if ((rc = cfrk_read_stats_launch(ctx, d.data, d.start, d.length, nN, nS, threshold, (cfrk_read_stats *)p_out))) return stage_drain(ctx, rc);
+  return cfrk_memcpy_d2h(ctx, out, p_out, (size_t)nS * sizeof *out);
 }
 
 static_assert(sizeof(cfrk_read_span) == 8, "cfrk_read_span is 8 bytes without padding");
@@ -769,48 +672,38 @@ int cfrk_global_read_spans(cfrk_ctx *ctx, const int8_t *data, const int64_t *sta
   if (!ctx) return CFRK_ERR_ARG;
   int rc = read_spans_check(ctx, nN, nS, data, start, length, out, mode);
   if (rc || nS == 0) return rc;
-  LayoutCheck lc;      // (the add's check of the struct-read layout, beside the copies)
-  lc.begin(data, start, length, nN, nS);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // staged through the query calls' slots: [data | start | length] in, the spans out; each part 256-byte aligned
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_start = up((size_t)nN + 64), o_length = o_start + up((size_t)nS * 8);
-  void *p_in, *p_out;
-  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_IN, o_length + (size_t)nS * 4, &p_in))) return rc;
-  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, (size_t)nS * sizeof(cfrk_read_span), &p_out))) return rc;
-  int8_t *d_data = (int8_t *)p_in;
-  int64_t *d_start = (int64_t *)((char *)p_in + o_start);
-  int32_t *d_length = (int32_t *)((char *)p_in + o_length);
-  if (nN) HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_start, start, (size_t)nS * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_length, length, (size_t)nS * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (lc.failed(ctx)) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
-    return CFRK_ERR_LAYOUT;
-  }
-  if ((rc = cfrk_read_spans_launch(ctx, d_data, d_start, d_length, nN, nS, min_count, max_count, mode, (cfrk_read_span *)p_out))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out, p_out, (size_t)nS * sizeof(cfrk_read_span), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return CFRK_OK;
+  // staged through the query calls' slots: the reads in, the spans out
+  void *p_out;
+  StagedReads d;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, (size_t)nS * sizeof *out, &p_out))) return rc;
+  if ((rc = stage_reads(ctx, BUF_QUERY_IN, data, start, length, nN, nS, STAGE_TABLE, nullptr, 0, &d))) return rc;
+  if ((rc = cfrk_read_spans_launch(ctx, d.data, d.start, d.length, nN, nS, min_count, max_count, mode, (cfrk_read_span *)p_out))) return stage_drain(ctx, rc);
+  return cfrk_memcpy_d2h(ctx, out, p_out, (size_t)nS * sizeof *out);
 }
 
 static int select_check(cfrk_ctx *ctx, const void *data, const void *start, const void *length, int64_t nN, int64_t nS,
                         int32_t min_len, const void *data_out, uint64_t cap_data, const void *start_out,
-                        const void *length_out, uint64_t cap_reads, const int64_t *nN_out, const int64_t *nS_out) {
+                        const void *length_out, uint64_t cap_reads, int64_t *nN_out, int64_t *nS_out) {
   if (nN < 0 || nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
   if (min_len < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "min_len %d is negative", (int)min_len);
   if (!nN_out || !nS_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL size output");
   if ((nS > 0 && (!start || !length)) || (nN > 0 && !data)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
   if ((cap_data > 0 && !data_out) || (cap_reads > 0 && (!start_out || !length_out)))
     return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL array with a capacity above 0");
+  *nN_out = *nS_out = 0;
   return CFRK_OK;
 }
 
-static int select_small(cfrk_ctx *ctx, int64_t nN, int64_t nS, uint64_t cap_data, uint64_t cap_reads) {
-  if ((uint64_t)nN > cap_data || (uint64_t)nS > cap_reads)
-    return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "select: %lld bytes of data and %lld reads, room for %llu and %llu", (long long)nN,
-                     (long long)nS, (unsigned long long)cap_data, (unsigned long long)cap_reads);
-  return CFRK_OK;
+// measure, refuse or place the outputs, emit: what both forms run on device buffers
+static int select_core(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN, int64_t nS,
+                       const cfrk_read_span *d_span, const uint8_t *d_keep, int32_t min_len, ReadsOut *o, int64_t *nN_out,
+                       int64_t *nS_out) {
+  int64_t on = 0, os = 0;
+  int rc = cfrk_select_measure(ctx, d_start, d_length, nN, nS, d_span, d_keep, min_len, &on, &os);
+  if (rc || (rc = reads_out_fit(ctx, "select", *o, on, os, nN_out, nS_out)) || os == 0) return rc;
+  if ((rc = reads_out_carve(ctx, o, on, os))) return rc;
+  return cfrk_select_emit(ctx, d_data, d_start, d_length, nN, nS, d_span, d_keep, min_len, o->data, o->start, o->length, o->index, on, os);
 }
 
 int cfrk_reads_select_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
@@ -821,17 +714,10 @@ int cfrk_reads_select_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t 
   if (!ctx) return CFRK_ERR_ARG;
   int rc = select_check(ctx, d_data, d_start, d_length, nN, nS, min_len, d_data_out, cap_data, d_start_out, d_length_out,
                         cap_reads, nN_out, nS_out);
-  if (rc) return rc;
-  *nN_out = *nS_out = 0;
-  if (nS == 0) return CFRK_OK;
+  if (rc || nS == 0) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int64_t on = 0, os = 0;
-  if ((rc = cfrk_select_measure(ctx, d_start, d_length, nN, nS, d_span, d_keep, min_len, &on, &os))) return rc;
-  *nN_out = on; *nS_out = os;
-  if ((rc = select_small(ctx, on, os, cap_data, cap_reads))) return rc;
-  if (os == 0) return CFRK_OK;
-  return cfrk_select_emit(ctx, d_data, d_start, d_length, nN, nS, d_span, d_keep, min_len, d_data_out, d_start_out,
-                          d_length_out, d_index_out, on, os);
+  ReadsOut o = {d_data_out, d_start_out, d_length_out, d_index_out, cap_data, cap_reads, -1, false};
+  return select_core(ctx, d_data, d_start, d_length, nN, nS, d_span, d_keep, min_len, &o, nN_out, nS_out);
 }
 
 int cfrk_reads_select(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
@@ -841,61 +727,24 @@ int cfrk_reads_select(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, c
   if (!ctx) return CFRK_ERR_ARG;
   int rc = select_check(ctx, data, start, length, nN, nS, min_len, data_out, cap_data, start_out, length_out, cap_reads,
                         nN_out, nS_out);
-  if (rc) return rc;
-  *nN_out = *nS_out = 0;
-  if (nS == 0) return CFRK_OK;
-  LayoutCheck lc;      // (the add's check of the struct-read layout, beside the copies)
-  lc.begin(data, start, length, nN, nS);
+  if (rc || nS == 0) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // [data | start | length | span | keep] in, each part 256-byte aligned
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_start = up((size_t)nN + 64), o_length = o_start + up((size_t)nS * 8), o_span = o_length + up((size_t)nS * 4);
-  const size_t o_keep = o_span + up(span ? (size_t)nS * sizeof(cfrk_read_span) : 0);
-  void *p_in;
-  if ((rc = cfrk_pool_get(ctx, BUF_SELECT_IN, o_keep + (keep ? (size_t)nS : 0), &p_in))) return rc;
-  int8_t *d_data = (int8_t *)p_in;
-  int64_t *d_start = (int64_t *)((char *)p_in + o_start);
-  int32_t *d_length = (int32_t *)((char *)p_in + o_length);
-  cfrk_read_span *d_span = span ? (cfrk_read_span *)((char *)p_in + o_span) : nullptr;
-  uint8_t *d_keep = keep ? (uint8_t *)((char *)p_in + o_keep) : nullptr;
-  if (nN) HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_start, start, (size_t)nS * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_length, length, (size_t)nS * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (span) HIP_TRY(ctx, hipMemcpyAsync(d_span, span, (size_t)nS * sizeof(cfrk_read_span), hipMemcpyHostToDevice, ctx->stream));
-  if (keep) HIP_TRY(ctx, hipMemcpyAsync(d_keep, keep, (size_t)nS, hipMemcpyHostToDevice, ctx->stream));
-  bool bad = lc.failed(ctx);
-  for (int64_t i = 0; !bad && span && i < nS; ++i) {
+  StagePart x[2] = {{span, span ? (size_t)nS * sizeof(cfrk_read_span) : 0, nullptr}, {keep, keep ? (size_t)nS : 0, nullptr}};
+  StagedReads d;
+  if ((rc = stage_reads(ctx, BUF_SELECT_IN, data, start, length, nN, nS, STAGE_TABLE, x, 2, &d))) return rc;
+  for (int64_t i = 0; span && i < nS; ++i) {
     const cfrk_read_span s = span[i];
     if (s.offset < 0 || s.length < 0 || (int64_t)s.offset + (int64_t)s.length > (int64_t)length[i]) {
       cfrk_fail(ctx, CFRK_ERR_LAYOUT, "read %lld: span {%d, %d} does not lie inside its %d bases", (long long)i, (int)s.offset,
                 (int)s.length, (int)length[i]);
-      bad = true;
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
+      return CFRK_ERR_LAYOUT;
     }
   }
-  if (bad) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
-    return CFRK_ERR_LAYOUT;
-  }
-  int64_t on = 0, os = 0;
-  if ((rc = cfrk_select_measure(ctx, d_start, d_length, nN, nS, d_span, d_keep, min_len, &on, &os))) return rc;
-  *nN_out = on; *nS_out = os;
-  if ((rc = select_small(ctx, on, os, cap_data, cap_reads))) return rc;
-  if (os == 0) return CFRK_OK;
-  // [data | start | length | index] out
-  const size_t q_start = up((size_t)on + 16), q_length = q_start + up((size_t)os * 8), q_index = q_length + up((size_t)os * 4);
-  void *p_out;
-  if ((rc = cfrk_pool_get(ctx, BUF_SELECT_OUT, q_index + (size_t)os * 8, &p_out))) return rc;
-  int8_t *o_data = (int8_t *)p_out;
-  int64_t *o_st = (int64_t *)((char *)p_out + q_start);
-  int32_t *o_len = (int32_t *)((char *)p_out + q_length);
-  int64_t *o_idx = (int64_t *)((char *)p_out + q_index);
-  if ((rc = cfrk_select_emit(ctx, d_data, d_start, d_length, nN, nS, d_span, d_keep, min_len, o_data, o_st, o_len, o_idx, on, os))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(data_out, o_data, (size_t)on, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(start_out, o_st, (size_t)os * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(length_out, o_len, (size_t)os * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (index_out) HIP_TRY(ctx, hipMemcpyAsync(index_out, o_idx, (size_t)os * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return CFRK_OK;
+  ReadsOut o = {nullptr, nullptr, nullptr, nullptr, cap_data, cap_reads, BUF_SELECT_OUT, true};
+  rc = select_core(ctx, d.data, d.start, d.length, nN, nS, (const cfrk_read_span *)x[0].dev, (const uint8_t *)x[1].dev, min_len, &o, nN_out, nS_out);
+  if (rc || *nS_out == 0) return stage_drain(ctx, rc);
+  return download_reads(ctx, o, data_out, start_out, length_out, index_out, *nN_out, *nS_out);
 }
 
 int cfrk_global_last_add_ms(cfrk_ctx *ctx, float *ms) {
@@ -919,6 +768,33 @@ static int sparse_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, int k, int flags,
   return CFRK_OK;
 }
 
+// count, nnz to the host, refuse or place the rows, compact: what both forms run on device buffers.  The device form
+// reads nnz alone; the host form's whole row_ptr comes down with it (h_row), and its rows go to parts of BUF_SPARSE_OUT.
+static int sparse_core(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN, int64_t nS,
+                       int k, int flags, int64_t *d_row, int64_t *h_row, uint64_t **d_keys, uint32_t **d_counts, uint64_t cap,
+                       uint64_t *nnz_out) {
+  int rc = cfrk_sparse_count(ctx, d_data, d_start, d_length, nN, nS, k, flags, d_row);
+  if (rc) return rc;
+  int64_t nnz = 0;
+  if (h_row) HIP_TRY(ctx, hipMemcpyAsync(h_row, d_row, (size_t)(nS + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  else HIP_TRY(ctx, hipMemcpyAsync(&nnz, d_row + nS, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (h_row) nnz = h_row[nS];
+  *nnz_out = (uint64_t)nnz;
+  if ((uint64_t)nnz > cap)
+    return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "%lld distinct (read, k-mer) pairs, room for %llu", (long long)nnz, (unsigned long long)cap);
+  if (nnz == 0) return CFRK_OK;
+  if (h_row) {
+    Carve c;
+    void *p;
+    const size_t o_keys = c.part((size_t)nnz * 8), o_cnt = c.part((size_t)nnz * 4);
+    if ((rc = cfrk_pool_get(ctx, BUF_SPARSE_OUT, c.end, &p))) return rc;
+    *d_keys = carve_at<uint64_t>(p, o_keys);
+    *d_counts = carve_at<uint32_t>(p, o_cnt);
+  }
+  return cfrk_sparse_compact(ctx, d_start, d_row, nS, *d_keys, *d_counts);
+}
+
 int cfrk_per_read_sparse_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
                                 int64_t nN, int64_t nS, int k, int flags, int64_t *d_row_ptr, uint64_t *d_keys,
                                 uint32_t *d_counts, uint64_t cap, uint64_t *nnz_out) {
@@ -931,15 +807,7 @@ int cfrk_per_read_sparse_device(cfrk_ctx *ctx, const int8_t *d_data, const int64
     return CFRK_OK;
   }
   if (!d_start || !d_length || (nN > 0 && !d_data)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
-  if ((rc = cfrk_sparse_count(ctx, d_data, d_start, d_length, nN, nS, k, flags, d_row_ptr))) return rc;
-  int64_t nnz = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&nnz, d_row_ptr + nS, 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  *nnz_out = (uint64_t)nnz;
-  if ((uint64_t)nnz > cap)
-    return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "%lld distinct (read, k-mer) pairs, room for %llu", (long long)nnz, (unsigned long long)cap);
-  if (nnz == 0) return CFRK_OK;
-  return cfrk_sparse_compact(ctx, d_start, d_row_ptr, nS, d_keys, d_counts);
+  return sparse_core(ctx, d_data, d_start, d_length, nN, nS, k, flags, d_row_ptr, nullptr, &d_keys, &d_counts, cap, nnz_out);
 }
 
 int cfrk_per_read_sparse(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
@@ -951,44 +819,16 @@ int cfrk_per_read_sparse(cfrk_ctx *ctx, const int8_t *data, const int64_t *start
   row_ptr[0] = 0;
   if (nS == 0) return CFRK_OK;
   if (!start || !length || (nN > 0 && !data)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
-  LayoutCheck lc;      // (the add's check of the struct-read layout, beside the copies)
-  lc.begin(data, start, length, nN, nS);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // staged through slots of their own (BUF_DATA may still be read by an open job's last add):
-  // [data | start | length | row_ptr], each part 256-byte aligned
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_start = up((size_t)nN + 64), o_length = o_start + up((size_t)nS * 8), o_row = o_length + up((size_t)nS * 4);
-  void *p_in;
-  if ((rc = cfrk_pool_get(ctx, BUF_SPARSE_IN, o_row + (size_t)(nS + 1) * 8, &p_in))) return rc;
-  int8_t *d_data = (int8_t *)p_in;
-  int64_t *d_start = (int64_t *)((char *)p_in + o_start);
-  int32_t *d_length = (int32_t *)((char *)p_in + o_length);
-  int64_t *d_row = (int64_t *)((char *)p_in + o_row);
-  if (nN) HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_start, start, (size_t)nS * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_length, length, (size_t)nS * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (lc.failed(ctx)) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
-    return CFRK_ERR_LAYOUT;
-  }
-  if ((rc = cfrk_sparse_count(ctx, d_data, d_start, d_length, nN, nS, k, flags, d_row))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(row_ptr, d_row, (size_t)(nS + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const uint64_t nnz = (uint64_t)row_ptr[nS];
-  *nnz_out = nnz;
-  if (nnz > cap)
-    return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "%llu distinct (read, k-mer) pairs, room for %llu", (unsigned long long)nnz, (unsigned long long)cap);
-  if (nnz == 0) return CFRK_OK;
-  void *p_out;
-  const size_t o_cnt = up((size_t)nnz * 8);
-  if ((rc = cfrk_pool_get(ctx, BUF_SPARSE_OUT, o_cnt + (size_t)nnz * 4, &p_out))) return rc;
-  uint64_t *d_keys = (uint64_t *)p_out;
-  uint32_t *d_cnt = (uint32_t *)((char *)p_out + o_cnt);
-  if ((rc = cfrk_sparse_compact(ctx, d_start, d_row, nS, d_keys, d_cnt))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(keys, d_keys, (size_t)nnz * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(counts, d_cnt, (size_t)nnz * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return CFRK_OK;
+  // staged through a slot of its own (BUF_DATA may still be read by an open job's last add), with room for row_ptr
+  StagePart row = {nullptr, (size_t)(nS + 1) * 8, nullptr};
+  StagedReads d;
+  if ((rc = stage_reads(ctx, BUF_SPARSE_IN, data, start, length, nN, nS, STAGE_TABLE, &row, 1, &d))) return rc;
+  uint64_t *d_keys = nullptr; uint32_t *d_cnt = nullptr;
+  rc = sparse_core(ctx, d.data, d.start, d.length, nN, nS, k, flags, (int64_t *)row.dev, row_ptr, &d_keys, &d_cnt, cap, nnz_out);
+  if (rc || *nnz_out == 0) return stage_drain(ctx, rc);
+  HIP_TRY(ctx, hipMemcpyAsync(keys, d_keys, (size_t)*nnz_out * 8, hipMemcpyDeviceToHost, ctx->stream));
+  return cfrk_memcpy_d2h(ctx, counts, d_cnt, (size_t)*nnz_out * 4);
 }
 
 /* ------------------------------------------------------------------ distinct sketch */
@@ -1027,22 +867,15 @@ int cfrk_distinct_sketch(cfrk_ctx *ctx, const int8_t *data, const int64_t *start
   if (windows_out) *windows_out = 0;
   if (nN == 0) return CFRK_OK;
   if (!data || !regs) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
-  LayoutCheck lc;      // (the add's check of the struct-read layout, beside the copy)
-  if (start && length) lc.begin(data, start, length, nN, nS);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // (staged through the query calls' slot: BUF_DATA may still be read by an open job's last add)
-  void *d_data;
   uint8_t *d_regs;
-  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_IN, (size_t)nN + 64, &d_data))) return rc;
+  StagedReads d;
   if ((rc = cfrk_sketch_stage(ctx, &d_regs))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(d_data, data, (size_t)nN, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = stage_reads(ctx, BUF_QUERY_IN, data, start, length, nN, nS, 0, nullptr, 0, &d))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(d_regs, regs, CFRK_SKETCH_REGS, hipMemcpyHostToDevice, ctx->stream));
-  if (lc.failed(ctx)) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
-    return CFRK_ERR_LAYOUT;
-  }
   const uint64_t *d_windows;
-  if ((rc = cfrk_sketch_launch(ctx, (const int8_t *)d_data, nN, k, flags, d_regs, &d_windows))) return rc;
+  if ((rc = cfrk_sketch_launch(ctx, d.data, nN, k, flags, d_regs, &d_windows))) return stage_drain(ctx, rc);
   HIP_TRY(ctx, hipMemcpyAsync(regs, d_regs, CFRK_SKETCH_REGS, hipMemcpyDeviceToHost, ctx->stream));
   if (windows_out) HIP_TRY(ctx, hipMemcpyAsync(windows_out, d_windows, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

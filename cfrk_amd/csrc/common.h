@@ -17,7 +17,9 @@
 #define CFRK_RUNS_MAX_GROUPS 16
 
 enum {  // pool slots
-  BUF_DATA = 0, BUF_START, BUF_LENGTH, BUF_FREQ, BUF_SPILL, BUF_EXPORT_LO, BUF_EXPORT_HI,
+  BUF_DATA = 0,                               // staging of cfrk_global_add and cfrk_per_read_dense (reads in)
+  BUF_START, BUF_LENGTH, BUF_FREQ,            // staging of cfrk_per_read_dense alone
+  BUF_SPILL, BUF_EXPORT_LO, BUF_EXPORT_HI,
   BUF_EXPORT_CNT, BUF_SCRATCH, BUF_MSP_L1, BUF_MSP_L2, BUF_MSP_OUTK, BUF_MSP_OUTC, BUF_MSP_AUX, BUF_MSP_OUTH,
   BUF_MSP_ACCK, BUF_MSP_ACCH, BUF_MSP_ACCC,   // lists of the passes of a multi-pass add, merged per leaf at the end
   BUF_MSP_LAYOUT,                             // exact second-level layout (stream bases and sizes)
@@ -25,16 +27,17 @@ enum {  // pool slots
   BUF_MSP_OVF1, BUF_MSP_LAYOUT1,              // the same for the level-1 regions
   BUF_RUNS_AUX,                               // pipelined runs exchange: segment cursors, used rows per group
   BUF_QUERY_INDEX,                            // read-only lookup index of the result (query.hip)
-  BUF_QUERY_IN, BUF_QUERY_OUT,                // staging of the host query / read-stats calls (keys or reads in, counts or rows out)
+  BUF_QUERY_IN, BUF_QUERY_OUT,                // staging of host forms (staging.h).  IN: cfrk_global_query (keys), _query_reads, _read_stats,
+                                              // _read_spans, cfrk_distinct_sketch (reads); OUT: the first four (counts or rows)
   BUF_SPARSE_KEYS, BUF_SPARSE_CNT,            // per-read sparse (sparse.hip): the rows at their reads' offsets, nN entries
   BUF_SPARSE_AUX,                             // block sums of the row-pointer scan
-  BUF_SPARSE_IN, BUF_SPARSE_OUT,              // staging of the host call (data, start, length, row_ptr in; keys, counts out)
+  BUF_SPARSE_IN, BUF_SPARSE_OUT,              // staging of cfrk_per_read_sparse alone (data, start, length, row_ptr in; keys, counts out)
   BUF_SKETCH,                                 // distinct sketch (sketch.hip): the workgroups' merged registers as words, the window count, the host form's registers
-  BUF_FASTA,                                  // FASTA parser (ingest.hip): size / error words, tile aggregates, their scan
-  BUF_FASTA_IN, BUF_FASTA_OUT,                // staging of the host form (text in; data, start, length out)
+  BUF_FASTA,                                  // FASTA and FASTQ parsers (ingest.hip, ingest_fastq.hip), both forms: size / error words, tile aggregates, their scan
+  BUF_FASTA_IN, BUF_FASTA_OUT,                // staging of cfrk_fasta_parse and cfrk_fastq_parse (text in; data, start, length out)
   BUF_SELECT,                                 // select (read_filter.hip): size words, the read tiles' aggregates, their scan
   BUF_SELECT_SRC,                             // the kept reads' source offsets
-  BUF_SELECT_IN, BUF_SELECT_OUT,              // staging of the host form (reads, spans, keep in; the selected reads out)
+  BUF_SELECT_IN, BUF_SELECT_OUT,              // staging of cfrk_reads_select alone (reads, spans, keep in; the selected reads and their index out)
   BUF_NSLOTS
 };
 

@@ -30,6 +30,7 @@
 // tile before the run), the tile aggregate carries the run's offset and the scan, which knows the carry, decides.
 #include "common.h"
 #include "ingest_bytes.h"
+#include "staging.h"
 
 #include <algorithm>
 
@@ -423,22 +424,20 @@ int fa_emit(cfrk_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, bool compat, 
   return CFRK_OK;
 }
 
+// measure, refuse or place the outputs, emit: what both forms run on device text (the callers plan)
+int fa_core(cfrk_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, int flags, const FaPlan &pl, ReadsOut *o, int64_t *nN_out, int64_t *nS_out) {
+  const bool compat = (flags & CFRK_COMPAT) != 0;
+  int64_t nN = 0, nS = 0;
+  int rc = fa_measure(ctx, d_text, nbytes, compat, pl, &nN, &nS);
+  if (rc || (rc = reads_out_fit(ctx, "FASTA", *o, nN, nS, nN_out, nS_out)) || (rc = reads_out_carve(ctx, o, nN, nS))) return rc;
+  return fa_emit(ctx, d_text, nbytes, compat, pl, o->data, o->start, o->length, nN, nS);
+}
+
 int fa_check(cfrk_ctx *ctx, const void *text, uint64_t nbytes, int flags, const void *data, uint64_t cap_data, const void *start,
              const void *length, uint64_t cap_reads, int64_t *nN_out, int64_t *nS_out) {
   if (!ctx) return CFRK_ERR_ARG;
   if (flags & ~CFRK_COMPAT) return cfrk_fail(ctx, CFRK_ERR_ARG, "flags 0x%x: the FASTA parser takes CFRK_COMPAT only", flags);
-  if (!nN_out || !nS_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL size output");
-  if (nbytes > 0 && !text) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL text");
-  if ((cap_data > 0 && !data) || (cap_reads > 0 && (!start || !length))) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL array with a capacity above 0");
-  if (nbytes > ((uint64_t)1 << 62)) return cfrk_fail(ctx, CFRK_ERR_ARG, "nbytes");
-  return CFRK_OK;
-}
-
-int fa_small(cfrk_ctx *ctx, int64_t nN, int64_t nS, uint64_t cap_data, uint64_t cap_reads) {
-  if ((uint64_t)nN > cap_data || (uint64_t)nS > cap_reads)
-    return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "FASTA: %lld bytes of data and %lld reads, room for %llu and %llu", (long long)nN, (long long)nS,
-                     (unsigned long long)cap_data, (unsigned long long)cap_reads);
-  return CFRK_OK;
+  return parse_check(ctx, text, nbytes, data, cap_data, start, length, cap_reads, nN_out, nS_out);
 }
 
 }  // namespace
@@ -446,50 +445,25 @@ int fa_small(cfrk_ctx *ctx, int64_t nN, int64_t nS, uint64_t cap_data, uint64_t 
 extern "C" int cfrk_fasta_parse_device(cfrk_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, int flags, int8_t *d_data, uint64_t cap_data,
                                        int64_t *d_start, int32_t *d_length, uint64_t cap_reads, int64_t *nN_out, int64_t *nS_out) {
   int rc = fa_check(ctx, d_text, nbytes, flags, d_data, cap_data, d_start, d_length, cap_reads, nN_out, nS_out);
-  if (rc) return rc;
-  *nN_out = *nS_out = 0;
-  if (nbytes == 0) return CFRK_OK;
+  if (rc || nbytes == 0) return rc;
   if (((uintptr_t)d_text & 15) != 0) return cfrk_fail(ctx, CFRK_ERR_ALIGN, "d_text %p", (const void *)d_text);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const bool compat = (flags & CFRK_COMPAT) != 0;
   FaPlan pl;
   if ((rc = fa_plan(ctx, nbytes, &pl))) return rc;
-  int64_t nN = 0, nS = 0;
-  if ((rc = fa_measure(ctx, d_text, nbytes, compat, pl, &nN, &nS))) return rc;
-  *nN_out = nN; *nS_out = nS;
-  if ((rc = fa_small(ctx, nN, nS, cap_data, cap_reads))) return rc;
-  return fa_emit(ctx, d_text, nbytes, compat, pl, d_data, d_start, d_length, nN, nS);
+  ReadsOut o = {d_data, d_start, d_length, nullptr, cap_data, cap_reads, -1, false};
+  return fa_core(ctx, d_text, nbytes, flags, pl, &o, nN_out, nS_out);
 }
 
 extern "C" int cfrk_fasta_parse(cfrk_ctx *ctx, const char *text, uint64_t nbytes, int flags, int8_t *data, uint64_t cap_data, int64_t *start,
                                 int32_t *length, uint64_t cap_reads, int64_t *nN_out, int64_t *nS_out) {
   int rc = fa_check(ctx, text, nbytes, flags, data, cap_data, start, length, cap_reads, nN_out, nS_out);
-  if (rc) return rc;
-  *nN_out = *nS_out = 0;
-  if (nbytes == 0) return CFRK_OK;
+  if (rc || nbytes == 0) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const bool compat = (flags & CFRK_COMPAT) != 0;
-  void *d_text;
-  if ((rc = cfrk_pool_get(ctx, BUF_FASTA_IN, (size_t)nbytes + 16, &d_text))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(d_text, text, (size_t)nbytes, hipMemcpyHostToDevice, ctx->stream));
   FaPlan pl;
-  if ((rc = fa_plan(ctx, nbytes, &pl))) return rc;
-  int64_t nN = 0, nS = 0;
-  if ((rc = fa_measure(ctx, (const uint8_t *)d_text, nbytes, compat, pl, &nN, &nS))) return rc;
-  *nN_out = nN; *nS_out = nS;
-  if ((rc = fa_small(ctx, nN, nS, cap_data, cap_reads))) return rc;
-  // [data | start | length], each part 256-byte aligned
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_start = up((size_t)nN + 16), o_length = o_start + up((size_t)nS * 8);
-  void *p_out;
-  if ((rc = cfrk_pool_get(ctx, BUF_FASTA_OUT, o_length + (size_t)nS * 4, &p_out))) return rc;
-  int8_t *d_data = (int8_t *)p_out;
-  int64_t *d_start = (int64_t *)((char *)p_out + o_start);
-  int32_t *d_length = (int32_t *)((char *)p_out + o_length);
-  if ((rc = fa_emit(ctx, (const uint8_t *)d_text, nbytes, compat, pl, d_data, d_start, d_length, nN, nS))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(data, d_data, (size_t)nN, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(start, d_start, (size_t)nS * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(length, d_length, (size_t)nS * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return CFRK_OK;
+  void *d_text;
+  if ((rc = fa_plan(ctx, nbytes, &pl)) || (rc = cfrk_pool_get(ctx, BUF_FASTA_IN, (size_t)nbytes + 16, &d_text))) return rc;   // (every slot before the copy)
+  HIP_TRY(ctx, hipMemcpyAsync(d_text, text, (size_t)nbytes, hipMemcpyHostToDevice, ctx->stream));
+  ReadsOut o = {nullptr, nullptr, nullptr, nullptr, cap_data, cap_reads, BUF_FASTA_OUT, false};
+  if ((rc = fa_core(ctx, (const uint8_t *)d_text, nbytes, flags, pl, &o, nN_out, nS_out))) return stage_drain(ctx, rc);
+  return download_reads(ctx, o, data, start, length, nullptr, *nN_out, *nS_out);
 }

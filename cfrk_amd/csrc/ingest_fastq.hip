@@ -31,6 +31,7 @@
 //   -- the host reads the error words back (second synchronisation): the length check's verdict --
 #include "common.h"
 #include "ingest_bytes.h"
+#include "staging.h"
 
 #include <algorithm>
 
@@ -428,22 +429,19 @@ int fq_emit(cfrk_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, int min_qual,
   return CFRK_OK;
 }
 
+// measure, refuse or place the outputs, emit: what both forms run on device text
+int fq_core(cfrk_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, int min_qual, const FqPlan &pl, ReadsOut *o, int64_t *nN_out, int64_t *nS_out) {
+  FqSizes sz;
+  int rc = fq_measure(ctx, d_text, nbytes, pl, &sz);
+  if (rc || (rc = reads_out_fit(ctx, "FASTQ", *o, sz.nN, sz.nS, nN_out, nS_out)) || (rc = reads_out_carve(ctx, o, sz.nN, sz.nS))) return rc;
+  return fq_emit(ctx, d_text, nbytes, min_qual, pl, o->data, o->start, o->length, sz);
+}
+
 int fq_check(cfrk_ctx *ctx, const void *text, uint64_t nbytes, int min_qual, const void *data, uint64_t cap_data, const void *start,
              const void *length, uint64_t cap_reads, int64_t *nN_out, int64_t *nS_out) {
   if (!ctx) return CFRK_ERR_ARG;
   if (min_qual < 0 || min_qual > CFRK_FASTQ_MAX_QUAL) return cfrk_fail(ctx, CFRK_ERR_ARG, "min_qual %d: 0 .. %d", min_qual, CFRK_FASTQ_MAX_QUAL);
-  if (!nN_out || !nS_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL size output");
-  if (nbytes > 0 && !text) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL text");
-  if ((cap_data > 0 && !data) || (cap_reads > 0 && (!start || !length))) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL array with a capacity above 0");
-  if (nbytes > ((uint64_t)1 << 62)) return cfrk_fail(ctx, CFRK_ERR_ARG, "nbytes");
-  return CFRK_OK;
-}
-
-int fq_small(cfrk_ctx *ctx, const FqSizes &sz, uint64_t cap_data, uint64_t cap_reads) {
-  if ((uint64_t)sz.nN > cap_data || (uint64_t)sz.nS > cap_reads)
-    return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "FASTQ: %lld bytes of data and %lld reads, room for %llu and %llu", (long long)sz.nN, (long long)sz.nS,
-                     (unsigned long long)cap_data, (unsigned long long)cap_reads);
-  return CFRK_OK;
+  return parse_check(ctx, text, nbytes, data, cap_data, start, length, cap_reads, nN_out, nS_out);
 }
 
 }  // namespace
@@ -451,48 +449,25 @@ int fq_small(cfrk_ctx *ctx, const FqSizes &sz, uint64_t cap_data, uint64_t cap_r
 extern "C" int cfrk_fastq_parse_device(cfrk_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, int min_qual, int8_t *d_data, uint64_t cap_data,
                                        int64_t *d_start, int32_t *d_length, uint64_t cap_reads, int64_t *nN_out, int64_t *nS_out) {
   int rc = fq_check(ctx, d_text, nbytes, min_qual, d_data, cap_data, d_start, d_length, cap_reads, nN_out, nS_out);
-  if (rc) return rc;
-  *nN_out = *nS_out = 0;
-  if (nbytes == 0) return CFRK_OK;
+  if (rc || nbytes == 0) return rc;
   if (((uintptr_t)d_text & 15) != 0) return cfrk_fail(ctx, CFRK_ERR_ALIGN, "d_text %p", (const void *)d_text);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   FqPlan pl;
   if ((rc = fq_plan(ctx, nbytes, &pl))) return rc;
-  FqSizes sz;
-  if ((rc = fq_measure(ctx, d_text, nbytes, pl, &sz))) return rc;
-  *nN_out = sz.nN; *nS_out = sz.nS;
-  if ((rc = fq_small(ctx, sz, cap_data, cap_reads))) return rc;
-  return fq_emit(ctx, d_text, nbytes, min_qual, pl, d_data, d_start, d_length, sz);
+  ReadsOut o = {d_data, d_start, d_length, nullptr, cap_data, cap_reads, -1, false};
+  return fq_core(ctx, d_text, nbytes, min_qual, pl, &o, nN_out, nS_out);
 }
 
 extern "C" int cfrk_fastq_parse(cfrk_ctx *ctx, const char *text, uint64_t nbytes, int min_qual, int8_t *data, uint64_t cap_data, int64_t *start,
                                 int32_t *length, uint64_t cap_reads, int64_t *nN_out, int64_t *nS_out) {
   int rc = fq_check(ctx, text, nbytes, min_qual, data, cap_data, start, length, cap_reads, nN_out, nS_out);
-  if (rc) return rc;
-  *nN_out = *nS_out = 0;
-  if (nbytes == 0) return CFRK_OK;
+  if (rc || nbytes == 0) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  void *d_text;
-  if ((rc = cfrk_pool_get(ctx, BUF_FASTA_IN, (size_t)nbytes + 16, &d_text))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(d_text, text, (size_t)nbytes, hipMemcpyHostToDevice, ctx->stream));
   FqPlan pl;
-  if ((rc = fq_plan(ctx, nbytes, &pl))) return rc;
-  FqSizes sz;
-  if ((rc = fq_measure(ctx, (const uint8_t *)d_text, nbytes, pl, &sz))) return rc;
-  *nN_out = sz.nN; *nS_out = sz.nS;
-  if ((rc = fq_small(ctx, sz, cap_data, cap_reads))) return rc;
-  // [data | start | length], each part 256-byte aligned
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_start = up((size_t)sz.nN + 16), o_length = o_start + up((size_t)sz.nS * 8);
-  void *p_out;
-  if ((rc = cfrk_pool_get(ctx, BUF_FASTA_OUT, o_length + (size_t)sz.nS * 4, &p_out))) return rc;
-  int8_t *d_data = (int8_t *)p_out;
-  int64_t *d_start = (int64_t *)((char *)p_out + o_start);
-  int32_t *d_length = (int32_t *)((char *)p_out + o_length);
-  if ((rc = fq_emit(ctx, (const uint8_t *)d_text, nbytes, min_qual, pl, d_data, d_start, d_length, sz))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(data, d_data, (size_t)sz.nN, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(start, d_start, (size_t)sz.nS * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(length, d_length, (size_t)sz.nS * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return CFRK_OK;
+  void *d_text;
+  if ((rc = fq_plan(ctx, nbytes, &pl)) || (rc = cfrk_pool_get(ctx, BUF_FASTA_IN, (size_t)nbytes + 16, &d_text))) return rc;   // (every slot before the copy)
+  HIP_TRY(ctx, hipMemcpyAsync(d_text, text, (size_t)nbytes, hipMemcpyHostToDevice, ctx->stream));
+  ReadsOut o = {nullptr, nullptr, nullptr, nullptr, cap_data, cap_reads, BUF_FASTA_OUT, false};
+  if ((rc = fq_core(ctx, (const uint8_t *)d_text, nbytes, min_qual, pl, &o, nN_out, nS_out))) return stage_drain(ctx, rc);
+  return download_reads(ctx, o, data, start, length, nullptr, *nN_out, *nS_out);
 }
