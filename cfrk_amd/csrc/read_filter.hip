@@ -2,9 +2,8 @@
 // bases that a run of windows whose counts lie in [min_count, max_count] covers), and the SELECT that compacts the kept,
 // trimmed reads into new struct-read buffers.  The trimmed read set stays on the device from text to second count.
 //
-// Spans.  The front end is read_stats.hip's: a group of 16 or 64 lanes owns a read, stages it in LDS, every lane rolls
-// its run of windows and looks them up in batches whose first-slot loads are issued together (QB); reads above
-// CFRK_SPANS_FAST_WINDOWS windows take one workgroup each.  The reduction is the "longest run of ones" monoid: a
+// Spans.  The three launches by size class and the walk over a read's windows are lane_group.h's and
+// read_windows.h's; what is the filter's is the reduction, the "longest run of ones" monoid: a
 // stretch of windows is summarised as {first window, windows, solid windows at its beginning, solid windows at its
 // end, longest solid run inside and where it begins}; two neighbouring stretches combine into their union (runs_join:
 // the run across the seam is a.suf + b.pre), associatively, so the lanes' stretches are combined in lane order by a
@@ -31,17 +30,11 @@
 #include "query_dev.h"
 #include "read_windows.h"
 
-#include <algorithm>
-
 namespace {
 
 // ---- spans ------------------------------------------------------------------------------------
 
-constexpr int SP_CAP16 = 256;                          // windows a 16-lane group takes
-constexpr int SP_CAP64 = CFRK_SPANS_FAST_WINDOWS;      // windows a 64-lane group takes (the fast path's capacity)
-constexpr int SP_STAGE_SLACK = 72;                     // k - 1 <= 63 bytes + skew <= 3 + dword round-up <= 3, a multiple of 8
 constexpr int SP_LONG_NT = 256;
-constexpr int SP_LONG_CHUNK = 32;                      // windows a thread of the long path rolls in a row
 
 // a stretch of windows [first, first + len) of one read
 struct Runs {
@@ -106,179 +99,73 @@ template <int G, int MODE, bool CANON>
 __device__ __forceinline__ void spans_read(const int8_t *__restrict__ data, int64_t nN, int64_t i, int64_t st, int nwin,
                                            const QIndex &q, uint32_t mn, uint32_t mx, int mode, int32_t *stage_dw,
                                            int lane, cfrk_read_span *__restrict__ out) {
-  constexpr bool TWO = MODE == 2;
-  constexpr int B = TWO ? QB / 2 : QB;                 // (a two-word slot is two 16-byte loads)
-  typedef typename RsKey<TWO>::type T;
-  const int k = q.k;
-  const uint4 *slots = static_cast<const uint4 *>(q.p);
-  const uint32_t *dense = static_cast<const uint32_t *>(q.p);
-  const int skew = stage_read<G>(data, nN, st, nwin + k - 1, stage_dw, lane);
-  wave_sync();
-  const int8_t *stage = reinterpret_cast<const int8_t *>(stage_dw) + skew;
-  const int per = (nwin + G - 1) / G;
-  const int t0 = lane * per, t1 = min(t0 + per, nwin);
-  Runs acc = runs_none(t0);
-  if (t0 < t1) {
-    Roller<TWO, CANON> R(k);
-    for (int p = t0; p < t0 + k - 1; ++p) R.push((int)stage[p]);
-    for (int w0 = t0; w0 < t1; w0 += B) {
-      T key[B];
-      uint4 v[B], v2[B];
-      uint32_t d[B];
-      bool ok[B];
-#pragma unroll
-      for (int u = 0; u < B; ++u) {                    // every first-slot load of the batch is issued here ...
-        const bool in = w0 + u < t1;
-        if (in) R.push((int)stage[w0 + u + k - 1]);
-        ok[u] = in && R.valid();
-        key[u] = R.key();
-        if (MODE == 0) {
-          d[u] = ok[u] ? dense[(uint64_t)key[u]] : 0u;
-        } else if (MODE == 1) {
-          v[u] = ok[u] ? slots[q_slot1((uint64_t)key[u], q.shift)] : make_uint4(0, 0, 0, 0);
-        } else {
-          const uint64_t h = q_slot2((uint64_t)key[u], (uint64_t)(key[u] >> (TWO ? 64 : 0)), q.shift);
-          v[u] = ok[u] ? slots[2 * h] : make_uint4(0, 0, 0, 0);
-          v2[u] = ok[u] ? slots[2 * h + 1] : make_uint4(0, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < B; ++u) {                    // ... before any is resolved
-        if (w0 + u >= t1) break;
-        bool solid = false;
-        if (ok[u]) {
-          uint32_t r;
-          const uint64_t lo = (uint64_t)key[u], hi = (uint64_t)(key[u] >> (TWO ? 64 : 0));
-          if (MODE == 0) {
-            r = d[u];
-          } else if (MODE == 1) {
-            if (v[u].z == 0) r = 0;
-            else if (q_lo(v[u]) == lo) r = v[u].z;
-            else r = q_find1(slots, q.mask, (q_slot1(lo, q.shift) + 1) & q.mask, lo);      // longer probes
-          } else {
-            if (v2[u].x == 0) r = 0;
-            else if (q_lo(v[u]) == lo && q_hi(v[u]) == hi) r = v2[u].x;
-            else r = q_find2(slots, q.mask, (q_slot2(lo, hi, q.shift) + 1) & q.mask, lo, hi);
-          }
-          solid = r >= mn && r <= mx;
-        }
-        runs_push(acc, w0 + u, solid);
-      }
-    }
-  }
+  Runs acc = runs_none(0);
+  int t0, t1;
+  staged_windows<G, MODE, CANON>(data, nN, st, nwin, q, stage_dw, lane, t0, t1, [&](int w, bool valid, uint32_t c) {
+    runs_push(acc, w, valid && c >= mn && c <= mx);
+  });
+  acc.first = t0;                                     // (runs_push leaves it alone)
   const Runs all = group_runs<G>(acc);
-  if (lane == 0) store_span(out, i, all, mode, k);
+  if (lane == 0) store_span(out, i, all, mode, q.k);
   wave_sync();     // the group's LDS is reused by its next read
 }
 
-// G = 16: reads of 0 .. SP_CAP16 windows (a read without windows gets {0, 0} here); G = 64: SP_CAP16 + 1 .. SP_CAP64
 template <int G, int MODE, bool CANON>
 __global__ __launch_bounds__(G == 16 ? 256 : 64) void read_spans_kernel(
     const int8_t *__restrict__ data, const int64_t *__restrict__ start, const int32_t *__restrict__ length, int64_t nN,
     int64_t nS, QIndex q, uint32_t mn, uint32_t mx, int mode, cfrk_read_span *__restrict__ out) {
-  constexpr int NT = (G == 16) ? 256 : 64;
-  constexpr int RPB = NT / G;
-  constexpr int CAP = (G == 16) ? SP_CAP16 : SP_CAP64;
-  __shared__ int32_t s_stage[RPB][(CAP + SP_STAGE_SLACK) / 4];
-  const int grp = threadIdx.x / G, lane = threadIdx.x % G;
-  const int k = q.k;
-  if (G == 16) {
-    for (int64_t i = (int64_t)blockIdx.x * RPB + grp; i < nS; i += (int64_t)gridDim.x * RPB) {
-      const int64_t st = start[i];
-      const int nwin = read_windows(st, length[i], nN, k);
-      if (nwin > SP_CAP16) continue;
-      if (nwin == 0) { if (lane == 0) store_span(out, i, runs_none(0), mode, k); continue; }
-      spans_read<G, MODE, CANON>(data, nN, i, st, nwin, q, mn, mx, mode, s_stage[grp], lane, out);
-    }
-  } else {
-    // the wave looks at 64 reads at a time and takes those of its size class one after the other
-    for (int64_t base = (int64_t)blockIdx.x * 64; base < nS; base += (int64_t)gridDim.x * 64) {
-      const int64_t mine = base + lane;
-      int w = 0;
-      if (mine < nS) w = read_windows(start[mine], length[mine], nN, k);
-      unsigned long long todo = __ballot(w > SP_CAP16 && w <= SP_CAP64);
-      while (todo) {
-        const int b = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const int64_t i = base + b;
-        const int64_t st = start[i];
-        const int nwin = read_windows(st, length[i], nN, k);
-        spans_read<G, MODE, CANON>(data, nN, i, st, nwin, q, mn, mx, mode, s_stage[0], lane, out);
-      }
-    }
-  }
+  constexpr int RPB = (G == 16 ? 256 : 64) / G;
+  constexpr int CAP = (G == 16) ? READ_CAP16 : READ_CAP64;
+  __shared__ int32_t s_stage[RPB][(CAP + READ_STAGE_SLACK) / 4];
+  const int grp = G == 16 ? threadIdx.x / G : 0, lane = threadIdx.x % G;
+  class_reads<G>(
+      start, length, nN, nS, q.k,
+      [&](int64_t i, int64_t st, int nwin) {
+        spans_read<G, MODE, CANON>(data, nN, i, st, nwin, q, mn, mx, mode, s_stage[grp], lane, out);
+      },
+      [&](int64_t i) { if (lane == 0) store_span(out, i, runs_none(0), mode, q.k); });
 }
 
-// long reads: every workgroup looks at SP_LONG_NT reads at a time, lists the long ones in LDS and takes them one after
-// the other.  A read is walked in rounds of SP_LONG_NT chunks of SP_LONG_CHUNK windows, chunk t of a round by thread t
-// (rolled from the read's bytes in device memory: st + p <= st + length - 1); the round's stretches are joined in
-// thread order -- a shuffle tree per wave, the waves' results through LDS -- and appended to what came before.
+// long reads.  A read is walked in rounds of SP_LONG_NT chunks, chunk t of a round by thread t; the round's stretches
+// are joined in thread order -- a shuffle tree per wave, the waves' results through LDS -- and appended to what came
+// before.
 template <int MODE, bool CANON>
 __global__ __launch_bounds__(SP_LONG_NT) void read_spans_long_kernel(
     const int8_t *__restrict__ data, const int64_t *__restrict__ start, const int32_t *__restrict__ length, int64_t nN,
     int64_t nS, QIndex q, uint32_t mn, uint32_t mx, int mode, cfrk_read_span *__restrict__ out) {
   constexpr int NW = SP_LONG_NT / 64;
-  __shared__ int s_list[SP_LONG_NT];
-  __shared__ int s_n;
   __shared__ Runs s_runs[2][NW];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int k = q.k;
   unsigned round = 0;                                   // (never reset: the two sets of s_runs alternate across reads too)
-  for (int64_t base = (int64_t)blockIdx.x * SP_LONG_NT; base < nS; base += (int64_t)gridDim.x * SP_LONG_NT) {
-    if (tid == 0) s_n = 0;
-    __syncthreads();
-    if (base + tid < nS && read_windows(start[base + tid], length[base + tid], nN, k) > SP_CAP64)
-      s_list[atomicAdd(&s_n, 1)] = tid;
-    __syncthreads();
-    const int nl = s_n;
-    for (int j = 0; j < nl; ++j) {
-      const int64_t i = base + s_list[j];
-      const int64_t st = start[i];
-      const int nwin = read_windows(st, length[i], nN, k);
-      Runs all = runs_none(0);
-      for (int64_t r0 = 0; r0 < nwin; r0 += (int64_t)SP_LONG_NT * SP_LONG_CHUNK, ++round) {
-        const int64_t c0 = r0 + (int64_t)tid * SP_LONG_CHUNK;
-        const int64_t c1 = c0 + SP_LONG_CHUNK < nwin ? c0 + SP_LONG_CHUNK : (int64_t)nwin;
-        Runs acc = runs_none((int)(c0 < nwin ? c0 : 0));
-        if (c0 < nwin) {
-          Roller<MODE == 2, CANON> R(k);
-          for (int64_t p = c0; p < c1 + k - 1; ++p) {
-            R.push((int)data[st + p]);
-            if (p >= c0 + k - 1) {
-              bool solid = false;
-              if (R.valid()) {
-                const uint32_t c = rs_lookup<MODE>(q, R.key());
-                solid = c >= mn && c <= mx;
-              }
-              runs_push(acc, (int)(p - (k - 1)), solid);
-            }
-          }
-        }
-        const Runs wv = group_runs<64>(acc);
-        Runs *buf = s_runs[round & 1u];
-        if (lane == 0) buf[wave] = wv;
-        __syncthreads();
+  // (the body does not end on a barrier: a round's barrier stands between its writes and its reads only)
+  long_reads<SP_LONG_NT, false>(start, length, nN, nS, q.k, [&](int64_t i, int64_t st, int nwin) {
+    Runs all = runs_none(0);
+    for (int64_t r0 = 0; r0 < nwin; r0 += (int64_t)SP_LONG_NT * LONG_CHUNK, ++round) {
+      const int64_t c0 = r0 + (int64_t)tid * LONG_CHUNK;
+      Runs acc = runs_none((int)(c0 < nwin ? c0 : 0));
+      long_chunk<MODE, CANON>(data, st, nwin, q, c0, [&](int w, bool valid, uint32_t c) {
+        runs_push(acc, w, valid && c >= mn && c <= mx);
+      });
+      const Runs wv = group_runs<64>(acc);
+      Runs *buf = s_runs[round & 1u];
+      if (lane == 0) buf[wave] = wv;
+      __syncthreads();
 #pragma unroll
-        for (int w = 0; w < NW; ++w) all = runs_join(all, buf[w]);   // (every thread: the same sums, no second barrier)
-      }
-      if (tid == 0) store_span(out, i, all, mode, k);
+      for (int w = 0; w < NW; ++w) all = runs_join(all, buf[w]);   // (every thread: the same sums, no second barrier)
     }
-    __syncthreads();                                    // s_list / s_n are written again
-  }
+    if (tid == 0) store_span(out, i, all, mode, q.k);
+  });
 }
 
 template <int MODE, bool CANON>
 void spans_launch_all(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
                       int64_t nS, const QIndex &q, uint32_t mn, uint32_t mx, int mode, cfrk_read_span *d_out) {
-  const int64_t cus = ctx->num_cus;
-  const unsigned g16 = (unsigned)std::min<int64_t>((nS + 15) / 16, cus * 64);
-  const unsigned g64 = (unsigned)std::min<int64_t>((nS + 63) / 64, cus * 64);
-  const unsigned glong = (unsigned)std::min<int64_t>((nS + SP_LONG_NT - 1) / SP_LONG_NT, cus * 4);
-  hipLaunchKernelGGL((read_spans_kernel<16, MODE, CANON>), dim3(g16), dim3(256), 0, ctx->stream, d_data, d_start,
+  const ClassGrids g = class_grids(nS, ctx->num_cus, SP_LONG_NT);
+  hipLaunchKernelGGL((read_spans_kernel<16, MODE, CANON>), dim3(g.g16), dim3(256), 0, ctx->stream, d_data, d_start,
                      d_length, nN, nS, q, mn, mx, mode, d_out);
-  hipLaunchKernelGGL((read_spans_kernel<64, MODE, CANON>), dim3(g64), dim3(64), 0, ctx->stream, d_data, d_start,
+  hipLaunchKernelGGL((read_spans_kernel<64, MODE, CANON>), dim3(g.g64), dim3(64), 0, ctx->stream, d_data, d_start,
                      d_length, nN, nS, q, mn, mx, mode, d_out);
-  hipLaunchKernelGGL((read_spans_long_kernel<MODE, CANON>), dim3(glong), dim3(SP_LONG_NT), 0, ctx->stream, d_data,
+  hipLaunchKernelGGL((read_spans_long_kernel<MODE, CANON>), dim3(g.glong), dim3(SP_LONG_NT), 0, ctx->stream, d_data,
                      d_start, d_length, nN, nS, q, mn, mx, mode, d_out);
 }
 

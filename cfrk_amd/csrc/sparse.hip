@@ -3,32 +3,27 @@
 // Semantics: the guarded ComputeFreq (what dense.hip does without CFRK_COMPAT), i.e. row i = the non-zero bins of the
 // dense row i -- without the dense layout's nS * 4^k int32, which ends the dense form at k = 15 (and in practice at 8).
 //
-// Count pass, sparse_count_kernel<G, CANON>: G lanes of one wave own a read (G = 16: up to 256 windows, four reads per
-// wave so that 150-base reads keep the lanes busy; G = 64: up to CFRK_SPARSE_FAST_WINDOWS = 2048 windows).  The read's
-// codes are staged in LDS with coalesced dword loads (as dense_kernel's LDS variant does); every lane rolls its run of
-// windows (forward key and, when canonical, the reverse complement); the keys go to LDS, an invalid window as the
-// all-ones word.  The group sorts its keys in LDS with a bitonic network whose compare-exchanges all point upwards
-// (so positions at and beyond n read as +infinity and a row needs no padding).  Invalid windows sort to the end: the
-// first (windows - invalid) keys are the valid ones (an all-T 32-mer is the all-ones word too, but equal words are
-// interchangeable).  Heads of runs of equal keys are flagged, a ballot gives every head its place, the run's end is
-// found by bisection in LDS, and (key, count) are stored -- neighbouring heads to neighbouring addresses -- into a
-// temporary slot of the context pool at the read's own offset start[i]: read i has at most length[i] windows and the
-// reads' byte ranges are disjoint, so nN entries suffice and no sizes are needed beforehand.  No HBM atomics, no
-// scratch.  The row's distinct count goes to row_ptr[i].
-// Long reads (more windows than the fast path holds): sparse_long_sort_kernel, one workgroup per read, writes the raw
-// keys to the read's temporary range and sorts them there with the same network (the range stays in the L2), then
-// sparse_runlength_kernel collapses the runs in place.  Exact for any length; a slow path, not the fast one.
+// Count pass, sparse_count_kernel<G, CANON>: G lanes of one wave own a read (the size classes and the three launches
+// are lane_group.h's).  The read's codes are staged in LDS; every lane rolls its run of windows (read_windows.h's
+// Roller); the keys go to LDS, an invalid window as the all-ones word.  The group sorts its keys in LDS with a bitonic
+// network whose compare-exchanges all point upwards (so positions at and beyond n read as +infinity and a row needs no
+// padding).  Invalid windows sort to the end: the first (windows - invalid) keys are the valid ones (an all-T 32-mer is
+// the all-ones word too, but equal words are interchangeable).  Heads of runs of equal keys are flagged, a ballot gives
+// every head its place, the run's end is found by bisection in LDS, and (key, count) are stored -- neighbouring heads
+// to neighbouring addresses -- into a temporary slot of the context pool at the read's own offset start[i]: read i has
+// at most length[i] windows and the reads' byte ranges are disjoint, so nN entries suffice and no sizes are needed
+// beforehand.  No HBM atomics, no scratch.  The row's distinct count goes to row_ptr[i].
+// Long reads: sparse_long_sort_kernel, one workgroup per read, writes the raw keys to the read's temporary range and
+// sorts them there with the same network (the range stays in the L2), then sparse_runlength_kernel collapses the runs
+// in place.  Exact for any length; a slow path, not the fast one.
 // Scan: three small kernels turn the counts into offsets in place (reduce per block, scan of the block sums, apply).
 // Compaction pass, sparse_compact_kernel: every row moves from its temporary place to row_ptr[i].
 #include "common.h"
 #include "lane_group.h"
-
-#include <algorithm>
+#include "read_windows.h"
 
 namespace {
 
-constexpr int SP_CAP16 = 256;                          // windows a 16-lane group holds
-constexpr int SP_CAP64 = CFRK_SPARSE_FAST_WINDOWS;     // windows a 64-lane group holds (the fast path's capacity)
 constexpr int SP_PAD = 16;                             // keys between the groups' arrays: neighbouring groups half a bank row apart
 constexpr int SP_STAGE_SLACK = 48;                     // k - 1 <= 31 bytes + skew <= 3 + dword round-up <= 3, kept a multiple of 8
 constexpr int SP_BIG_ROW = 4096;                       // compaction: rows above this are copied by the whole workgroup
@@ -44,24 +39,11 @@ __device__ __forceinline__ int run_end(const uint64_t *a, int idx, int n, uint64
   return lo;
 }
 
-// one base into the rolling forward / reverse-complement keys; run = valid bases in a row
-__device__ __forceinline__ void roll(int c, uint64_t &fwd, uint64_t &rc, int &run, uint64_t mask, int rcshift) {
-  if (c < 0 || c > 3) {
-    run = 0;
-  } else {
-    fwd = ((fwd << 2) | (uint64_t)c) & mask;
-    rc = (rc >> 2) | ((uint64_t)(3 - c) << rcshift);
-    ++run;
-  }
-}
-
 template <int G, bool CANON>
 __device__ __forceinline__ void count_read(const int8_t *__restrict__ data, int64_t nN, int64_t i, int64_t st, int nwin,
                                            int k, uint64_t *keys, int32_t *stage_dw, int lane, int wave_lane,
                                            uint64_t *__restrict__ tmp_keys, uint32_t *__restrict__ tmp_cnt,
                                            int64_t *__restrict__ row_ptr) {
-  const uint64_t mask = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1);
-  const int rcshift = 2 * (k - 1);
   const int skew = stage_read<G>(data, nN, st, nwin + k - 1, stage_dw, lane);
   wave_sync();
   const int8_t *stage = reinterpret_cast<const int8_t *>(stage_dw) + skew;
@@ -69,13 +51,12 @@ __device__ __forceinline__ void count_read(const int8_t *__restrict__ data, int6
   const int t0 = lane * per, t1 = min(t0 + per, nwin);
   int invalid = 0;
   if (t0 < t1) {
-    uint64_t fwd = 0, rc = 0;
-    int run = 0;
+    Roller<false, CANON> R(k);
     for (int p = t0; p < t1 + k - 1; ++p) {
-      roll((int)stage[p], fwd, rc, run, mask, rcshift);
+      R.push((int)stage[p]);
       if (p >= t0 + k - 1) {
-        uint64_t key = CANON ? (fwd < rc ? fwd : rc) : fwd;
-        if (run < k) { key = ~0ull; ++invalid; }
+        uint64_t key = R.key();
+        if (!R.valid()) { key = ~0ull; ++invalid; }
         keys[p - (k - 1)] = key;
       }
     }
@@ -105,141 +86,95 @@ __device__ __forceinline__ void count_read(const int8_t *__restrict__ data, int6
   wave_sync();     // the group's LDS is reused by its next read
 }
 
-// G = 16: reads of 0 .. SP_CAP16 windows (a read without windows gets its zero here); G = 64: SP_CAP16 + 1 .. SP_CAP64
 template <int G, bool CANON>
 __global__ __launch_bounds__(G == 16 ? 256 : 64) void sparse_count_kernel(
     const int8_t *__restrict__ data, const int64_t *__restrict__ start, const int32_t *__restrict__ length, int64_t nN,
     int64_t nS, int k, uint64_t *__restrict__ tmp_keys, uint32_t *__restrict__ tmp_cnt, int64_t *__restrict__ row_ptr) {
-  constexpr int NT = (G == 16) ? 256 : 64;
-  constexpr int RPB = NT / G;
-  constexpr int CAP = (G == 16) ? SP_CAP16 : SP_CAP64;
+  constexpr int RPB = (G == 16 ? 256 : 64) / G;
+  constexpr int CAP = (G == 16) ? READ_CAP16 : READ_CAP64;
   __shared__ uint64_t s_keys[RPB][CAP + SP_PAD];
   __shared__ int32_t s_stage[RPB][(CAP + SP_STAGE_SLACK) / 4];
-  const int grp = threadIdx.x / G, lane = threadIdx.x % G, wave_lane = threadIdx.x & 63;
-  if (G == 16) {
-    for (int64_t i = (int64_t)blockIdx.x * RPB + grp; i < nS; i += (int64_t)gridDim.x * RPB) {
-      const int64_t st = start[i];
-      const int nwin = read_windows(st, length[i], nN, k);
-      if (nwin > SP_CAP16) continue;
-      if (nwin == 0) { if (lane == 0) row_ptr[i] = 0; continue; }
-      count_read<G, CANON>(data, nN, i, st, nwin, k, s_keys[grp], s_stage[grp], lane, wave_lane, tmp_keys, tmp_cnt, row_ptr);
-    }
-  } else {
-    // the wave looks at 64 reads at a time and counts those of its size class one after the other
-    for (int64_t base = (int64_t)blockIdx.x * 64; base < nS; base += (int64_t)gridDim.x * 64) {
-      const int64_t mine = base + lane;
-      int w = 0;
-      if (mine < nS) w = read_windows(start[mine], length[mine], nN, k);
-      unsigned long long todo = __ballot(w > SP_CAP16 && w <= SP_CAP64);
-      while (todo) {
-        const int b = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const int64_t i = base + b;
-        const int64_t st = start[i];
-        const int nwin = read_windows(st, length[i], nN, k);
-        count_read<G, CANON>(data, nN, i, st, nwin, k, s_keys[0], s_stage[0], lane, wave_lane, tmp_keys, tmp_cnt, row_ptr);
-      }
-    }
-  }
+  const int grp = G == 16 ? threadIdx.x / G : 0, lane = threadIdx.x % G, wave_lane = threadIdx.x & 63;
+  class_reads<G>(
+      start, length, nN, nS, k,
+      [&](int64_t i, int64_t st, int nwin) {
+        count_read<G, CANON>(data, nN, i, st, nwin, k, s_keys[grp], s_stage[grp], lane, wave_lane, tmp_keys, tmp_cnt,
+                             row_ptr);
+      },
+      [&](int64_t i) { if (lane == 0) row_ptr[i] = 0; });
 }
 
 // ---- long reads -----------------------------------------------------------------------------
 
 constexpr int SP_LONG_NT = 1024;
 
-// every workgroup looks at SP_LONG_NT reads at a time, lists the long ones in LDS and takes them one after the other:
 // raw keys (invalid windows as the all-ones word) into the read's temporary range, sorted there.  row_ptr[i] receives
 // the number of VALID windows (sparse_runlength_kernel turns it into the distinct count).
 template <bool CANON>
 __global__ __launch_bounds__(SP_LONG_NT) void sparse_long_sort_kernel(
     const int8_t *__restrict__ data, const int64_t *__restrict__ start, const int32_t *__restrict__ length, int64_t nN,
     int64_t nS, int k, uint64_t *tmp_keys, int64_t *__restrict__ row_ptr) {
-  __shared__ int s_list[SP_LONG_NT];
-  __shared__ int s_n, s_invalid;
+  __shared__ int s_invalid;
   const int tid = threadIdx.x;
-  const uint64_t mask = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1);
-  const int rcshift = 2 * (k - 1);
-  for (int64_t base = (int64_t)blockIdx.x * SP_LONG_NT; base < nS; base += (int64_t)gridDim.x * SP_LONG_NT) {
-    if (tid == 0) s_n = 0;
+  // (the body ends on a barrier: s_invalid is reset by the next read)
+  long_reads<SP_LONG_NT, true>(start, length, nN, nS, k, [&](int64_t i, int64_t st, int nwin) {
+    uint64_t *seg = tmp_keys + st;                     // length[i] >= nwin entries
+    if (tid == 0) s_invalid = 0;
     __syncthreads();
-    if (base + tid < nS && read_windows(start[base + tid], length[base + tid], nN, k) > SP_CAP64)
-      s_list[atomicAdd(&s_n, 1)] = tid;
-    __syncthreads();
-    const int nl = s_n;
-    for (int q = 0; q < nl; ++q) {
-      const int64_t i = base + s_list[q];
-      const int64_t st = start[i];
-      const int nwin = read_windows(st, length[i], nN, k);
-      uint64_t *seg = tmp_keys + st;                   // length[i] >= nwin entries
-      if (tid == 0) s_invalid = 0;
-      __syncthreads();
-      int invalid = 0;
-      for (int c0 = tid * 32; c0 < nwin; c0 += SP_LONG_NT * 32) {
-        const int c1 = min(c0 + 32, nwin);
-        uint64_t fwd = 0, rc = 0;
-        int run = 0;
-        for (int p = c0; p < c1 + k - 1; ++p) {        // st + p <= st + length[i] - 1
-          roll((int)data[st + p], fwd, rc, run, mask, rcshift);
-          if (p >= c0 + k - 1) {
-            uint64_t key = CANON ? (fwd < rc ? fwd : rc) : fwd;
-            if (run < k) { key = ~0ull; ++invalid; }
-            seg[p - (k - 1)] = key;
-          }
+    int invalid = 0;
+    for (int c0 = tid * 32; c0 < nwin; c0 += SP_LONG_NT * 32) {
+      const int c1 = min(c0 + 32, nwin);
+      Roller<false, CANON> R(k);
+      for (int p = c0; p < c1 + k - 1; ++p) {          // st + p <= st + length[i] - 1
+        R.push((int)data[st + p]);
+        if (p >= c0 + k - 1) {
+          uint64_t key = R.key();
+          if (!R.valid()) { key = ~0ull; ++invalid; }
+          seg[p - (k - 1)] = key;
         }
       }
-      if (invalid) atomicAdd(&s_invalid, invalid);
-      __syncthreads();
-      sort_keys(seg, nwin, tid, SP_LONG_NT, BlockSync());
-      if (tid == 0) row_ptr[i] = nwin - s_invalid;
-      __syncthreads();
     }
-  }
+    if (invalid) atomicAdd(&s_invalid, invalid);
+    __syncthreads();
+    sort_keys(seg, nwin, tid, SP_LONG_NT, BlockSync());
+    if (tid == 0) row_ptr[i] = nwin - s_invalid;
+    __syncthreads();
+  });
 }
 
 // runs of equal keys of every long read -> (key, count), in place at the front of the read's temporary range
 __global__ __launch_bounds__(256) void sparse_runlength_kernel(
     const int64_t *__restrict__ start, const int32_t *__restrict__ length, int64_t nN, int64_t nS, int k,
     uint64_t *tmp_keys, uint32_t *tmp_cnt, int64_t *row_ptr) {
-  __shared__ int s_list[256];
-  __shared__ int s_n;
   __shared__ int s_wsum[4];
   const int tid = threadIdx.x, wl = tid & 63, wv = tid >> 6;
-  for (int64_t base = (int64_t)blockIdx.x * 256; base < nS; base += (int64_t)gridDim.x * 256) {
-    if (tid == 0) s_n = 0;
-    __syncthreads();
-    if (base + tid < nS && read_windows(start[base + tid], length[base + tid], nN, k) > SP_CAP64)
-      s_list[atomicAdd(&s_n, 1)] = tid;
-    __syncthreads();
-    const int nl = s_n;
-    for (int q = 0; q < nl; ++q) {
-      const int64_t i = base + s_list[q];
-      const int64_t st = start[i];
-      const int nvalid = (int)row_ptr[i];
-      uint64_t *seg = tmp_keys + st;
-      uint32_t *cseg = tmp_cnt + st;
-      int running = 0;
-      // a tile reads its keys (and its heads their runs' ends) before anything of it is written; what it writes lies
-      // at or below the indices it read, so later tiles still find their keys (seg[tile - 1] can only have been
-      // replaced by itself)
-      for (int t0 = 0; t0 < nvalid; t0 += 256) {
-        const int idx = t0 + tid;
-        const bool act = idx < nvalid;
-        const uint64_t key = act ? seg[idx] : 0;
-        const bool head = act && (idx == 0 || seg[idx - 1] != key);
-        const int end = head ? run_end(seg, idx, nvalid, key) : 0;
-        const unsigned long long m = __ballot(head);
-        if (wl == 0) s_wsum[wv] = __popcll(m);
-        __syncthreads();
-        int pos = running + __popcll(m & ((1ull << wl) - 1)), total = 0;
-        for (int w = 0; w < 4; ++w) { if (w < wv) pos += s_wsum[w]; total += s_wsum[w]; }
-        if (head) { seg[pos] = key; cseg[pos] = (uint32_t)(end - idx); }
-        running += total;
-        __syncthreads();
-      }
-      if (tid == 0) row_ptr[i] = running;
+  // (the body ends on a barrier, also for a read without a tile)
+  long_reads<256, true>(start, length, nN, nS, k, [&](int64_t i, int64_t st, int) {
+    const int nvalid = (int)row_ptr[i];
+    uint64_t *seg = tmp_keys + st;
+    uint32_t *cseg = tmp_cnt + st;
+    int running = 0;
+    // a tile reads its keys (and its heads their runs' ends) before anything of it is written; what it writes lies
+    // at or below the indices it read, so later tiles still find their keys (seg[tile - 1] can only have been
+    // replaced by itself)
+    for (int t0 = 0; t0 < nvalid; t0 += 256) {
+      const int idx = t0 + tid;
+      const bool act = idx < nvalid;
+      const uint64_t key = act ? seg[idx] : 0;
+      const bool head = act && (idx == 0 || seg[idx - 1] != key);
+      const int end = head ? run_end(seg, idx, nvalid, key) : 0;
+      const unsigned long long m = __ballot(head);
+      if (wl == 0) s_wsum[wv] = __popcll(m);
+      __syncthreads();
+      int pos = running + __popcll(m & ((1ull << wl) - 1)), total = 0;
+      for (int w = 0; w < 4; ++w) { if (w < wv) pos += s_wsum[w]; total += s_wsum[w]; }
+      if (head) { seg[pos] = key; cseg[pos] = (uint32_t)(end - idx); }
+      running += total;
       __syncthreads();
     }
-  }
+    if (tid == 0) row_ptr[i] = running;
+    __syncthreads();
+  });
 }
 
 // ---- counts -> offsets ------------------------------------------------------------------------
@@ -361,11 +296,9 @@ int cfrk_sparse_count(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_star
   uint64_t *tk = (uint64_t *)p_keys;
   uint32_t *tc = (uint32_t *)p_cnt;
   int64_t *bsum = (int64_t *)p_aux;
-  const int64_t cus = ctx->num_cus;
-  const unsigned g16 = (unsigned)std::min<int64_t>((nS + 15) / 16, cus * 8);
-  const unsigned g64 = (unsigned)std::min<int64_t>((nS + 63) / 64, cus * 8);
-  const unsigned glong = (unsigned)std::min<int64_t>((nS + SP_LONG_NT - 1) / SP_LONG_NT, cus);
-  const unsigned grl = (unsigned)std::min<int64_t>((nS + 255) / 256, cus * 4);
+  const int64_t cus = ctx->num_cus;                   // (the caps are this file's own, lower than class_grids')
+  const unsigned g16 = reads_grid(nS, 16, cus * 8), g64 = reads_grid(nS, 64, cus * 8);
+  const unsigned glong = reads_grid(nS, SP_LONG_NT, cus), grl = reads_grid(nS, 256, cus * 4);
 #define CFRK_SPARSE_COUNT(G_, C_, GRID_)                                                                          \
   hipLaunchKernelGGL((sparse_count_kernel<G_, C_>), dim3(GRID_), dim3(G_ == 16 ? 256 : 64), 0, ctx->stream, d_data, \
                      d_start, d_length, nN, nS, k, tk, tc, d_row_ptr)
@@ -395,7 +328,7 @@ int cfrk_sparse_count(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_star
 // Moves the rows of the most recent cfrk_sparse_count (same d_start, d_row_ptr, nS) to d_keys / d_counts; enqueued.
 int cfrk_sparse_compact(cfrk_ctx *ctx, const int64_t *d_start, const int64_t *d_row_ptr, int64_t nS, uint64_t *d_keys,
                         uint32_t *d_counts) {
-  const unsigned grid = (unsigned)std::min<int64_t>((nS + 15) / 16, (int64_t)ctx->num_cus * 16);
+  const unsigned grid = reads_grid(nS, 16, (int64_t)ctx->num_cus * 16);
   hipLaunchKernelGGL(sparse_compact_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_start, d_row_ptr, nS,
                      (const uint64_t *)ctx->pool[BUF_SPARSE_KEYS].p, (const uint32_t *)ctx->pool[BUF_SPARSE_CNT].p, d_keys,
                      d_counts);
