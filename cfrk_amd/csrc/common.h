@@ -38,6 +38,11 @@ enum {  // pool slots
   BUF_SELECT,                                 // select (read_filter.hip): size words, the read tiles' aggregates, their scan
   BUF_SELECT_SRC,                             // the kept reads' source offsets
   BUF_SELECT_IN, BUF_SELECT_OUT,              // staging of cfrk_reads_select alone (reads, spans, keep in; the selected reads and their index out)
+  BUF_TEXT_INDEX,                             // text index (text_out.hip), both forms: size / error words, tile aggregates, their scan
+  BUF_TEXT_IN, BUF_TEXT_OUT,                  // staging of cfrk_text_index alone (text in; records out)
+  BUF_EMIT,                                   // text emitter (text_out.hip): size words, the read tiles' aggregates, their scan
+  BUF_EMIT_OFF,                               // the kept reads' output offsets and input indices
+  BUF_EMIT_IN, BUF_EMIT_OUT,                  // staging of cfrk_reads_emit_text alone (reads, spans, keep, records, text in; text out)
   BUF_NSLOTS
 };
 

@@ -56,6 +56,14 @@
 //                    filtered by abundance against the whole result, as FASTA: ">" + the record's number in QFILE, then
 //                    its kept bases on one line.  On the device: cfrk_global_read_spans_device, cfrk_reads_select_device,
 //                    one copy back, cfrk_host_format_fasta.  One device (not with --gpus above 1), not with --batch or --sparse
+//   --filter-names   (with --filter-out) the output records keep the names they have in QFILE: the whole header line behind
+//                    its '>' / '@', verbatim.  QFILE's text goes to the device, cfrk_text_index_device finds every record's
+//                    header and quality line in it, and cfrk_reads_emit_text_device writes the output text there in place of
+//                    the select: one copy back, no formatting on the host
+//   --filter-format fasta|fastq  (with --filter-out) the output format.  fasta is the default and alone changes nothing;
+//                    fastq writes '@' name, the kept bases, '+' and the matching slice of the record's quality line: it
+//                    needs a FASTQ QFILE and implies --filter-names.  A base that --min-qual masked for counting is not
+//                    masked here (QFILE is read unmasked); any other invalid base reads N
 //   --filter-min-count T / --filter-max-count U  a window is solid when T <= count <= U (defaults 2 and no upper bound)
 //   --filter-trim longest|prefix|none  keep the longest solid run (the default; the earliest on a tie), the run that
 //                    begins at the read's first window (khmer's filter-abund), or the whole read (no spans)
@@ -136,6 +144,8 @@ struct Options {
   uint32_t filter_min_count = 2, filter_max_count = CFRK_COUNT_MAX;   // --filter-min-count T, --filter-max-count U
   int filter_trim = CFRK_SPAN_LONGEST; // --filter-trim: CFRK_SPAN_LONGEST / CFRK_SPAN_PREFIX, -1 = none
   long filter_min_len = -1;            // --filter-min-len L (-1: k)
+  bool filter_names = false;           // --filter-names (implied by --filter-format fastq)
+  int filter_format = CFRK_TEXT_FASTA; // --filter-format: CFRK_TEXT_FASTA / CFRK_TEXT_FASTQ
   bool filter_median = false;          // --filter-min-median A / --filter-max-median B
   uint32_t filter_min_median = 0, filter_max_median = 0xFFFFFFFFu;
   bool estimate = false, estimate_only = false, auto_hint = false;   // --estimate, --estimate-only, --auto-hint
@@ -375,6 +385,19 @@ int write_histo(const Options &o, const Spectrum &sp) {
 
 // --query: the query reads (parsed once, clean FASTA) and the answers of one result for every window of them
 cfrk_batch g_qreads{};
+int g_qformat = CFRK_FORMAT_FASTA;       // what QFILE was read as
+std::vector<char> g_qtext;              // --filter-names: QFILE's bytes
+
+// 0, or 1 (the error reported)
+int read_whole_file(const char *path, std::vector<char> &buf) {
+  FILE *f = fopen(path, "rb");
+  if (!f) { fprintf(stderr, "cfrk: cannot read %s\n", path); return 1; }
+  char tmp[1 << 16];
+  size_t got;
+  while ((got = fread(tmp, 1, sizeof tmp, f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
+  fclose(f);
+  return 0;
+}
 
 // 0, or the exit status (the error reported)
 int query_answers(cfrk_ctx *ctx, std::vector<uint32_t> &ans) {
@@ -416,6 +439,8 @@ int write_query_stats(const Options &o, cfrk_ctx *ctx) {
 }
 
 // --filter-out: the query reads trimmed to their solid spans and filtered, on the device, written to FFILE as FASTA
+// named by record number (select, one copy back, formatted here), or -- --filter-names -- as FASTA / FASTQ text with
+// QFILE's names and qualities, written on the device (index, emit, one copy back)
 int write_filter(const Options &o, cfrk_ctx *ctx, int k) {
   const cfrk_batch &q = g_qreads;
   const size_t nN = (size_t)q.nN, nS = (size_t)q.nS;
@@ -423,16 +448,21 @@ int write_filter(const Options &o, cfrk_ctx *ctx, int k) {
   std::vector<int64_t> start, index;
   std::vector<int32_t> length;
   int64_t onN = 0, onS = 0;
+  const bool names = o.filter_names;
+  std::string buf;
   if (nS) {
     void *d_data = nullptr, *d_start = nullptr, *d_length = nullptr, *d_span = nullptr, *d_keep = nullptr, *d_stats = nullptr;
     void *o_data = nullptr, *o_start = nullptr, *o_length = nullptr, *o_index = nullptr;
+    void *d_text = nullptr, *d_rec = nullptr, *d_out = nullptr;
     const char *what = "cfrk_device_alloc";
     int rc;
     const bool trim = o.filter_trim >= 0;
     if (!(rc = cfrk_device_alloc(ctx, nN + 16, &d_data)) && !(rc = cfrk_device_alloc(ctx, nS * 8, &d_start)) &&
-        !(rc = cfrk_device_alloc(ctx, nS * 4, &d_length)) && !(rc = cfrk_device_alloc(ctx, nN + 16, &o_data)) &&
-        !(rc = cfrk_device_alloc(ctx, nS * 8, &o_start)) && !(rc = cfrk_device_alloc(ctx, nS * 4, &o_length)) &&
-        !(rc = cfrk_device_alloc(ctx, nS * 8, &o_index)) && !(trim && (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_span), &d_span))) &&
+        !(rc = cfrk_device_alloc(ctx, nS * 4, &d_length)) &&
+        !(!names && ((rc = cfrk_device_alloc(ctx, nN + 16, &o_data)) || (rc = cfrk_device_alloc(ctx, nS * 8, &o_start)) ||
+                     (rc = cfrk_device_alloc(ctx, nS * 4, &o_length)) || (rc = cfrk_device_alloc(ctx, nS * 8, &o_index)))) &&
+        !(names && ((rc = cfrk_device_alloc(ctx, g_qtext.size() + 16, &d_text)) || (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_text_record), &d_rec)))) &&
+        !(trim && (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_span), &d_span))) &&
         !(o.filter_median && ((rc = cfrk_device_alloc(ctx, nS, &d_keep)) || (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_stats), &d_stats))))) {
       what = "cfrk_memcpy_h2d";
       if (!(rc = cfrk_memcpy_h2d(ctx, d_data, q.data, nN)) && !(rc = cfrk_memcpy_h2d(ctx, d_start, q.start, nS * 8)))
@@ -454,14 +484,42 @@ int write_filter(const Options &o, cfrk_ctx *ctx, int k) {
           rc = cfrk_memcpy_h2d(ctx, d_keep, keep.data(), nS);
         }
       }
-      if (!rc) {
+      const long min_len = o.filter_min_len >= 0 ? o.filter_min_len : (long)k;
+      if (!rc && names) {
+        // the index of QFILE's text numbers the records as the host parser did; the emitter sizes, then writes
+        const int tfmt = g_qformat == CFRK_FORMAT_FASTQ ? CFRK_TEXT_FASTQ : CFRK_TEXT_FASTA;
+        int64_t inS = 0;
+        uint64_t onb = 0;
+        what = "cfrk_memcpy_h2d";
+        if (!(rc = cfrk_memcpy_h2d(ctx, d_text, g_qtext.data(), g_qtext.size()))) {
+          what = "cfrk_text_index_device";
+          rc = cfrk_text_index_device(ctx, (const uint8_t *)d_text, g_qtext.size(), tfmt, (cfrk_text_record *)d_rec, nS, &inS);
+        }
+        if (!rc && inS != q.nS) {
+          fprintf(stderr, "cfrk: %s: %lld records parsed, %lld indexed\n", o.query, (long long)q.nS, (long long)inS);
+          rc = CFRK_ERR_LAYOUT;
+        }
+        for (int pass = 0; pass < 2 && !rc; ++pass) {
+          what = "cfrk_reads_emit_text_device";
+          rc = cfrk_reads_emit_text_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS,
+                                           (const cfrk_read_span *)d_span, (const uint8_t *)d_keep, (int32_t)min_len, (const uint8_t *)d_text,
+                                           g_qtext.size(), (const cfrk_text_record *)d_rec, o.filter_format, (uint8_t *)d_out, pass ? onb : 0, &onb, &onS);
+          if (pass == 0 && rc == CFRK_ERR_SMALL_BUF) { what = "cfrk_device_alloc"; rc = cfrk_device_alloc(ctx, onb + 16, &d_out); }
+          else break;
+        }
+        if (!rc && onb) {
+          what = "cfrk_memcpy_d2h";
+          buf.resize((size_t)onb);
+          rc = cfrk_memcpy_d2h(ctx, &buf[0], d_out, (size_t)onb);
+        }
+      }
+      if (!rc && !names) {
         what = "cfrk_reads_select_device";
-        const long min_len = o.filter_min_len >= 0 ? o.filter_min_len : (long)k;
         rc = cfrk_reads_select_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS,
                                       (const cfrk_read_span *)d_span, (const uint8_t *)d_keep, (int32_t)min_len, (int8_t *)o_data, nN,
                                       (int64_t *)o_start, (int32_t *)o_length, (int64_t *)o_index, nS, &onN, &onS);
       }
-      if (!rc) {
+      if (!rc && !names) {
         what = "cfrk_memcpy_d2h";
         data.resize((size_t)onN); start.resize((size_t)onS); length.resize((size_t)onS); index.resize((size_t)onS);
         if (onS && !(rc = cfrk_memcpy_d2h(ctx, data.data(), o_data, (size_t)onN)) && !(rc = cfrk_memcpy_d2h(ctx, start.data(), o_start, (size_t)onS * 8)) &&
@@ -470,13 +528,14 @@ int write_filter(const Options &o, cfrk_ctx *ctx, int k) {
       }
     }
     const int rc2 = cfrk_ctx_sync(ctx);
-    for (void *d : {d_data, d_start, d_length, d_span, d_keep, d_stats, o_data, o_start, o_length, o_index}) if (d) cfrk_device_free(ctx, d);
+    for (void *d : {d_data, d_start, d_length, d_span, d_keep, d_stats, o_data, o_start, o_length, o_index, d_text, d_rec, d_out}) if (d) cfrk_device_free(ctx, d);
     if (rc) return die(ctx, rc, what);
     if (rc2) return die(ctx, rc2, "cfrk_ctx_sync");
   }
-  std::string buf;
-  buf.resize(cfrk_host_format_fasta(data.data(), start.data(), length.data(), index.data(), onS, nullptr, 0));
-  cfrk_host_format_fasta(data.data(), start.data(), length.data(), index.data(), onS, &buf[0], buf.size());
+  if (!names) {
+    buf.resize(cfrk_host_format_fasta(data.data(), start.data(), length.data(), index.data(), onS, nullptr, 0));
+    cfrk_host_format_fasta(data.data(), start.data(), length.data(), index.data(), onS, &buf[0], buf.size());
+  }
   FILE *f = fopen(o.filter_out, "wb");
   if (!f) { fprintf(stderr, "cfrk: cannot write %s\n", o.filter_out); return 1; }
   const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
@@ -1075,15 +1134,20 @@ int main(int argc, char **argv) {
     else if (!strncmp(argv[i], "--filter-", 9)) {
       const char *opt = argv[i];
       static const char *const known[] = {"--filter-out", "--filter-min-count", "--filter-max-count", "--filter-trim", "--filter-min-len",
-                                          "--filter-min-median", "--filter-max-median"};
+                                          "--filter-min-median", "--filter-max-median", "--filter-names", "--filter-format"};
       bool is_known = false;
       for (const char *n : known) is_known = is_known || !strcmp(opt, n);
       if (!is_known) { fprintf(stderr, "cfrk: unknown option %s\n", opt); return 1; }
+      if (!strcmp(opt, "--filter-names")) { o.filter_names = true; filter_opt_set = true; continue; }
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", opt); return 1; }
       const char *v = argv[++i];
       if (!strcmp(opt, "--filter-out")) { o.filter_out = v; continue; }
       filter_opt_set = true;
-      if (!strcmp(opt, "--filter-trim")) {
+      if (!strcmp(opt, "--filter-format")) {
+        if (!strcmp(v, "fasta")) o.filter_format = CFRK_TEXT_FASTA;
+        else if (!strcmp(v, "fastq")) { o.filter_format = CFRK_TEXT_FASTQ; o.filter_names = true; }
+        else { fprintf(stderr, "cfrk: --filter-format takes fasta or fastq, not '%s'\n", v); return 1; }
+      } else if (!strcmp(opt, "--filter-trim")) {
         if (!strcmp(v, "longest")) o.filter_trim = CFRK_SPAN_LONGEST;
         else if (!strcmp(v, "prefix")) o.filter_trim = CFRK_SPAN_PREFIX;
         else if (!strcmp(v, "none")) o.filter_trim = -1;
@@ -1154,7 +1218,13 @@ int main(int argc, char **argv) {
   if (o.query && batch_n >= 0) { fprintf(stderr, "cfrk: --query writes one file: not with --batch\n"); return 1; }
   if (o.query_db && !pos.empty()) { fprintf(stderr, "cfrk: --query-db takes no positional arguments\n"); return 1; }
   if (o.query_db && o.min_qual_set) { fprintf(stderr, "cfrk: --min-qual applies to the FASTQ input that is counted: not with --query-db\n"); return 1; }
-  if (o.query && read_reads(o.query, file_format(o, o.query), 0, 0, &g_qreads)) return 1;
+  if (o.query) g_qformat = file_format(o, o.query);
+  if (o.filter_format == CFRK_TEXT_FASTQ && g_qformat != CFRK_FORMAT_FASTQ) {
+    fprintf(stderr, "cfrk: --filter-format fastq needs a FASTQ --query file: %s is read as FASTA\n", o.query);
+    return 1;
+  }
+  if (o.query && read_reads(o.query, g_qformat, 0, 0, &g_qreads)) return 1;
+  if (o.filter_names && read_whole_file(o.query, g_qtext)) return 1;
   struct QFree { ~QFree() { if (g_qreads.data) cfrk_host_free_batch(&g_qreads); } } qfree;
   if (o.query_db) return run_query_db(o);
   if (pos.size() < 3) {

@@ -42,6 +42,13 @@ READ_SPAN_DTYPE = np.dtype([("offset", "<i4"), ("length", "<i4")])
 CFRK_SELECT_TILE_BYTES = 16384       # select: bytes of data_out per workgroup of the copy
 CFRK_SELECT_TILE_READS = 256         # reads per workgroup of its per-read passes
 CFRK_SELECT_SCAN_TILES = 1024        # tiles of reads per block of its tile scan
+CFRK_TEXT_FASTA = 0                  # text index / emitter: the format of a text
+CFRK_TEXT_FASTQ = 1
+CFRK_TEXT_TILE_BYTES = 16384         # text index: text bytes per workgroup
+CFRK_TEXT_SCAN_TILES = 1024          # tiles per block of its tile scan
+CFRK_EMIT_TILE_BYTES = 16384         # text emitter: bytes of output per workgroup of the copy
+# cfrk_text_record: where a record's header line and quality line lie in its text
+TEXT_RECORD_DTYPE = np.dtype([("head_off", "<i8"), ("qual_off", "<i8"), ("head_len", "<i4"), ("qual_len", "<i4")])
 CFRK_SKETCH_LOG2M = 14               # distinct sketch: log2 of its registers
 CFRK_SKETCH_REGS = 16384             # one uint8 register per bucket
 CFRK_FASTA_TILE_BYTES = 16384        # device FASTA parser: text bytes per workgroup
@@ -124,6 +131,10 @@ def load_library():
         "cfrk_global_read_spans_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, C.c_uint32, i32, vp], C.c_int),
         "cfrk_reads_select": ([vp, vp, vp, vp, i64, i64, vp, vp, C.c_int32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_reads_select_device": ([vp, vp, vp, vp, i64, i64, vp, vp, C.c_int32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "cfrk_text_index": ([vp, vp, u64, i32, vp, u64, C.POINTER(i64)], C.c_int),
+        "cfrk_text_index_device": ([vp, vp, u64, i32, vp, u64, C.POINTER(i64)], C.c_int),
+        "cfrk_reads_emit_text": ([vp, vp, vp, vp, i64, i64, vp, vp, C.c_int32, vp, u64, vp, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)], C.c_int),
+        "cfrk_reads_emit_text_device": ([vp, vp, vp, vp, i64, i64, vp, vp, C.c_int32, vp, u64, vp, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)], C.c_int),
         "cfrk_global_export_device": ([vp, vp, vp, vp, u64, C.c_int, C.POINTER(u64)], C.c_int),
         "cfrk_global_digest": ([vp, C.POINTER(u64)], C.c_int),
         "cfrk_global_last_add_ms": ([vp, C.POINTER(C.c_float)], C.c_int),
@@ -477,6 +488,86 @@ class Context:
             e.nN, e.nS = nN_o.value, nS_o.value
             raise
         return nN_o.value, nS_o.value
+
+    # -- text out: the record index of a text, the kept reads written back as FASTA / FASTQ text ---
+    def index_text(self, text, fmt):
+        """text (bytes or a uint8 array), fmt CFRK_TEXT_FASTA / CFRK_TEXT_FASTQ -> np.ndarray[nS] of TEXT_RECORD_DTYPE:
+        where each record's header line and quality line lie in the text.  Defined for every text (no grammar is
+        checked).  A sizes-only call, then the call into an array of exactly that size."""
+        text = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+        nS = C.c_int64()
+        rc = self._L.cfrk_text_index(self._h, _ptr(text), text.size, int(fmt), None, 0, C.byref(nS))
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.check(rc, "cfrk_text_index")
+        rec = np.zeros(nS.value, TEXT_RECORD_DTYPE)
+        if rc == CFRK_ERR_SMALL_BUF:
+            self.check(self._L.cfrk_text_index(self._h, _ptr(text), text.size, int(fmt), _ptr(rec), rec.size, C.byref(nS)),
+                       "cfrk_text_index")
+        return rec
+
+    def index_text_device(self, d_text, nbytes, fmt, d_rec, cap_reads):
+        """device form: d_text 16-byte aligned, d_rec room for cap_reads records of 24 bytes -> nS; d_rec may be 0 with
+        capacity 0 (sizes only).  Raises CfrkError (code CFRK_ERR_SMALL_BUF, with .nS set, nothing written) when the
+        array is too small.  Synchronises once, returns with the scatter enqueued on the context stream."""
+        nS = C.c_int64()
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_text_index_device(self._h, vp(d_text), nbytes, int(fmt), vp(d_rec), cap_reads, C.byref(nS))
+        try:
+            self.check(rc, "cfrk_text_index_device")
+        except CfrkError as e:
+            e.nS = nS.value
+            raise
+        return nS.value
+
+    def emit_reads(self, data, start, length, text, rec, spans=None, keep=None, min_len=0, out_format=CFRK_TEXT_FASTA):
+        """-> bytes: the reads select_reads() would keep, trimmed to their spans, as FASTA or FASTQ text (out_format) in
+        input order, named as in `text` (the text they were parsed from) and, as FASTQ, with the matching slice of
+        their quality line; rec = index_text(text, its format).  A span outside its read, a record outside the text and
+        FASTQ output without a quality line as long as the read raise CfrkError (CFRK_ERR_LAYOUT).  Needs no job."""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        text = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+        rec = np.ascontiguousarray(rec, TEXT_RECORD_DTYPE)
+        nS = len(length)
+        if len(start) != nS or len(rec) != nS:
+            raise ValueError("start, length and rec differ in size")
+        if spans is not None:
+            spans = np.ascontiguousarray(spans, READ_SPAN_DTYPE)
+            if len(spans) != nS:
+                raise ValueError("one span per read")
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
+            if len(keep) != nS:
+                raise ValueError("one keep byte per read")
+        nb, ns = C.c_uint64(), C.c_int64()
+        head = (self._h, _ptr(data), _ptr(start), _ptr(length), len(data), nS, _ptr(spans), _ptr(keep), int(min_len),
+                _ptr(text), text.size, _ptr(rec), int(out_format))
+        rc = self._L.cfrk_reads_emit_text(*head, None, 0, C.byref(nb), C.byref(ns))
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.check(rc, "cfrk_reads_emit_text")
+            return b""
+        out = np.empty(nb.value, np.uint8)
+        self.check(self._L.cfrk_reads_emit_text(*head, _ptr(out), out.size, C.byref(nb), C.byref(ns)), "cfrk_reads_emit_text")
+        return out.tobytes()
+
+    def emit_reads_device(self, d_data, d_start, d_length, nN, nS, d_span, d_keep, min_len, d_text, nbytes, d_rec,
+                          out_format, d_out, cap_out):
+        """device form -> (bytes of text, reads written); d_span 0: whole reads, d_keep 0: all; d_out may be 0 with
+        capacity 0 (sizes only) and must not overlap the input.  Raises CfrkError (code CFRK_ERR_SMALL_BUF, with
+        .nbytes and .nS set, nothing written) when d_out is too small.  Synchronises once, returns with the copy
+        enqueued on the context stream."""
+        nb, ns = C.c_uint64(), C.c_int64()
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_reads_emit_text_device(self._h, vp(d_data), vp(d_start), vp(d_length), nN, nS, vp(d_span), vp(d_keep),
+                                                 int(min_len), vp(d_text), nbytes, vp(d_rec), int(out_format), vp(d_out),
+                                                 cap_out, C.byref(nb), C.byref(ns))
+        try:
+            self.check(rc, "cfrk_reads_emit_text_device")
+        except CfrkError as e:
+            e.nbytes, e.nS = nb.value, ns.value
+            raise
+        return nb.value, ns.value
 
     def synth_reads_device(self, r0, R, L, Glen, d_data, d_start=None, d_length=None,
                            seedG=1, seedR=2, seedS=3, uniform=False):

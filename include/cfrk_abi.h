@@ -492,6 +492,91 @@ int cfrk_reads_select(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, c
                       int32_t *length_out, int64_t *index_out, uint64_t cap_reads,
                       int64_t *nN_out, int64_t *nS_out);
 
+/* ---- text out: the record index of a text, and the kept reads written back as FASTA / FASTQ text ---------------- */
+
+/* The parsers keep no names and no qualities.  The INDEX of a text says where each record's header line and quality
+ * line lie in it; the EMITTER writes kept (and trimmed) reads back out as text with their original names and the
+ * matching slice of their quality line.  Text stays on the device from file to filtered file.
+ *
+ * Index.  Defined for EVERY text, not only for the texts a parser accepts: it validates no grammar.
+ * Lines (both formats, the FASTQ grammar above): a line ends at '\n' or at the text's end; a trailing '\n' opens no
+ *   line; a line's length excludes its '\n' and one '\r' directly in front of that '\n', or one '\r' that is the
+ *   text's last byte.  Lines and records are numbered from 0.
+ * CFRK_TEXT_FASTA: record r is the r-th line whose first byte is '>' (lines in front of the first header belong to no
+ *   record); qual_off = -1, qual_len = 0.  The record numbering of cfrk_fasta_parse_device, in both of its modes.
+ * CFRK_TEXT_FASTQ: nS = (number of lines) / 4, rounded down; record r's header is line 4r and its quality line is line
+ *   4r + 3, whatever bytes they begin with; an empty line has length 0 and the offset at which it would begin.  For a
+ *   text cfrk_fastq_parse_device accepts this is its numbering, and qual_len == length[r].
+ * CFRK_ERR_LAYOUT: a header or quality line of more than 2^31 - 1 bytes (cfrk_last_error names the record; only a text
+ *   of 2^31 bytes or more can hold one, and only for such a text does the call wait at its end as well).
+ * CFRK_ERR_ARG: a format other than the two, a NULL size output, a NULL text with nbytes > 0, a NULL array with
+ *   cap_reads > 0.  CFRK_ERR_ALIGN: d_text not 16-byte aligned.  Empty text: nS = 0.
+ * Capacities: cap_reads = (nbytes + 1) / 2 (FASTA) and (nbytes + 1) / 4 (FASTQ: four lines take at least three '\n')
+ *   always suffice; for a text its parser accepts, so does the parser's bound.  When nS > cap_reads the call returns CFRK_ERR_SMALL_BUF with *nS_out complete and
+ *   nothing written; a NULL array with capacity 0 is that "sizes only" call.
+ * Device form: a tile reduce, a one-workgroup scan of the tile aggregates in blocks of CFRK_TEXT_SCAN_TILES and a
+ *   scatter, as separate launches on the context stream (no workgroup waits for another one; the work per thread is
+ *   bounded whatever the text holds).  The thread on a line's closing '\n' (or on the text's last byte) writes the
+ *   line's fields; the line may have begun any number of tiles before, so the scan carries the start of the line that
+ *   is open at a tile's beginning, whether that line is a header (FASTA) and the count that numbers the records (FASTQ:
+ *   newlines, FASTA: header lines).  It synchronises ONCE, for nS, and returns with the scatter enqueued.  Temporary
+ *   device memory, kept in the context's pool: 64 bytes + 24 bytes per tile of CFRK_TEXT_TILE_BYTES.
+ * Host form: host text in, host records out; stages through the pool; synchronous.
+ *
+ * Emitter.  Read i is KEPT by exactly the rule of cfrk_reads_select (keep, span inside the read, min_len; span NULL =
+ * whole reads); its name and qualities come from rec[i], the index of the text the reads were parsed from (nS entries).
+ * Output, the kept reads in input order:
+ *   CFRK_TEXT_FASTA   '>' name '\n' bases '\n'
+ *   CFRK_TEXT_FASTQ   '@' name '\n' bases "\n+\n" quals '\n'
+ *   name  = the header line without its first byte: head_len - 1 bytes from head_off + 1 (nothing when head_len is 0),
+ *           copied verbatim;  bases = the span's codes as ACGT, N for any other code (cfrk_host_format_fasta's rule: a
+ *           base masked by min_qual reads N);  quals = text[qual_off + span.offset .. + span.length), copied verbatim.
+ *   *nbytes_out = bytes of text, *nS_out = reads written.
+ * Capacities: when *nbytes_out > cap_out the call returns CFRK_ERR_SMALL_BUF with both sizes complete and nothing
+ *   written; NULL with capacity 0 is the "sizes only" call.  d_out must not overlap the inputs.
+ * A record's header range is [head_off, head_off + head_len), its quality range [qual_off, qual_off + qual_len); the
+ *   pair {-1, 0} (what the FASTA index writes) stands for "no quality line" and is a valid quality range.
+ * Device form: checks nothing and never reads or writes outside its buffers.  In addition to the select's silent
+ *   drops, a read is dropped when its record's header or quality range does not lie inside [0, nbytes] (a negative
+ *   field included), or when the output is FASTQ and the record has no quality line or qual_len != length[i].
+ *   A per-read measure pass reduced per tile of CFRK_SELECT_TILE_READS reads, a one-workgroup scan in blocks of
+ *   CFRK_SELECT_SCAN_TILES, a pass that writes each kept read's output offset and input index (8 + 8 bytes per kept
+ *   read in the pool), and the copy, balanced by OUTPUT bytes: one workgroup per CFRK_EMIT_TILE_BYTES of d_out finds the
+ *   reads that meet its tile by a search in the output offsets, gathers name bytes, translated codes, literal bytes and
+ *   quality bytes through LDS and writes whole 16-byte blocks.  It synchronises ONCE, for the sizes, and returns with
+ *   the copy enqueued.  No alignment requirement on any byte array.
+ * Host form: refuses all of the above with CFRK_ERR_LAYOUT (cfrk_last_error names the read), for every read whatever
+ *   its keep byte; checks start / length like cfrk_global_add; stages through the pool; synchronous.
+ * CFRK_ERR_ARG: as the select (negative sizes or min_len, NULL size outputs, NULL start / length with nS > 0, NULL data
+ *   with nN > 0, NULL output with a capacity above 0), an out_format other than the two, a NULL rec with nS > 0, a NULL
+ *   text with nbytes > 0.  nS = 0 is fine.
+ * None of the four calls needs a global job or touches one that is open on the same context. */
+#define CFRK_TEXT_FASTA 0
+#define CFRK_TEXT_FASTQ 1
+#define CFRK_TEXT_TILE_BYTES 16384
+#define CFRK_TEXT_SCAN_TILES 1024
+#define CFRK_EMIT_TILE_BYTES 16384
+typedef struct cfrk_text_record {   /* 24 bytes, no padding */
+  int64_t head_off;   /* offset in the text of the header line's first byte (its '>' / '@')        */
+  int64_t qual_off;   /* FASTQ: offset of the quality line's first byte; FASTA: -1                 */
+  int32_t head_len;   /* bytes of the header line, marker included, line end excluded              */
+  int32_t qual_len;   /* FASTQ: bytes of the quality line, line end excluded; FASTA: 0             */
+} cfrk_text_record;
+int cfrk_text_index_device(cfrk_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, int format,
+                           cfrk_text_record *d_rec, uint64_t cap_reads, int64_t *nS_out);
+int cfrk_text_index(cfrk_ctx *ctx, const char *text, uint64_t nbytes, int format,
+                    cfrk_text_record *rec, uint64_t cap_reads, int64_t *nS_out);
+int cfrk_reads_emit_text_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                int64_t nN, int64_t nS, const cfrk_read_span *d_span, const uint8_t *d_keep,
+                                int32_t min_len, const uint8_t *d_text, uint64_t nbytes,
+                                const cfrk_text_record *d_rec, int out_format, uint8_t *d_out, uint64_t cap_out,
+                                uint64_t *nbytes_out, int64_t *nS_out);
+int cfrk_reads_emit_text(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
+                         int64_t nN, int64_t nS, const cfrk_read_span *span, const uint8_t *keep,
+                         int32_t min_len, const char *text, uint64_t nbytes,
+                         const cfrk_text_record *rec, int out_format, char *out, uint64_t cap_out,
+                         uint64_t *nbytes_out, int64_t *nS_out);
+
 /* Unsorted export into device buffers, grouped into `parts` contiguous segments by
  * owner(key) = (mix(key) >> 32) % parts (key-owner partition for the multi-GPU
  * merge).  part_counts (host, `parts` entries) receives the segment sizes.  Synchronises. */
