@@ -134,6 +134,8 @@ __device__ __forceinline__ void l1_put(const MspView &v, uint32_t reg, uint32_t 
 // so that every record is expanded once (msp2.hip does the same; SUB_BITS: msp_shared.h).  2 KB more staging per
 // wave: two workgroups per CU instead of three.
 #define P1_MARK(text) asm volatile("; " text)
+// the same for the parts of the leaf kernel's scan of the complete stream (p3_body, phase 1a; tools/p3_isa_account.py)
+#define P3_MARK(text) asm volatile("; " text)
 template <int P1B_TR, bool SUB = false>
 struct P1Lds {
   static constexpr int STAGE = 4096 + 3 * 512 + P1B_TR * 128 + (SUB ? 2048 : 0);     // bytes of staging per wave
@@ -872,10 +874,13 @@ __device__ __forceinline__ uint32_t rtab_diff(uint4 e, uint4 rec) {
 // The record table of the ordinary path is keyed by the record's FIRST k-mer: a truncated run that
 // is a prefix of a complete run shares it, so it finds its complete twin by probing from the same
 // slot (a suffix is a prefix of the other strand's twin after a reverse complement).
-__device__ __forceinline__ uint32_t rtab_slot_k(uint4 rec, int k, int log_slots) {
+__device__ __forceinline__ uint32_t rtab_prod_k(uint4 rec, int k) {
   const uint32_t y = (k >= 32) ? rec.y : (rec.y & ~(0xFFFFFFFFu >> (2 * k - 32)));   // 16 <= k: the top 2k-32 bits of y
   const uint32_t t = rec.x ^ __builtin_amdgcn_alignbit(y, y, 11);
-  return (t * 0x9E3779B1u) >> (32 - log_slots);
+  return t * 0x9E3779B1u;
+}
+__device__ __forceinline__ uint32_t rtab_slot_k(uint4 rec, int k, int log_slots) {
+  return rtab_prod_k(rec, k) >> (32 - log_slots);
 }
 // do the first `len` bases (32 <= 2*len <= 96 bits) of two records agree?
 __device__ __forceinline__ bool rec_prefix_equal(uint4 e, uint4 r, int len) {
@@ -1183,7 +1188,7 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
   // record table, and every copy of such a run (~50 each at C3's depth) took the slow path: compaction
   // across the wave plus the probe loop -- there is such a record in nearly every wave-step.  While the
   // stream is scanned the k-mer table's memory is idle: it holds a direct-mapped cache of DC entries
-  // (same entry format, own hash) in which a displaced run is installed by the probe loop that placed or
+  // (same entry format; its slot: other bits of the slot hash's product, dc_slot below) in which a displaced run is installed by the probe loop that placed or
   // found it.  A record that misses its home slot looks there next (one more LDS read) and counts in the
   // cache entry; after the scan the cache's counts are added to the table's entries and the memory
   // becomes the k-mer table.  Only first sightings and cache conflicts still take the slow path.
@@ -1247,21 +1252,27 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
     uint32_t Lh = 0;
     int c = 0;                       // wave-uniform
     const bool weighted = !SHARED && (mode & P3_WEIGHTED) != 0u;   // (an owner's leaves are never shared)
-    auto dc_slot = [&](const uint4 rec) {
-      const uint32_t t_ = rec.y ^ __builtin_amdgcn_alignbit(rec.x, rec.x, 7) ^ __builtin_amdgcn_alignbit(rec.z, rec.z, 19) ^ ((rec.w & 63u) << 25);
-      return __umulhi(t_ * 0x85EBCA77u, (uint32_t)DC);
-    };
-    auto drain = [&](int cnt) {
+    // the cache slot comes from the product the home slot is the top bits of (p = rtab_prod_k): the RT_LOG + 2 bits
+    // below them, scaled to the DC = 3/4 * 4096 entries -- three full-rate instructions, where a hash of its own over
+    // the whole record was nine with two multiplies.  Runs with one first k-mer share a cache slot (the compare is
+    // exact; the second comer takes the slow path as any conflict does).
+    static_assert(DC == 3 << RT_LOG, "dc_slot scales RT_LOG + 2 bits by 3/4");
+    auto dc_slot = [&](uint32_t p) { return (((p >> (30 - 2 * RT_LOG)) & (4u * RT - 1u)) * 3u) >> 2; };
+    // FAST: the scan of the headline case (below) -- table, mask, trips and increment are constants there
+    auto drain = [&](auto fast_, int cnt) {
+      constexpr bool FAST = decltype(fast_)::value;
+      P3_MARK("P3_PART_DRAIN");
       uint32_t h = Lh | ((lane < cnt) ? 0u : RT_DONE);
-      rtab_insert_loop(tab, L, h, tab_mask, tab_trips, weighted ? ((L.w >> 6) << 6) : (1u << 6));
+      if (FAST) rtab_insert_loop(rtab, L, h);
+      else rtab_insert_loop(tab, L, h, tab_mask, tab_trips, weighted ? ((L.w >> 6) << 6) : (1u << 6));
       // no room in the record table: a leaf with more distinct runs than it holds (low coverage
       // of a large genome).  Dedupe is pointless there: the whole leaf is counted from its streams.
       if ((int32_t)h >= 0) rt_fail = 1u;
       // a record that ended up away from its home slot goes into the cache (count 0: what the table's entry
       // holds stays there), so that its next copies find it with one look instead of coming through here
-      if (use_cache && lane < cnt && (int32_t)h < 0 && ((h ^ Lh) & tab_mask) != 0u) {
+      if ((FAST || use_cache) && lane < cnt && (int32_t)h < 0 && ((h ^ Lh) & (FAST ? (uint32_t)(RT - 1) : tab_mask)) != 0u) {
         uint32_t *dmeta = reinterpret_cast<uint32_t *>(dcache);
-        const uint32_t cs = dc_slot(L);
+        const uint32_t cs = dc_slot(rtab_prod_k(L, k));
         if (atomicCAS(&dmeta[4 * cs + 3], RT_EMPTY, RT_LOCK) == RT_EMPTY) {
           dmeta[4 * cs + 0] = L.x; dmeta[4 * cs + 1] = L.y; dmeta[4 * cs + 2] = L.z;
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1269,15 +1280,29 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
         }
       }
     };
+    // the lanes of `mask` (= __ballot(left)) hand their record and home slot to the wave's leftover set
+    auto leftover = [&](auto fast_, const uint4 rec, uint32_t h, bool left, unsigned long long mask) {
+      P3_MARK("P3_PART_APPEND");
+      const int n = __popcll(mask);
+      if (c + n > 64) { drain(fast_, c); c = 0; }
+      uint32_t set[5] = {L.x, L.y, L.z, L.w, Lh};
+      const uint32_t mine_[5] = {rec.x, rec.y, rec.z, rec.w, h};
+      wave_append<5>(set, mine_, left, mask, c, n);
+      L = make_uint4(set[0], set[1], set[2], set[3]); Lh = set[4];
+      c = __builtin_amdgcn_readfirstlane(c + n);             // (uniform: the compiler keeps it in a scalar register)
+    };
     auto home = [&](const uint4 rec, bool valid) {
-      const uint32_t h = big_first ? rtab_slot(rec, tab_log) : rtab_slot_k(rec, k, tab_log);
+      P3_MARK("P3_PART_HOME");
+      const uint32_t p = rtab_prod_k(rec, k);
+      const uint32_t h = big_first ? rtab_slot(rec, tab_log) : (p >> (32 - RT_LOG));
       const uint4 e = tab[h];
       const bool match = valid && rtab_diff(e, rec) == 0u;
       if (match) atomicAdd(&rmeta[4 * h + 3], weighted ? ((rec.w >> 6) << 6) : (1u << 6));
       bool left = valid && !match;
       if (use_cache && __ballot(left)) {
+        P3_MARK("P3_PART_CACHE");
         uint32_t *dmeta = reinterpret_cast<uint32_t *>(dcache);
-        const uint32_t cs = dc_slot(rec);
+        const uint32_t cs = dc_slot(p);
         const uint4 ce = dcache[cs];
         const bool chit = left && rtab_diff(ce, rec) == 0u;
         if (chit) atomicAdd(&dmeta[4 * cs + 3], weighted ? ((rec.w >> 6) << 6) : (1u << 6));
@@ -1285,15 +1310,62 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
       }
       const unsigned long long mask = __ballot(left);
       if (mask == 0ull) return;
-      const int n = __popcll(mask);
-      if (c + n > 64) { drain(c); c = 0; }
-      uint32_t set[5] = {L.x, L.y, L.z, L.w, Lh};
-      const uint32_t mine_[5] = {rec.x, rec.y, rec.z, rec.w, h};
-      wave_append<5>(set, mine_, left, mask, c, n);
-      L = make_uint4(set[0], set[1], set[2], set[3]); Lh = set[4];
-      c += n;
+      leftover(std::false_type{}, rec, h, left, mask);
     };
-    if (!SHARED) {
+    // THE CASE THE HEADLINE WORKLOAD RUNS -- reads counted on one GPU at k >= 28, or a leaf too small for the pool-wide
+    // table: multiplicity 1, the 1024-slot table, cache on -- has a scan of its own.  Table, mask and increment are
+    // constants; the cache entry is read NEXT TO the table's entry (at load 0.3 some lane of the wave needs it in nearly
+    // every step: the look is no longer a second round trip behind a ballot), and the one lane-wise add goes to
+    // whichever of the two matched.  FULL: every lane holds a record (the main loop; the tail is peeled).
+    [[maybe_unused]] auto home_fast = [&](auto full_, const uint4 rec, bool valid) {
+      constexpr bool FULL = decltype(full_)::value;
+      constexpr uint32_t RT_W0 = 4u * (uint32_t)DC;            // the record table's first word in the pool
+      uint32_t *const pmeta = reinterpret_cast<uint32_t *>(pool);
+      P3_MARK("P3_PART_HOME");
+      const uint32_t p = rtab_prod_k(rec, k);
+      const uint32_t h = p >> (32 - RT_LOG), cs = dc_slot(p);
+      const uint4 e = rtab[h];
+      const uint4 ce = dcache[cs];
+      const uint32_t d0 = rtab_diff(e, rec);
+      P3_MARK("P3_PART_CACHE");
+      const uint32_t d1 = rtab_diff(ce, rec);
+      // no branch around the add: a lane without a hit adds 0 (as rtab_insert_loop does) -- exec-mask bookkeeping is
+      // scalar issue slots in every step, the add of 0 costs nothing the other lanes' add does not pay already
+      const bool match = d0 == 0u, hit = min(d0, d1) == 0u;   // (never both: a run is cached because it is NOT in its home slot)
+      const bool take = FULL ? hit : (valid && hit);
+      atomicAdd(&pmeta[match ? (RT_W0 + 4u * h + 3u) : (4u * cs + 3u)], take ? (1u << 6) : 0u);
+      const bool left = FULL ? !hit : (valid && !hit);
+      const unsigned long long mask = __ballot(left);
+      if (mask == 0ull) return;
+      leftover(std::true_type{}, rec, h, left, mask);
+    };
+    bool fast = false;
+    if constexpr (!SHARED && !LISTS) fast = !weighted && !big_first && !(v.dbg & CFRK_ABL_P3_NO_RTAB);
+    if (fast) {
+      if constexpr (!SHARED && !LISTS) {
+        const uint32_t n32 = (uint32_t)n1a;                    // (< HUGE_LEAF)
+        uint32_t wb = __builtin_amdgcn_readfirstlane((uint32_t)(tid - lane));   // the wave's first record: a scalar
+        P3_MARK("P3_PART_LOAD");
+        for (; wb + (uint32_t)P3_THREADS + 64u <= n32; wb += 2u * P3_THREADS) {
+          const uint4 rec0 = src[wb + lane], rec1 = src[wb + P3_THREADS + lane];
+          home_fast(std::true_type{}, rec0, true);
+          home_fast(std::true_type{}, rec1, true);
+          P3_MARK("P3_PART_LOAD");
+        }
+        // the tail: at most two wave-steps, the only ones with lanes past the end
+#pragma unroll 1
+        for (int u = 0; u < 2 && wb < n32; ++u, wb += P3_THREADS) {
+          const bool vv = wb + lane < n32;
+          uint4 rec = zero4;
+          if (vv) rec = src[wb + lane];
+          home_fast(std::false_type{}, rec, vv);
+          P3_MARK("P3_PART_LOAD");
+        }
+        if (c) drain(std::true_type{}, c);
+        c = 0;
+      }
+    } else if (!SHARED) {
+      P3_MARK("P3_PART_LOAD");
       for (uint64_t r = tid; r < ((n1a + 63) & ~63ull) && !(v.dbg & CFRK_ABL_P3_NO_RTAB); r += 2ull * P3_THREADS) {
         const uint64_t r1 = r + P3_THREADS;
         const bool v0 = r < n1a, v1 = r1 < n1a;
@@ -1302,6 +1374,7 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
         if (v1) rec1 = LISTS ? ld_c(r1) : src[r1];
         home(rec0, v0);
         home(rec1, v1);
+        P3_MARK("P3_PART_LOAD");
       }
     } else {
       // a shared leaf: most records read here are another workgroup's.  The one lane in 2^sub_bits that
@@ -1320,6 +1393,7 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
         Cr = make_uint4(set[0], set[1], set[2], set[3]);
         cc += n;
       };
+      P3_MARK("P3_PART_LOAD");
       for (uint64_t r = tid; r < ((n1a + 63) & ~63ull); r += 2ull * P3_THREADS) {
         const uint64_t r1 = r + P3_THREADS;
         const bool v0 = r < n1a, v1 = r1 < n1a;
@@ -1328,12 +1402,14 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
         if (v1) rec1 = src[r1];
         cfeed(rec0, v0 && mine(rec0.w));
         if (r1 < ((n1a + 63) & ~63ull)) cfeed(rec1, v1 && mine(rec1.w));       // (wave-uniform)
+        P3_MARK("P3_PART_LOAD");
       }
       if (cc) home(Cr, lane < cc);
     }
-    if (c) drain(c);
+    if (c) drain(std::false_type{}, c);
     if ((v.dbg & CFRK_DEBUG_FORCE_RT_OVERFLOW) && !big_first) rt_fail = 1u;
   }
+  P3_MARK("P3_PART_MERGE");
   __syncthreads();
   if (use_cache) {
     // the cache's counts go to the table's entries (the run is there: it was placed before it was cached;
@@ -1355,6 +1431,7 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
       for (int s = tid; s < TS; s += P3_THREADS) { keys[s] = CFRK_EMPTY_KEY; cnts[s] = 0; }
     __syncthreads();
   }
+  P3_MARK("P3_PART_END");
   // ---- phase 2: k-mer by k-mer -- every distinct complete record of the record table (weight =
   //      its multiplicity) and the truncated runs (weight 1).  Both are first listed SORTED BY
   //      LENGTH (counting sort of 16-bit indices in LDS): a wave expands 64 records in lock-step
