@@ -1791,6 +1791,59 @@ __global__ __launch_bounds__(P3_THREADS) void msp_merge_kernel(const uint64_t *_
   });
 }
 
+// ---------------------------------------------------------------------------- multi-GPU by runs
+// Strong scaling: with the reads split over N ranks every rank still meets almost every locus, so
+// counting on every rank and exchanging (key, count) lists (above) makes each rank expand every
+// distinct run and ship ~D entries -- neither shrinks with N.  Here a rank only partitions and
+// deduplicates (P1, P2, the leaf kernel in P3_EXPORT mode) and ships, per leaf, its distinct
+// complete runs with multiplicities plus its truncated runs to the leaf's owner
+// (owner(leaf) = leaf % parts); the owner lines the N lists of each of its leaves up as that
+// leaf's streams and runs the ordinary leaf kernel on them (P3_WEIGHTED): expansion and counting
+// happen once, for 1/N of the leaves.
+
+// The record format as the stages of the exchange see it (msp_runs.h): 16-byte records, one row of the packed buffer
+// each; stream class 1 of a leaf holds its complete runs, class 0 its truncated ones; header word w, a note parks in x.
+struct RunsFmt1 {
+  typedef uint4 Rec;
+  typedef MspView View;
+  static constexpr int ROWS = 1, NC = NCLS, COMPLETE = 1;
+  static constexpr uint32_t EMPTY = RT_EMPTY, DONE = RT_DONE;
+  // (a note names a list position in 11 bits; every position of the 1024-slot record table fits: no limit to test)
+  static_assert((((uint32_t)RT - 1u) << 5 | 31u) < RUNS_NO_NOTE, "every list position fits a note that never equals the padding value");
+  static __device__ __forceinline__ uint32_t note_pos_max(uint32_t /* dbg */) { return ~0u; }
+  static __device__ __forceinline__ uint32_t count(const MspView &v, uint32_t leaf, int cl) {
+    return (uint32_t)min((uint64_t)v.cnt2[NCLS * leaf + cl], v.exact ? (uint64_t)v.lcap[NCLS * leaf + cl] : (cl == 1 ? v.cap2c : v.cap2t));
+  }
+  static __device__ __forceinline__ uint4 *stream(const MspView &v, uint32_t leaf, int cl) {
+    if (v.exact) return v.rec2 + v.lbase[NCLS * leaf + cl];
+    return v.rec2 + (uint64_t)(leaf >> v.sel_bits) * (v.cap2c + v.cap2t) + (cl == 1 ? 0ull : v.cap2c);
+  }
+  struct Trunc {                                   // the n truncated runs of a leaf
+    uint4 *s; uint64_t n;
+    __device__ __forceinline__ uint4 *at(uint64_t g) const { return s + g; }
+  };
+  static __device__ __forceinline__ Trunc trunc(const MspView &v, uint32_t leaf) { return Trunc{stream(v, leaf, 0), count(v, leaf, 0)}; }
+  static __device__ __forceinline__ uint32_t hdr(uint4 r) { return r.w; }
+  static __device__ __forceinline__ void set_hdr(uint4 *q, uint32_t w) { q->w = w; }
+  static __device__ __forceinline__ uint32_t note(uint4 r) { return r.x; }
+  static __device__ __forceinline__ void set_note(uint4 *q, uint32_t note) { q->x = note; q->w = RUN_NOTED; }
+  static __device__ __forceinline__ uint32_t slot(uint4 rec, int k, int log) { return rtab_slot_k(rec, k, log); }
+  static __device__ __forceinline__ uint4 revcomp(uint4 rec, int len) { return revcomp_record(rec, len); }
+  static __device__ __forceinline__ bool prefix_equal(uint4 e, uint4 rec, int len) { return rec_prefix_equal(e, rec, len); }
+  // the first len bases of a twin under a header of their own
+  static __device__ __forceinline__ uint4 prefix(uint4 twin, int len, uint32_t w) {
+    const int rb = 2 * len - 32;                                      // bits of the run beyond the first word: 0 .. 64
+    const uint32_t my = (rb >= 32) ? 0xFFFFFFFFu : ~(0xFFFFFFFFu >> rb);
+    const uint32_t mz = (rb <= 32) ? 0u : ((rb >= 64) ? 0xFFFFFFFFu : ~(0xFFFFFFFFu >> (rb - 32)));
+    return make_uint4(twin.x, twin.y & my, twin.z & mz, w);
+  }
+  static __device__ __forceinline__ uint4 zero() { return make_uint4(0u, 0u, 0u, 0u); }
+  static __device__ __forceinline__ uint4 load(const uint4 *q) { return *q; }
+  static __device__ __forceinline__ void store(uint4 *q, uint4 r) { *q = r; }
+  static __device__ __forceinline__ uint4 load_row(const uint4 *rows, uint64_t i) { return rows[i]; }
+  static __device__ __forceinline__ void store_row(uint4 *rows, uint64_t i, uint4 r) { rows[i] = r; }
+};
+
 // The exporting side of the runs exchange needs none of the leaf kernel's k-mer machinery: a small
 // workgroup per leaf (256 threads, 16 KB of LDS: eight or more per CU) deduplicates the leaf's
 // complete runs in the 1024-entry record table and leaves the distinct ones, header word =
@@ -1799,22 +1852,21 @@ __global__ __launch_bounds__(P3_THREADS) void msp_merge_kernel(const uint64_t *_
 // A leaf with more distinct runs than the table holds leaves as it is (multiplicity 1 each): the
 // owner's table merges what can be merged.
 // Truncated runs (read ends: two per read, each unique -- most of what a rank would ship) are then
-// looked up in the same table, exactly as the leaf kernel anchors them: one that is a prefix of a
-// distinct complete run of this rank (a suffix, read on the other strand; canonical counting only)
-// is replaced by a 16-bit NOTE, position of that run in the leaf's list << 5 | n-1.  The owner
-// rebuilds the run from its twin.  A noted record is marked in place (w = RUN_NOTED, x = the note);
-// leaf_off[leaf] = how many were noted.
+// looked up in the same table (runs_find_twin): one that is a prefix of a distinct complete run of
+// this rank is replaced by a 16-bit NOTE.  The owner rebuilds the run from its twin.  A noted record
+// is marked in place (w = RUN_NOTED, x = the note); leaf_off[leaf] = how many were noted.
 constexpr int DX_THREADS = 256, DX_INFL = 4;
 __global__ __launch_bounds__(DX_THREADS) void msp_dedupe_export_kernel(int k, int canon, MspView v) {
+  typedef RunsFmt1 F;
   __shared__ uint4 rtab[RT];
   __shared__ uint16_t sidx[RT];                    // record-table slot -> position in the leaf's list
   __shared__ uint32_t wsum[DX_THREADS / 64];
   __shared__ uint32_t rt_fail, noted;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const uint32_t leaf = blockIdx.x;
-  const uint64_t n1 = min((uint64_t)v.cnt2[NCLS * leaf + 1], v.exact ? (uint64_t)v.lcap[NCLS * leaf + 1] : v.cap2c);
+  const uint64_t n1 = F::count(v, leaf, 1);
   if (n1 == 0) return;
-  uint4 *const stream = v.exact ? v.rec2 + v.lbase[NCLS * leaf + 1] : v.rec2 + (uint64_t)(leaf >> v.sel_bits) * (v.cap2c + v.cap2t);
+  uint4 *const stream = F::stream(v, leaf, 1);
   for (int s = tid; s < RT; s += DX_THREADS) rtab[s] = make_uint4(0u, 0u, 0u, RT_EMPTY);
   // (a leaf of 2^19 complete runs or more leaves undeduplicated: see HUGE_LEAF)
   const bool too_many = n1 >= HUGE_LEAF_SENDER;
@@ -1868,73 +1920,20 @@ __global__ __launch_bounds__(DX_THREADS) void msp_dedupe_export_kernel(int k, in
   uint32_t nd;
   if (rt_fail) {
     // (every record was read before the barrier; the rewrite touches the header word only)
-    for (uint64_t i = tid; i < n1; i += DX_THREADS) stream[i].w = (1u << 6) | (stream[i].w & 63u);
+    for (uint64_t i = tid; i < n1; i += DX_THREADS) F::set_hdr(&stream[i], (1u << 6) | (F::hdr(stream[i]) & 63u));
     nd = (uint32_t)n1;
   } else {
-    // occupied slots -> head of the stream (four slots per thread)
-    // (two passes over LDS: an array of entries would live in scratch memory)
+    // occupied slots -> head of the stream (four slots per thread), truncated runs -> notes
     constexpr int PER = RT / DX_THREADS;
     const uint32_t *meta = reinterpret_cast<const uint32_t *>(rtab);
-    uint32_t mine = 0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) mine += (meta[4 * (PER * tid + i) + 3] != RT_EMPTY) ? 1u : 0u;
-    uint32_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(incl, d);
-      if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
+    auto occupied = [&](uint32_t s) { return meta[4 * s + 3] != RT_EMPTY; };
+    auto get = [&](uint32_t s) { return rtab[s]; };
+    const uint32_t at0 = runs_rank_slots<DX_THREADS, PER>(sidx, wsum, occupied, &nd);
+    runs_emit_slots<PER>(at0, occupied, get, [&](uint32_t at, uint4 e) { stream[at] = e; });
     __syncthreads();
-    uint32_t base = 0, total = 0;
-    for (int w = 0; w < DX_THREADS / 64; ++w) { const uint32_t x = wsum[w]; base += (w < wave) ? x : 0u; total += x; }
-    uint32_t at = base + incl - mine;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const uint4 e = rtab[PER * tid + i];
-      sidx[PER * tid + i] = (uint16_t)at;
-      if (e.w != RT_EMPTY) stream[at++] = e;
-    }
-    nd = total;
-    __syncthreads();
-    // truncated runs -> notes (the lookup of the leaf kernel's anchoring, msp_p3_kernel)
-    const uint64_t nt = min((uint64_t)v.cnt2[NCLS * leaf + 0], v.exact ? (uint64_t)v.lcap[NCLS * leaf + 0] : v.cap2t);
-    uint4 *const trunc = v.exact ? v.rec2 + v.lbase[NCLS * leaf + 0] : stream + v.cap2c;
-    for (uint64_t g0 = 0; g0 < nt && !(v.dbg & CFRK_DEBUG_NO_ANCHORS); g0 += (uint64_t)DX_INFL * DX_THREADS) {
-      uint4 recs[DX_INFL];
-#pragma unroll
-      for (int u = 0; u < DX_INFL; ++u) {
-        const uint64_t g = g0 + (uint64_t)u * DX_THREADS + tid;
-        recs[u] = zero4;
-        if (g < nt) recs[u] = trunc[g];
-      }
-#pragma unroll
-      for (int u = 0; u < DX_INFL; ++u) {
-      const uint64_t g = g0 + (uint64_t)u * DX_THREADS + tid;
-      const bool valid = g < nt;
-      uint4 rec = recs[u];
-      const uint32_t nm1 = rec.w & 31u;
-      const bool lc = (rec.w & 64u) != 0u, rc_ = (rec.w & 128u) != 0u;
-      const bool suf = canon && valid && !lc && rc_;
-      if (suf) rec = revcomp_record(rec, (int)nm1 + k);
-      const bool anchored = suf || (valid && lc && !rc_);
-      uint32_t h = anchored ? rtab_slot_k(rec, k, RT_LOG) : RT_DONE;
-      uint32_t found = 0xFFFFFFFFu;
-      for (int it = 0; it < 32 && __ballot((int32_t)h >= 0); ++it) {
-        const bool p = (int32_t)h >= 0;
-        const uint32_t hh = h & (uint32_t)(RT - 1);
-        const uint4 e2 = rtab[hh];
-        const bool empty = e2.w == RT_EMPTY;
-        const bool hit = p && !empty && (e2.w & 31u) >= nm1 && rec_prefix_equal(e2, rec, (int)nm1 + k);
-        found = hit ? hh : found;
-        h = (p && !hit && !empty) ? ((hh + 1u) & (uint32_t)(RT - 1)) : (h | RT_DONE);
-      }
-      const bool hit = found != 0xFFFFFFFFu;
-      if (hit) { trunc[g].x = ((uint32_t)sidx[found] << 5) | nm1; trunc[g].w = RUN_NOTED; }
-      const unsigned long long hb = __ballot(hit);
-      if (lane == 0 && hb) atomicAdd(&noted, (uint32_t)__popcll(hb));
-      }
-    }
+    const F::Trunc tr = F::trunc(v, leaf);
+    runs_note_truncated<F, DX_THREADS, DX_INFL, RT_LOG>(tr, (v.dbg & CFRK_DEBUG_NO_ANCHORS) ? 0ull : tr.n, k, canon, sidx, F::note_pos_max(v.dbg), get, &noted,
+      [&](uint64_t g, bool, uint32_t note) { if (note != RUNS_NO_NOTE) F::set_note(tr.at(g), note); });
     __syncthreads();
   }
   if (tid == 0) { v.leaf_n[leaf] = nd; v.leaf_off[leaf] = noted; }
@@ -1943,17 +1942,12 @@ __global__ __launch_bounds__(DX_THREADS) void msp_dedupe_export_kernel(int k, in
 // ------------------------------------------------------------------- multi-GPU by runs, PIPELINED (round 5)
 // The sender's half of the pipelined exchange: deduplication AND packing in one kernel, one group of leaves at a
 // time, straight into the send buffer -- no rewrite of the streams, no sizes / plan / gather kernels, no host
-// round trip (the gather alone was 0.21 ms of a 5.1 ms critical path at N = 8).
-// The leaves of an owner are cut into `ngroups` ranges of local indices; group g of owner p has its segment at
-// rows [(g * parts + p) * seg_cap, ...) of the send buffer: header (row 0 = {rows used, leaves, first local leaf,
-// magic}, written by msp_runs_group_finish_kernel; then one uint4 {row offset, distinct, truncated, noted} per local
-// leaf) followed by the leaves' rows in the order their workgroups CLAIM them (one atomic on the segment's cursor
-// per leaf; the header says where each leaf went).  Only the used rows of a segment travel.
+// round trip (the gather alone was 0.21 ms of a 5.1 ms critical path at N = 8).  (Segments,
+// headers and the claim: msp_runs.h, RunsSend.)  Only the used rows of a segment travel.
 // A leaf's rows: [distinct complete runs, header word = multiplicity << 6 | n-1][truncated runs that found no twin]
-// [notes: 16 bits each, position of the twin in the leaf's list << 5 | n-1, eight per row, padded with 0xFFFF].
-// One workgroup per leaf, everything a thread needs of the complete stream in flight at once (DS_INFL loads: a
-// shard's leaf is ~2700 records); the truncated runs are looked up once, their verdict (note or record) waits in LDS
-// for the leaf's row count, then they are written from a second read that hits the L2.
+// [notes].  One workgroup per leaf, everything a thread needs of the complete stream in flight at once (DS_INFL
+// loads: a shard's leaf is ~2700 records); the truncated runs are looked up once, their verdict (note or record) waits
+// in LDS for the leaf's row count, then they are written from a second read that hits the L2.
 // SPLIT RECORD TABLE.  With 16-byte entries {bases x 3, meta} the count word of every slot sits in LDS bank 3 mod 4: a
 // wave's 64 ds_add on it land on 8 of the 32 banks and serialise 8 ways -- 62 % of this kernel's LDS-active cycles were
 // bank conflicts, the LDS was busy for 76 % of its time (profiles/r05/dedupe_send_pmc_before_split_table.txt).  Here the
@@ -1985,27 +1979,26 @@ __device__ __forceinline__ void ds_insert_loop(uint32_t *rb, uint32_t *rm, uint4
   }
 }
 __global__ __launch_bounds__(DS_THREADS) void msp_dedupe_send_kernel(int k, int canon, MspView v, RunsSend sg) {
+  typedef RunsFmt1 F;
   __shared__ uint32_t rb[3 * RT];                  // record table: the bases of slot s at rb[3 s .. 3 s + 2] ...
   __shared__ uint32_t rm[RT];                      // ... its meta word (count << 6 | n-1; RT_EMPTY, RT_LOCK) at rm[s]
   __shared__ uint16_t sidx[RT];                    // record-table slot -> position in the leaf's list
-  __shared__ uint16_t tres[DS_TCAP];               // truncated run g: its note, or 0xFFFF = travels as a record
+  __shared__ uint16_t tres[DS_TCAP];               // truncated run g: its note, or RUNS_NO_NOTE = travels as a record
   __shared__ uint32_t wsum[DS_THREADS / 64];
   __shared__ uint32_t rt_fail, noted, cu, cn, row0;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const uint32_t leaf = sg.leaf0 + blockIdx.x;
   const uint32_t own = leaf % (uint32_t)sg.parts, ll = leaf / (uint32_t)sg.parts;
   uint4 *const seg = sg.packed + (uint64_t)own * sg.seg_cap;
   const uint32_t hrows = 1u + sg.lcount;
   uint4 *const entry = seg + 1u + (ll - sg.ll0);
-  const uint64_t n1 = min((uint64_t)v.cnt2[NCLS * leaf + 1], v.exact ? (uint64_t)v.lcap[NCLS * leaf + 1] : v.cap2c);
-  const uint64_t nt64 = min((uint64_t)v.cnt2[NCLS * leaf + 0], v.exact ? (uint64_t)v.lcap[NCLS * leaf + 0] : v.cap2t);
-  if (n1 + nt64 == 0) { if (tid == 0) *entry = make_uint4(0u, 0u, 0u, 0u); return; }
-  const uint4 *const c1 = v.exact ? v.rec2 + v.lbase[NCLS * leaf + 1] : v.rec2 + (uint64_t)(leaf >> v.sel_bits) * (v.cap2c + v.cap2t);
-  const uint4 *const c0 = v.exact ? v.rec2 + v.lbase[NCLS * leaf + 0] : c1 + v.cap2c;
+  const uint64_t n1 = F::count(v, leaf, 1);
+  const F::Trunc tr = F::trunc(v, leaf);
+  if (n1 + tr.n == 0) { if (tid == 0) *entry = make_uint4(0u, 0u, 0u, 0u); return; }
+  const uint4 *const c1 = F::stream(v, leaf, 1);
   const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
-  // (a leaf of 2^19 complete runs or more leaves undeduplicated: see HUGE_LEAF; a row count beyond 32 bits cannot be claimed)
+  // (a leaf of 2^19 complete runs or more leaves undeduplicated: see HUGE_LEAF)
   const bool too_many = n1 >= HUGE_LEAF_SENDER;
-  const bool unclaimable = n1 + nt64 >= 0xFFFFFFFFull;
   // the first round of the complete stream is asked for before anything else is done
   uint4 recs[DS_INFL];
 #pragma unroll
@@ -2063,207 +2056,46 @@ __global__ __launch_bounds__(DS_THREADS) void msp_dedupe_send_kernel(int k, int 
   }
   __syncthreads();
   const bool plain = rt_fail != 0u;                 // no deduplication: every complete run leaves with multiplicity 1, no notes
-  const uint32_t nt = (uint32_t)min(nt64, (uint64_t)0xFFFFFFFFull);
-  uint32_t nd, at0 = 0;
+  const uint32_t nt = (uint32_t)min(tr.n, (uint64_t)0xFFFFFFFFull);
+  const bool anchors = !(v.dbg & CFRK_DEBUG_NO_ANCHORS);
+  uint32_t nd = (uint32_t)n1, at0 = 0;
   constexpr int PER = RT / DS_THREADS;
-  if (plain) {
-    nd = (uint32_t)min(n1, (uint64_t)0xFFFFFFFFull);
-  } else {
-    // occupied slots -> positions in the leaf's list (four slots per thread)
-    uint32_t mine = 0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) mine += (rm[PER * tid + i] != RT_EMPTY) ? 1u : 0u;
-    const uint32_t incl = dev_wave_scan_incl(mine);
-    if (lane == 63) wsum[wave] = incl;
+  auto occupied = [&](uint32_t s) { return rm[s] != RT_EMPTY; };
+  auto get = [&](uint32_t s) { return make_uint4(rb[3 * s], rb[3 * s + 1], rb[3 * s + 2], rm[s]); };
+  if (!plain) {
+    // occupied slots -> positions in the leaf's list (four slots per thread); then the first DS_TCAP truncated runs are
+    // looked up, their verdict waits in LDS
+    at0 = runs_rank_slots<DS_THREADS, PER>(sidx, wsum, occupied, &nd);
     __syncthreads();
-    uint32_t base = 0, total = 0;
-    for (int w = 0; w < DS_THREADS / 64; ++w) { const uint32_t x = wsum[w]; base += (w < wave) ? x : 0u; total += x; }
-    at0 = base + incl - mine;
-    uint32_t at = at0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      sidx[PER * tid + i] = (uint16_t)at;
-      if (rm[PER * tid + i] != RT_EMPTY) ++at;
-    }
-    nd = total;
-    __syncthreads();
-    // truncated runs: which of the first DS_TCAP are a prefix of a distinct complete run of this rank (a suffix, read on
-    // the other strand; canonical counting only)?  The verdict waits in LDS (the lookup of the leaf kernel's anchoring)
-    const uint32_t tlook = (v.dbg & CFRK_DEBUG_NO_ANCHORS) ? 0u : min(nt, (uint32_t)DS_TCAP);
-    for (uint32_t g0 = 0; g0 < tlook; g0 += DS_THREADS) {
-      const uint32_t g = g0 + tid;
-      const bool valid = g < tlook;
-      uint4 rec = zero4;
-      if (valid) rec = c0[g];
-      const uint32_t nm1 = rec.w & 31u;
-      const bool lc = (rec.w & 64u) != 0u, rc_ = (rec.w & 128u) != 0u;
-      const bool suf = canon && valid && !lc && rc_;
-      if (suf) rec = revcomp_record(rec, (int)nm1 + k);
-      const bool anchored = suf || (valid && lc && !rc_);
-      uint32_t h = anchored ? rtab_slot_k(rec, k, RT_LOG) : RT_DONE;
-      uint32_t found = 0xFFFFFFFFu;
-      for (int it = 0; it < 32 && __ballot((int32_t)h >= 0); ++it) {
-        const bool p = (int32_t)h >= 0;
-        const uint32_t hh = h & (uint32_t)(RT - 1);
-        const uint4 e2 = make_uint4(rb[3 * hh], rb[3 * hh + 1], rb[3 * hh + 2], rm[hh]);
-        const bool empty = e2.w == RT_EMPTY;
-        const bool hit = p && !empty && (e2.w & 31u) >= nm1 && rec_prefix_equal(e2, rec, (int)nm1 + k);
-        found = hit ? hh : found;
-        h = (p && !hit && !empty) ? ((hh + 1u) & (uint32_t)(RT - 1)) : (h | RT_DONE);
-      }
-      const bool hit = found != 0xFFFFFFFFu;
-      if (valid) tres[g] = hit ? (uint16_t)(((uint32_t)sidx[found] << 5) | nm1) : (uint16_t)0xFFFFu;
-      const unsigned long long hb = __ballot(hit);
-      if (lane == 0 && hb) atomicAdd(&noted, (uint32_t)__popcll(hb));
-    }
+    runs_note_truncated<F, DS_THREADS, 1, RT_LOG>(tr, anchors ? min(nt, (uint32_t)DS_TCAP) : 0u, k, canon, sidx, F::note_pos_max(v.dbg), get, &noted,
+      [&](uint64_t g, bool valid, uint32_t note) { if (valid) tres[g] = (uint16_t)note; });
     __syncthreads();
   }
   const uint32_t na = plain ? 0u : noted, nu = nt - na;
-  const uint64_t rows = (uint64_t)nd + nu + (na + NOTES_PER_ROW - 1) / NOTES_PER_ROW;
-  if (tid == 0) {
-    // one claim per leaf; a segment that runs out of room (or a flood that cannot be claimed at all) shows in its
-    // cursor -- used rows > seg_cap -- and the host takes the classic exchange instead
-    const uint32_t claim = unclaimable ? 0xFFFFFFFFu : (uint32_t)rows;
-    const uint32_t pos = atomicAdd(&sg.cursor[own], claim);
-    const bool fits = !unclaimable && (uint64_t)pos + rows <= sg.seg_cap - hrows && pos + claim >= pos;
-    if (!fits) atomicMax(&sg.cursor[own], 0xFFFFFFF0u);              // (stays "too many" whatever is added later)
-    *entry = fits ? make_uint4(pos, nd, nu, na) : make_uint4(0u, 0u, 0u, 0u);
-    row0 = fits ? pos : 0xFFFFFFFFu;
-  }
+  if (tid == 0) row0 = runs_claim_rows<F>(sg, own, entry, hrows, nd, nu, na);
   __syncthreads();
-  if (row0 == 0xFFFFFFFFu) return;
+  if (row0 == RUNS_NO_ROOM) return;
   uint4 *const dst = seg + hrows + row0;
-  if (plain) {
-    for (uint64_t i = tid; i < n1; i += DS_THREADS) { uint4 r = c1[i]; r.w = (1u << 6) | (r.w & 63u); dst[i] = r; }
-    for (uint32_t i = tid; i < nt; i += DS_THREADS) dst[nd + i] = c0[i];
-    return;
-  }
-  {
-    uint32_t at = at0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const uint32_t sl = PER * tid + i, m = rm[sl];
-      if (m != RT_EMPTY) dst[at++] = make_uint4(rb[3 * sl], rb[3 * sl + 1], rb[3 * sl + 2], m);
-    }
-  }
-  uint16_t *const notes = reinterpret_cast<uint16_t *>(dst + nd + nu);
-  for (uint32_t i = tid; i < ((nt + 63u) & ~63u); i += DS_THREADS) {
-    const bool valid = i < nt;
-    const uint32_t note = (valid && i < (uint32_t)DS_TCAP && !(v.dbg & CFRK_DEBUG_NO_ANCHORS)) ? (uint32_t)tres[i] : 0xFFFFu;
-    const bool isn = valid && note != 0xFFFFu;
-    const unsigned long long mn = __ballot(isn), mu = __ballot(valid && !isn);
-    uint32_t bn = 0, bu = 0;
-    if (lane == 0) {
-      if (mn) bn = atomicAdd(&cn, (uint32_t)__popcll(mn));
-      if (mu) bu = atomicAdd(&cu, (uint32_t)__popcll(mu));
-    }
-    bn = __shfl(bn, 0); bu = __shfl(bu, 0);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    if (isn) { const uint32_t at = bn + (uint32_t)__popcll(mn & below); if (at < na) notes[at] = (uint16_t)note; }
-    else if (valid) { const uint32_t at = bu + (uint32_t)__popcll(mu & below); if (at < nu) dst[nd + at] = c0[i]; }
-  }
-  const uint32_t pad = (NOTES_PER_ROW - na % NOTES_PER_ROW) % NOTES_PER_ROW;
-  if ((uint32_t)tid < pad) notes[na + tid] = 0xFFFFu;
+  if (plain) { runs_write_plain<F, DS_THREADS>(dst, c1, nd, tr, nt); return; }
+  runs_emit_slots<PER>(at0, occupied, get, [&](uint32_t at, uint4 e) { dst[at] = e; });
+  runs_split_truncated<F, false>(tr, nt, nu, na, dst + nd, &cu, &cn, DS_THREADS,
+    [&](uint32_t i, const uint4 &) { return (i < (uint32_t)DS_TCAP && anchors) ? (uint32_t)tres[i] : RUNS_NO_NOTE; });
 }
 
-// ---------------------------------------------------------------------------- multi-GPU by runs
-// Strong scaling: with the reads split over N ranks every rank still meets almost every locus, so
-// counting on every rank and exchanging (key, count) lists (above) makes each rank expand every
-// distinct run and ship ~D entries -- neither shrinks with N.  Here a rank only partitions and
-// deduplicates (P1, P2, the leaf kernel in P3_EXPORT mode) and ships, per leaf, its distinct
-// complete runs with multiplicities plus its truncated runs to the leaf's owner
-// (owner(leaf) = leaf % parts); the owner lines the N lists of each of its leaves up as that
-// leaf's streams and runs the ordinary leaf kernel on them (P3_WEIGHTED): expansion and counting
-// happen once, for 1/N of the leaves.
-
-// sender: what every leaf contributes -- n1 distinct complete runs, nt truncated runs as records, na as
-// notes, rows in all -- one thread per leaf, coalesced (the plan kernel below used to gather these
-// four words per leaf itself, three times over, 64 dependent strided loads per thread each time:
-// 0.50 ms of a 5.9 ms critical path at N = 8)
+// the shared kernels of the one-shot exchange (msp_runs.h) under the names the profiles know
 __global__ __launch_bounds__(256) void msp_runs_sizes_kernel(MspView v, uint4 *__restrict__ sz, unsigned long long *__restrict__ plan_sync) {
-  const uint32_t leaf = blockIdx.x * 256u + threadIdx.x;
-  if (leaf < 72u) plan_sync[leaf] = 0ull;                      // (the plan kernel's look-back words)
-  if (leaf >= (uint32_t)NLEAF) return;
-  uint32_t n1 = 0, na = 0;
-  uint32_t nt = (uint32_t)min((uint64_t)v.cnt2[NCLS * leaf + 0], v.exact ? (uint64_t)v.lcap[NCLS * leaf + 0] : v.cap2t);
-  if (v.cnt2[NCLS * leaf + 1]) {                               // (a leaf without complete runs never wrote its counts)
-    n1 = v.leaf_n[leaf];
-    na = min((uint32_t)v.leaf_off[leaf], nt);
-  }
-  nt -= na;
-  sz[leaf] = make_uint4(n1, nt, na, n1 + nt + (na + NOTES_PER_ROW - 1) / NOTES_PER_ROW);
+  runs_sizes<RunsFmt1>(v, sz, plan_sync);
 }
-
-// sender: leaf -> [nd distinct complete runs][nu truncated runs][na notes, 8 per row] at record
-// dst_off[leaf] of the send buffer (the truncated stream holds records and noted records mixed)
 __global__ __launch_bounds__(256) void msp_runs_gather_kernel(MspView v, const uint64_t *__restrict__ dst_off, uint4 *__restrict__ out,
-                                                              const uint64_t *__restrict__ plan_rows, const uint64_t *__restrict__ seg_start, int parts, uint64_t cap_rows) {
+                                                                       const uint64_t *__restrict__ plan_rows, const uint64_t *__restrict__ seg_start, int parts, uint64_t cap_rows) {
   __shared__ uint32_t cu, cn;
-  if (plan_rows[parts] > cap_rows) return;         // the buffer is too small: nothing was planned
-  const uint32_t leaf = blockIdx.x;
-  const int lane = threadIdx.x & 63;
-  const bool has1 = v.cnt2[NCLS * leaf + 1] != 0u;
-  const uint32_t nd = has1 ? v.leaf_n[leaf] : 0u;
-  const uint32_t nt = (uint32_t)min((uint64_t)v.cnt2[NCLS * leaf + 0], v.exact ? (uint64_t)v.lcap[NCLS * leaf + 0] : v.cap2t);
-  const uint32_t na = has1 ? min((uint32_t)v.leaf_off[leaf], nt) : 0u;
-  const uint32_t nu = nt - na;
-  if (threadIdx.x == 0) runs_write_header(out, seg_start, parts, blockIdx.x, nd, nu, na);
-  const uint4 *c1 = v.exact ? v.rec2 + v.lbase[NCLS * leaf + 1] : v.rec2 + (uint64_t)(leaf >> v.sel_bits) * (v.cap2c + v.cap2t);
-  const uint4 *c0 = v.exact ? v.rec2 + v.lbase[NCLS * leaf + 0] : c1 + v.cap2c;
-  uint4 *dst = out + dst_off[leaf];
-  for (uint32_t i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = c1[i];
-  if (na == 0u) {
-    for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) dst[nd + i] = c0[i];
-    return;
-  }
-  if (threadIdx.x == 0) { cu = 0u; cn = 0u; }
-  __syncthreads();
-  uint16_t *notes = reinterpret_cast<uint16_t *>(dst + nd + nu);
-  for (uint32_t i = threadIdx.x; i < ((nt + 63u) & ~63u); i += blockDim.x) {
-    const bool valid = i < nt;
-    uint4 rec = make_uint4(0u, 0u, 0u, 0u);
-    if (valid) rec = c0[i];
-    const bool isn = valid && rec.w == RUN_NOTED;
-    const unsigned long long mn = __ballot(isn), mu = __ballot(valid && !isn);
-    uint32_t bn = 0, bu = 0;
-    if (lane == 0) {
-      if (mn) bn = atomicAdd(&cn, (uint32_t)__popcll(mn));
-      if (mu) bu = atomicAdd(&cu, (uint32_t)__popcll(mu));
-    }
-    bn = __shfl(bn, 0); bu = __shfl(bu, 0);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    // (the counts of the plan bound both: a stream that changed under us cannot write outside the leaf's rows)
-    if (isn) { const uint32_t at = bn + (uint32_t)__popcll(mn & below); if (at < na) notes[at] = (uint16_t)rec.x; }
-    else if (valid) { const uint32_t at = bu + (uint32_t)__popcll(mu & below); if (at < nu) dst[nd + at] = rec; }
-  }
-  const uint32_t pad = (NOTES_PER_ROW - na % NOTES_PER_ROW) % NOTES_PER_ROW;
-  if (threadIdx.x < pad) notes[na + threadIdx.x] = 0xFFFFu;
+  runs_gather<RunsFmt1>(v, dst_off, out, plan_rows, seg_start, parts, cap_rows, &cu, &cn);
 }
-
-// owner: segment (source rank, local leaf) of the received buffer -> its place in the leaf's two streams
-// A note becomes the run it stands for: the first n k-mers of its twin, closed on the left only (a
-// prefix -- of the twin as the sender stored it, whichever strand the read showed).
 __global__ __launch_bounds__(256) void msp_runs_scatter_kernel(const uint4 *__restrict__ in, RunsRecv rr, int lpp, int k,
-                                                               const uint64_t *__restrict__ src_off,
-                                                               const uint64_t *__restrict__ dst1, const uint64_t *__restrict__ dst0,
-                                                               uint4 *__restrict__ rec2) {
-  const uint32_t seg = blockIdx.x;
-  const uint32_t r = seg / (uint32_t)lpp, ll = seg - r * (uint32_t)lpp;
-  const uint32_t *hdr = reinterpret_cast<const uint32_t *>(in + rr.rstart[r]);
-  const uint32_t nd = hdr[3 * ll], nt = hdr[3 * ll + 1], na = hdr[3 * ll + 2];
-  const uint4 *src = in + src_off[seg];
-  for (uint32_t i = threadIdx.x; i < nd; i += blockDim.x) rec2[dst1[seg] + i] = src[i];
-  for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) rec2[dst0[seg] + i] = src[nd + i];
-  const uint16_t *notes = reinterpret_cast<const uint16_t *>(src + nd + nt);
-  for (uint32_t i = threadIdx.x; i < na; i += blockDim.x) {          // (nd > 0: the layout kernel checked)
-    const uint32_t note = notes[i];
-    const uint4 twin = src[min(note >> 5, nd - 1u)];                  // a position outside the list is not followed
-    const uint32_t nm1 = min(note & 31u, twin.w & 31u);
-    const int rb = 2 * ((int)nm1 + k) - 32;                           // bits of the run beyond the first word: 0 .. 64
-    const uint32_t my = (rb >= 32) ? 0xFFFFFFFFu : ~(0xFFFFFFFFu >> rb);
-    const uint32_t mz = (rb <= 32) ? 0u : ((rb >= 64) ? 0xFFFFFFFFu : ~(0xFFFFFFFFu >> (rb - 32)));
-    rec2[dst0[seg] + nt + i] = make_uint4(twin.x, twin.y & my, twin.z & mz, 64u | nm1);
-  }
+                                                                        const uint64_t *__restrict__ src_off,
+                                                                        const uint64_t *__restrict__ dst1, const uint64_t *__restrict__ dst0,
+                                                                        uint4 *__restrict__ rec2) {
+  runs_scatter<RunsFmt1>(in, rr, lpp, k, src_off, dst1, dst0, rec2);
 }
 
 // the few records that did not fit their leaf stream: counted k-mer by k-mer in the HBM table

@@ -1470,44 +1470,84 @@ __global__ __launch_bounds__(Q3_THREADS) void msp2_merge_kernel(const uint64_t *
 constexpr int DX2_INFL = 2;
 // A note is 16 bits: position of the twin in the leaf's list << 5 | n-1 -- 11 bits of position
 constexpr uint32_t NOTE_POS_MAX = 2047u;
-static_assert((NOTE_POS_MAX << 5 | 29u) < 0xFFFFu, "a note never equals the padding value");
+static_assert((NOTE_POS_MAX << 5 | 29u) < RUNS_NO_NOTE, "a note never equals the padding value");
 
-// stream cl (0..2 truncated, 3 complete) of a leaf and how many records it holds (one pass: sel_bits = 0)
-__device__ __forceinline__ Rec2 *x2_stream(const View2 &v, uint32_t leaf, int cl) {
-  if (v.exact) return v.rec2 + v.lbase[NCLS * leaf + cl];
-  return v.rec2 + (uint64_t)leaf * (v.cap2c + 3 * v.cap2t) + (cl == 3 ? 0ull : v.cap2c + (uint64_t)cl * v.cap2t);
-}
-__device__ __forceinline__ uint32_t x2_count(const View2 &v, uint32_t leaf, int cl) {
-  return (uint32_t)min((uint64_t)v.cnt2[NCLS * leaf + cl], v.exact ? (uint64_t)v.lcap[NCLS * leaf + cl] : (cl == 3 ? v.cap2c : v.cap2t));
-}
+// The record format as the stages of the exchange see it (msp_runs.h): 32-byte records, two rows of the packed buffer
+// each; stream class 3 of a leaf holds its complete runs, classes 0..2 its truncated ones (one pass: sel_bits = 0);
+// header word b.w, a note parks in a.x.
+struct RunsFmt2 {
+  typedef Rec2 Rec;
+  typedef View2 View;
+  static constexpr int ROWS = 2, NC = NCLS, COMPLETE = 3;
+  static constexpr uint32_t EMPTY = R2_EMPTY, DONE = R2_DONE;
+  // (a twin beyond position 2047 of a long list cannot be named by a note: the run travels as a record;
+  //  CFRK_DEBUG_SMALL_WAVE_CAP lowers the limit to 15 so that tests reach this at small sizes)
+  static __device__ __forceinline__ uint32_t note_pos_max(uint32_t dbg) { return (dbg & CFRK_DEBUG_SMALL_WAVE_CAP) ? 15u : NOTE_POS_MAX; }
+  static __device__ __forceinline__ uint32_t count(const View2 &v, uint32_t leaf, int cl) {
+    return (uint32_t)min((uint64_t)v.cnt2[NCLS * leaf + cl], v.exact ? (uint64_t)v.lcap[NCLS * leaf + cl] : (cl == 3 ? v.cap2c : v.cap2t));
+  }
+  static __device__ __forceinline__ Rec2 *stream(const View2 &v, uint32_t leaf, int cl) {
+    if (v.exact) return v.rec2 + v.lbase[NCLS * leaf + cl];
+    return v.rec2 + (uint64_t)leaf * (v.cap2c + 3 * v.cap2t) + (cl == 3 ? 0ull : v.cap2c + (uint64_t)cl * v.cap2t);
+  }
+  struct Trunc {                                   // the n truncated runs of a leaf: its three streams one behind the other
+    Rec2 *s0, *s1, *s2; uint32_t t0; uint64_t t1, n;
+    __device__ __forceinline__ Rec2 *at(uint64_t g) const { return (g < t0) ? s0 + g : (g < t1) ? s1 + (g - t0) : s2 + (g - t1); }
+  };
+  static __device__ __forceinline__ Trunc trunc(const View2 &v, uint32_t leaf) {
+    const uint32_t t0 = count(v, leaf, 0);
+    const uint64_t t1 = (uint64_t)t0 + count(v, leaf, 1);
+    return Trunc{stream(v, leaf, 0), stream(v, leaf, 1), stream(v, leaf, 2), t0, t1, t1 + count(v, leaf, 2)};
+  }
+  static __device__ __forceinline__ uint32_t hdr(const Rec2 &r) { return r.b.w; }
+  static __device__ __forceinline__ void set_hdr(Rec2 *q, uint32_t w) { q->b.w = w; }
+  static __device__ __forceinline__ uint32_t note(const Rec2 &r) { return r.a.x; }
+  static __device__ __forceinline__ void set_note(Rec2 *q, uint32_t note) { q->a.x = note; q->b.w = RUN_NOTED; }
+  static __device__ __forceinline__ uint32_t slot(const Rec2 &rec, int k, int log) { return r2_slot_k(rec, k, log); }
+  static __device__ __forceinline__ Rec2 revcomp(const Rec2 &rec, int len) { return revcomp_record2(rec, len); }
+  static __device__ __forceinline__ bool prefix_equal(const Rec2 &e, const Rec2 &rec, int len) { return rec2_prefix_equal(e, rec, len); }
+  // the first len bases (33 .. 93) of a twin under a header of their own; the spare word b.z stays
+  static __device__ __forceinline__ Rec2 prefix(const Rec2 &twin, int len, uint32_t w) {
+    auto mk = [&](int i) {                                            // mask of word i: bits 32 i .. 32 i + 31 of the string
+      const int b = 2 * len - 32 * i;
+      return (b >= 32) ? 0xFFFFFFFFu : ((b <= 0) ? 0u : ~(0xFFFFFFFFu >> b));
+    };
+    return Rec2{make_uint4(twin.a.x, twin.a.y, twin.a.z & mk(2), twin.a.w & mk(3)), make_uint4(twin.b.x & mk(4), twin.b.y & mk(5), twin.b.z, w)};
+  }
+  static __device__ __forceinline__ Rec2 zero() { return Rec2{make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)}; }
+  // (the halves as two vectors: a Rec2 copied as a whole through a pointer picked among streams goes through scratch memory)
+  static __device__ __forceinline__ Rec2 load(const Rec2 *q) { const uint4 a = q->a, b = q->b; return Rec2{a, b}; }
+  static __device__ __forceinline__ void store(Rec2 *q, const Rec2 &r) { q->a = r.a; q->b = r.b; }
+  static __device__ __forceinline__ Rec2 load_row(const uint4 *rows, uint64_t i) { const uint4 a = rows[2 * i], b = rows[2 * i + 1]; return Rec2{a, b}; }
+  static __device__ __forceinline__ void store_row(uint4 *rows, uint64_t i, const Rec2 &r) { rows[2 * i] = r.a; rows[2 * i + 1] = r.b; }
+};
 
 // One workgroup per leaf.  The leaf's complete stream -> its DISTINCT runs, header = multiplicity << 6 |
 // n-1 (the extra minimizer-hash bits in b.z stay), at the head of the stream; leaf_n[leaf] = how many.
 // A leaf with more distinct runs than the table holds leaves as it is (multiplicity 1 each).
 // Truncated runs that are a prefix of a distinct run of this rank (a suffix, read on the other strand)
-// become notes: marked in place (b.w = RUN_NOTED, a.x = position of the run in the list << 5 | n-1);
-// leaf_off[leaf] = how many.
+// become notes, marked in place; leaf_off[leaf] = how many.
 // RX_LOG / DX2_THREADS: 2048 slots (64 KB of LDS) and 256 threads, two workgroups per CU, for leaves of a few
 // hundred distinct runs; 4096 slots (128 KB) and 1024 threads, one per CU, for the leaves of a job with far
 // more distinct k-mers than its leaf tables hold (configs[4]: ~2000 distinct runs per leaf and rank) --
 // with the small table those leaves left undeduplicated: 53 GB per rank instead of 5.
 template <int RX_LOG, int DX2_THREADS>
 __global__ __launch_bounds__(DX2_THREADS) void msp2_dedupe_export_kernel(int k, int canon, View2 v) {
+  typedef RunsFmt2 F;
   constexpr int RX = 1 << RX_LOG;
   // the record table, SPLIT (r2s_insert_loop): slot s = {ra[s], {rb[s].x, rb[s].y, rz[s], rst[s]}}
   __shared__ uint4 ra[RX];
   __shared__ uint2 rb[RX];
   __shared__ uint32_t rz[RX], rst[RX];
-  auto rt_get = [&](uint32_t s_) { const uint2 e = rb[s_]; return Rec2{ra[s_], make_uint4(e.x, e.y, rz[s_], rst[s_])}; };
   __shared__ uint16_t sidx[RX];                    // record-table slot -> position in the leaf's list
   __shared__ uint32_t wsum[DX2_THREADS / 64];
   __shared__ uint32_t rt_fail, noted;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const uint32_t leaf = blockIdx.x;
-  const uint32_t n1 = x2_count(v, leaf, 3);
+  const uint32_t n1 = F::count(v, leaf, 3);
   if (n1 == 0) return;
-  Rec2 *const stream = x2_stream(v, leaf, 3);
-  const Rec2 zrec = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
+  Rec2 *const stream = F::stream(v, leaf, 3);
+  const Rec2 zrec = F::zero();
   for (int s = tid; s < RX; s += DX2_THREADS) rst[s] = R2_EMPTY;
   // (a leaf of 2^19 complete runs or more leaves undeduplicated: msp.hip, HUGE_LEAF)
   const bool too_many = (uint64_t)n1 >= Q3_HUGE_LEAF_SENDER;
@@ -1533,62 +1573,19 @@ __global__ __launch_bounds__(DX2_THREADS) void msp2_dedupe_export_kernel(int k, 
   uint32_t nd;
   if (rt_fail) {
     // (every record was read before the barrier; the rewrite touches the header word only)
-    for (uint32_t i = tid; i < n1; i += DX2_THREADS) stream[i].b.w = (1u << 6) | (stream[i].b.w & 63u);
+    for (uint32_t i = tid; i < n1; i += DX2_THREADS) F::set_hdr(&stream[i], (1u << 6) | (F::hdr(stream[i]) & 63u));
     nd = n1;
   } else {
-    // occupied slots -> head of the stream (eight slots per thread)
+    // occupied slots -> head of the stream (eight slots per thread), truncated runs -> notes
     constexpr int PER = RX / DX2_THREADS;
-    uint32_t mine = 0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) mine += (rst[PER * tid + i] != R2_EMPTY) ? 1u : 0u;
-    const uint32_t incl = dev_wave_scan_incl(mine);
-    if (lane == 63) wsum[wave] = incl;
+    auto occupied = [&](uint32_t s) { return rst[s] != R2_EMPTY; };
+    auto get = [&](uint32_t s) { const uint2 e = rb[s]; return Rec2{ra[s], make_uint4(e.x, e.y, rz[s], rst[s])}; };
+    const uint32_t at0 = runs_rank_slots<DX2_THREADS, PER>(sidx, wsum, occupied, &nd);
+    runs_emit_slots<PER>(at0, occupied, get, [&](uint32_t at, const Rec2 &e) { stream[at] = e; });
     __syncthreads();
-    uint32_t base = 0, total = 0;
-    for (int w = 0; w < DX2_THREADS / 64; ++w) { const uint32_t x = wsum[w]; base += (w < wave) ? x : 0u; total += x; }
-    uint32_t at = base + incl - mine;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const Rec2 e = rt_get(PER * tid + i);
-      sidx[PER * tid + i] = (uint16_t)at;
-      if (e.b.w != R2_EMPTY) stream[at++] = e;
-    }
-    nd = total;
-    __syncthreads();
-    // truncated runs -> notes (the lookup of the leaf kernel's anchoring, msp2_p3_kernel)
-    for (int cl = 0; cl < 3 && !(v.dbg & CFRK_DEBUG_NO_ANCHORS); ++cl) {
-      const uint32_t nt = x2_count(v, leaf, cl);
-      Rec2 *const trunc = x2_stream(v, leaf, cl);
-      for (uint32_t g0 = 0; g0 < nt; g0 += DX2_THREADS) {
-        const uint32_t g = g0 + tid;
-        const bool valid = g < nt;
-        Rec2 rec = zrec;
-        if (valid) rec = trunc[g];
-        const uint32_t nm1 = rec.b.w & 31u;
-        const bool lc = (rec.b.w & 64u) != 0u, rc_ = (rec.b.w & 128u) != 0u;
-        const bool suf = canon && valid && !lc && rc_;
-        if (suf) rec = revcomp_record2(rec, (int)nm1 + k);
-        const bool anchored = suf || (valid && lc && !rc_);
-        uint32_t h = anchored ? r2_slot_k(rec, k, RX_LOG) : R2_DONE;
-        uint32_t found = 0xFFFFFFFFu;
-        for (int it = 0; it < 32 && __ballot((int32_t)h >= 0); ++it) {
-          const bool p = (int32_t)h >= 0;
-          const uint32_t hh = h & (uint32_t)(RX - 1);
-          const Rec2 e2 = rt_get(hh);
-          const bool empty = e2.b.w == R2_EMPTY;
-          const bool hit = p && !empty && (e2.b.w & 31u) >= nm1 && rec2_prefix_equal(e2, rec, (int)nm1 + k);
-          found = hit ? hh : found;
-          h = (p && !hit && !empty) ? ((hh + 1u) & (uint32_t)(RX - 1)) : (h | R2_DONE);
-        }
-        // (a twin beyond position 2047 of a long list cannot be named by a note: the run travels as a record;
-        //  CFRK_DEBUG_SMALL_WAVE_CAP lowers the limit to 15 so that tests reach this at small sizes)
-        const uint32_t pos_max = (v.dbg & CFRK_DEBUG_SMALL_WAVE_CAP) ? 15u : NOTE_POS_MAX;
-        const bool hit = found != 0xFFFFFFFFu && (uint32_t)sidx[found] <= pos_max;
-        if (hit) { trunc[g].a.x = ((uint32_t)sidx[found] << 5) | nm1; trunc[g].b.w = RUN_NOTED; }
-        const unsigned long long hb = __ballot(hit);
-        if (lane == 0 && hb) atomicAdd(&noted, (uint32_t)__popcll(hb));
-      }
-    }
+    const F::Trunc tr = F::trunc(v, leaf);
+    runs_note_truncated<F, DX2_THREADS, 1, RX_LOG>(tr, (v.dbg & CFRK_DEBUG_NO_ANCHORS) ? 0ull : tr.n, k, canon, sidx, F::note_pos_max(v.dbg), get, &noted,
+      [&](uint64_t g, bool, uint32_t note) { if (note != RUNS_NO_NOTE) F::set_note(tr.at(g), note); });
     __syncthreads();
   }
   if (tid == 0) { v.leaf_n[leaf] = nd; v.leaf_off[leaf] = noted; }
@@ -1611,6 +1608,7 @@ __global__ __launch_bounds__(DX2_THREADS) void msp2_dedupe_export_kernel(int k, 
 constexpr int DS2_INFL = 4;
 template <int DS2_LOG, int DS2_THREADS, bool SUB, int DS2_TCAP = (SUB ? 6144 : 2048)>
 __global__ __launch_bounds__(DS2_THREADS) void msp2_dedupe_send_kernel(int k, int canon, View2 v, RunsSend sg) {
+  typedef RunsFmt2 F;
   constexpr int RX = 1 << DS2_LOG;
   // SPLIT record table (r2s_insert_loop): bases 0..63, bases 64..95 and the state words are three arrays
   __shared__ uint4 ra[RX];
@@ -1619,26 +1617,22 @@ __global__ __launch_bounds__(DS2_THREADS) void msp2_dedupe_send_kernel(int k, in
   __shared__ uint32_t rz_[SUB ? RX : 1];
   uint32_t *const rz = SUB ? rz_ : nullptr;
   __shared__ uint16_t sidx[RX];                    // record-table slot -> position in the leaf's list
-  __shared__ uint16_t tres[DS2_TCAP];              // truncated run g: its note, or 0xFFFF = travels as a record
+  __shared__ uint16_t tres[DS2_TCAP];              // truncated run g: its note, or RUNS_NO_NOTE = travels as a record
   __shared__ uint32_t wsum[DS2_THREADS / 64];
   __shared__ uint32_t rt_fail, noted, cu, cn, row0;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const uint32_t leaf = sg.leaf0 + blockIdx.x;
   const uint32_t own = leaf % (uint32_t)sg.parts, ll = leaf / (uint32_t)sg.parts;
   uint4 *const seg = sg.packed + (uint64_t)own * sg.seg_cap;
   const uint32_t hrows = 1u + sg.lcount;
   uint4 *const entry = seg + 1u + (ll - sg.ll0);
-  const uint32_t n1 = x2_count(v, leaf, 3);
-  const uint32_t t0 = x2_count(v, leaf, 0);
-  const uint64_t t1 = (uint64_t)t0 + x2_count(v, leaf, 1), nt64 = t1 + x2_count(v, leaf, 2);
-  if ((uint64_t)n1 + nt64 == 0) { if (tid == 0) *entry = make_uint4(0u, 0u, 0u, 0u); return; }
-  const Rec2 *const c3 = x2_stream(v, leaf, 3);
-  const Rec2 *const s0 = x2_stream(v, leaf, 0), *const s1 = x2_stream(v, leaf, 1), *const s2 = x2_stream(v, leaf, 2);
-  auto trunc_at = [&](uint64_t g) { return (g < t0) ? s0 + g : (g < t1) ? s1 + (g - t0) : s2 + (g - t1); };
-  const Rec2 zrec = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
-  // (a leaf of 2^19 complete runs or more leaves undeduplicated: msp.hip, HUGE_LEAF; a row count beyond 32 bits cannot be claimed)
+  const uint32_t n1 = F::count(v, leaf, 3);
+  const F::Trunc tr = F::trunc(v, leaf);
+  if ((uint64_t)n1 + tr.n == 0) { if (tid == 0) *entry = make_uint4(0u, 0u, 0u, 0u); return; }
+  const Rec2 *const c3 = F::stream(v, leaf, 3);
+  const Rec2 zrec = F::zero();
+  // (a leaf of 2^19 complete runs or more leaves undeduplicated: msp.hip, HUGE_LEAF)
   const bool too_many = (uint64_t)n1 >= Q3_HUGE_LEAF_SENDER;
-  const bool unclaimable = 2ull * ((uint64_t)n1 + nt64) >= 0xFFFFFFF0ull;
   // the first round of the complete stream is asked for before anything else is done
   Rec2 recs[DS2_INFL];
 #pragma unroll
@@ -1670,222 +1664,47 @@ __global__ __launch_bounds__(DS2_THREADS) void msp2_dedupe_send_kernel(int k, in
   }
   __syncthreads();
   const bool plain = rt_fail != 0u;                 // no deduplication: every complete run leaves with multiplicity 1, no notes
-  const uint32_t nt = (uint32_t)min(nt64, (uint64_t)0xFFFFFFFFull);
-  uint32_t nd, at0 = 0;
+  const uint32_t nt = (uint32_t)min(tr.n, (uint64_t)0xFFFFFFFFull);
+  const bool anchors = !(v.dbg & CFRK_DEBUG_NO_ANCHORS);
+  uint32_t nd = n1, at0 = 0;
   constexpr int PER = RX / DS2_THREADS;
-  if (plain) {
-    nd = n1;
-  } else {
-    // occupied slots -> positions in the leaf's list (eight slots per thread)
-    uint32_t mine = 0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) mine += (rst[PER * tid + i] != R2_EMPTY) ? 1u : 0u;
-    const uint32_t incl = dev_wave_scan_incl(mine);
-    if (lane == 63) wsum[wave] = incl;
+  auto occupied = [&](uint32_t s) { return rst[s] != R2_EMPTY; };
+  // (the spare word takes no part in the lookup's comparison)
+  auto get = [&](uint32_t s) { const uint2 e = rb[s]; return Rec2{ra[s], make_uint4(e.x, e.y, SUB ? rz_[s] : 0u, rst[s])}; };
+  if (!plain) {
+    // occupied slots -> positions in the leaf's list (eight slots per thread); then the first DS2_TCAP truncated runs are
+    // looked up, their verdict waits in LDS
+    at0 = runs_rank_slots<DS2_THREADS, PER>(sidx, wsum, occupied, &nd);
     __syncthreads();
-    uint32_t base = 0, total = 0;
-    for (int w = 0; w < DS2_THREADS / 64; ++w) { const uint32_t x = wsum[w]; base += (w < wave) ? x : 0u; total += x; }
-    at0 = base + incl - mine;
-    uint32_t at = at0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      sidx[PER * tid + i] = (uint16_t)at;
-      if (rst[PER * tid + i] != R2_EMPTY) ++at;
-    }
-    nd = total;
-    __syncthreads();
-    // truncated runs: which of the first DS2_TCAP are a prefix of a distinct complete run of this rank (a suffix, read on
-    // the other strand)?  The verdict waits in LDS (the lookup of the leaf kernel's anchoring)
-    const uint32_t tlook = (v.dbg & CFRK_DEBUG_NO_ANCHORS) ? 0u : min(nt, (uint32_t)DS2_TCAP);
-    const uint32_t pos_max = (v.dbg & CFRK_DEBUG_SMALL_WAVE_CAP) ? 15u : NOTE_POS_MAX;
-    for (uint32_t g0 = 0; g0 < tlook; g0 += DS2_THREADS) {
-      const uint32_t g = g0 + tid;
-      const bool valid = g < tlook;
-      Rec2 rec = zrec;
-      if (valid) rec = *trunc_at(g);
-      const uint32_t nm1 = rec.b.w & 31u;
-      const bool lc = (rec.b.w & 64u) != 0u, rc_ = (rec.b.w & 128u) != 0u;
-      const bool suf = canon && valid && !lc && rc_;
-      if (suf) rec = revcomp_record2(rec, (int)nm1 + k);
-      const bool anchored = suf || (valid && lc && !rc_);
-      uint32_t h = anchored ? r2_slot_k(rec, k, DS2_LOG) : R2_DONE;
-      uint32_t found = 0xFFFFFFFFu;
-      for (int it = 0; it < 32 && __ballot((int32_t)h >= 0); ++it) {
-        const bool p = (int32_t)h >= 0;
-        const uint32_t hh = h & (uint32_t)(RX - 1);
-        const uint2 eb2 = rb[hh];
-        const Rec2 e2 = {ra[hh], make_uint4(eb2.x, eb2.y, 0u, rst[hh])};      // (the spare word takes no part in the comparison)
-        const bool empty = e2.b.w == R2_EMPTY;
-        const bool hit = p && !empty && (e2.b.w & 31u) >= nm1 && rec2_prefix_equal(e2, rec, (int)nm1 + k);
-        found = hit ? hh : found;
-        h = (p && !hit && !empty) ? ((hh + 1u) & (uint32_t)(RX - 1)) : (h | R2_DONE);
-      }
-      // (a twin beyond position 2047 of a long list cannot be named by a note: the run travels as a record)
-      const bool hit = found != 0xFFFFFFFFu && (uint32_t)sidx[found & (uint32_t)(RX - 1)] <= pos_max;
-      if (valid) tres[g] = hit ? (uint16_t)(((uint32_t)sidx[found] << 5) | nm1) : (uint16_t)0xFFFFu;
-      const unsigned long long hb = __ballot(hit);
-      if (lane == 0 && hb) atomicAdd(&noted, (uint32_t)__popcll(hb));
-    }
+    runs_note_truncated<F, DS2_THREADS, 1, DS2_LOG>(tr, anchors ? min(nt, (uint32_t)DS2_TCAP) : 0u, k, canon, sidx, F::note_pos_max(v.dbg), get, &noted,
+      [&](uint64_t g, bool valid, uint32_t note) { if (valid) tres[g] = (uint16_t)note; });
     __syncthreads();
   }
   const uint32_t na = plain ? 0u : noted, nu = nt - na;
-  const uint64_t rows = 2ull * ((uint64_t)nd + nu) + (na + NOTES_PER_ROW - 1) / NOTES_PER_ROW;
-  if (tid == 0) {
-    // one claim per leaf; a segment that runs out of room (or a flood that cannot be claimed at all) shows in its
-    // cursor -- used rows > seg_cap -- and the host takes the classic exchange instead
-    const uint32_t claim = unclaimable ? 0xFFFFFFFFu : (uint32_t)rows;
-    const uint32_t pos = atomicAdd(&sg.cursor[own], claim);
-    const bool fits = !unclaimable && (uint64_t)pos + rows <= sg.seg_cap - hrows && pos + claim >= pos;
-    if (!fits) atomicMax(&sg.cursor[own], 0xFFFFFFF0u);              // (stays "too many" whatever is added later)
-    *entry = fits ? make_uint4(pos, nd, nu, na) : make_uint4(0u, 0u, 0u, 0u);
-    row0 = fits ? pos : 0xFFFFFFFFu;
-  }
+  if (tid == 0) row0 = runs_claim_rows<F>(sg, own, entry, hrows, nd, nu, na);
   __syncthreads();
-  if (row0 == 0xFFFFFFFFu) return;
+  if (row0 == RUNS_NO_ROOM) return;
   uint4 *const dst = seg + hrows + row0;
-  if (plain) {
-    // (the halves as two vectors: a Rec2 copied as a whole goes through scratch memory here)
-    for (uint32_t i = tid; i < n1; i += DS2_THREADS) {
-      const uint4 a = c3[i].a;
-      uint4 b = c3[i].b;
-      b.w = (1u << 6) | (b.w & 63u);
-      dst[2 * (uint64_t)i] = a; dst[2 * (uint64_t)i + 1] = b;
-    }
-    uint4 *const dt = dst + 2 * (uint64_t)nd;
-    for (uint32_t i = tid; i < nt; i += DS2_THREADS) {
-      const Rec2 *q = trunc_at(i);
-      const uint4 a = q->a, b = q->b;
-      dt[2 * (uint64_t)i] = a; dt[2 * (uint64_t)i + 1] = b;
-    }
-    return;
-  }
-  {
-    uint32_t at = at0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const uint32_t sl = PER * tid + i, st = rst[sl];
-      if (st != R2_EMPTY) { const uint2 eb2 = rb[sl]; dst[2 * at] = ra[sl]; dst[2 * at + 1] = make_uint4(eb2.x, eb2.y, SUB ? rz_[sl] : 0u, st); ++at; }
-    }
-  }
-  uint4 *const dt = dst + 2 * (uint64_t)nd;
-  uint16_t *const notes = reinterpret_cast<uint16_t *>(dt + 2 * (uint64_t)nu);
-  for (uint32_t i = tid; i < ((nt + 63u) & ~63u); i += DS2_THREADS) {
-    const bool valid = i < nt;
-    const uint32_t note = (valid && i < (uint32_t)DS2_TCAP && !(v.dbg & CFRK_DEBUG_NO_ANCHORS)) ? (uint32_t)tres[i] : 0xFFFFu;
-    const bool isn = valid && note != 0xFFFFu;
-    const unsigned long long mn = __ballot(isn), mu = __ballot(valid && !isn);
-    uint32_t bn = 0, bu = 0;
-    if (lane == 0) {
-      if (mn) bn = atomicAdd(&cn, (uint32_t)__popcll(mn));
-      if (mu) bu = atomicAdd(&cu, (uint32_t)__popcll(mu));
-    }
-    bn = __shfl(bn, 0); bu = __shfl(bu, 0);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    if (isn) { const uint32_t at = bn + (uint32_t)__popcll(mn & below); if (at < na) notes[at] = (uint16_t)note; }
-    else if (valid) {
-      const uint32_t at = bu + (uint32_t)__popcll(mu & below);
-      if (at < nu) { const Rec2 *q = trunc_at(i); const uint4 a = q->a, b = q->b; dt[2 * (uint64_t)at] = a; dt[2 * (uint64_t)at + 1] = b; }
-    }
-  }
-  const uint32_t pad = (NOTES_PER_ROW - na % NOTES_PER_ROW) % NOTES_PER_ROW;
-  if ((uint32_t)tid < pad) notes[na + tid] = 0xFFFFu;
+  if (plain) { runs_write_plain<F, DS2_THREADS>(dst, c3, nd, tr, nt); return; }
+  runs_emit_slots<PER>(at0, occupied, get, [&](uint32_t at, const Rec2 &e) { F::store_row(dst, at, e); });
+  runs_split_truncated<F, false>(tr, nt, nu, na, dst + 2 * (uint64_t)nd, &cu, &cn, DS2_THREADS,
+    [&](uint32_t i, const Rec2 &) { return (i < (uint32_t)DS2_TCAP && anchors) ? (uint32_t)tres[i] : RUNS_NO_NOTE; });
 }
 
-// sender: what every leaf contributes -- n1 distinct complete runs, nt truncated runs as records, na as
-// notes, rows in all (two per record) -- one thread per leaf
+// the shared kernels of the one-shot exchange (msp_runs.h) under the names the profiles know
 __global__ __launch_bounds__(256) void msp2_runs_sizes_kernel(View2 v, uint4 *__restrict__ sz, unsigned long long *__restrict__ plan_sync) {
-  const uint32_t leaf = blockIdx.x * 256u + threadIdx.x;
-  if (leaf < 72u) plan_sync[leaf] = 0ull;                      // (the plan kernel's look-back words)
-  if (leaf >= (uint32_t)NLEAF) return;
-  uint32_t n1 = 0, na = 0;
-  uint32_t nt = x2_count(v, leaf, 0) + x2_count(v, leaf, 1) + x2_count(v, leaf, 2);
-  if (v.cnt2[NCLS * leaf + 3]) {                               // (a leaf without complete runs never wrote its counts)
-    n1 = v.leaf_n[leaf];
-    na = min((uint32_t)v.leaf_off[leaf], nt);
-  }
-  nt -= na;
-  sz[leaf] = make_uint4(n1, nt, na, 2u * (n1 + nt) + (na + NOTES_PER_ROW - 1) / NOTES_PER_ROW);
+  runs_sizes<RunsFmt2>(v, sz, plan_sync);
 }
-
-// sender: leaf -> [nd distinct complete runs][nu truncated runs][na notes, 8 per row] at row dst_off[leaf]
-// of the send buffer (the three truncated streams hold records and noted records mixed)
 __global__ __launch_bounds__(256) void msp2_runs_gather_kernel(View2 v, const uint64_t *__restrict__ dst_off, uint4 *__restrict__ out,
-                                                               const uint64_t *__restrict__ plan_rows, const uint64_t *__restrict__ seg_start, int parts, uint64_t cap_rows) {
+                                                                        const uint64_t *__restrict__ plan_rows, const uint64_t *__restrict__ seg_start, int parts, uint64_t cap_rows) {
   __shared__ uint32_t cu, cn;
-  if (plan_rows[parts] > cap_rows) return;         // the buffer is too small: nothing was planned
-  const uint32_t leaf = blockIdx.x;
-  const int lane = threadIdx.x & 63;
-  const bool has1 = v.cnt2[NCLS * leaf + 3] != 0u;
-  const uint32_t nd = has1 ? v.leaf_n[leaf] : 0u;
-  const uint32_t t0 = x2_count(v, leaf, 0), t1 = t0 + x2_count(v, leaf, 1), nt = t1 + x2_count(v, leaf, 2);
-  const uint32_t na = has1 ? min((uint32_t)v.leaf_off[leaf], nt) : 0u;
-  const uint32_t nu = nt - na;
-  if (threadIdx.x == 0) runs_write_header(out, seg_start, parts, blockIdx.x, nd, nu, na);
-  const Rec2 *c3 = x2_stream(v, leaf, 3);
-  const Rec2 *s0 = x2_stream(v, leaf, 0), *s1 = x2_stream(v, leaf, 1), *s2 = x2_stream(v, leaf, 2);
-  auto trunc_at = [&](uint32_t g) { return (g < t0) ? s0 + g : (g < t1) ? s1 + (g - t0) : s2 + (g - t1); };
-  uint4 *dst = out + dst_off[leaf];
-  for (uint32_t i = threadIdx.x; i < nd; i += blockDim.x) { const Rec2 r = c3[i]; dst[2 * i] = r.a; dst[2 * i + 1] = r.b; }
-  uint4 *dt = dst + 2 * (uint64_t)nd;
-  if (na == 0u) {
-    for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) { const Rec2 r = *trunc_at(i); dt[2 * i] = r.a; dt[2 * i + 1] = r.b; }
-    return;
-  }
-  if (threadIdx.x == 0) { cu = 0u; cn = 0u; }
-  __syncthreads();
-  uint16_t *notes = reinterpret_cast<uint16_t *>(dt + 2 * (uint64_t)nu);
-  for (uint32_t i = threadIdx.x; i < ((nt + 63u) & ~63u); i += blockDim.x) {
-    const bool valid = i < nt;
-    Rec2 rec = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
-    if (valid) rec = *trunc_at(i);
-    const bool isn = valid && rec.b.w == RUN_NOTED;
-    const unsigned long long mn = __ballot(isn), mu = __ballot(valid && !isn);
-    uint32_t bn = 0, bu = 0;
-    if (lane == 0) {
-      if (mn) bn = atomicAdd(&cn, (uint32_t)__popcll(mn));
-      if (mu) bu = atomicAdd(&cu, (uint32_t)__popcll(mu));
-    }
-    bn = __shfl(bn, 0); bu = __shfl(bu, 0);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    // (the counts of the plan bound both: a stream that changed under us cannot write outside the leaf's rows)
-    if (isn) { const uint32_t at = bn + (uint32_t)__popcll(mn & below); if (at < na) notes[at] = (uint16_t)rec.a.x; }
-    else if (valid) { const uint32_t at = bu + (uint32_t)__popcll(mu & below); if (at < nu) { dt[2 * at] = rec.a; dt[2 * at + 1] = rec.b; } }
-  }
-  const uint32_t pad = (NOTES_PER_ROW - na % NOTES_PER_ROW) % NOTES_PER_ROW;
-  if (threadIdx.x < pad) notes[na + threadIdx.x] = 0xFFFFu;
+  runs_gather<RunsFmt2>(v, dst_off, out, plan_rows, seg_start, parts, cap_rows, &cu, &cn);
 }
-
-// owner: segment (source rank, local leaf) of the received buffer -> its place in the leaf's complete
-// stream and its (one) stream of truncated runs.  A note becomes the run it stands for: the first n
-// k-mers of its twin, closed on the left only.
 __global__ __launch_bounds__(256) void msp2_runs_scatter_kernel(const uint4 *__restrict__ in, RunsRecv rr, int lpp, int k,
-                                                                const uint64_t *__restrict__ src_off,
-                                                                const uint64_t *__restrict__ dst1, const uint64_t *__restrict__ dst0,
-                                                                Rec2 *__restrict__ rec2) {
-  const uint32_t seg = blockIdx.x;
-  const uint32_t r = seg / (uint32_t)lpp, ll = seg - r * (uint32_t)lpp;
-  const uint32_t *hdr = reinterpret_cast<const uint32_t *>(in + rr.rstart[r]);
-  const uint32_t nd = hdr[3 * ll], nt = hdr[3 * ll + 1], na = hdr[3 * ll + 2];
-  const uint4 *src = in + src_off[seg];
-  for (uint32_t i = threadIdx.x; i < nd; i += blockDim.x) { Rec2 q; q.a = src[2 * i]; q.b = src[2 * i + 1]; rec2[dst1[seg] + i] = q; }
-  const uint4 *st = src + 2 * (uint64_t)nd;
-  for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) { Rec2 q; q.a = st[2 * i]; q.b = st[2 * i + 1]; rec2[dst0[seg] + i] = q; }
-  const uint16_t *notes = reinterpret_cast<const uint16_t *>(st + 2 * (uint64_t)nt);
-  for (uint32_t i = threadIdx.x; i < na; i += blockDim.x) {          // (nd > 0: the layout kernel checked)
-    const uint32_t note = notes[i];
-    const uint32_t ti = min(note >> 5, nd - 1u);                      // a position outside the list is not followed
-    const uint4 ta = src[2 * ti], tb = src[2 * ti + 1];
-    const uint32_t nm1 = min(note & 31u, tb.w & 31u);
-    const int len = (int)nm1 + k;                                     // bases of the run: 33 .. 93
-    auto mk = [&](int w) {                                            // mask of word w: bits 32 w .. 32 w + 31 of the string
-      const int b = 2 * len - 32 * w;
-      return (b >= 32) ? 0xFFFFFFFFu : ((b <= 0) ? 0u : ~(0xFFFFFFFFu >> b));
-    };
-    Rec2 q;
-    q.a = make_uint4(ta.x, ta.y, ta.z & mk(2), ta.w & mk(3));
-    q.b = make_uint4(tb.x & mk(4), tb.y & mk(5), tb.z, 64u | nm1);
-    rec2[dst0[seg] + nt + i] = q;
-  }
+                                                                         const uint64_t *__restrict__ src_off,
+                                                                         const uint64_t *__restrict__ dst1, const uint64_t *__restrict__ dst0,
+                                                                         Rec2 *__restrict__ rec2) {
+  runs_scatter<RunsFmt2>(in, rr, lpp, k, src_off, dst1, dst0, rec2);
 }
 
 }  // namespace

@@ -1,13 +1,18 @@
-// msp_runs.h -- the parts of the multi-GPU exchange by runs that do not depend on the record format.  Device side:
-// where every leaf's rows go in the packed buffer (sender) and where every received segment goes in the owner's
-// leaf streams.  Host side: the whole call sequence of the one-shot and the pipelined exchange -- scratch buffers,
-// plan and layout kernels, read-backs and the checks of what arrived -- with the kernels that read or write records
-// handed in as launch lambdas.  Included by msp.hip (16-byte records, one row each) and msp2.hip (32-byte records,
-// two rows each) inside their anonymous namespaces; msp_shared.h holds what the two share outside the exchange.
+// msp_runs.h -- the multi-GPU exchange by runs, for both key widths.  Device side: where every leaf's rows go in the
+// packed buffer (sender) and where every received segment goes in the owner's leaf streams, and the STAGES that read or
+// write records -- slot ranking, twin lookup, note / record split, row claim, the sizes / gather / scatter kernels --
+// templated on a description of the record format (RunsFmt1 in msp.hip: 16-byte records, one row each; RunsFmt2 in
+// msp2.hip: 32-byte records, two rows each).  The wire format -- note encoding, padding, RUN_NOTED, headers, the claim
+// protocol -- is written down here and nowhere else; the two files keep their dedupe kernels' complete-stream scans and
+// thin __global__ wrappers that give the shared kernels their names.  Host side: the whole call sequence of the
+// one-shot and the pipelined exchange -- scratch buffers, plan and layout kernels, read-backs and the checks of what
+// arrived -- with the kernel launches handed in as lambdas.  Included by msp.hip and msp2.hip inside their anonymous
+// namespaces; msp_shared.h holds what the two share outside the exchange.
 #pragma once
 
 constexpr uint32_t RUN_NOTED = 0xFFFFFFFFu;        // (a record's header word has the top 8 bits clear)
 constexpr int NOTES_PER_ROW = 8;
+__host__ __device__ constexpr uint32_t runs_note_rows(uint32_t na) { return (na + NOTES_PER_ROW - 1) / NOTES_PER_ROW; }
 // Packed form, one segment per owner: [header: the owner's leaves_per_part x (distinct, truncated,
 // noted) sizes, uint32 triples, padded to whole 16-byte rows][leaf after leaf: the distinct complete
 // runs, the truncated runs, the notes (16 bits each, eight per row)].
@@ -107,7 +112,7 @@ __global__ __launch_bounds__(256) void msp_runs_layout1_kernel(const uint4 *__re
   for (int r = 0; r < parts; ++r) {
     const uint32_t *hdr = reinterpret_cast<const uint32_t *>(packed + rr.rstart[r]);
     const uint32_t a = hdr[3 * ll], b = hdr[3 * ll + 1], c = hdr[3 * ll + 2];
-    rows[(size_t)r * lpp + ll] = (uint32_t)RMUL * (a + b) + (c + NOTES_PER_ROW - 1) / NOTES_PER_ROW;
+    rows[(size_t)r * lpp + ll] = (uint32_t)RMUL * (a + b) + runs_note_rows(c);
     if (c && !a) err = 1;                                      // notes without a run they could point at
     d1[(size_t)r * lpp + ll] = n1;
     n1 += a;
@@ -210,6 +215,240 @@ __global__ __launch_bounds__(64) void msp_runs_group_finish_kernel(RunsSend sg, 
   }
   if (p == 0) used[sg.parts] = (stats[ST_SPILLED] || stats[ST_ONES] || stats[ST_L1OVF] || stats[ST_L2OVF] || stats[ST_OVFN] ||
                                 stats[ST_OVFN1] || stats[ST_CWRAP] || stats[ST_OVERFLOW]) ? 1ull : 0ull;
+}
+
+// ------------------------------------------------------------------- the stages that read or write records
+// F: the record format (RunsFmt1, RunsFmt2) -- F::Rec, F::View, F::ROWS rows per record, F::NC stream classes per leaf of
+// which F::COMPLETE holds the complete runs, F::count / F::stream / F::trunc (the truncated streams, concatenated),
+// header and note words, F::slot / F::revcomp / F::prefix_equal / F::prefix, records as rows of the packed buffer.
+// A NOTE is 16 bits: position of the twin in the leaf's list << 5 | n-1; 0xFFFF pads the last row and never is a note.
+constexpr uint32_t RUNS_NO_NOTE = 0xFFFFu, RUNS_NO_TWIN = 0xFFFFFFFFu, RUNS_NO_ROOM = 0xFFFFFFFFu;
+
+// rank the occupied slots of a record table of PER * THREADS slots, thread t looking at slots [PER t, PER t + PER):
+// sidx[slot] = position in the leaf's list, *total = the list's length; returns the position of the thread's first
+// occupied slot.  (One barrier inside; wsum: a word per wave.  The caller's barrier makes sidx visible.)
+template <int THREADS, int PER, class Occ>
+__device__ __forceinline__ uint32_t runs_rank_slots(uint16_t *sidx, uint32_t *wsum, Occ occupied, uint32_t *total) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  uint32_t mine = 0;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) mine += occupied(PER * tid + i) ? 1u : 0u;
+  const uint32_t incl = dev_wave_scan_incl(mine);
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  uint32_t base = 0, all = 0;
+  for (int w = 0; w < THREADS / 64; ++w) { const uint32_t x = wsum[w]; base += (w < wave) ? x : 0u; all += x; }
+  const uint32_t at0 = base + incl - mine;
+  uint32_t at = at0;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    sidx[PER * tid + i] = (uint16_t)at;
+    if (occupied(PER * tid + i)) ++at;
+  }
+  *total = all;
+  return at0;
+}
+// ... and the occupied slots, in that order: put(position, entry) from at0 on -- to rows of the packed buffer, or to the
+// head of the leaf's own stream.  (Two passes over LDS: an array of entries would live in scratch memory.)
+template <int PER, class Occ, class Get, class Put>
+__device__ __forceinline__ void runs_emit_slots(uint32_t at0, Occ occupied, Get get, Put put) {
+  uint32_t at = at0;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const uint32_t s = PER * threadIdx.x + i;
+    if (occupied(s)) put(at++, get(s));
+  }
+}
+
+// Is truncated run `rec` a prefix of a distinct complete run of this rank (a suffix, read on the other strand; canonical
+// counting only)?  Looked up in the record table of 2^LOG slots (get(slot): the entry) exactly as the leaf kernel anchors
+// it: from the slot of its first k-mer, at most 32 trips, an entry at least as long whose first n + k - 1 bases agree.
+// Returns the twin's slot or RUNS_NO_TWIN; *nm1 = the run's n-1.
+template <class F, int LOG, class Get>
+__device__ __forceinline__ uint32_t runs_find_twin(typename F::Rec rec, bool valid, int k, int canon, Get get, uint32_t *nm1_out) {
+  constexpr uint32_t MASK = (1u << LOG) - 1u;
+  const uint32_t w = F::hdr(rec), nm1 = w & 31u;
+  const bool lc = (w & 64u) != 0u, rc_ = (w & 128u) != 0u;
+  const bool suf = canon && valid && !lc && rc_;
+  if (suf) rec = F::revcomp(rec, (int)nm1 + k);
+  const bool anchored = suf || (valid && lc && !rc_);
+  uint32_t h = anchored ? F::slot(rec, k, LOG) : F::DONE;
+  uint32_t found = RUNS_NO_TWIN;
+  for (int it = 0; it < 32 && __ballot((int32_t)h >= 0); ++it) {
+    const bool p = (int32_t)h >= 0;
+    const uint32_t hh = h & MASK;
+    const typename F::Rec e = get(hh);
+    const bool empty = F::hdr(e) == F::EMPTY;
+    const bool hit = p && !empty && (F::hdr(e) & 31u) >= nm1 && F::prefix_equal(e, rec, (int)nm1 + k);
+    found = hit ? hh : found;
+    h = (p && !hit && !empty) ? ((hh + 1u) & MASK) : (h | F::DONE);
+  }
+  *nm1_out = nm1;
+  return found;
+}
+// the first n truncated runs of a leaf: out(g, valid, note) with the note of run g, RUNS_NO_NOTE where it has no twin
+// (or one beyond list position pos_max, which a note cannot name); *noted += the notes.  INFL runs per thread are asked
+// for before the first is looked up.
+template <class F, int THREADS, int INFL, int LOG, class Get, class Out>
+__device__ __forceinline__ void runs_note_truncated(const typename F::Trunc &tr, uint64_t n, int k, int canon, const uint16_t *sidx,
+                                                    uint32_t pos_max, Get get, uint32_t *noted, Out out) {
+  const int tid = threadIdx.x;
+  for (uint64_t g0 = 0; g0 < n; g0 += (uint64_t)INFL * THREADS) {
+    typename F::Rec recs[INFL];
+#pragma unroll
+    for (int u = 0; u < INFL; ++u) {
+      const uint64_t g = g0 + (uint64_t)u * THREADS + tid;
+      recs[u] = F::zero();
+      if (g < n) recs[u] = F::load(tr.at(g));
+    }
+#pragma unroll
+    for (int u = 0; u < INFL; ++u) {
+      const uint64_t g = g0 + (uint64_t)u * THREADS + tid;
+      uint32_t nm1;
+      const uint32_t found = runs_find_twin<F, LOG>(recs[u], g < n, k, canon, get, &nm1);
+      const uint32_t pos = sidx[found & ((1u << LOG) - 1u)];
+      const bool hit = found != RUNS_NO_TWIN && pos <= pos_max;
+      out(g, g < n, hit ? ((pos << 5) | nm1) : RUNS_NO_NOTE);
+      const unsigned long long hb = __ballot(hit);
+      if ((tid & 63) == 0 && hb) atomicAdd(noted, (uint32_t)__popcll(hb));
+    }
+  }
+}
+
+// a leaf's nt truncated runs -> [the nu that travel as records, at rows dt][the na notes, NOTES_PER_ROW per row, the last
+// row padded] in stream order.  note_of(i, rec): the note of run i or RUNS_NO_NOTE.  READ_FIRST: the verdict is in the
+// run itself (marked in place), so the run is read into rec before note_of is asked; otherwise only the runs that travel
+// as records are read.  (cu, cn: two LDS cursors, zero and visible on entry.  nu and na bound both kinds: a stream that
+// changed under us cannot write outside the leaf's rows.)
+template <class F, bool READ_FIRST, class NoteOf>
+__device__ __forceinline__ void runs_split_truncated(const typename F::Trunc &tr, uint32_t nt, uint32_t nu, uint32_t na, uint4 *dt,
+                                                     uint32_t *cu, uint32_t *cn, uint32_t threads, NoteOf note_of) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  uint16_t *const notes = reinterpret_cast<uint16_t *>(dt + (uint64_t)F::ROWS * nu);
+  for (uint32_t i = tid; i < ((nt + 63u) & ~63u); i += threads) {
+    const bool valid = i < nt;
+    typename F::Rec rec = F::zero();
+    if (READ_FIRST && valid) rec = F::load(tr.at(i));
+    const uint32_t note = valid ? note_of(i, rec) : RUNS_NO_NOTE;
+    const bool isn = note != RUNS_NO_NOTE;
+    const unsigned long long mn = __ballot(isn), mu = __ballot(valid && !isn);
+    uint32_t bn = 0, bu = 0;
+    if (lane == 0) {
+      if (mn) bn = atomicAdd(cn, (uint32_t)__popcll(mn));
+      if (mu) bu = atomicAdd(cu, (uint32_t)__popcll(mu));
+    }
+    bn = __shfl(bn, 0); bu = __shfl(bu, 0);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (isn) { const uint32_t at = bn + (uint32_t)__popcll(mn & below); if (at < na) notes[at] = (uint16_t)note; }
+    else if (valid) {
+      const uint32_t at = bu + (uint32_t)__popcll(mu & below);
+      if (at < nu) { if (!READ_FIRST) rec = F::load(tr.at(i)); F::store_row(dt, at, rec); }
+    }
+  }
+  const uint32_t pad = (NOTES_PER_ROW - na % NOTES_PER_ROW) % NOTES_PER_ROW;
+  if ((uint32_t)tid < pad) notes[na + tid] = (uint16_t)RUNS_NO_NOTE;
+}
+
+// pipelined sender, one thread of the leaf's workgroup: claim the leaf's rows behind the header of its owner's segment
+// (one atomic) and write the leaf's header entry; returns the first row or RUNS_NO_ROOM.  A segment that runs out of
+// room shows in its cursor -- used rows > seg_cap -- and the host takes the classic exchange instead; so does a flood
+// whose rows no segment can hold (seg_cap <= 0xFFFFFFF0: runs_export_async_host), which is not claimed at all.
+template <class F>
+__device__ __forceinline__ uint32_t runs_claim_rows(const RunsSend &sg, uint32_t own, uint4 *entry, uint32_t hrows,
+                                                    uint32_t nd, uint32_t nu, uint32_t na) {
+  const uint64_t rows = (uint64_t)F::ROWS * ((uint64_t)nd + nu) + runs_note_rows(na);
+  const bool unclaimable = rows >= 0xFFFFFFF0ull;
+  const uint32_t claim = unclaimable ? 0xFFFFFFFFu : (uint32_t)rows;
+  const uint32_t pos = atomicAdd(&sg.cursor[own], claim);
+  const bool fits = !unclaimable && (uint64_t)pos + rows <= sg.seg_cap - hrows && pos + claim >= pos;
+  if (!fits) atomicMax(&sg.cursor[own], 0xFFFFFFF0u);              // (stays "too many" whatever is added later)
+  *entry = fits ? make_uint4(pos, nd, nu, na) : make_uint4(0u, 0u, 0u, 0u);
+  return fits ? pos : RUNS_NO_ROOM;
+}
+
+// pipelined sender, a leaf that was not deduplicated: its n1 complete runs with multiplicity 1 and its nt truncated runs
+// as they are, no notes
+template <class F, int THREADS>
+__device__ __forceinline__ void runs_write_plain(uint4 *dst, const typename F::Rec *c1, uint32_t n1, const typename F::Trunc &tr, uint32_t nt) {
+  for (uint32_t i = threadIdx.x; i < n1; i += THREADS) {
+    typename F::Rec r = F::load(c1 + i);
+    F::set_hdr(&r, (1u << 6) | (F::hdr(r) & 63u));
+    F::store_row(dst, i, r);
+  }
+  uint4 *const dt = dst + (uint64_t)F::ROWS * n1;
+  for (uint32_t i = threadIdx.x; i < nt; i += THREADS) F::store_row(dt, i, F::load(tr.at(i)));
+}
+
+// one-shot sender: what every leaf contributes -- n1 distinct complete runs, nt truncated runs as records, na as
+// notes, rows in all -- one thread per leaf, coalesced (the plan kernel used to gather these four words per leaf
+// itself, three times over, 64 dependent strided loads per thread each time: 0.50 ms of a 5.9 ms critical path at N = 8)
+template <class F>
+__device__ __forceinline__ void runs_sizes(const typename F::View &v, uint4 *__restrict__ sz, unsigned long long *__restrict__ plan_sync) {
+  const uint32_t leaf = blockIdx.x * 256u + threadIdx.x;
+  if (leaf < 72u) plan_sync[leaf] = 0ull;                      // (the plan kernel's look-back words)
+  if (leaf >= (uint32_t)NLEAF) return;
+  uint32_t n1 = 0, na = 0;
+  uint32_t nt = (uint32_t)F::trunc(v, leaf).n;
+  if (v.cnt2[F::NC * leaf + F::COMPLETE]) {                    // (a leaf without complete runs never wrote its counts)
+    n1 = v.leaf_n[leaf];
+    na = min((uint32_t)v.leaf_off[leaf], nt);
+  }
+  nt -= na;
+  sz[leaf] = make_uint4(n1, nt, na, (uint32_t)F::ROWS * (n1 + nt) + runs_note_rows(na));
+}
+
+// one-shot sender: leaf -> [nd distinct complete runs][nu truncated runs][na notes] at row dst_off[leaf] of the send
+// buffer (the truncated streams hold records and noted records mixed: msp_dedupe_export_kernel and its two-word twin
+// mark a noted record in place, header word = RUN_NOTED, the note parked in F::note)
+template <class F>
+__device__ __forceinline__ void runs_gather(const typename F::View &v, const uint64_t *__restrict__ dst_off, uint4 *__restrict__ out,
+                                            const uint64_t *__restrict__ plan_rows, const uint64_t *__restrict__ seg_start, int parts,
+                                            uint64_t cap_rows, uint32_t *cu, uint32_t *cn) {
+  if (plan_rows[parts] > cap_rows) return;         // the buffer is too small: nothing was planned
+  const uint32_t leaf = blockIdx.x;
+  const bool has1 = v.cnt2[F::NC * leaf + F::COMPLETE] != 0u;
+  const uint32_t nd = has1 ? v.leaf_n[leaf] : 0u;
+  const typename F::Trunc tr = F::trunc(v, leaf);
+  const uint32_t nt = (uint32_t)tr.n;
+  const uint32_t na = has1 ? min((uint32_t)v.leaf_off[leaf], nt) : 0u;
+  const uint32_t nu = nt - na;
+  if (threadIdx.x == 0) runs_write_header(out, seg_start, parts, leaf, nd, nu, na);
+  const typename F::Rec *c1 = F::stream(v, leaf, F::COMPLETE);
+  uint4 *dst = out + dst_off[leaf];
+  for (uint32_t i = threadIdx.x; i < nd; i += blockDim.x) F::store_row(dst, i, F::load(c1 + i));
+  uint4 *dt = dst + (uint64_t)F::ROWS * nd;
+  if (na == 0u) {
+    for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) F::store_row(dt, i, F::load(tr.at(i)));
+    return;
+  }
+  if (threadIdx.x == 0) { *cu = 0u; *cn = 0u; }
+  __syncthreads();
+  runs_split_truncated<F, true>(tr, nt, nu, na, dt, cu, cn, blockDim.x, [](uint32_t, const typename F::Rec &r) {
+    return F::hdr(r) == RUN_NOTED ? (F::note(r) & 0xFFFFu) : RUNS_NO_NOTE;
+  });
+}
+
+// owner: segment (source rank, local leaf) of the received buffer -> its place in the leaf's complete stream and its
+// (one) stream of truncated runs.  A note becomes the run it stands for: the first n k-mers of its twin, closed on the
+// left only (a prefix -- of the twin as the sender stored it, whichever strand the read showed).
+template <class F>
+__device__ __forceinline__ void runs_scatter(const uint4 *__restrict__ in, const RunsRecv &rr, int lpp, int k, const uint64_t *__restrict__ src_off,
+                                             const uint64_t *__restrict__ dst1, const uint64_t *__restrict__ dst0, typename F::Rec *__restrict__ rec2) {
+  const uint32_t seg = blockIdx.x;
+  const uint32_t r = seg / (uint32_t)lpp, ll = seg - r * (uint32_t)lpp;
+  const uint32_t *hdr = reinterpret_cast<const uint32_t *>(in + rr.rstart[r]);
+  const uint32_t nd = hdr[3 * ll], nt = hdr[3 * ll + 1], na = hdr[3 * ll + 2];
+  const uint4 *src = in + src_off[seg];
+  for (uint32_t i = threadIdx.x; i < nd; i += blockDim.x) F::store(&rec2[dst1[seg] + i], F::load_row(src, i));
+  const uint4 *st = src + (uint64_t)F::ROWS * nd;
+  for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) F::store(&rec2[dst0[seg] + i], F::load_row(st, i));
+  const uint16_t *notes = reinterpret_cast<const uint16_t *>(st + (uint64_t)F::ROWS * nt);
+  for (uint32_t i = threadIdx.x; i < na; i += blockDim.x) {        // (nd > 0: the layout kernel checked)
+    const uint32_t note = notes[i];
+    const typename F::Rec twin = F::load_row(src, min(note >> 5, nd - 1u));   // a position outside the list is not followed
+    const uint32_t nm1 = min(note & 31u, F::hdr(twin) & 31u);
+    F::store(&rec2[dst0[seg] + nt + i], F::prefix(twin, (int)nm1 + k, 64u | nm1));
+  }
 }
 
 

@@ -119,7 +119,7 @@ def expect(ctx, data, k, canonical):
     gh.add(data)
     want = orc.global_count(data, k, orc.ORC_CANONICAL if canonical else 0)
     d = gh.digest()
-    assert d == orc.digest(*want)
+    assert d == orc.digest(*want, two_word=k > 32)
     return d, want
 
 
@@ -250,28 +250,39 @@ def _shards(data, R, L, world):
     return [np.ascontiguousarray(data[(R * r // world) * (L + 1):(R * (r + 1) // world) * (L + 1)]) for r in range(world)]
 
 
-@pytest.mark.parametrize("world", [1, 2])
-def test_one_leaf_through_the_runs_exchange_weighted(ctx, world):
-    """export_runs_device on one context into merge_runs_device on another: the owner's leaf kernel counts DISTINCT runs
-    with their multiplicities (P3_WEIGHTED: the general scan, increment = the record's weight)"""
+def _heaviest_leaf(host, rows, world, rows_per_record=1):
+    """the (distinct, truncated, noted) header triple of the leaf with the most rows in one rank's packed buffer
+    (msp_runs.h: every owner's segment starts with one triple per leaf of that owner)"""
+    lpp = -(-65536 // world)
+    best, at = (0, 0, 0), 0
+    for r in rows:
+        hdr = host[at:at + (lpp * 12 + 15) // 16].view(np.uint32).reshape(-1)[:3 * lpp].reshape(lpp, 3)
+        nd, nu, na = (int(x) for x in hdr[np.argmax(rows_per_record * (hdr[:, 0] + hdr[:, 1]) + (hdr[:, 2] + 7) // 8)])
+        if nd + nu + na > sum(best):
+            best = (nd, nu, na)
+        at += r
+    return best
+
+
+def _export_runs(ctx, shard, k, flags, world, min_leaf):
+    """one rank: a CFRK_RUNS_ONLY add and the one-shot export -> (packed rows as uint64 [rows, 2], rows per owner)"""
     import cfrk_amd
-    k, flags, R, L = 31, cfrk_amd.CFRK_CANONICAL, 1200, 150
-    rng = np.random.default_rng(7400 + world)
-    genome, pos = planted_genome(rng, mmer_len(k), 150)
-    data, _, _ = refsem.flatten(sample_reads(rng, genome, R))
-    want_digest, want = expect(ctx, data, k, True)
-    sends = []                                        # per rank: (packed rows as uint64 [rows, 2], rows per owner)
-    for shard in _shards(data, R, L, world):
-        g = cfrk_amd.GlobalCounter(ctx, k, flags | cfrk_amd.CFRK_RUNS_ONLY, 0)
-        g.add(shard)
-        assert g.msp_info()["l2_max_leaf"] >= 5 * R // world
-        cap = 1 << 18
-        d = ctx.alloc(cap * 16)
-        rows = g.export_runs_device(d, cap, world)
-        host = np.empty((sum(rows), 2), np.uint64)
-        ctx.d2h(host, d)
-        ctx.free(d)
-        sends.append((host, rows))
+    g = cfrk_amd.GlobalCounter(ctx, k, flags | cfrk_amd.CFRK_RUNS_ONLY, 0)
+    g.add(shard)
+    if min_leaf:
+        assert g.msp_info()["l2_max_leaf"] >= min_leaf
+    cap = 1 << 18
+    d = ctx.alloc(cap * 16)
+    rows = g.export_runs_device(d, cap, world)
+    host = np.empty((sum(rows), 2), np.uint64)
+    ctx.d2h(host, d)
+    ctx.free(d)
+    return host, rows
+
+
+def _merge_runs(sends, k, flags, world, want_digest):
+    """every owner merges what the ranks sent it -> {key: count} over all owners (two-word keys: key = (lo, hi))"""
+    import cfrk_amd
     merged = {}
     c2 = cfrk_amd.Context(0)
     try:
@@ -286,13 +297,91 @@ def test_one_leaf_through_the_runs_exchange_weighted(ctx, world):
                 assert og.digest() == want_digest
             lo, hi, cnt = og.export()
             c2.free(d)
-            for key, c in zip(lo, cnt):
-                assert int(key) not in merged                 # owners hold disjoint key sets
-                merged[int(key)] = int(c)
+            for i, (key, c) in enumerate(zip(lo, cnt)):
+                key = int(key) if k <= 32 else (int(key), int(hi[i]))
+                assert key not in merged                      # owners hold disjoint key sets
+                merged[key] = int(c)
     finally:
         c2.close()
-    wlo, _, wcnt = want
-    assert len(merged) == len(wlo) and all(merged[int(a)] == int(b) for a, b in zip(wlo, wcnt))
+    return merged
+
+
+def _same_counts(merged, want, k):
+    wlo, whi, wcnt = want
+    keys = [int(a) for a in wlo] if k <= 32 else [(int(a), int(b)) for a, b in zip(wlo, whi)]
+    assert len(merged) == len(keys) and all(merged[a] == int(b) for a, b in zip(keys, wcnt))
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_one_leaf_through_the_runs_exchange_weighted(ctx, world):
+    """export_runs_device on one context into merge_runs_device on another: the owner's leaf kernel counts DISTINCT runs
+    with their multiplicities (P3_WEIGHTED: the general scan, increment = the record's weight)"""
+    import cfrk_amd
+    k, flags, R, L = 31, cfrk_amd.CFRK_CANONICAL, 1200, 150
+    rng = np.random.default_rng(7400 + world)
+    genome, pos = planted_genome(rng, mmer_len(k), 150)
+    data, _, _ = refsem.flatten(sample_reads(rng, genome, R))
+    want_digest, want = expect(ctx, data, k, True)
+    sends = [_export_runs(ctx, shard, k, flags, world, 5 * R // world) for shard in _shards(data, R, L, world)]
+    _same_counts(_merge_runs(sends, k, flags, world, want_digest), want, k)
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_one_leaf_with_more_distinct_runs_than_the_senders_table_through_the_runs_exchange(ctx, world):
+    """the (1500, 2000) load of CASES: every rank's leaf holds more distinct complete runs than the sender's record table
+    has slots -- the table fails for real (not by CFRK_DEBUG_FORCE_RT_OVERFLOW), the runs leave undeduplicated with
+    multiplicity 1 and without notes, and the owner's table merges them"""
+    import cfrk_amd
+    k, flags, R, L = 31, cfrk_amd.CFRK_CANONICAL, 2000, 150
+    rng = np.random.default_rng(7600 + world)
+    genome, pos = planted_genome(rng, mmer_len(k), 750)
+    data, _, _ = refsem.flatten(sample_reads(rng, genome, R))
+    want_digest, want = expect(ctx, data, k, True)
+    sends = [_export_runs(ctx, shard, k, flags, world, 5 * R // world) for shard in _shards(data, R, L, world)]
+    for host, rows in sends:
+        nd, nu, na = _heaviest_leaf(host, rows, world)
+        print("heaviest leaf: distinct", nd, "truncated", nu, "noted", na)
+        # (undeduplicated: as many "distinct" runs as the leaf has complete records -- ~9 per read --, far more than the
+        #  ~1500 runs that are distinct, which no 1024-slot table holds)
+        assert nd >= 5 * R // world and nd > RT and na == 0 and nu > 0
+    _same_counts(_merge_runs(sends, k, flags, world, want_digest), want, k)
+
+
+def mmer_len2(k):
+    """msp2.hip: msp2_count_tiles"""
+    return 14 if k & 1 else 13
+
+
+@pytest.mark.parametrize("k,world", [(31, 1), (31, 2), (47, 1), (47, 2)])
+def test_one_leaf_with_thousands_of_truncated_runs_noted_and_not_through_the_runs_exchange(ctx, k, world):
+    """>= 3000 reads of the 300-run genome: several thousand read ends in one leaf, nearly all of them a prefix of a
+    complete run of their rank (notes); a few reads of a second genome whose outer occurrences only ever meet a read's
+    end have no twin (records).  The split of the truncated stream then runs many trips with both cursors moving, and a
+    note count that is no multiple of 8 leaves padding behind.  k = 47: the same through the two-word kernels (no
+    msp_info() of the record levels there: the packed header alone says what the leaf holds)."""
+    import cfrk_amd
+    flags, R, L = cfrk_amd.CFRK_CANONICAL, 3000, 150
+    m = mmer_len(k) if k <= 32 else mmer_len2(k)
+    rng = np.random.default_rng(7700 + 10 * k + world)
+    genome, pos = planted_genome(rng, m, 150)
+    lonely, lpos = planted_genome(rng, m, 3)
+    shards, sends = [], []
+    for r in range(world):
+        reads = sample_reads(rng, genome, R // world) + pad_reads(lonely, lpos, m, 4)
+        for extra in range(9):
+            shard, _, _ = refsem.flatten(reads)
+            host, rows = _export_runs(ctx, shard, k, flags, world, 5 * R // world if k <= 32 else 0)
+            nd, nu, na = _heaviest_leaf(host, rows, world, 1 if k <= 32 else 2)
+            if na % 8:
+                break
+            reads = reads + sample_reads(rng, genome, 1)        # (one more read: two more read ends)
+        print("rank", r, "heaviest leaf: distinct", nd, "truncated", nu, "noted", na, "extra reads", extra)
+        assert na > 0 and nu > 0 and na % 8 != 0 and nu + na >= 2 * (R // world) - 200 and nd >= 150
+        shards.append(shard)
+        sends.append((host, rows))
+    data = np.concatenate(shards)
+    want_digest, want = expect(ctx, data, k, True)
+    _same_counts(_merge_runs(sends, k, flags, world, want_digest), want, k)
 
 
 @pytest.mark.parametrize("world", [1, 2])
