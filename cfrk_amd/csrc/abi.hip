@@ -747,6 +747,73 @@ int cfrk_reads_select(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, c
   return download_reads(ctx, o, data_out, start_out, length_out, index_out, *nN_out, *nS_out);
 }
 
+/* ------------------------------------------------------------------ digital normalisation */
+
+static int normalize_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, int64_t batch_reads, const void *data, const void *start,
+                           const void *length, const void *keep, const int64_t *n_kept) {
+  if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "normalize before begin");
+  if (ctx->g_flags & CFRK_RUNS_ONLY) return cfrk_fail(ctx, CFRK_ERR_STATE, "a CFRK_RUNS_ONLY job holds runs, not counts");
+  if (nN < 0 || nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (batch_reads < 1) return cfrk_fail(ctx, CFRK_ERR_ARG, "batch_reads %lld: at least 1", (long long)batch_reads);
+  if (!n_kept) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL n_kept");
+  if (nS > 0 && (!data || !start || !length || !keep)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  return CFRK_OK;
+}
+
+// what both forms run on device buffers: the result into the HBM table as a merge puts it there, every round enqueued,
+// one synchronisation at the end for the kept reads and the overflow flag.  nS >= 1.
+static int normalize_core(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+                          int64_t nS, uint32_t cutoff, int64_t batch_reads, uint8_t *d_keep, int64_t *n_kept) {
+  ctx->q_valid = false;
+  int rc = cfrk_msp_flush_to_table(ctx);
+  if (rc) return rc;
+  cfrk_msp_note_table_write(ctx);
+  void *p;
+  if ((rc = cfrk_pool_get(ctx, BUF_NORMALIZE, sizeof(unsigned long long), &p))) return rc;
+  unsigned long long *d_kept = (unsigned long long *)p;
+  HIP_TRY(ctx, hipMemsetAsync(d_kept, 0, sizeof *d_kept, ctx->stream));
+  if ((rc = cfrk_normalize_launch(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, d_keep, d_kept))) return rc;
+  // snapshot of the flags for the next begin(), as an add leaves it
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_stats, ctx->g_stats, ST_NWORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  ctx->h_stats_valid = true;
+  unsigned long long kept = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&kept, d_kept, sizeof kept, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *n_kept = (int64_t)kept;
+  if (ctx->h_stats[ST_OVERFLOW]) return cfrk_fail(ctx, CFRK_ERR_TABLE_FULL, "table of %llu slots overflowed", (unsigned long long)ctx->g_cap);
+  return CFRK_OK;
+}
+
+int cfrk_global_normalize_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                 int64_t nN, int64_t nS, uint32_t cutoff, int64_t batch_reads, uint8_t *d_keep,
+                                 int64_t *n_kept) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = normalize_check(ctx, nN, nS, batch_reads, d_data, d_start, d_length, d_keep, n_kept);
+  if (rc) return rc;
+  *n_kept = 0;
+  if (nS == 0) return CFRK_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return normalize_core(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, d_keep, n_kept);
+}
+
+int cfrk_global_normalize(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                          int64_t nS, uint32_t cutoff, int64_t batch_reads, uint8_t *keep, int64_t *n_kept) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = normalize_check(ctx, nN, nS, batch_reads, data, start, length, keep, n_kept);
+  if (rc) return rc;
+  *n_kept = 0;
+  if (nS == 0) return CFRK_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // staged through the query calls' slot: the reads in, room for the keep bytes behind them
+  StagePart x[1] = {{nullptr, (size_t)nS, nullptr}};
+  StagedReads d;
+  if ((rc = stage_reads(ctx, BUF_QUERY_IN, data, start, length, nN, nS, STAGE_TABLE, x, 1, &d))) return rc;
+  if ((rc = normalize_core(ctx, d.data, d.start, d.length, nN, nS, cutoff, batch_reads, (uint8_t *)x[0].dev, n_kept)) &&
+      rc != CFRK_ERR_TABLE_FULL) return stage_drain(ctx, rc);
+  const int rc2 = cfrk_memcpy_d2h(ctx, keep, x[0].dev, (size_t)nS);
+  return rc ? rc : rc2;
+}
+
 int cfrk_global_last_add_ms(cfrk_ctx *ctx, float *ms) {
   if (!ctx || !ms) return CFRK_ERR_ARG;
   if (!ctx->ev_valid) return cfrk_fail(ctx, CFRK_ERR_STATE, "no add recorded");

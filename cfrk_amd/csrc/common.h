@@ -28,7 +28,8 @@ enum {  // pool slots
   BUF_RUNS_AUX,                               // pipelined runs exchange: segment cursors, used rows per group
   BUF_QUERY_INDEX,                            // read-only lookup index of the result (query.hip)
   BUF_QUERY_IN, BUF_QUERY_OUT,                // staging of host forms (staging.h).  IN: cfrk_global_query (keys), _query_reads, _read_stats,
-                                              // _read_spans, cfrk_distinct_sketch (reads); OUT: the first four (counts or rows)
+                                              // _read_spans, cfrk_distinct_sketch (reads), cfrk_global_normalize (reads and keep bytes);
+                                              // OUT: the first four (counts or rows)
   BUF_SPARSE_KEYS, BUF_SPARSE_CNT,            // per-read sparse (sparse.hip): the rows at their reads' offsets, nN entries
   BUF_SPARSE_AUX,                             // block sums of the row-pointer scan
   BUF_SPARSE_IN, BUF_SPARSE_OUT,              // staging of cfrk_per_read_sparse alone (data, start, length, row_ptr in; keys, counts out)
@@ -43,6 +44,7 @@ enum {  // pool slots
   BUF_EMIT,                                   // text emitter (text_out.hip): size words, the read tiles' aggregates, their scan
   BUF_EMIT_OFF,                               // the kept reads' output offsets and input indices
   BUF_EMIT_IN, BUF_EMIT_OUT,                  // staging of cfrk_reads_emit_text alone (reads, spans, keep, records, text in; text out)
+  BUF_NORMALIZE,                              // normalise (normalize.hip): the call's kept-read counter
   BUF_NSLOTS
 };
 
@@ -156,6 +158,10 @@ int cfrk_select_measure(cfrk_ctx *ctx, const int64_t *d_start, const int32_t *d_
 int cfrk_select_emit(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
                      int64_t nS, const cfrk_read_span *d_span, const uint8_t *d_keep, int32_t min_len, int8_t *d_data_out,
                      int64_t *d_start_out, int32_t *d_length_out, int64_t *d_index_out, int64_t nN_out, int64_t nS_out);
+// normalize.hip: every round of a normalise call (judge into d_keep, insert the kept reads), left enqueued; the kept reads
+// are added to *d_kept.  The result must live in the HBM table.  nS >= 1, batch_reads >= 1.
+int cfrk_normalize_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+                          int64_t nS, uint32_t cutoff, int64_t batch_reads, uint8_t *d_keep, unsigned long long *d_kept);
 // sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
 // enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
 int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,

@@ -1,5 +1,5 @@
 // lane_group.h -- what the kernels that give every read to a group of lanes (or to a workgroup) share (sparse.hip,
-// read_stats.hip, read_filter.hip): the size classes of reads and their launch grids, the phase boundary of a wave,
+// read_stats.hip, read_filter.hip, normalize.hip): the size classes of reads and their launch grids, the phase boundary of a wave,
 // the sums over a group, the bitonic network that sorts a group's LDS array in place, the window count of a read that
 // may lie anywhere, the staging of a read in LDS, and the two walkers over the reads of a batch:
 //   class_reads<G>    the reads of a lane group's size class, one after the other by the group

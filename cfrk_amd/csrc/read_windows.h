@@ -1,4 +1,5 @@
-// read_windows.h -- the windows of one read: the rolling key of the last k bases (sparse.hip too), and what the kernels
+// read_windows.h -- the windows of one read: the rolling key of the last k bases (sparse.hip and normalize.hip too, whose
+// walkers look up in the live table and stand in normalize.hip), and what the kernels
 // that look every window up in the index share (read_stats.hip, read_filter.hip): the lookup of one key in the
 // index's form, the sums, minimum and maximum over a group of lanes, and the two walkers
 //   staged_windows<G, MODE, CANON>   a lane group's read: staged in LDS, the windows split over the lanes, looked up

@@ -45,13 +45,15 @@ __device__ __forceinline__ void sat_add_cas(uint32_t *cnt, uint32_t cur, uint32_
 // the k = 32 all-T forward key lives in a 64-bit side word (ST_ONES): clamped where it is read
 __device__ __forceinline__ uint32_t sat_ones(uint64_t ones) { return ones > (uint64_t)CFRK_COUNT_MAX ? CFRK_COUNT_MAX : (uint32_t)ones; }
 
-__device__ __forceinline__ void table_add1(const TableView &t, uint64_t key, uint32_t add) {
+// max_probe: normalize.hip passes table_probe_limit(), which ends the walk of a full small table after one lap
+__device__ __forceinline__ void table_add1(const TableView &t, uint64_t key, uint32_t add,
+                                           uint32_t max_probe = CFRK_MAX_PROBE) {
   if (key == CFRK_EMPTY_KEY) {
     atomicAdd((unsigned long long *)&t.stats[ST_ONES], (unsigned long long)add);
     return;
   }
   uint64_t h = dev_mix64(key) >> t.shift;
-  for (uint32_t probe = 0; probe < CFRK_MAX_PROBE; ++probe) {
+  for (uint32_t probe = 0; probe < max_probe; ++probe) {
     uint64_t cur = ld_agent(&t.lo[h]);   // a stale read can only show EMPTY; the CAS decides
     if (cur == CFRK_EMPTY_KEY) {
       cur = atomicCAS((unsigned long long *)&t.lo[h], (unsigned long long)CFRK_EMPTY_KEY,
@@ -67,11 +69,12 @@ __device__ __forceinline__ void table_add1(const TableView &t, uint64_t key, uin
   t.stats[ST_OVERFLOW] = 1;
 }
 
-__device__ __forceinline__ void table_add2(const TableView &t, uint64_t lo, uint64_t hi, uint32_t add) {
+__device__ __forceinline__ void table_add2(const TableView &t, uint64_t lo, uint64_t hi, uint32_t add,
+                                           uint32_t max_probe = CFRK_MAX_PROBE) {
   uint64_t h = dev_mix64(lo ^ dev_mix64(hi)) >> t.shift;
   uint32_t probe = 0, spins = 0;
   if (add > CFRK_COUNT_MAX) add = CFRK_COUNT_MAX;    // (a published count is never the LOCKED pattern)
-  while (probe < CFRK_MAX_PROBE && spins < (1u << 24)) {
+  while (probe < max_probe && spins < (1u << 24)) {
     uint32_t c = ld_agent(&t.cnt[h]);
     if (c == 0) {
       uint32_t old = atomicCAS(&t.cnt[h], 0u, LOCKED);
@@ -104,6 +107,43 @@ __device__ __forceinline__ void table_add2(const TableView &t, uint64_t lo, uint
   t.stats[ST_OVERFLOW] = 1;
 }
 
+// probes after which a walk has seen every slot (or CFRK_MAX_PROBE of them, the writers' own bound)
+__host__ __device__ __forceinline__ uint32_t table_probe_limit(const TableView &t) {
+  return t.mask < (uint64_t)CFRK_MAX_PROBE ? (uint32_t)t.mask + 1u : CFRK_MAX_PROBE;
+}
+
+// Read-only lookups in the writers' layout, for kernels that run while NO writer does (normalize.hip's judge: the
+// table is complete, plain loads).  table_find*_from probe from slot h on, at most `limit` slots, so that a full table
+// ends the walk and nothing outside the arrays is read; 0 when the key is absent.
+// One-word table: lo[] is the slot state (CFRK_EMPTY_KEY = empty), the count is read once the key matched.
+__device__ __forceinline__ uint32_t table_find1_from(const TableView &t, uint64_t h, uint64_t key, uint32_t limit) {
+  for (uint32_t probe = 0; probe < limit; ++probe) {
+    const uint64_t cur = t.lo[h];
+    if (cur == CFRK_EMPTY_KEY) return 0;
+    if (cur == key) return t.cnt[h];
+    h = (h + 1) & t.mask;
+  }
+  return 0;
+}
+__device__ __forceinline__ uint32_t table_find1(const TableView &t, uint64_t key, uint32_t limit) {
+  if (key == CFRK_EMPTY_KEY) return sat_ones(t.stats[ST_ONES]);     // (k = 32 all-T, non-canonical: the side word)
+  return table_find1_from(t, dev_mix64(key) >> t.shift, key, limit);
+}
+// Two-word table: cnt[] is the slot state (0 = empty; LOCKED is a writer's and cannot be met here), the key words are
+// valid wherever it is not 0.
+__device__ __forceinline__ uint32_t table_find2_from(const TableView &t, uint64_t h, uint64_t lo, uint64_t hi,
+                                                     uint32_t limit) {
+  for (uint32_t probe = 0; probe < limit; ++probe) {
+    const uint32_t c = t.cnt[h];
+    if (c == 0) return 0;
+    if (t.lo[h] == lo && t.hi[h] == hi) return c;
+    h = (h + 1) & t.mask;
+  }
+  return 0;
+}
+__device__ __forceinline__ uint32_t table_find2(const TableView &t, uint64_t lo, uint64_t hi, uint32_t limit) {
+  return table_find2_from(t, dev_mix64(lo ^ dev_mix64(hi)) >> t.shift, lo, hi, limit);
+}
 
 // where digest / export read the result from
 struct ResultSrc {

@@ -70,6 +70,20 @@
 //   --filter-min-len L  drop a read whose kept part is shorter than L bases (default k)
 //   --filter-min-median A / --filter-max-median B  keep only the reads whose median window count (cfrk_global_read_stats;
 //                    0 for a read without a valid window) is at least A / at most B
+//   --normalize-out NFILE --normalize-cutoff C  (global, one device) digital normalisation: the input reads are NORMALISED
+//                    instead of added (cfrk_global_normalize_device): taken in rounds of B reads, a read is kept -- and only
+//                    then counted -- iff it has a valid window and the median count of its k-mers among the reads kept before
+//                    its round is below C.  out.cfrk, --binary and --histo then describe the kept reads; NFILE receives the
+//                    kept reads untrimmed, through the writer of --filter-out: FASTA, ">" + the record's number in the input.
+//                    The capacity hint and its retry on an overflowing table are those of a plain run.  Not with --gpus
+//                    above 1, --batch, --device-parse, --sparse or --query-db
+//   --normalize-batch B  reads per round (default CFRK_NORMALIZE_BATCH); 1 is the streaming rule of khmer's
+//                    normalize-by-median, a larger B is faster and can over-admit only reads of one round that cover the
+//                    same locus
+//   --normalize-names / --normalize-format fasta|fastq  (with --normalize-out) NFILE keeps the names -- and, as fastq, the
+//                    qualities -- the records have in the input: the input's text goes to the device and
+//                    cfrk_text_index_device / cfrk_reads_emit_text_device write NFILE there, exactly as --filter-names and
+//                    --filter-format do for FFILE.  Either option selects this writer; fastq needs a FASTQ input
 //   --query-only     (with --query) write OFILE / SFILE / FFILE only: the counts are not exported and the output path is left
 //                    untouched
 //   --query-db DB.bin  (with --query, no positional arguments) query a saved --binary count file without recounting; k and
@@ -148,6 +162,11 @@ struct Options {
   int filter_format = CFRK_TEXT_FASTA; // --filter-format: CFRK_TEXT_FASTA / CFRK_TEXT_FASTQ
   bool filter_median = false;          // --filter-min-median A / --filter-max-median B
   uint32_t filter_min_median = 0, filter_max_median = 0xFFFFFFFFu;
+  const char *normalize_out = nullptr; // --normalize-out NFILE
+  uint32_t normalize_cutoff = 0;       // --normalize-cutoff C
+  long long normalize_batch = CFRK_NORMALIZE_BATCH;   // --normalize-batch B
+  bool normalize_names = false;        // --normalize-names, --normalize-format
+  int normalize_format = CFRK_TEXT_FASTA;             // --normalize-format: CFRK_TEXT_FASTA / CFRK_TEXT_FASTQ
   bool estimate = false, estimate_only = false, auto_hint = false;   // --estimate, --estimate-only, --auto-hint
   bool device_parse = false;                                        // --device-parse
   bool text_copy_plain = true;                                      // --text-copy plain (the default) | staged
@@ -438,109 +457,147 @@ int write_query_stats(const Options &o, cfrk_ctx *ctx) {
   return 0;
 }
 
-// --filter-out: the query reads trimmed to their solid spans and filtered, on the device, written to FFILE as FASTA
-// named by record number (select, one copy back, formatted here), or -- --filter-names -- as FASTA / FASTQ text with
-// QFILE's names and qualities, written on the device (index, emit, one copy back)
-int write_filter(const Options &o, cfrk_ctx *ctx, int k) {
-  const cfrk_batch &q = g_qreads;
+// 0, or 1 (the error reported)
+int write_whole_file(const char *path, const std::string &buf) {
+  FILE *f = fopen(path, "wb");
+  if (!f) { fprintf(stderr, "cfrk: cannot write %s\n", path); return 1; }
+  const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+  if (fclose(f) != 0 || !ok) { fprintf(stderr, "cfrk: cannot write %s\n", path); return 1; }
+  return 0;
+}
+
+// The reads that d_span / d_keep / min_len leave of the batch q on the device (only q's sizes are read), as text in buf:
+// FASTA named by record number (select, one copy back, formatted here), or -- names -- FASTA / FASTQ text with the names
+// and qualities the records have in `text`, the file q was parsed from, written on the device (index, emit, one copy
+// back).  What --filter-out and --normalize-out share.  0, or a CFRK_ERR_* code with *what naming the call.
+int emit_selected(cfrk_ctx *ctx, const cfrk_batch &q, const void *d_data, const void *d_start, const void *d_length, const void *d_span,
+                  const void *d_keep, long min_len, bool names, const std::vector<char> &text, int text_format, int out_format,
+                  const char *text_path, std::string &buf, const char **what) {
   const size_t nN = (size_t)q.nN, nS = (size_t)q.nS;
   std::vector<int8_t> data;
   std::vector<int64_t> start, index;
   std::vector<int32_t> length;
   int64_t onN = 0, onS = 0;
-  const bool names = o.filter_names;
-  std::string buf;
+  int rc = 0;
   if (nS) {
-    void *d_data = nullptr, *d_start = nullptr, *d_length = nullptr, *d_span = nullptr, *d_keep = nullptr, *d_stats = nullptr;
     void *o_data = nullptr, *o_start = nullptr, *o_length = nullptr, *o_index = nullptr;
     void *d_text = nullptr, *d_rec = nullptr, *d_out = nullptr;
-    const char *what = "cfrk_device_alloc";
-    int rc;
-    const bool trim = o.filter_trim >= 0;
-    if (!(rc = cfrk_device_alloc(ctx, nN + 16, &d_data)) && !(rc = cfrk_device_alloc(ctx, nS * 8, &d_start)) &&
-        !(rc = cfrk_device_alloc(ctx, nS * 4, &d_length)) &&
-        !(!names && ((rc = cfrk_device_alloc(ctx, nN + 16, &o_data)) || (rc = cfrk_device_alloc(ctx, nS * 8, &o_start)) ||
+    *what = "cfrk_device_alloc";
+    if (!(!names && ((rc = cfrk_device_alloc(ctx, nN + 16, &o_data)) || (rc = cfrk_device_alloc(ctx, nS * 8, &o_start)) ||
                      (rc = cfrk_device_alloc(ctx, nS * 4, &o_length)) || (rc = cfrk_device_alloc(ctx, nS * 8, &o_index)))) &&
-        !(names && ((rc = cfrk_device_alloc(ctx, g_qtext.size() + 16, &d_text)) || (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_text_record), &d_rec)))) &&
-        !(trim && (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_span), &d_span))) &&
-        !(o.filter_median && ((rc = cfrk_device_alloc(ctx, nS, &d_keep)) || (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_stats), &d_stats))))) {
-      what = "cfrk_memcpy_h2d";
-      if (!(rc = cfrk_memcpy_h2d(ctx, d_data, q.data, nN)) && !(rc = cfrk_memcpy_h2d(ctx, d_start, q.start, nS * 8)))
-        rc = cfrk_memcpy_h2d(ctx, d_length, q.length, nS * 4);
-      if (!rc && trim) {
-        what = "cfrk_global_read_spans_device";
-        rc = cfrk_global_read_spans_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS,
-                                           o.filter_min_count, o.filter_max_count, o.filter_trim, (cfrk_read_span *)d_span);
-      }
-      if (!rc && o.filter_median) {
-        // the rows come down (32 bytes per read), the keep bytes go up (1 byte per read)
-        what = "cfrk_global_read_stats_device";
-        std::vector<cfrk_read_stats> st(nS);
-        std::vector<uint8_t> keep(nS);
-        if (!(rc = cfrk_global_read_stats_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS, 0,
-                                                 (cfrk_read_stats *)d_stats)) &&
-            !(rc = cfrk_memcpy_d2h(ctx, st.data(), d_stats, nS * sizeof(cfrk_read_stats)))) {
-          for (size_t i = 0; i < nS; ++i) keep[i] = st[i].median >= o.filter_min_median && st[i].median <= o.filter_max_median;
-          rc = cfrk_memcpy_h2d(ctx, d_keep, keep.data(), nS);
-        }
-      }
-      const long min_len = o.filter_min_len >= 0 ? o.filter_min_len : (long)k;
-      if (!rc && names) {
-        // the index of QFILE's text numbers the records as the host parser did; the emitter sizes, then writes
-        const int tfmt = g_qformat == CFRK_FORMAT_FASTQ ? CFRK_TEXT_FASTQ : CFRK_TEXT_FASTA;
+        !(names && ((rc = cfrk_device_alloc(ctx, text.size() + 16, &d_text)) || (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_text_record), &d_rec))))) {
+      if (names) {
+        // the index of the file's text numbers the records as the host parser did; the emitter sizes, then writes
         int64_t inS = 0;
         uint64_t onb = 0;
-        what = "cfrk_memcpy_h2d";
-        if (!(rc = cfrk_memcpy_h2d(ctx, d_text, g_qtext.data(), g_qtext.size()))) {
-          what = "cfrk_text_index_device";
-          rc = cfrk_text_index_device(ctx, (const uint8_t *)d_text, g_qtext.size(), tfmt, (cfrk_text_record *)d_rec, nS, &inS);
+        *what = "cfrk_memcpy_h2d";
+        if (!(rc = cfrk_memcpy_h2d(ctx, d_text, text.data(), text.size()))) {
+          *what = "cfrk_text_index_device";
+          rc = cfrk_text_index_device(ctx, (const uint8_t *)d_text, text.size(), text_format, (cfrk_text_record *)d_rec, nS, &inS);
         }
         if (!rc && inS != q.nS) {
-          fprintf(stderr, "cfrk: %s: %lld records parsed, %lld indexed\n", o.query, (long long)q.nS, (long long)inS);
+          fprintf(stderr, "cfrk: %s: %lld records parsed, %lld indexed\n", text_path, (long long)q.nS, (long long)inS);
           rc = CFRK_ERR_LAYOUT;
         }
         for (int pass = 0; pass < 2 && !rc; ++pass) {
-          what = "cfrk_reads_emit_text_device";
+          *what = "cfrk_reads_emit_text_device";
           rc = cfrk_reads_emit_text_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS,
                                            (const cfrk_read_span *)d_span, (const uint8_t *)d_keep, (int32_t)min_len, (const uint8_t *)d_text,
-                                           g_qtext.size(), (const cfrk_text_record *)d_rec, o.filter_format, (uint8_t *)d_out, pass ? onb : 0, &onb, &onS);
-          if (pass == 0 && rc == CFRK_ERR_SMALL_BUF) { what = "cfrk_device_alloc"; rc = cfrk_device_alloc(ctx, onb + 16, &d_out); }
+                                           text.size(), (const cfrk_text_record *)d_rec, out_format, (uint8_t *)d_out, pass ? onb : 0, &onb, &onS);
+          if (pass == 0 && rc == CFRK_ERR_SMALL_BUF) { *what = "cfrk_device_alloc"; rc = cfrk_device_alloc(ctx, onb + 16, &d_out); }
           else break;
         }
         if (!rc && onb) {
-          what = "cfrk_memcpy_d2h";
+          *what = "cfrk_memcpy_d2h";
           buf.resize((size_t)onb);
           rc = cfrk_memcpy_d2h(ctx, &buf[0], d_out, (size_t)onb);
         }
-      }
-      if (!rc && !names) {
-        what = "cfrk_reads_select_device";
+      } else {
+        *what = "cfrk_reads_select_device";
         rc = cfrk_reads_select_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS,
                                       (const cfrk_read_span *)d_span, (const uint8_t *)d_keep, (int32_t)min_len, (int8_t *)o_data, nN,
                                       (int64_t *)o_start, (int32_t *)o_length, (int64_t *)o_index, nS, &onN, &onS);
-      }
-      if (!rc && !names) {
-        what = "cfrk_memcpy_d2h";
-        data.resize((size_t)onN); start.resize((size_t)onS); length.resize((size_t)onS); index.resize((size_t)onS);
-        if (onS && !(rc = cfrk_memcpy_d2h(ctx, data.data(), o_data, (size_t)onN)) && !(rc = cfrk_memcpy_d2h(ctx, start.data(), o_start, (size_t)onS * 8)) &&
-            !(rc = cfrk_memcpy_d2h(ctx, length.data(), o_length, (size_t)onS * 4)))
-          rc = cfrk_memcpy_d2h(ctx, index.data(), o_index, (size_t)onS * 8);
+        if (!rc) {
+          *what = "cfrk_memcpy_d2h";
+          data.resize((size_t)onN); start.resize((size_t)onS); length.resize((size_t)onS); index.resize((size_t)onS);
+          if (onS && !(rc = cfrk_memcpy_d2h(ctx, data.data(), o_data, (size_t)onN)) && !(rc = cfrk_memcpy_d2h(ctx, start.data(), o_start, (size_t)onS * 8)) &&
+              !(rc = cfrk_memcpy_d2h(ctx, length.data(), o_length, (size_t)onS * 4)))
+            rc = cfrk_memcpy_d2h(ctx, index.data(), o_index, (size_t)onS * 8);
+        }
       }
     }
     const int rc2 = cfrk_ctx_sync(ctx);
-    for (void *d : {d_data, d_start, d_length, d_span, d_keep, d_stats, o_data, o_start, o_length, o_index, d_text, d_rec, d_out}) if (d) cfrk_device_free(ctx, d);
-    if (rc) return die(ctx, rc, what);
-    if (rc2) return die(ctx, rc2, "cfrk_ctx_sync");
+    for (void *d : {o_data, o_start, o_length, o_index, d_text, d_rec, d_out}) if (d) cfrk_device_free(ctx, d);
+    if (rc) return rc;
+    if (rc2) { *what = "cfrk_ctx_sync"; return rc2; }
   }
   if (!names) {
     buf.resize(cfrk_host_format_fasta(data.data(), start.data(), length.data(), index.data(), onS, nullptr, 0));
     cfrk_host_format_fasta(data.data(), start.data(), length.data(), index.data(), onS, &buf[0], buf.size());
   }
-  FILE *f = fopen(o.filter_out, "wb");
-  if (!f) { fprintf(stderr, "cfrk: cannot write %s\n", o.filter_out); return 1; }
-  const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
-  if (fclose(f) != 0 || !ok) { fprintf(stderr, "cfrk: cannot write %s\n", o.filter_out); return 1; }
   return 0;
+}
+
+// --filter-out: the query reads trimmed to their solid spans and filtered, on the device, written to FFILE as FASTA
+// named by record number, or -- --filter-names -- as FASTA / FASTQ text with QFILE's names and qualities (emit_selected)
+int write_filter(const Options &o, cfrk_ctx *ctx, int k) {
+  const cfrk_batch &q = g_qreads;
+  const size_t nN = (size_t)q.nN, nS = (size_t)q.nS;
+  std::string buf;
+  void *d_data = nullptr, *d_start = nullptr, *d_length = nullptr, *d_span = nullptr, *d_keep = nullptr, *d_stats = nullptr;
+  const char *what = "cfrk_device_alloc";
+  int rc = 0;
+  const bool trim = o.filter_trim >= 0;
+  if (nS && !(rc = cfrk_device_alloc(ctx, nN + 16, &d_data)) && !(rc = cfrk_device_alloc(ctx, nS * 8, &d_start)) &&
+      !(rc = cfrk_device_alloc(ctx, nS * 4, &d_length)) &&
+      !(trim && (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_span), &d_span))) &&
+      !(o.filter_median && ((rc = cfrk_device_alloc(ctx, nS, &d_keep)) || (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_stats), &d_stats))))) {
+    what = "cfrk_memcpy_h2d";
+    if (!(rc = cfrk_memcpy_h2d(ctx, d_data, q.data, nN)) && !(rc = cfrk_memcpy_h2d(ctx, d_start, q.start, nS * 8)))
+      rc = cfrk_memcpy_h2d(ctx, d_length, q.length, nS * 4);
+    if (!rc && trim) {
+      what = "cfrk_global_read_spans_device";
+      rc = cfrk_global_read_spans_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS,
+                                         o.filter_min_count, o.filter_max_count, o.filter_trim, (cfrk_read_span *)d_span);
+    }
+    if (!rc && o.filter_median) {
+      // the rows come down (32 bytes per read), the keep bytes go up (1 byte per read)
+      what = "cfrk_global_read_stats_device";
+      std::vector<cfrk_read_stats> st(nS);
+      std::vector<uint8_t> keep(nS);
+      if (!(rc = cfrk_global_read_stats_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS, 0,
+                                               (cfrk_read_stats *)d_stats)) &&
+          !(rc = cfrk_memcpy_d2h(ctx, st.data(), d_stats, nS * sizeof(cfrk_read_stats)))) {
+        for (size_t i = 0; i < nS; ++i) keep[i] = st[i].median >= o.filter_min_median && st[i].median <= o.filter_max_median;
+        rc = cfrk_memcpy_h2d(ctx, d_keep, keep.data(), nS);
+      }
+    }
+  }
+  const long min_len = o.filter_min_len >= 0 ? o.filter_min_len : (long)k;
+  if (!rc)
+    rc = emit_selected(ctx, q, d_data, d_start, d_length, d_span, d_keep, min_len, o.filter_names, g_qtext,
+                       g_qformat == CFRK_FORMAT_FASTQ ? CFRK_TEXT_FASTQ : CFRK_TEXT_FASTA, o.filter_format, o.query, buf, &what);
+  const int rc2 = nS ? cfrk_ctx_sync(ctx) : 0;
+  for (void *d : {d_data, d_start, d_length, d_span, d_keep, d_stats}) if (d) cfrk_device_free(ctx, d);
+  if (rc) return die(ctx, rc, what);
+  if (rc2) return die(ctx, rc2, "cfrk_ctx_sync");
+  return write_whole_file(o.filter_out, buf);
+}
+
+// --normalize-out: the input's text and format, as the writer of the kept reads needs them
+std::vector<char> g_ntext;              // --normalize-names: the input file's bytes
+int g_nformat = CFRK_FORMAT_FASTA;
+const char *g_npath = "";
+
+// the kept reads (d_keep, as the normalise call left it) untrimmed, to NFILE
+int write_normalized(const Options &o, cfrk_ctx *ctx, const cfrk_batch &b, const void *d_data, const void *d_start, const void *d_length,
+                     const void *d_keep) {
+  std::string buf;
+  const char *what = "";
+  const int rc = emit_selected(ctx, b, d_data, d_start, d_length, nullptr, d_keep, 0, o.normalize_names, g_ntext,
+                               g_nformat == CFRK_FORMAT_FASTQ ? CFRK_TEXT_FASTQ : CFRK_TEXT_FASTA, o.normalize_format, g_npath, buf, &what);
+  if (rc) return die(ctx, rc, what);
+  return write_whole_file(o.normalize_out, buf);
 }
 
 // the global result (ascending keys) as sparse text or in the binary form
@@ -617,6 +674,19 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
   uint64_t hint = std::min<uint64_t>(std::max<uint64_t>(hint_max / 16, 1ull << 20), hint_max);
   if (o.auto_hint && est.have) hint = std::min<uint64_t>(est.hint, hint_max);
   uint64_t n = 0;
+  // --normalize-out: the reads go to the device once; every attempt normalises them from there into its fresh job
+  struct DeviceReads {
+    cfrk_ctx *ctx;
+    void *data = nullptr, *start = nullptr, *length = nullptr, *keep = nullptr;
+    ~DeviceReads() { for (void *d : {data, start, length, keep}) if (d) cfrk_device_free(ctx, d); }
+  } nr{ctx};
+  if (o.normalize_out && batch.nS > 0) {
+    const size_t nN = (size_t)batch.nN, nS = (size_t)batch.nS;
+    if ((rc = cfrk_device_alloc(ctx, nN + 16, &nr.data)) || (rc = cfrk_device_alloc(ctx, nS * 8, &nr.start)) ||
+        (rc = cfrk_device_alloc(ctx, nS * 4, &nr.length)) || (rc = cfrk_device_alloc(ctx, nS, &nr.keep))) return die(ctx, rc, "cfrk_device_alloc");
+    if ((rc = cfrk_memcpy_h2d(ctx, nr.data, batch.data, nN)) || (rc = cfrk_memcpy_h2d(ctx, nr.start, batch.start, nS * 8)) ||
+        (rc = cfrk_memcpy_h2d(ctx, nr.length, batch.length, nS * 4))) return die(ctx, rc, "cfrk_memcpy_h2d");
+  }
   // (the phase times add up over the attempts: a batch counted three times shows three times the seconds)
   double add_s = 0, finish_s = 0;
   g_timing.begin = 0;
@@ -627,7 +697,14 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
     if ((rc = cfrk_global_begin(ctx, o.k, o.canonical ? CFRK_CANONICAL : 0, hint))) return die(ctx, rc, "cfrk_global_begin");
     const double t0 = now_s();
     g_timing.begin += t0 - tb;
-    if (on_device) { if (batch.nN > 0 && (rc = cfrk_global_add_device(ctx, d_data, batch.nN))) return die(ctx, rc, "cfrk_global_add_device"); }
+    if (o.normalize_out) {
+      int64_t kept = 0;
+      rc = batch.nS > 0 ? cfrk_global_normalize_device(ctx, (const int8_t *)nr.data, (const int64_t *)nr.start, (const int32_t *)nr.length, batch.nN,
+                                                       batch.nS, o.normalize_cutoff, o.normalize_batch, (uint8_t *)nr.keep, &kept) : 0;
+      if (rc == CFRK_ERR_TABLE_FULL && hint < hint_max) { hint = std::min<uint64_t>(hint * 8, hint_max); continue; }
+      if (rc) return die(ctx, rc, "cfrk_global_normalize_device");
+    }
+    else if (on_device) { if (batch.nN > 0 && (rc = cfrk_global_add_device(ctx, d_data, batch.nN))) return die(ctx, rc, "cfrk_global_add_device"); }
     else if ((rc = cfrk_global_add(ctx, batch.data, batch.start, batch.length, batch.nN, batch.nS))) return die(ctx, rc, "cfrk_global_add");
     const double t1 = now_s();
     rc = cfrk_global_finish(ctx, &n);
@@ -638,6 +715,7 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
   // (counts are 32-bit and saturate: the result is complete, the user is told)
   if (rc == CFRK_ERR_COUNT_OVERFLOW) fprintf(stderr, "cfrk: warning: %s\n", cfrk_last_error(ctx));
   else if (rc) return die(ctx, rc, "cfrk_global_finish");
+  if (o.normalize_out && (rc = write_normalized(o, ctx, batch, nr.data, nr.start, nr.length, nr.keep))) return rc;
   const double t2 = now_s();
   // the spectrum is taken before the batch is freed: its copies do not wait behind the page returns
   if (o.histo) {
@@ -946,6 +1024,14 @@ int run_file(const Options &o, const char *in, const char *outp, std::vector<Wor
     fmt = file_format(o, in);
     if (!format_allowed(o, in, fmt)) return 1;
   }
+  if (o.normalize_out) {
+    if (o.normalize_format == CFRK_TEXT_FASTQ && fmt != CFRK_FORMAT_FASTQ) {
+      fprintf(stderr, "cfrk: --normalize-format fastq needs a FASTQ input: %s is read as FASTA\n", in);
+      return 1;
+    }
+    g_nformat = fmt; g_npath = in;
+    if (o.normalize_names && read_whole_file(in, g_ntext)) return 1;
+  }
   double t0 = now_s();
   int rc;
   DeviceText dt;
@@ -1078,7 +1164,7 @@ int main(int argc, char **argv) {
   std::vector<const char *> pos;
   Options o;
   int batch_n = -1;
-  bool range_set = false, stats_below_set = false, filter_opt_set = false;
+  bool range_set = false, stats_below_set = false, filter_opt_set = false, normalize_opt_set = false, normalize_cutoff_set = false;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--all-chunks")) o.all_chunks = true;
     else if (!strcmp(argv[i], "--native")) o.native = true;
@@ -1166,6 +1252,32 @@ int main(int argc, char **argv) {
         else { o.filter_max_median = x; o.filter_median = true; }
       }
     }
+    else if (!strncmp(argv[i], "--normalize-", 12)) {
+      const char *opt = argv[i];
+      static const char *const known[] = {"--normalize-out", "--normalize-cutoff", "--normalize-batch", "--normalize-names", "--normalize-format"};
+      bool is_known = false;
+      for (const char *n : known) is_known = is_known || !strcmp(opt, n);
+      if (!is_known) { fprintf(stderr, "cfrk: unknown option %s\n", opt); return 1; }
+      if (!strcmp(opt, "--normalize-names")) { o.normalize_names = true; normalize_opt_set = true; continue; }
+      if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", opt); return 1; }
+      const char *v = argv[++i];
+      if (!strcmp(opt, "--normalize-out")) { o.normalize_out = v; continue; }
+      normalize_opt_set = true;
+      if (!strcmp(opt, "--normalize-format")) {
+        if (!strcmp(v, "fasta")) o.normalize_format = CFRK_TEXT_FASTA;
+        else if (!strcmp(v, "fastq")) o.normalize_format = CFRK_TEXT_FASTQ;
+        else { fprintf(stderr, "cfrk: --normalize-format takes fasta or fastq, not '%s'\n", v); return 1; }
+        o.normalize_names = true;
+      } else if (!strcmp(opt, "--normalize-batch")) {
+        char *end = nullptr;
+        const long long B = strtoll(v, &end, 10);
+        if (!*v || *end || B < 1) { fprintf(stderr, "cfrk: --normalize-batch needs a number of reads (an integer from 1), not '%s'\n", v); return 1; }
+        o.normalize_batch = B;
+      } else {
+        if (!parse_count(v, &o.normalize_cutoff)) { fprintf(stderr, "cfrk: %s needs a count (an integer from 0 to 4294967295), not '%s'\n", opt, v); return 1; }
+        normalize_cutoff_set = true;
+      }
+    }
     else if (!strcmp(argv[i], "--histo") || !strcmp(argv[i], "--min-count") || !strcmp(argv[i], "--max-count")) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
       const char *opt = argv[i], *v = argv[++i];
@@ -1218,6 +1330,13 @@ int main(int argc, char **argv) {
   if (o.query && batch_n >= 0) { fprintf(stderr, "cfrk: --query writes one file: not with --batch\n"); return 1; }
   if (o.query_db && !pos.empty()) { fprintf(stderr, "cfrk: --query-db takes no positional arguments\n"); return 1; }
   if (o.query_db && o.min_qual_set) { fprintf(stderr, "cfrk: --min-qual applies to the FASTQ input that is counted: not with --query-db\n"); return 1; }
+  if ((o.normalize_out || normalize_opt_set) && (!o.global || o.sparse)) { fprintf(stderr, "cfrk: --normalize-out and the --normalize- options need --global\n"); return 1; }
+  if (normalize_opt_set && !o.normalize_out) { fprintf(stderr, "cfrk: the --normalize- options need --normalize-out NFILE\n"); return 1; }
+  if (o.normalize_out && !normalize_cutoff_set) { fprintf(stderr, "cfrk: --normalize-out needs --normalize-cutoff C\n"); return 1; }
+  if (o.normalize_out && (o.gpus > 1 || batch_n >= 0 || o.device_parse || o.query_db)) {
+    fprintf(stderr, "cfrk: --normalize-out runs on one device and writes one file: not with --gpus above 1, --batch, --device-parse or --query-db\n");
+    return 1;
+  }
   if (o.query) g_qformat = file_format(o, o.query);
   if (o.filter_format == CFRK_TEXT_FASTQ && g_qformat != CFRK_FORMAT_FASTQ) {
     fprintf(stderr, "cfrk: --filter-format fastq needs a FASTQ --query file: %s is read as FASTA\n", o.query);

@@ -37,6 +37,7 @@ READ_STATS_DTYPE = np.dtype([("windows", "<u4"), ("present", "<u4"), ("below", "
 CFRK_SPAN_PREFIX = 0                 # read spans: the solid run that begins at window 0 (the filter-abund rule)
 CFRK_SPAN_LONGEST = 1                # the longest solid run, the earliest one on a tie
 CFRK_SPANS_FAST_WINDOWS = 2048       # read spans: windows per read a lane group takes (longer reads: a workgroup each)
+CFRK_NORMALIZE_BATCH = 262144        # normalise: reads per round when the caller names no batch
 # cfrk_read_span: bases [offset, offset + length) of a read
 READ_SPAN_DTYPE = np.dtype([("offset", "<i4"), ("length", "<i4")])
 CFRK_SELECT_TILE_BYTES = 16384       # select: bytes of data_out per workgroup of the copy
@@ -129,6 +130,8 @@ def load_library():
         "cfrk_global_read_stats_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
         "cfrk_global_read_spans": ([vp, vp, vp, vp, i64, i64, C.c_uint32, C.c_uint32, i32, vp], C.c_int),
         "cfrk_global_read_spans_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, C.c_uint32, i32, vp], C.c_int),
+        "cfrk_global_normalize": ([vp, vp, vp, vp, i64, i64, C.c_uint32, i64, vp, C.POINTER(i64)], C.c_int),
+        "cfrk_global_normalize_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, i64, vp, C.POINTER(i64)], C.c_int),
         "cfrk_reads_select": ([vp, vp, vp, vp, i64, i64, vp, vp, C.c_int32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_reads_select_device": ([vp, vp, vp, vp, i64, i64, vp, vp, C.c_int32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_text_index": ([vp, vp, u64, i32, vp, u64, C.POINTER(i64)], C.c_int),
@@ -845,6 +848,35 @@ class GlobalCounter:
         self.ctx.check(self._L.cfrk_global_read_spans_device(self.ctx._h, vp(d_data), vp(d_start), vp(d_length), nN, nS,
                                                              int(min_count), int(max_count), int(mode), vp(d_out)),
                        "cfrk_global_read_spans_device")
+
+    def normalize(self, data, start, length, cutoff, batch_reads=CFRK_NORMALIZE_BATCH):
+        """digital normalisation (normalize-by-median) -> (keep, n_kept): the reads are taken in rounds of batch_reads;
+        a read is kept (keep[i] = 1) iff it has a valid window and the lower median of its windows' counts in the job,
+        as it stands at the beginning of the read's round, is below `cutoff`; only kept reads are counted into the job"""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        nS = len(length)
+        if len(start) != nS:
+            raise ValueError("start and length differ in size")
+        if not 0 <= int(cutoff) <= 0xFFFFFFFF:
+            raise ValueError("cutoff outside 0 .. 2^32 - 1")
+        keep = np.zeros(nS, np.uint8)
+        n = C.c_int64(0)
+        self.ctx.check(self._L.cfrk_global_normalize(self.ctx._h, _ptr(data), _ptr(start), _ptr(length), len(data), nS,
+                                                     int(cutoff), int(batch_reads), _ptr(keep), C.byref(n)),
+                       "cfrk_global_normalize")
+        return keep, int(n.value)
+
+    def normalize_device(self, d_data, d_start, d_length, nN, nS, cutoff, d_keep, batch_reads=CFRK_NORMALIZE_BATCH):
+        """device form of normalize(): d_keep nS bytes; no alignment requirement; every round is enqueued on the
+        context stream, one synchronisation at the end; returns the number of kept reads"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        n = C.c_int64(0)
+        self.ctx.check(self._L.cfrk_global_normalize_device(self.ctx._h, vp(d_data), vp(d_start), vp(d_length), nN, nS,
+                                                            int(cutoff), int(batch_reads), vp(d_keep), C.byref(n)),
+                       "cfrk_global_normalize_device")
+        return int(n.value)
 
     def export_device(self, d_lo, d_hi, d_cnt, cap, parts=1):
         pc = (C.c_uint64 * parts)()

@@ -311,6 +311,40 @@ int cfrk_global_read_spans(cfrk_ctx *ctx, const int8_t *data, const int64_t *sta
                            int64_t nN, int64_t nS, uint32_t min_count, uint32_t max_count, int mode,
                            cfrk_read_span *out);
 
+/* Digital normalisation (normalize-by-median): the reads of the call are counted into the job ONLY while the k-mers they
+ * carry are still rare among the reads kept so far, and keep[i] says which were.  The reads are taken in rounds of
+ * batch_reads consecutive reads; round r holds the reads [r * batch_reads, min((r + 1) * batch_reads, nS)).
+ *   judge    every read of the round against the job's counts as they stand at the beginning of the round: everything
+ *            added, merged or normalised into the job before, plus the kept reads of this call's earlier rounds.  The
+ *            windows of read i are those of cfrk_global_read_stats (the starts p in [start[i], start[i] + length[i] - k]
+ *            whose k codes are all 0..3, canonicalised in a CFRK_CANONICAL job); an absent k-mer counts 0, a saturated
+ *            key reads CFRK_COUNT_MAX.  The read is KEPT iff it has a valid window and the lower median of its windows'
+ *            counts (cfrk_read_stats.median) is below cutoff.
+ *   insert   every valid window of every kept read of the round adds 1 to its key (saturating, as an add).
+ * batch_reads = 1 is the streaming rule of khmer's normalize-by-median, with exact counts; a larger batch can over-admit
+ * only reads of one round that cover the same locus, and is faster.  cutoff = 0 keeps nothing, cutoff = 0xFFFFFFFF keeps
+ * every read with a valid window.  Keep bytes and counts do not depend on scheduling.  1 <= k <= 64, reads of any length.
+ * A result held by a partitioned path is folded into the HBM table first, as cfrk_global_merge_device does, so the table
+ * must have room for it (capacity_hint).  After the call the job is an ordinary job that also holds the counts of the
+ * kept reads: finish, digest, export, histogram, queries, read statistics and spans, further adds, merges and
+ * normalise calls all work on it.
+ * Errors: CFRK_ERR_STATE before begin and on a CFRK_RUNS_ONLY job; CFRK_ERR_ARG for negative sizes, batch_reads < 1, a
+ * NULL n_kept and NULL arrays with nS > 0 (nS = 0 is fine: *n_kept = 0, nothing changes); CFRK_ERR_TABLE_FULL when the
+ * table overflowed during the call: the keep bytes of the rounds judged after the overflow are unspecified, nothing
+ * outside the buffers is accessed, and finish / digest report the same code.
+ * Device form: no alignment requirement; start / length are not checked: a read whose range does not lie inside
+ * [0, nN) gets keep 0 (never an access outside the buffers).  Every keep byte is written (0 or 1).  All rounds are
+ * enqueued on the context stream without a host synchronisation between them; the call synchronises once at the end
+ * for *n_kept and the overflow flag.
+ * Host form: checks start and length like cfrk_global_add (CFRK_ERR_LAYOUT), stages through the pool, synchronous. */
+#define CFRK_NORMALIZE_BATCH 262144  /* what the Python and CLI layers pass when the caller names no batch */
+int cfrk_global_normalize_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                 int64_t nN, int64_t nS, uint32_t cutoff, int64_t batch_reads,
+                                 uint8_t *d_keep /* nS bytes, 0 or 1 */, int64_t *n_kept);
+int cfrk_global_normalize(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
+                          int64_t nN, int64_t nS, uint32_t cutoff, int64_t batch_reads,
+                          uint8_t *keep, int64_t *n_kept);
+
 /* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
 
 /* How many DISTINCT k-mers will a job hold?  One streaming pass over the reads answers it to about 1 % before anything
