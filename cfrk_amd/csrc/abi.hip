@@ -682,6 +682,55 @@ int cfrk_global_read_spans(cfrk_ctx *ctx, const int8_t *data, const int64_t *sta
   return cfrk_memcpy_d2h(ctx, out, p_out, (size_t)nS * sizeof *out);
 }
 
+static_assert(sizeof(cfrk_read_fix) == 8, "cfrk_read_fix is 8 bytes without padding");
+
+static int correct_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, const void *data, const void *start, const void *length,
+                         const void *data_out) {
+  int rc = query_check(ctx, nN);
+  if (rc) return rc;
+  if (nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (nS > 0 && (!data || !start || !length)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (nN > 0 && (!data || !data_out)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL data buffer with nN > 0");
+  return CFRK_OK;
+}
+
+// what both forms run on device buffers: the copy, then the kernels that store the corrected bases into it
+static int correct_core(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+                        int64_t nS, uint32_t min_count, int8_t *d_data_out, cfrk_read_fix *d_fix) {
+  if (nN > 0) HIP_TRY(ctx, hipMemcpyAsync(d_data_out, d_data, (size_t)nN, hipMemcpyDeviceToDevice, ctx->stream));
+  if (nS == 0) return CFRK_OK;
+  return cfrk_read_correct_launch(ctx, d_data, d_start, d_length, nN, nS, min_count, d_data_out, d_fix);
+}
+
+int cfrk_global_correct_reads_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                     int64_t nN, int64_t nS, uint32_t min_count, int8_t *d_data_out, cfrk_read_fix *d_fix) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = correct_check(ctx, nN, nS, d_data, d_start, d_length, d_data_out);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return correct_core(ctx, d_data, d_start, d_length, nN, nS, min_count, d_data_out, d_fix);
+}
+
+int cfrk_global_correct_reads(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                              int64_t nS, uint32_t min_count, int8_t *data_out, cfrk_read_fix *fix) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = correct_check(ctx, nN, nS, data, start, length, data_out);
+  if (rc) return rc;
+  if (nS == 0) {                                        // no read, nothing to look up: the bytes alone
+    if (nN > 0) memcpy(data_out, data, (size_t)nN);
+    return CFRK_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // staged through the query calls' slot: the reads in, room for the corrected data and the rows behind them
+  StagePart x[2] = {{nullptr, (size_t)nN, nullptr}, {nullptr, fix ? (size_t)nS * sizeof *fix : 0, nullptr}};
+  StagedReads d;
+  if ((rc = stage_reads(ctx, BUF_QUERY_IN, data, start, length, nN, nS, STAGE_TABLE, x, 2, &d))) return rc;
+  if ((rc = correct_core(ctx, d.data, d.start, d.length, nN, nS, min_count, (int8_t *)x[0].dev, (cfrk_read_fix *)x[1].dev)))
+    return stage_drain(ctx, rc);
+  if (fix) HIP_TRY(ctx, hipMemcpyAsync(fix, x[1].dev, (size_t)nS * sizeof *fix, hipMemcpyDeviceToHost, ctx->stream));
+  return cfrk_memcpy_d2h(ctx, data_out, x[0].dev, (size_t)nN);
+}
+
 static int select_check(cfrk_ctx *ctx, const void *data, const void *start, const void *length, int64_t nN, int64_t nS,
                         int32_t min_len, const void *data_out, uint64_t cap_data, const void *start_out,
                         const void *length_out, uint64_t cap_reads, int64_t *nN_out, int64_t *nS_out) {

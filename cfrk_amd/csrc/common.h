@@ -28,7 +28,8 @@ enum {  // pool slots
   BUF_RUNS_AUX,                               // pipelined runs exchange: segment cursors, used rows per group
   BUF_QUERY_INDEX,                            // read-only lookup index of the result (query.hip)
   BUF_QUERY_IN, BUF_QUERY_OUT,                // staging of host forms (staging.h).  IN: cfrk_global_query (keys), _query_reads, _read_stats,
-                                              // _read_spans, cfrk_distinct_sketch (reads), cfrk_global_normalize (reads and keep bytes);
+                                              // _read_spans, cfrk_distinct_sketch (reads), cfrk_global_normalize (reads and keep bytes),
+                                              // cfrk_global_correct_reads (reads in; corrected data and rows out);
                                               // OUT: the first four (counts or rows)
   BUF_SPARSE_KEYS, BUF_SPARSE_CNT,            // per-read sparse (sparse.hip): the rows at their reads' offsets, nN entries
   BUF_SPARSE_AUX,                             // block sums of the row-pointer scan
@@ -158,6 +159,10 @@ int cfrk_select_measure(cfrk_ctx *ctx, const int64_t *d_start, const int32_t *d_
 int cfrk_select_emit(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
                      int64_t nS, const cfrk_read_span *d_span, const uint8_t *d_keep, int32_t min_len, int8_t *d_data_out,
                      int64_t *d_start_out, int32_t *d_length_out, int64_t *d_index_out, int64_t nN_out, int64_t nS_out);
+// read_correct.hip: the corrected bases into d_data_out (a copy of d_data by stream order) and one cfrk_read_fix per read
+// (d_fix may be NULL) from the same index; the kernels are left enqueued.  nS >= 1.
+int cfrk_read_correct_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                             int64_t nN, int64_t nS, uint32_t min_count, int8_t *d_data_out, cfrk_read_fix *d_fix);
 // normalize.hip: every round of a normalise call (judge into d_keep, insert the kept reads), left enqueued; the kept reads
 // are added to *d_kept.  The result must live in the HBM table.  nS >= 1, batch_reads >= 1.
 int cfrk_normalize_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,

@@ -70,6 +70,19 @@
 //   --filter-min-len L  drop a read whose kept part is shorter than L bases (default k)
 //   --filter-min-median A / --filter-max-median B  keep only the reads whose median window count (cfrk_global_read_stats;
 //                    0 for a read without a valid window) is at least A / at most B
+//   --correct-out CFILE --correct-min-count T  (with --query; --query-out becomes optional) spectral error correction
+//                    (cfrk_global_correct_reads_device): the reads of QFILE go to the device, and wherever one wrong base
+//                    explains an isolated run of weak windows (count < T in the whole result) and exactly one other base makes
+//                    all of them solid, that base is written back.  ALL reads of QFILE are written to CFILE, corrected or
+//                    not, through the writer of --filter-out (no span, no keep bytes, minimum length 0): FASTA, ">" + the
+//                    record's number in QFILE.  A base that is not ACGT (QFILE is read unmasked, as for --filter-out) is an
+//                    invalid code: a weak run next to it is not attempted, and it is written as N.  One device (not with
+//                    --gpus above 1), not with --batch or --sparse
+//   --correct-names / --correct-format fasta|fastq  (with --correct-out) CFILE keeps the names -- and, as fastq, the quality
+//                    lines, unchanged -- the records have in QFILE, as --filter-names and --filter-format do for FFILE.
+//                    fastq needs a FASTQ QFILE and implies --correct-names
+//   --correct-report RFILE  (with --correct-out) one line per query record, in record order: the weak runs of the read that
+//                    were corrected and those that were left alone (cfrk_read_fix), tab-separated
 //   --normalize-out NFILE --normalize-cutoff C  (global, one device) digital normalisation: the input reads are NORMALISED
 //                    instead of added (cfrk_global_normalize_device): taken in rounds of B reads, a read is kept -- and only
 //                    then counted -- iff it has a valid window and the median count of its k-mers among the reads kept before
@@ -84,7 +97,7 @@
 //                    qualities -- the records have in the input: the input's text goes to the device and
 //                    cfrk_text_index_device / cfrk_reads_emit_text_device write NFILE there, exactly as --filter-names and
 //                    --filter-format do for FFILE.  Either option selects this writer; fastq needs a FASTQ input
-//   --query-only     (with --query) write OFILE / SFILE / FFILE only: the counts are not exported and the output path is left
+//   --query-only     (with --query) write OFILE / SFILE / FFILE / CFILE only: the counts are not exported and the output path is left
 //                    untouched
 //   --query-db DB.bin  (with --query, no positional arguments) query a saved --binary count file without recounting; k and
 //                    the canonical bit come from its header
@@ -162,6 +175,11 @@ struct Options {
   int filter_format = CFRK_TEXT_FASTA; // --filter-format: CFRK_TEXT_FASTA / CFRK_TEXT_FASTQ
   bool filter_median = false;          // --filter-min-median A / --filter-max-median B
   uint32_t filter_min_median = 0, filter_max_median = 0xFFFFFFFFu;
+  const char *correct_out = nullptr;   // --correct-out CFILE
+  uint32_t correct_min_count = 0;      // --correct-min-count T
+  bool correct_names = false;          // --correct-names (implied by --correct-format fastq)
+  int correct_format = CFRK_TEXT_FASTA;   // --correct-format: CFRK_TEXT_FASTA / CFRK_TEXT_FASTQ
+  const char *correct_report = nullptr;   // --correct-report RFILE
   const char *normalize_out = nullptr; // --normalize-out NFILE
   uint32_t normalize_cutoff = 0;       // --normalize-cutoff C
   long long normalize_batch = CFRK_NORMALIZE_BATCH;   // --normalize-batch B
@@ -584,6 +602,50 @@ int write_filter(const Options &o, cfrk_ctx *ctx, int k) {
   return write_whole_file(o.filter_out, buf);
 }
 
+// --correct-out: the query reads corrected against the whole result on the device; every read is written to CFILE through
+// emit_selected (the corrected buffer, no span, no keep bytes), the cfrk_read_fix rows to --correct-report's RFILE
+int write_correct(const Options &o, cfrk_ctx *ctx) {
+  const cfrk_batch &q = g_qreads;
+  const size_t nN = (size_t)q.nN, nS = (size_t)q.nS;
+  std::string buf;
+  std::vector<cfrk_read_fix> fix(nS);
+  void *d_data = nullptr, *d_start = nullptr, *d_length = nullptr, *d_out = nullptr, *d_fix = nullptr;
+  const char *what = "cfrk_device_alloc";
+  int rc = 0;
+  if (nS && !(rc = cfrk_device_alloc(ctx, nN + 16, &d_data)) && !(rc = cfrk_device_alloc(ctx, nS * 8, &d_start)) &&
+      !(rc = cfrk_device_alloc(ctx, nS * 4, &d_length)) && !(rc = cfrk_device_alloc(ctx, nN + 16, &d_out)) &&
+      !(rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_fix), &d_fix))) {
+    what = "cfrk_memcpy_h2d";
+    if (!(rc = cfrk_memcpy_h2d(ctx, d_data, q.data, nN)) && !(rc = cfrk_memcpy_h2d(ctx, d_start, q.start, nS * 8)))
+      rc = cfrk_memcpy_h2d(ctx, d_length, q.length, nS * 4);
+    if (!rc) {
+      what = "cfrk_global_correct_reads_device";
+      rc = cfrk_global_correct_reads_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS,
+                                            o.correct_min_count, (int8_t *)d_out, (cfrk_read_fix *)d_fix);
+    }
+    if (!rc && o.correct_report) {
+      what = "cfrk_memcpy_d2h";
+      rc = cfrk_memcpy_d2h(ctx, fix.data(), d_fix, nS * sizeof(cfrk_read_fix));
+    }
+  }
+  if (!rc)
+    rc = emit_selected(ctx, q, d_out, d_start, d_length, nullptr, nullptr, 0, o.correct_names, g_qtext,
+                       g_qformat == CFRK_FORMAT_FASTQ ? CFRK_TEXT_FASTQ : CFRK_TEXT_FASTA, o.correct_format, o.query, buf, &what);
+  const int rc2 = nS ? cfrk_ctx_sync(ctx) : 0;
+  for (void *d : {d_data, d_start, d_length, d_out, d_fix}) if (d) cfrk_device_free(ctx, d);
+  if (rc) return die(ctx, rc, what);
+  if (rc2) return die(ctx, rc2, "cfrk_ctx_sync");
+  if (write_whole_file(o.correct_out, buf)) return 1;
+  if (!o.correct_report) return 0;
+  std::string rep;
+  char line[32];
+  for (size_t i = 0; i < nS; ++i) {
+    snprintf(line, sizeof line, "%u\t%u\n", (unsigned)fix[i].fixed, (unsigned)fix[i].left);
+    rep += line;
+  }
+  return write_whole_file(o.correct_report, rep);
+}
+
 // --normalize-out: the input's text and format, as the writer of the kept reads needs them
 std::vector<char> g_ntext;              // --normalize-names: the input file's bytes
 int g_nformat = CFRK_FORMAT_FASTA;
@@ -736,6 +798,7 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
       g_timing.stats = now_s() - s0;
     }
     if (o.filter_out && (rc = write_filter(o, ctx, o.k))) return rc;
+    if (o.correct_out && (rc = write_correct(o, ctx))) return rc;
   }
   if (early_free && owned) *early_free = std::thread([owned] { cfrk_host_free_batch(owned); });
   cfrk_global_last_add_ms(ctx, &g_timing.count_kernels_ms);
@@ -1152,6 +1215,7 @@ int run_query_db(const Options &o) {
   const double s0 = now_s();
   if (o.query_stats && (rc = write_query_stats(o, ctx))) return rc;
   if (o.filter_out && (rc = write_filter(o, ctx, k))) return rc;
+  if (o.correct_out && (rc = write_correct(o, ctx))) return rc;
   if (o.timing && o.query_stats)
     fprintf(stderr, "cfrk-timing {\"entries\": %llu, \"query_s\": %.4f, \"stats_s\": %.4f}\n", (unsigned long long)n, s0 - q0, now_s() - s0);
   else if (o.timing) fprintf(stderr, "cfrk-timing {\"entries\": %llu, \"query_s\": %.4f}\n", (unsigned long long)n, now_s() - q0);
@@ -1164,7 +1228,7 @@ int main(int argc, char **argv) {
   std::vector<const char *> pos;
   Options o;
   int batch_n = -1;
-  bool range_set = false, stats_below_set = false, filter_opt_set = false, normalize_opt_set = false, normalize_cutoff_set = false;
+  bool range_set = false, stats_below_set = false, filter_opt_set = false, correct_opt_set = false, correct_min_count_set = false, normalize_opt_set = false, normalize_cutoff_set = false;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--all-chunks")) o.all_chunks = true;
     else if (!strcmp(argv[i], "--native")) o.native = true;
@@ -1252,6 +1316,28 @@ int main(int argc, char **argv) {
         else { o.filter_max_median = x; o.filter_median = true; }
       }
     }
+    else if (!strncmp(argv[i], "--correct-", 10)) {
+      const char *opt = argv[i];
+      static const char *const known[] = {"--correct-out", "--correct-min-count", "--correct-names", "--correct-format", "--correct-report"};
+      bool is_known = false;
+      for (const char *n : known) is_known = is_known || !strcmp(opt, n);
+      if (!is_known) { fprintf(stderr, "cfrk: unknown option %s\n", opt); return 1; }
+      if (!strcmp(opt, "--correct-names")) { o.correct_names = true; correct_opt_set = true; continue; }
+      if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", opt); return 1; }
+      const char *v = argv[++i];
+      if (!strcmp(opt, "--correct-out")) { o.correct_out = v; continue; }
+      correct_opt_set = true;
+      if (!strcmp(opt, "--correct-format")) {
+        if (!strcmp(v, "fasta")) o.correct_format = CFRK_TEXT_FASTA;
+        else if (!strcmp(v, "fastq")) { o.correct_format = CFRK_TEXT_FASTQ; o.correct_names = true; }
+        else { fprintf(stderr, "cfrk: --correct-format takes fasta or fastq, not '%s'\n", v); return 1; }
+      } else if (!strcmp(opt, "--correct-report")) {
+        o.correct_report = v;
+      } else {
+        if (!parse_count(v, &o.correct_min_count)) { fprintf(stderr, "cfrk: %s needs a count (an integer from 0 to 4294967295), not '%s'\n", opt, v); return 1; }
+        correct_min_count_set = true;
+      }
+    }
     else if (!strncmp(argv[i], "--normalize-", 12)) {
       const char *opt = argv[i];
       static const char *const known[] = {"--normalize-out", "--normalize-cutoff", "--normalize-batch", "--normalize-names", "--normalize-format"};
@@ -1292,7 +1378,7 @@ int main(int argc, char **argv) {
   }
   // (refused here: before the input is parsed or a device is opened)
   if (o.sparse && (o.global || o.binary || o.histo || o.histo_only || range_set || o.query || o.query_out || o.query_only ||
-                   o.query_db || o.query_stats || stats_below_set || o.filter_out || filter_opt_set)) {
+                   o.query_db || o.query_stats || stats_below_set || o.filter_out || filter_opt_set || o.correct_out || correct_opt_set)) {
     fprintf(stderr, "cfrk: --sparse is a per-read mode: not with --global, --binary, --histo, --query or --min-count / --max-count\n");
     return 1;
   }
@@ -1324,7 +1410,11 @@ int main(int argc, char **argv) {
   if (stats_below_set && !o.query_stats) { fprintf(stderr, "cfrk: --stats-below needs --query-stats SFILE\n"); return 1; }
   if ((o.filter_out || filter_opt_set) && !o.query) { fprintf(stderr, "cfrk: --filter-out and the --filter- options need --query QFILE\n"); return 1; }
   if (filter_opt_set && !o.filter_out) { fprintf(stderr, "cfrk: the --filter- options need --filter-out FFILE\n"); return 1; }
-  if (o.query && !o.query_out && !o.query_stats && !o.filter_out) { fprintf(stderr, "cfrk: --query needs --query-out OFILE, --query-stats SFILE or --filter-out FFILE\n"); return 1; }
+  if (correct_opt_set && !o.correct_out) { fprintf(stderr, "cfrk: the --correct- options need --correct-out CFILE\n"); return 1; }
+  if (o.correct_out && !o.query) { fprintf(stderr, "cfrk: --correct-out and the --correct- options need --query QFILE\n"); return 1; }
+  if (o.correct_out && !correct_min_count_set) { fprintf(stderr, "cfrk: --correct-out needs --correct-min-count T\n"); return 1; }
+  if (o.query && !o.query_out && !o.query_stats && !o.filter_out && !o.correct_out) { fprintf(stderr, "cfrk: --query needs --query-out OFILE, --query-stats SFILE, --filter-out FFILE or --correct-out CFILE\n"); return 1; }
+  if (o.correct_out && o.gpus > 1) { fprintf(stderr, "cfrk: --correct-out runs on one device: not with --gpus above 1\n"); return 1; }
   if (o.filter_out && o.gpus > 1) { fprintf(stderr, "cfrk: --filter-out runs on one device: not with --gpus above 1\n"); return 1; }
   if (o.query_stats && o.gpus > 1) { fprintf(stderr, "cfrk: --query-stats runs on one device: not with --gpus above 1\n"); return 1; }
   if (o.query && batch_n >= 0) { fprintf(stderr, "cfrk: --query writes one file: not with --batch\n"); return 1; }
@@ -1342,8 +1432,12 @@ int main(int argc, char **argv) {
     fprintf(stderr, "cfrk: --filter-format fastq needs a FASTQ --query file: %s is read as FASTA\n", o.query);
     return 1;
   }
+  if (o.correct_format == CFRK_TEXT_FASTQ && g_qformat != CFRK_FORMAT_FASTQ) {
+    fprintf(stderr, "cfrk: --correct-format fastq needs a FASTQ --query file: %s is read as FASTA\n", o.query);
+    return 1;
+  }
   if (o.query && read_reads(o.query, g_qformat, 0, 0, &g_qreads)) return 1;
-  if (o.filter_names && read_whole_file(o.query, g_qtext)) return 1;
+  if ((o.filter_names || o.correct_names) && read_whole_file(o.query, g_qtext)) return 1;
   struct QFree { ~QFree() { if (g_qreads.data) cfrk_host_free_batch(&g_qreads); } } qfree;
   if (o.query_db) return run_query_db(o);
   if (pos.size() < 3) {

@@ -40,6 +40,8 @@ CFRK_SPANS_FAST_WINDOWS = 2048       # read spans: windows per read a lane group
 CFRK_NORMALIZE_BATCH = 262144        # normalise: reads per round when the caller names no batch
 # cfrk_read_span: bases [offset, offset + length) of a read
 READ_SPAN_DTYPE = np.dtype([("offset", "<i4"), ("length", "<i4")])
+# cfrk_read_fix: weak runs of a read that were corrected / left alone
+READ_FIX_DTYPE = np.dtype([("fixed", "<u4"), ("left", "<u4")])
 CFRK_SELECT_TILE_BYTES = 16384       # select: bytes of data_out per workgroup of the copy
 CFRK_SELECT_TILE_READS = 256         # reads per workgroup of its per-read passes
 CFRK_SELECT_SCAN_TILES = 1024        # tiles of reads per block of its tile scan
@@ -130,6 +132,8 @@ def load_library():
         "cfrk_global_read_stats_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
         "cfrk_global_read_spans": ([vp, vp, vp, vp, i64, i64, C.c_uint32, C.c_uint32, i32, vp], C.c_int),
         "cfrk_global_read_spans_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, C.c_uint32, i32, vp], C.c_int),
+        "cfrk_global_correct_reads": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp, vp], C.c_int),
+        "cfrk_global_correct_reads_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp, vp], C.c_int),
         "cfrk_global_normalize": ([vp, vp, vp, vp, i64, i64, C.c_uint32, i64, vp, C.POINTER(i64)], C.c_int),
         "cfrk_global_normalize_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, i64, vp, C.POINTER(i64)], C.c_int),
         "cfrk_reads_select": ([vp, vp, vp, vp, i64, i64, vp, vp, C.c_int32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
@@ -848,6 +852,34 @@ class GlobalCounter:
         self.ctx.check(self._L.cfrk_global_read_spans_device(self.ctx._h, vp(d_data), vp(d_start), vp(d_length), nN, nS,
                                                              int(min_count), int(max_count), int(mode), vp(d_out)),
                        "cfrk_global_read_spans_device")
+
+    def correct_reads(self, data, start, length, min_count):
+        """spectral correction of substitution errors against the job's result -> (data_out, fix): data_out is data with
+        the base written back wherever one wrong base explains an isolated run of weak windows (count < min_count) and
+        exactly one other base makes all of them solid; fix is np.ndarray[nS] of READ_FIX_DTYPE, the weak runs of every
+        read that were corrected / left alone.  The rule is in include/cfrk_abi.h; the job is only read."""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        nS = len(length)
+        if len(start) != nS:
+            raise ValueError("start and length differ in size")
+        if not 0 <= int(min_count) <= 0xFFFFFFFF:
+            raise ValueError("min_count outside 0 .. 2^32 - 1")
+        out = np.empty_like(data)
+        fix = np.zeros(nS, READ_FIX_DTYPE)
+        self.ctx.check(self._L.cfrk_global_correct_reads(self.ctx._h, _ptr(data), _ptr(start), _ptr(length), len(data), nS,
+                                                         int(min_count), _ptr(out), _ptr(fix)),
+                       "cfrk_global_correct_reads")
+        return out, fix
+
+    def correct_reads_device(self, d_data, d_start, d_length, nN, nS, min_count, d_data_out, d_fix=None):
+        """device form of correct_reads(): d_data_out nN bytes that do not overlap d_data, d_fix nS rows of 8 bytes or
+        None; no alignment requirement; returns with the copy and the last kernel enqueued on the context stream"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self.ctx.check(self._L.cfrk_global_correct_reads_device(self.ctx._h, vp(d_data), vp(d_start), vp(d_length), nN, nS,
+                                                                int(min_count), vp(d_data_out), vp(d_fix)),
+                       "cfrk_global_correct_reads_device")
 
     def normalize(self, data, start, length, cutoff, batch_reads=CFRK_NORMALIZE_BATCH):
         """digital normalisation (normalize-by-median) -> (keep, n_kept): the reads are taken in rounds of batch_reads;

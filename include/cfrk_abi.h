@@ -311,6 +311,50 @@ int cfrk_global_read_spans(cfrk_ctx *ctx, const int8_t *data, const int64_t *sta
                            int64_t nN, int64_t nS, uint32_t min_count, uint32_t max_count, int mode,
                            cfrk_read_span *out);
 
+/* Spectral correction of substitution errors: the base that a counted spectrum supports is written back where one wrong
+ * base explains an isolated stretch of weak windows (the rule of Quake, Musket, Lighter and BFC, without state between
+ * reads).  A read has L bases, codes c[0..L), and windows w = 0 .. W-1 with W = L - k + 1: the windows of
+ * cfrk_global_read_stats.  The count comes from the job's index, canonicalised in a CFRK_CANONICAL job; an absent k-mer
+ * counts 0, a saturated key reads CFRK_COUNT_MAX.
+ *   A window is INVALID when one of its k codes is not 0..3.  A valid window is SOLID when count >= min_count and WEAK
+ *   otherwise.  A WEAK RUN [a, b] is a maximal stretch of consecutive weak windows, of n = b - a + 1 windows.  Its left
+ *   neighbour is none (a == 0), solid or invalid; its right neighbour is none (b == W-1), solid or invalid.
+ * A run is ATTEMPTED in exactly three cases; each names one position p, and all windows of the run contain p:
+ *   interior   left solid, right solid, n == k    p = b
+ *   head       left none,  right solid, n <= k    p = b
+ *   tail       left solid, right none,  n <= k    p = a + k - 1
+ * Every other run is not attempted: n > k, an interior run shorter than k, a run with an invalid neighbour, a run that
+ * is the whole read (left none and right none).
+ * For an attempted run, take each of the three bases x != c[p].  Base x PASSES iff every window of [a, b], read with c[p]
+ * replaced by x, has count >= min_count.  If exactly one x passes, the output read has x at p and the run is FIXED; with
+ * none or more than one, nothing is written.
+ * Every run is judged against the ORIGINAL read.  Two attempted runs never share a base (their positions lie at least
+ * k + 1 apart, because a non-weak window separates them), so the result does not depend on any order.  min_count = 0
+ * makes nothing weak and the output equals the input.  Indels are out of scope; two errors within k bases of each other
+ * give one run longer than k and are left alone.
+ * Output: data_out is data, byte for byte (terminators and bytes that belong to no read included), except the corrected
+ * bases; start and length do not change.  data_out must not overlap data.  fix (may be NULL) gets one row per read.
+ * 1 <= k <= 64, reads of any length: reads of up to CFRK_SPANS_FAST_WINDOWS windows are handled by a group of lanes in
+ * LDS, longer ones by a workgroup on a slower, exact path.  No temporary device memory beyond the job's index.
+ * Errors and job state are those of cfrk_global_read_spans: CFRK_ERR_STATE before begin and on a CFRK_RUNS_ONLY job,
+ * CFRK_ERR_TABLE_FULL and CFRK_ERR_NOMEM as the query calls, CFRK_ERR_ARG for negative sizes, for NULL data / start /
+ * length with nS > 0 and for NULL data_out with nN > 0.  nS = 0 still copies the bytes.  The job is only read: its digest
+ * is the same before and after.
+ * Device form: no alignment requirement; start / length are not checked: a read whose range does not lie inside
+ * [0, nN) gets {0, 0} and its bytes are only copied (never an access outside the buffers).  The copy and the kernels are
+ * enqueued on the context stream; returns with the last kernel enqueued (the index build of a job's first query
+ * synchronises).
+ * Host form: checks start and length like cfrk_global_add (CFRK_ERR_LAYOUT), stages through the pool, synchronous. */
+typedef struct cfrk_read_fix {   /* 8 bytes, no padding */
+  uint32_t fixed;   /* weak runs of the read that were corrected (= bases changed)          */
+  uint32_t left;    /* weak runs that were not: not attempted, no base passed, or ambiguous */
+} cfrk_read_fix;
+int cfrk_global_correct_reads_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                     int64_t nN, int64_t nS, uint32_t min_count,
+                                     int8_t *d_data_out /* nN bytes */, cfrk_read_fix *d_fix /* nS rows, may be NULL */);
+int cfrk_global_correct_reads(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
+                              int64_t nN, int64_t nS, uint32_t min_count, int8_t *data_out, cfrk_read_fix *fix);
+
 /* Digital normalisation (normalize-by-median): the reads of the call are counted into the job ONLY while the k-mers they
  * carry are still rare among the reads kept so far, and keep[i] says which were.  The reads are taken in rounds of
  * batch_reads consecutive reads; round r holds the reads [r * batch_reads, min((r + 1) * batch_reads, nS)).
