@@ -810,46 +810,57 @@ static int normalize_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, int64_t batch_
 }
 
 // what both forms run on device buffers: the result into the HBM table as a merge puts it there, every round enqueued,
-// one synchronisation at the end for the kept reads and the overflow flag.  nS >= 1.
+// one synchronisation at the end for the kept reads and the overflow flag.  nS >= 1.  mode < 0: reads on their own; else
+// interleaved pairs joined by that CFRK_PAIR_* mode, the kept reads being twice the kept pairs the joins counted.
 static int normalize_core(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
-                          int64_t nS, uint32_t cutoff, int64_t batch_reads, uint8_t *d_keep, int64_t *n_kept) {
+                          int64_t nS, uint32_t cutoff, int64_t batch_reads, int mode, uint8_t *d_keep, int64_t *n_kept) {
   ctx->q_valid = false;
   int rc = cfrk_msp_flush_to_table(ctx);
   if (rc) return rc;
   cfrk_msp_note_table_write(ctx);
   void *p;
-  if ((rc = cfrk_pool_get(ctx, BUF_NORMALIZE, sizeof(unsigned long long), &p))) return rc;
-  unsigned long long *d_kept = (unsigned long long *)p;
-  HIP_TRY(ctx, hipMemsetAsync(d_kept, 0, sizeof *d_kept, ctx->stream));
-  if ((rc = cfrk_normalize_launch(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, d_keep, d_kept))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_NORMALIZE, 5 * sizeof(unsigned long long), &p))) return rc;
+  unsigned long long *d_kept = (unsigned long long *)p;     // [kept reads the judge counted | the joins' four pair counts]
+  HIP_TRY(ctx, hipMemsetAsync(d_kept, 0, 5 * sizeof *d_kept, ctx->stream));
+  if (mode < 0) rc = cfrk_normalize_launch(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, d_keep, d_kept);
+  else rc = cfrk_normalize_pairs_launch(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, mode, d_keep, d_kept, d_kept + 1);
+  if (rc) return rc;
   // snapshot of the flags for the next begin(), as an add leaves it
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_stats, ctx->g_stats, ST_NWORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   ctx->h_stats_valid = true;
   unsigned long long kept = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&kept, d_kept, sizeof kept, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&kept, mode < 0 ? d_kept : d_kept + 1, sizeof kept, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  *n_kept = (int64_t)kept;
+  *n_kept = (int64_t)(mode < 0 ? kept : 2 * kept);
   if (ctx->h_stats[ST_OVERFLOW]) return cfrk_fail(ctx, CFRK_ERR_TABLE_FULL, "table of %llu slots overflowed", (unsigned long long)ctx->g_cap);
   return CFRK_OK;
 }
 
-int cfrk_global_normalize_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
-                                 int64_t nN, int64_t nS, uint32_t cutoff, int64_t batch_reads, uint8_t *d_keep,
-                                 int64_t *n_kept) {
+// what a paired call asks in addition: whole pairs in the call and in every round
+static int normalize_pairs_check(cfrk_ctx *ctx, int64_t nS, int64_t batch_reads, int mode) {
+  if (mode != CFRK_PAIR_BOTH && mode != CFRK_PAIR_EITHER) return cfrk_fail(ctx, CFRK_ERR_ARG, "mode %d: CFRK_PAIR_BOTH or CFRK_PAIR_EITHER", mode);
+  if (nS & 1) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld interleaved reads: an odd number", (long long)nS);
+  if (batch_reads & 1) return cfrk_fail(ctx, CFRK_ERR_ARG, "batch_reads %lld: a round holds whole pairs", (long long)batch_reads);
+  return CFRK_OK;
+}
+
+// the device and the host form, of reads on their own (mode < 0) and of pairs
+static int normalize_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+                            int64_t nS, uint32_t cutoff, int64_t batch_reads, int mode, uint8_t *d_keep, int64_t *n_kept) {
   if (!ctx) return CFRK_ERR_ARG;
   int rc = normalize_check(ctx, nN, nS, batch_reads, d_data, d_start, d_length, d_keep, n_kept);
-  if (rc) return rc;
+  if (rc || (mode >= 0 && (rc = normalize_pairs_check(ctx, nS, batch_reads, mode)))) return rc;
   *n_kept = 0;
   if (nS == 0) return CFRK_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  return normalize_core(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, d_keep, n_kept);
+  return normalize_core(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, mode, d_keep, n_kept);
 }
 
-int cfrk_global_normalize(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
-                          int64_t nS, uint32_t cutoff, int64_t batch_reads, uint8_t *keep, int64_t *n_kept) {
+static int normalize_host(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN, int64_t nS,
+                          uint32_t cutoff, int64_t batch_reads, int mode, uint8_t *keep, int64_t *n_kept) {
   if (!ctx) return CFRK_ERR_ARG;
   int rc = normalize_check(ctx, nN, nS, batch_reads, data, start, length, keep, n_kept);
-  if (rc) return rc;
+  if (rc || (mode >= 0 && (rc = normalize_pairs_check(ctx, nS, batch_reads, mode)))) return rc;
   *n_kept = 0;
   if (nS == 0) return CFRK_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -857,10 +868,34 @@ int cfrk_global_normalize(cfrk_ctx *ctx, const int8_t *data, const int64_t *star
   StagePart x[1] = {{nullptr, (size_t)nS, nullptr}};
   StagedReads d;
   if ((rc = stage_reads(ctx, BUF_QUERY_IN, data, start, length, nN, nS, STAGE_TABLE, x, 1, &d))) return rc;
-  if ((rc = normalize_core(ctx, d.data, d.start, d.length, nN, nS, cutoff, batch_reads, (uint8_t *)x[0].dev, n_kept)) &&
+  if ((rc = normalize_core(ctx, d.data, d.start, d.length, nN, nS, cutoff, batch_reads, mode, (uint8_t *)x[0].dev, n_kept)) &&
       rc != CFRK_ERR_TABLE_FULL) return stage_drain(ctx, rc);
   const int rc2 = cfrk_memcpy_d2h(ctx, keep, x[0].dev, (size_t)nS);
   return rc ? rc : rc2;
+}
+
+int cfrk_global_normalize_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                 int64_t nN, int64_t nS, uint32_t cutoff, int64_t batch_reads, uint8_t *d_keep,
+                                 int64_t *n_kept) {
+  return normalize_device(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, -1, d_keep, n_kept);
+}
+
+int cfrk_global_normalize(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                          int64_t nS, uint32_t cutoff, int64_t batch_reads, uint8_t *keep, int64_t *n_kept) {
+  return normalize_host(ctx, data, start, length, nN, nS, cutoff, batch_reads, -1, keep, n_kept);
+}
+
+int cfrk_global_normalize_pairs_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                       int64_t nN, int64_t nS, uint32_t cutoff, int64_t batch_reads, int mode, uint8_t *d_keep,
+                                       int64_t *n_kept) {
+  if (ctx && mode < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "mode %d: CFRK_PAIR_BOTH or CFRK_PAIR_EITHER", mode);
+  return normalize_device(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, mode, d_keep, n_kept);
+}
+
+int cfrk_global_normalize_pairs(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                                int64_t nS, uint32_t cutoff, int64_t batch_reads, int mode, uint8_t *keep, int64_t *n_kept) {
+  if (ctx && mode < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "mode %d: CFRK_PAIR_BOTH or CFRK_PAIR_EITHER", mode);
+  return normalize_host(ctx, data, start, length, nN, nS, cutoff, batch_reads, mode, keep, n_kept);
 }
 
 int cfrk_global_last_add_ms(cfrk_ctx *ctx, float *ms) {

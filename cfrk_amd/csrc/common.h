@@ -45,7 +45,9 @@ enum {  // pool slots
   BUF_EMIT,                                   // text emitter (text_out.hip): size words, the read tiles' aggregates, their scan
   BUF_EMIT_OFF,                               // the kept reads' output offsets and input indices
   BUF_EMIT_IN, BUF_EMIT_OUT,                  // staging of cfrk_reads_emit_text alone (reads, spans, keep, records, text in; text out)
-  BUF_NORMALIZE,                              // normalise (normalize.hip): the call's kept-read counter
+  BUF_NORMALIZE,                              // normalise (normalize.hip): the call's kept-read counter; a paired call's four pair counts behind it
+  BUF_PAIRS,                                  // pairs (pairs.hip): the join's four counts, the name check's two results
+  BUF_PAIRS_IN,                               // staging of cfrk_reads_pair_keep and cfrk_text_pair_check alone
   BUF_NSLOTS
 };
 
@@ -167,6 +169,16 @@ int cfrk_read_correct_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t 
 // are added to *d_kept.  The result must live in the HBM table.  nS >= 1, batch_reads >= 1.
 int cfrk_normalize_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
                           int64_t nS, uint32_t cutoff, int64_t batch_reads, uint8_t *d_keep, unsigned long long *d_kept);
+// normalize.hip: the same for interleaved pairs (nS and batch_reads even): a join launch between judge and insert applies
+// `mode` to the keep bytes in place.  The judge kernels' own count goes to *d_scratch; the kept PAIRS are added to *d_pairs.
+int cfrk_normalize_pairs_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+                                int64_t nS, uint32_t cutoff, int64_t batch_reads, int mode, uint8_t *d_keep,
+                                unsigned long long *d_scratch, unsigned long long *d_pairs);
+// pairs.hip: the join of n_pairs >= 1 pairs left enqueued, its four counts ADDED to d_counts[0 .. 4)
+int cfrk_pair_join_launch(cfrk_ctx *ctx, int64_t n_pairs, int stride, int mode, int32_t min_len, const uint8_t *d_keep_a,
+                          const uint8_t *d_keep_b, const cfrk_read_span *d_span_a, const cfrk_read_span *d_span_b,
+                          const int32_t *d_length_a, const int32_t *d_length_b, uint8_t *d_pair_a, uint8_t *d_pair_b,
+                          uint8_t *d_orphan_a, uint8_t *d_orphan_b, unsigned long long *d_counts);
 // sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
 // enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
 int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,

@@ -6,6 +6,10 @@
 // rounds: the stream orders judge(r) < insert(r) < judge(r + 1), so a judge kernel never runs beside a writer and reads
 // the table with plain loads (table.h: table_find1 / table_find2), and the inserts are commutative saturating adds
 // (table_add1 / table_add2).  Keep bytes and counts are therefore independent of scheduling.
+// A paired call (interleaved mates 2j, 2j + 1) puts ONE more launch between the two phases of a round: the join of
+// pairs.hip rewrites the round's keep bytes in place so that both mates of a pair carry the same byte, and counts the
+// kept pairs.  It is a launch of its own and not part of the insert kernels because the two mates of a pair may belong
+// to different size classes, hence to different launches; the kernels of this file are the same in both kinds of call.
 //
 // The judge needs no median select: with W valid windows the lower median is element (W - 1) / 2 of the sorted counts,
 // which is below the cutoff iff more than (W - 1) / 2 counts are -- one count per lane and one sum across the group.
@@ -236,9 +240,10 @@ __global__ __launch_bounds__(NORM_LONG_NT) void normalize_insert_long_kernel(
   });
 }
 
-// the six launches of one round: reads [0, nS) of the arrays as they are passed
+// the launches of one round: reads [0, nS) of the arrays as they are passed; judge, then (paired calls: the join of
+// pairs.hip between the two) insert
 template <bool TWO, bool CANON>
-void launch_round(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+void launch_judge(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
                   int64_t nS, const TableView &t, uint32_t cutoff, uint8_t *d_keep, unsigned long long *d_kept) {
   const ClassGrids g = class_grids(nS, ctx->num_cus, NORM_LONG_NT);
   const int k = ctx->g_k;
@@ -248,12 +253,52 @@ void launch_round(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, c
                      d_length, nN, nS, k, t, cutoff, d_keep, d_kept);
   hipLaunchKernelGGL((normalize_judge_long_kernel<TWO, CANON>), dim3(g.glong), dim3(NORM_LONG_NT), 0, ctx->stream, d_data,
                      d_start, d_length, nN, nS, k, t, cutoff, d_keep, d_kept);
+}
+template <bool TWO, bool CANON>
+void launch_insert(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+                   int64_t nS, const TableView &t, const uint8_t *d_keep) {
+  const ClassGrids g = class_grids(nS, ctx->num_cus, NORM_LONG_NT);
+  const int k = ctx->g_k;
   hipLaunchKernelGGL((normalize_insert_kernel<16, TWO, CANON>), dim3(g.g16), dim3(256), 0, ctx->stream, d_data, d_start,
                      d_length, nN, nS, k, t, d_keep);
   hipLaunchKernelGGL((normalize_insert_kernel<64, TWO, CANON>), dim3(g.g64), dim3(64), 0, ctx->stream, d_data, d_start,
                      d_length, nN, nS, k, t, d_keep);
   hipLaunchKernelGGL((normalize_insert_long_kernel<TWO, CANON>), dim3(g.glong), dim3(NORM_LONG_NT), 0, ctx->stream, d_data,
                      d_start, d_length, nN, nS, k, t, d_keep);
+}
+
+// every round of a call; d_pairs NULL: reads on their own (the judge counts the kept reads into *d_kept); else interleaved
+// pairs, `mode` applied to the round's keep bytes in place by the join, which adds its four counts to d_pairs[0 .. 4)
+template <bool TWO, bool CANON>
+int launch_rounds(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN, int64_t nS,
+                  uint32_t cutoff, int64_t batch_reads, int mode, uint8_t *d_keep, unsigned long long *d_kept,
+                  unsigned long long *d_pairs) {
+  const TableView t = cfrk_table_view(ctx);
+  for (int64_t off = 0; off < nS;) {
+    const int64_t nb = nS - off < batch_reads ? nS - off : batch_reads;
+    launch_judge<TWO, CANON>(ctx, d_data, d_start + off, d_length + off, nN, nb, t, cutoff, d_keep + off, d_kept);
+    if (d_pairs) {
+      HIP_TRY(ctx, hipGetLastError());
+      if (const int rc = cfrk_pair_join_launch(ctx, nb / 2, 2, mode, 0, d_keep + off, d_keep + off + 1, nullptr, nullptr, nullptr,
+                                               nullptr, d_keep + off, d_keep + off + 1, nullptr, nullptr, d_pairs)) return rc;
+    }
+    launch_insert<TWO, CANON>(ctx, d_data, d_start + off, d_length + off, nN, nb, t, d_keep + off);
+    HIP_TRY(ctx, hipGetLastError());
+    off += nb;
+  }
+  return CFRK_OK;
+}
+
+int launch_call(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN, int64_t nS,
+                uint32_t cutoff, int64_t batch_reads, int mode, uint8_t *d_keep, unsigned long long *d_kept,
+                unsigned long long *d_pairs) {
+  const bool canon = (ctx->g_flags & CFRK_CANONICAL) != 0;
+  if (ctx->g_two) {
+    if (canon) return launch_rounds<true, true>(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, mode, d_keep, d_kept, d_pairs);
+    return launch_rounds<true, false>(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, mode, d_keep, d_kept, d_pairs);
+  }
+  if (canon) return launch_rounds<false, true>(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, mode, d_keep, d_kept, d_pairs);
+  return launch_rounds<false, false>(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, mode, d_keep, d_kept, d_pairs);
 }
 
 }  // namespace
@@ -264,19 +309,14 @@ void launch_round(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, c
 // synchronisation.  Arguments are checked by the callers (abi.hip).  nS >= 1, batch_reads >= 1.
 int cfrk_normalize_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
                           int64_t nS, uint32_t cutoff, int64_t batch_reads, uint8_t *d_keep, unsigned long long *d_kept) {
-  const TableView t = cfrk_table_view(ctx);
-  const bool canon = (ctx->g_flags & CFRK_CANONICAL) != 0;
-  for (int64_t off = 0; off < nS;) {
-    const int64_t nb = nS - off < batch_reads ? nS - off : batch_reads;
-    if (ctx->g_two) {
-      if (canon) launch_round<true, true>(ctx, d_data, d_start + off, d_length + off, nN, nb, t, cutoff, d_keep + off, d_kept);
-      else launch_round<true, false>(ctx, d_data, d_start + off, d_length + off, nN, nb, t, cutoff, d_keep + off, d_kept);
-    } else {
-      if (canon) launch_round<false, true>(ctx, d_data, d_start + off, d_length + off, nN, nb, t, cutoff, d_keep + off, d_kept);
-      else launch_round<false, false>(ctx, d_data, d_start + off, d_length + off, nN, nb, t, cutoff, d_keep + off, d_kept);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    off += nb;
-  }
-  return CFRK_OK;
+  return launch_call(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, 0, d_keep, d_kept, nullptr);
+}
+
+// The same for interleaved pairs: judge (the kernels' own count of kept reads goes to *d_scratch, which nobody reads),
+// join, insert per round; the join's counts are added to d_pairs[0 .. 4) (zeroed by the caller), the kept reads of the
+// call are twice its kept pairs.  nS >= 2, nS and batch_reads even: a round holds whole pairs.
+int cfrk_normalize_pairs_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+                                int64_t nS, uint32_t cutoff, int64_t batch_reads, int mode, uint8_t *d_keep,
+                                unsigned long long *d_scratch, unsigned long long *d_pairs) {
+  return launch_call(ctx, d_data, d_start, d_length, nN, nS, cutoff, batch_reads, mode, d_keep, d_scratch, d_pairs);
 }

@@ -97,6 +97,29 @@
 //                    qualities -- the records have in the input: the input's text goes to the device and
 //                    cfrk_text_index_device / cfrk_reads_emit_text_device write NFILE there, exactly as --filter-names and
 //                    --filter-format do for FFILE.  Either option selects this writer; fastq needs a FASTQ input
+//   --paired         paired-end reads, interleaved: records 2j and 2j + 1 of the file the reads come from are the mates of
+//                    pair j.  That file is QFILE for --filter-out and --correct-out and the input for --normalize-out.  An odd
+//                    number of records is an error.  Where the file's text is on the device (the --*-names / --*-format
+//                    writers) the mates' names are compared there (cfrk_text_pair_check_device: the header up to the first
+//                    blank, a trailing /1 with /2 dropped) and the first pair that does not match is an error that shows both
+//                    headers.  --filter-out: FFILE receives a read only together with its mate (cfrk_reads_pair_keep_device,
+//                    CFRK_PAIR_BOTH, on the spans, --filter-min-len and the median keep bytes), so FFILE stays a valid
+//                    interleaved file.  --normalize-out: cfrk_global_normalize_pairs_device replaces the single-read call: a
+//                    pair is kept or dropped as a whole.  --correct-out writes every read: pairing is only checked.  One of
+//                    the three outputs is needed.  Not with --gpus above 1 or --batch
+//   --pair-check on|off  (with --paired / --query2) off skips the comparison of the mates' names
+//   --pair-mode either|both  (with --paired --normalize-out) keep a pair if either mate would be kept (the default: khmer's
+//                    normalize-by-median --paired) or only if both would be
+//   --query2 QFILE2  (with --query and --filter-out / --correct-out) paired-end reads in two files: record j of QFILE and
+//                    record j of QFILE2 are the mates of pair j; unequal record counts are an error.  Spans, statistics and
+//                    correction run per file; the join runs on the two files' arrays side by side
+//   --filter-out2 FFILE2  (with --query2, required with --filter-out) QFILE2's mates of the kept pairs, written from
+//                    QFILE2's own text
+//   --filter-orphans OFILE  (with --paired / --query2 and --filter-out) the reads that pass the filter while their mate does
+//                    not, in input order (QFILE's, then QFILE2's), through the same writer.  Without it they are dropped; a
+//                    line on stderr says how many there were either way
+//   --correct-out2 CFILE2  (with --query2, required with --correct-out) QFILE2's reads, corrected; --correct-report lists
+//                    QFILE's records, then QFILE2's
 //   --query-only     (with --query) write OFILE / SFILE / FFILE / CFILE only: the counts are not exported and the output path is left
 //                    untouched
 //   --query-db DB.bin  (with --query, no positional arguments) query a saved --binary count file without recounting; k and
@@ -191,6 +214,10 @@ struct Options {
   int format = -1;                                                  // --format: CFRK_FORMAT_FASTA / _FASTQ, -1 = by the first byte
   int min_qual = 0;                                                 // --min-qual
   bool min_qual_set = false;
+  bool paired = false, pair_check = true;                           // --paired, --pair-check on|off
+  int pair_mode = CFRK_PAIR_EITHER;                                 // --pair-mode (the normalise call's; the filter joins by CFRK_PAIR_BOTH)
+  const char *query2 = nullptr, *filter_out2 = nullptr, *filter_orphans = nullptr, *correct_out2 = nullptr;
+  bool mates() const { return paired || query2; }
 };
 
 // --timing: wall-clock seconds by phase (one file; with --batch the last file's)
@@ -424,6 +451,15 @@ int write_histo(const Options &o, const Spectrum &sp) {
 cfrk_batch g_qreads{};
 int g_qformat = CFRK_FORMAT_FASTA;       // what QFILE was read as
 std::vector<char> g_qtext;              // --filter-names: QFILE's bytes
+cfrk_batch g_qreads2{};                 // --query2: QFILE2's reads and bytes (the format is QFILE's)
+std::vector<char> g_qtext2;
+
+// --paired: an interleaved file holds whole pairs; 1 (the error reported) when it does not
+int odd_records(const char *path, int64_t nS) {
+  if (!(nS & 1)) return 0;
+  fprintf(stderr, "cfrk: --paired: %s holds %lld records, an odd number: the last read has no mate\n", path, (long long)nS);
+  return 1;
+}
 
 // 0, or 1 (the error reported)
 int read_whole_file(const char *path, std::vector<char> &buf) {
@@ -556,56 +592,153 @@ int emit_selected(cfrk_ctx *ctx, const cfrk_batch &q, const void *d_data, const 
   return 0;
 }
 
-// --filter-out: the query reads trimmed to their solid spans and filtered, on the device, written to FFILE as FASTA
-// named by record number, or -- --filter-names -- as FASTA / FASTQ text with QFILE's names and qualities (emit_selected)
-int write_filter(const Options &o, cfrk_ctx *ctx, int k) {
-  const cfrk_batch &q = g_qreads;
-  const size_t nN = (size_t)q.nN, nS = (size_t)q.nS;
-  std::string buf;
-  void *d_data = nullptr, *d_start = nullptr, *d_length = nullptr, *d_span = nullptr, *d_keep = nullptr, *d_stats = nullptr;
+// --paired / --query2 with a names writer: the mates' names compared on the device.  The text(s) go up and are indexed for
+// this alone (the writers index their own copy again behind it); text_b NULL: one interleaved text, pairs are records
+// 2j and 2j + 1.  0, or the exit status with the error reported: the first bad pair shows both headers.
+int check_mate_names(cfrk_ctx *ctx, int64_t n_pairs, int text_format, const std::vector<char> &text_a, const char *path_a,
+                     const std::vector<char> *text_b, const char *path_b) {
+  if (n_pairs == 0) return 0;
+  const int64_t per = text_b ? n_pairs : 2 * n_pairs;              // records of a text
+  const std::vector<char> &tb = text_b ? *text_b : text_a;
+  void *d_ta = nullptr, *d_tb = nullptr, *d_ra = nullptr, *d_rb = nullptr;
   const char *what = "cfrk_device_alloc";
-  int rc = 0;
-  const bool trim = o.filter_trim >= 0;
-  if (nS && !(rc = cfrk_device_alloc(ctx, nN + 16, &d_data)) && !(rc = cfrk_device_alloc(ctx, nS * 8, &d_start)) &&
-      !(rc = cfrk_device_alloc(ctx, nS * 4, &d_length)) &&
-      !(trim && (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_span), &d_span))) &&
-      !(o.filter_median && ((rc = cfrk_device_alloc(ctx, nS, &d_keep)) || (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_stats), &d_stats))))) {
+  int64_t first = -1, bad = 0, got = 0;
+  cfrk_text_record ra{}, rb{};
+  int rc;
+  auto up = [&](const std::vector<char> &t, const char *path, void **d_t, void **d_r) {
+    what = "cfrk_device_alloc";
+    if ((rc = cfrk_device_alloc(ctx, t.size() + 16, d_t)) || (rc = cfrk_device_alloc(ctx, (size_t)per * sizeof(cfrk_text_record), d_r))) return;
     what = "cfrk_memcpy_h2d";
-    if (!(rc = cfrk_memcpy_h2d(ctx, d_data, q.data, nN)) && !(rc = cfrk_memcpy_h2d(ctx, d_start, q.start, nS * 8)))
-      rc = cfrk_memcpy_h2d(ctx, d_length, q.length, nS * 4);
-    if (!rc && trim) {
-      what = "cfrk_global_read_spans_device";
-      rc = cfrk_global_read_spans_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS,
-                                         o.filter_min_count, o.filter_max_count, o.filter_trim, (cfrk_read_span *)d_span);
-    }
-    if (!rc && o.filter_median) {
-      // the rows come down (32 bytes per read), the keep bytes go up (1 byte per read)
-      what = "cfrk_global_read_stats_device";
-      std::vector<cfrk_read_stats> st(nS);
-      std::vector<uint8_t> keep(nS);
-      if (!(rc = cfrk_global_read_stats_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS, 0,
-                                               (cfrk_read_stats *)d_stats)) &&
-          !(rc = cfrk_memcpy_d2h(ctx, st.data(), d_stats, nS * sizeof(cfrk_read_stats)))) {
-        for (size_t i = 0; i < nS; ++i) keep[i] = st[i].median >= o.filter_min_median && st[i].median <= o.filter_max_median;
-        rc = cfrk_memcpy_h2d(ctx, d_keep, keep.data(), nS);
-      }
+    if ((rc = cfrk_memcpy_h2d(ctx, *d_t, t.data(), t.size()))) return;
+    what = "cfrk_text_index_device";
+    if ((rc = cfrk_text_index_device(ctx, (const uint8_t *)*d_t, t.size(), text_format, (cfrk_text_record *)*d_r, (uint64_t)per, &got))) return;
+    if (got != per) { fprintf(stderr, "cfrk: %s: %lld records parsed, %lld indexed\n", path, (long long)per, (long long)got); rc = CFRK_ERR_LAYOUT; }
+  };
+  up(text_a, path_a, &d_ta, &d_ra);
+  if (!rc && text_b) up(tb, path_b, &d_tb, &d_rb);
+  if (!rc) {
+    const cfrk_text_record *rec_a = (const cfrk_text_record *)d_ra, *rec_b = text_b ? (const cfrk_text_record *)d_rb : rec_a + 1;
+    what = "cfrk_text_pair_check_device";
+    rc = cfrk_text_pair_check_device(ctx, n_pairs, text_b ? 1 : 2, (const uint8_t *)d_ta, text_a.size(), rec_a,
+                                     (const uint8_t *)(text_b ? d_tb : d_ta), tb.size(), rec_b, &first, &bad);
+    if (!rc && bad) {
+      const int64_t stride = text_b ? 1 : 2;
+      what = "cfrk_memcpy_d2h";
+      if (!(rc = cfrk_memcpy_d2h(ctx, &ra, rec_a + first * stride, sizeof ra))) rc = cfrk_memcpy_d2h(ctx, &rb, rec_b + first * stride, sizeof rb);
     }
   }
-  const long min_len = o.filter_min_len >= 0 ? o.filter_min_len : (long)k;
-  if (!rc)
-    rc = emit_selected(ctx, q, d_data, d_start, d_length, d_span, d_keep, min_len, o.filter_names, g_qtext,
-                       g_qformat == CFRK_FORMAT_FASTQ ? CFRK_TEXT_FASTQ : CFRK_TEXT_FASTA, o.filter_format, o.query, buf, &what);
-  const int rc2 = nS ? cfrk_ctx_sync(ctx) : 0;
-  for (void *d : {d_data, d_start, d_length, d_span, d_keep, d_stats}) if (d) cfrk_device_free(ctx, d);
+  const int rc2 = cfrk_ctx_sync(ctx);
+  for (void *d : {d_ta, d_tb, d_ra, d_rb}) if (d) cfrk_device_free(ctx, d);
   if (rc) return die(ctx, rc, what);
   if (rc2) return die(ctx, rc2, "cfrk_ctx_sync");
-  return write_whole_file(o.filter_out, buf);
+  if (!bad) return 0;
+  // (the index wrote both records from these very texts: their header ranges lie inside them)
+  fprintf(stderr, "cfrk: pair %lld: the mates' names differ: '%.*s' (%s) and '%.*s' (%s); %lld pair(s) in all (--pair-check off skips this check)\n",
+          (long long)first, (int)ra.head_len, text_a.data() + ra.head_off, path_a, (int)rb.head_len, tb.data() + rb.head_off, text_b ? path_b : path_a,
+          (long long)bad);
+  return 1;
+}
+
+// --filter-out: one file's reads on the device with what the filter computes of them: the solid spans (--filter-trim) and
+// the keep bytes of the median rule (--filter-min-median / --filter-max-median); NULL where the run asks for neither
+struct FilterSide {
+  cfrk_ctx *ctx;
+  void *d_data = nullptr, *d_start = nullptr, *d_length = nullptr, *d_span = nullptr, *d_keep = nullptr, *d_stats = nullptr;
+  ~FilterSide() { for (void *d : {d_data, d_start, d_length, d_span, d_keep, d_stats}) if (d) cfrk_device_free(ctx, d); }   // (the caller has synchronised)
+  int prepare(const Options &o, const cfrk_batch &q, const char **what) {
+    const size_t nN = (size_t)q.nN, nS = (size_t)q.nS;
+    const bool trim = o.filter_trim >= 0;
+    int rc = 0;
+    *what = "cfrk_device_alloc";
+    if (nS && !(rc = cfrk_device_alloc(ctx, nN + 16, &d_data)) && !(rc = cfrk_device_alloc(ctx, nS * 8, &d_start)) &&
+        !(rc = cfrk_device_alloc(ctx, nS * 4, &d_length)) &&
+        !(trim && (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_span), &d_span))) &&
+        !(o.filter_median && ((rc = cfrk_device_alloc(ctx, nS, &d_keep)) || (rc = cfrk_device_alloc(ctx, nS * sizeof(cfrk_read_stats), &d_stats))))) {
+      *what = "cfrk_memcpy_h2d";
+      if (!(rc = cfrk_memcpy_h2d(ctx, d_data, q.data, nN)) && !(rc = cfrk_memcpy_h2d(ctx, d_start, q.start, nS * 8)))
+        rc = cfrk_memcpy_h2d(ctx, d_length, q.length, nS * 4);
+      if (!rc && trim) {
+        *what = "cfrk_global_read_spans_device";
+        rc = cfrk_global_read_spans_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS,
+                                           o.filter_min_count, o.filter_max_count, o.filter_trim, (cfrk_read_span *)d_span);
+      }
+      if (!rc && o.filter_median) {
+        // the rows come down (32 bytes per read), the keep bytes go up (1 byte per read)
+        *what = "cfrk_global_read_stats_device";
+        std::vector<cfrk_read_stats> st(nS);
+        std::vector<uint8_t> keep(nS);
+        if (!(rc = cfrk_global_read_stats_device(ctx, (const int8_t *)d_data, (const int64_t *)d_start, (const int32_t *)d_length, q.nN, q.nS, 0,
+                                                 (cfrk_read_stats *)d_stats)) &&
+            !(rc = cfrk_memcpy_d2h(ctx, st.data(), d_stats, nS * sizeof(cfrk_read_stats)))) {
+          for (size_t i = 0; i < nS; ++i) keep[i] = st[i].median >= o.filter_min_median && st[i].median <= o.filter_max_median;
+          rc = cfrk_memcpy_h2d(ctx, d_keep, keep.data(), nS);
+        }
+      }
+    }
+    return rc;
+  }
+};
+
+// the query reads trimmed to their solid spans and filtered, on the device, written to FFILE as FASTA named by record
+// number, or -- --filter-names -- as FASTA / FASTQ text with QFILE's names and qualities (emit_selected).
+// --paired / --query2: the spans, --filter-min-len and the median keep bytes are joined per pair on the device
+// (CFRK_PAIR_BOTH); FFILE (and FFILE2) receive whole pairs, --filter-orphans' OFILE the survivors whose mate did not
+// survive, every file through the same writer with the joined bytes as its keep bytes.
+int write_filter(const Options &o, cfrk_ctx *ctx, int k) {
+  const cfrk_batch &q = g_qreads, &q2 = g_qreads2;
+  const size_t nS = (size_t)q.nS;
+  const int tf = g_qformat == CFRK_FORMAT_FASTQ ? CFRK_TEXT_FASTQ : CFRK_TEXT_FASTA;
+  const long min_len = o.filter_min_len >= 0 ? o.filter_min_len : (long)k;
+  std::string buf, buf2, orphans;
+  FilterSide a{ctx}, b{ctx};
+  void *d_pair = nullptr, *d_orphan = nullptr;
+  const char *what = "";
+  cfrk_pair_counts pc{};
+  auto emit = [&](const cfrk_batch &r, const FilterSide &f, const void *d_keep, const std::vector<char> &text, const char *path, std::string &out) {
+    return emit_selected(ctx, r, f.d_data, f.d_start, f.d_length, f.d_span, d_keep, min_len, o.filter_names, text, tf, o.filter_format, path, out, &what);
+  };
+  int rc = a.prepare(o, q, &what);
+  if (!rc && o.query2) rc = b.prepare(o, q2, &what);
+  if (!rc && !o.mates()) rc = emit(q, a, a.d_keep, g_qtext, o.query, buf);
+  else if (!rc && nS) {
+    // mate B of pair j: the next element of the one file's arrays, or element j of QFILE2's; the joined bytes of both
+    // layouts lie in one array of a byte per read (QFILE2's behind QFILE's)
+    const size_t step = o.query2 ? 0 : 1, total = o.query2 ? 2 * nS : nS, off_b = o.query2 ? nS : 1;
+    const FilterSide &fb = o.query2 ? b : a;
+    what = "cfrk_device_alloc";
+    if (!(rc = cfrk_device_alloc(ctx, total, &d_pair)) && !(rc = cfrk_device_alloc(ctx, total, &d_orphan))) {
+      what = "cfrk_reads_pair_keep_device";
+      rc = cfrk_reads_pair_keep_device(ctx, (int64_t)(o.query2 ? nS : nS / 2), o.query2 ? 1 : 2, CFRK_PAIR_BOTH, (int32_t)min_len,
+                                       (const uint8_t *)a.d_keep, fb.d_keep ? (const uint8_t *)fb.d_keep + step : nullptr,
+                                       (const cfrk_read_span *)a.d_span, fb.d_span ? (const cfrk_read_span *)fb.d_span + step : nullptr,
+                                       (const int32_t *)a.d_length, (const int32_t *)fb.d_length + step, (uint8_t *)d_pair,
+                                       (uint8_t *)d_pair + off_b, (uint8_t *)d_orphan, (uint8_t *)d_orphan + off_b, &pc);
+    }
+    if (!rc) rc = emit(q, a, d_pair, g_qtext, o.query, buf);
+    if (!rc && o.query2) rc = emit(q2, b, (const uint8_t *)d_pair + nS, g_qtext2, o.query2, buf2);
+    if (!rc && o.filter_orphans) rc = emit(q, a, d_orphan, g_qtext, o.query, orphans);
+    if (!rc && o.filter_orphans && o.query2) {
+      std::string more;
+      if (!(rc = emit(q2, b, (const uint8_t *)d_orphan + nS, g_qtext2, o.query2, more))) orphans += more;
+    }
+  }
+  const int rc2 = nS ? cfrk_ctx_sync(ctx) : 0;
+  for (void *d : {d_pair, d_orphan}) if (d) cfrk_device_free(ctx, d);
+  if (rc) return die(ctx, rc, what);
+  if (rc2) return die(ctx, rc2, "cfrk_ctx_sync");
+  if (o.mates())
+    fprintf(stderr, "cfrk: filter: %lld pairs kept, %lld orphans (%lld + %lld) %s, %lld pairs dropped\n", (long long)pc.pairs,
+            (long long)(pc.orphans_a + pc.orphans_b), (long long)pc.orphans_a, (long long)pc.orphans_b,
+            o.filter_orphans ? "written" : "dropped", (long long)pc.dropped);
+  if (write_whole_file(o.filter_out, buf)) return 1;
+  if (o.query2 && write_whole_file(o.filter_out2, buf2)) return 1;
+  return o.filter_orphans ? write_whole_file(o.filter_orphans, orphans) : 0;
 }
 
 // --correct-out: the query reads corrected against the whole result on the device; every read is written to CFILE through
 // emit_selected (the corrected buffer, no span, no keep bytes), the cfrk_read_fix rows to --correct-report's RFILE
-int write_correct(const Options &o, cfrk_ctx *ctx) {
-  const cfrk_batch &q = g_qreads;
+int write_correct(const Options &o, cfrk_ctx *ctx, const cfrk_batch &q, const std::vector<char> &qtext, const char *qpath, const char *out_path,
+                  std::string *report) {
   const size_t nN = (size_t)q.nN, nS = (size_t)q.nS;
   std::string buf;
   std::vector<cfrk_read_fix> fix(nS);
@@ -629,21 +762,36 @@ int write_correct(const Options &o, cfrk_ctx *ctx) {
     }
   }
   if (!rc)
-    rc = emit_selected(ctx, q, d_out, d_start, d_length, nullptr, nullptr, 0, o.correct_names, g_qtext,
-                       g_qformat == CFRK_FORMAT_FASTQ ? CFRK_TEXT_FASTQ : CFRK_TEXT_FASTA, o.correct_format, o.query, buf, &what);
+    rc = emit_selected(ctx, q, d_out, d_start, d_length, nullptr, nullptr, 0, o.correct_names, qtext,
+                       g_qformat == CFRK_FORMAT_FASTQ ? CFRK_TEXT_FASTQ : CFRK_TEXT_FASTA, o.correct_format, qpath, buf, &what);
   const int rc2 = nS ? cfrk_ctx_sync(ctx) : 0;
   for (void *d : {d_data, d_start, d_length, d_out, d_fix}) if (d) cfrk_device_free(ctx, d);
   if (rc) return die(ctx, rc, what);
   if (rc2) return die(ctx, rc2, "cfrk_ctx_sync");
-  if (write_whole_file(o.correct_out, buf)) return 1;
+  if (write_whole_file(out_path, buf)) return 1;
   if (!o.correct_report) return 0;
-  std::string rep;
   char line[32];
   for (size_t i = 0; i < nS; ++i) {
     snprintf(line, sizeof line, "%u\t%u\n", (unsigned)fix[i].fixed, (unsigned)fix[i].left);
-    rep += line;
+    *report += line;
   }
-  return write_whole_file(o.correct_report, rep);
+  return 0;
+}
+
+// QFILE to CFILE and, with --query2, QFILE2 to CFILE2; the report lists QFILE's records, then QFILE2's
+int write_correct(const Options &o, cfrk_ctx *ctx) {
+  std::string report;
+  if (const int rc = write_correct(o, ctx, g_qreads, g_qtext, o.query, o.correct_out, &report)) return rc;
+  if (o.query2)
+    if (const int rc = write_correct(o, ctx, g_qreads2, g_qtext2, o.query2, o.correct_out2, &report)) return rc;
+  return o.correct_report ? write_whole_file(o.correct_report, report) : 0;
+}
+
+// --paired / --query2: the names of the query file's mates, where its text is held for a names writer
+int check_query_pairs(const Options &o, cfrk_ctx *ctx) {
+  if (!o.mates() || !o.pair_check || !((o.filter_out && o.filter_names) || (o.correct_out && o.correct_names))) return 0;
+  const int tf = g_qformat == CFRK_FORMAT_FASTQ ? CFRK_TEXT_FASTQ : CFRK_TEXT_FASTA;
+  return check_mate_names(ctx, o.query2 ? g_qreads.nS : g_qreads.nS / 2, tf, g_qtext, o.query, o.query2 ? &g_qtext2 : nullptr, o.query2);
 }
 
 // --normalize-out: the input's text and format, as the writer of the kept reads needs them
@@ -742,6 +890,11 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
     void *data = nullptr, *start = nullptr, *length = nullptr, *keep = nullptr;
     ~DeviceReads() { for (void *d : {data, start, length, keep}) if (d) cfrk_device_free(ctx, d); }
   } nr{ctx};
+  if (o.normalize_out && o.paired) {
+    if (odd_records(g_npath, batch.nS)) return 1;
+    if (o.pair_check && o.normalize_names &&
+        (rc = check_mate_names(ctx, batch.nS / 2, g_nformat == CFRK_FORMAT_FASTQ ? CFRK_TEXT_FASTQ : CFRK_TEXT_FASTA, g_ntext, g_npath, nullptr, nullptr))) return rc;
+  }
   if (o.normalize_out && batch.nS > 0) {
     const size_t nN = (size_t)batch.nN, nS = (size_t)batch.nS;
     if ((rc = cfrk_device_alloc(ctx, nN + 16, &nr.data)) || (rc = cfrk_device_alloc(ctx, nS * 8, &nr.start)) ||
@@ -761,10 +914,15 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
     g_timing.begin += t0 - tb;
     if (o.normalize_out) {
       int64_t kept = 0;
-      rc = batch.nS > 0 ? cfrk_global_normalize_device(ctx, (const int8_t *)nr.data, (const int64_t *)nr.start, (const int32_t *)nr.length, batch.nN,
-                                                       batch.nS, o.normalize_cutoff, o.normalize_batch, (uint8_t *)nr.keep, &kept) : 0;
+      if (batch.nS == 0) rc = 0;
+      else if (o.paired)
+        rc = cfrk_global_normalize_pairs_device(ctx, (const int8_t *)nr.data, (const int64_t *)nr.start, (const int32_t *)nr.length, batch.nN,
+                                                batch.nS, o.normalize_cutoff, o.normalize_batch, o.pair_mode, (uint8_t *)nr.keep, &kept);
+      else
+        rc = cfrk_global_normalize_device(ctx, (const int8_t *)nr.data, (const int64_t *)nr.start, (const int32_t *)nr.length, batch.nN,
+                                          batch.nS, o.normalize_cutoff, o.normalize_batch, (uint8_t *)nr.keep, &kept);
       if (rc == CFRK_ERR_TABLE_FULL && hint < hint_max) { hint = std::min<uint64_t>(hint * 8, hint_max); continue; }
-      if (rc) return die(ctx, rc, "cfrk_global_normalize_device");
+      if (rc) return die(ctx, rc, o.paired ? "cfrk_global_normalize_pairs_device" : "cfrk_global_normalize_device");
     }
     else if (on_device) { if (batch.nN > 0 && (rc = cfrk_global_add_device(ctx, d_data, batch.nN))) return die(ctx, rc, "cfrk_global_add_device"); }
     else if ((rc = cfrk_global_add(ctx, batch.data, batch.start, batch.length, batch.nN, batch.nS))) return die(ctx, rc, "cfrk_global_add");
@@ -797,6 +955,7 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
       if ((rc = write_query_stats(o, ctx))) return rc;
       g_timing.stats = now_s() - s0;
     }
+    if ((rc = check_query_pairs(o, ctx))) return rc;
     if (o.filter_out && (rc = write_filter(o, ctx, o.k))) return rc;
     if (o.correct_out && (rc = write_correct(o, ctx))) return rc;
   }
@@ -1214,6 +1373,7 @@ int run_query_db(const Options &o) {
   }
   const double s0 = now_s();
   if (o.query_stats && (rc = write_query_stats(o, ctx))) return rc;
+  if ((rc = check_query_pairs(o, ctx))) return rc;
   if (o.filter_out && (rc = write_filter(o, ctx, k))) return rc;
   if (o.correct_out && (rc = write_correct(o, ctx))) return rc;
   if (o.timing && o.query_stats)
@@ -1229,6 +1389,7 @@ int main(int argc, char **argv) {
   Options o;
   int batch_n = -1;
   bool range_set = false, stats_below_set = false, filter_opt_set = false, correct_opt_set = false, correct_min_count_set = false, normalize_opt_set = false, normalize_cutoff_set = false;
+  bool pair_opt_set = false, pair_mode_set = false;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--all-chunks")) o.all_chunks = true;
     else if (!strcmp(argv[i], "--native")) o.native = true;
@@ -1267,6 +1428,19 @@ int main(int argc, char **argv) {
       o.min_qual = (int)q; o.min_qual_set = true;
     }
     else if (!strcmp(argv[i], "--query-only")) o.query_only = true;
+    else if (!strcmp(argv[i], "--paired")) o.paired = true;
+    else if (!strcmp(argv[i], "--pair-check") || !strcmp(argv[i], "--pair-mode") || !strcmp(argv[i], "--query2")) {
+      if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
+      const char *opt = argv[i], *v = argv[++i];
+      if (!strcmp(opt, "--query2")) o.query2 = v;
+      else if (!strcmp(opt, "--pair-check")) {
+        if (strcmp(v, "on") && strcmp(v, "off")) { fprintf(stderr, "cfrk: --pair-check takes on or off, not '%s'\n", v); return 1; }
+        o.pair_check = !strcmp(v, "on"); pair_opt_set = true;
+      } else {
+        if (strcmp(v, "either") && strcmp(v, "both")) { fprintf(stderr, "cfrk: --pair-mode takes either or both, not '%s'\n", v); return 1; }
+        o.pair_mode = !strcmp(v, "both") ? CFRK_PAIR_BOTH : CFRK_PAIR_EITHER; pair_mode_set = true;
+      }
+    }
     else if (!strcmp(argv[i], "--query") || !strcmp(argv[i], "--query-out") || !strcmp(argv[i], "--query-db")) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
       const char *opt = argv[i], *v = argv[++i];
@@ -1284,7 +1458,8 @@ int main(int argc, char **argv) {
     else if (!strncmp(argv[i], "--filter-", 9)) {
       const char *opt = argv[i];
       static const char *const known[] = {"--filter-out", "--filter-min-count", "--filter-max-count", "--filter-trim", "--filter-min-len",
-                                          "--filter-min-median", "--filter-max-median", "--filter-names", "--filter-format"};
+                                          "--filter-min-median", "--filter-max-median", "--filter-names", "--filter-format",
+                                          "--filter-out2", "--filter-orphans"};
       bool is_known = false;
       for (const char *n : known) is_known = is_known || !strcmp(opt, n);
       if (!is_known) { fprintf(stderr, "cfrk: unknown option %s\n", opt); return 1; }
@@ -1292,6 +1467,8 @@ int main(int argc, char **argv) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", opt); return 1; }
       const char *v = argv[++i];
       if (!strcmp(opt, "--filter-out")) { o.filter_out = v; continue; }
+      if (!strcmp(opt, "--filter-out2")) { o.filter_out2 = v; continue; }
+      if (!strcmp(opt, "--filter-orphans")) { o.filter_orphans = v; continue; }
       filter_opt_set = true;
       if (!strcmp(opt, "--filter-format")) {
         if (!strcmp(v, "fasta")) o.filter_format = CFRK_TEXT_FASTA;
@@ -1318,7 +1495,8 @@ int main(int argc, char **argv) {
     }
     else if (!strncmp(argv[i], "--correct-", 10)) {
       const char *opt = argv[i];
-      static const char *const known[] = {"--correct-out", "--correct-min-count", "--correct-names", "--correct-format", "--correct-report"};
+      static const char *const known[] = {"--correct-out", "--correct-min-count", "--correct-names", "--correct-format", "--correct-report",
+                                          "--correct-out2"};
       bool is_known = false;
       for (const char *n : known) is_known = is_known || !strcmp(opt, n);
       if (!is_known) { fprintf(stderr, "cfrk: unknown option %s\n", opt); return 1; }
@@ -1326,6 +1504,7 @@ int main(int argc, char **argv) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", opt); return 1; }
       const char *v = argv[++i];
       if (!strcmp(opt, "--correct-out")) { o.correct_out = v; continue; }
+      if (!strcmp(opt, "--correct-out2")) { o.correct_out2 = v; continue; }
       correct_opt_set = true;
       if (!strcmp(opt, "--correct-format")) {
         if (!strcmp(v, "fasta")) o.correct_format = CFRK_TEXT_FASTA;
@@ -1413,6 +1592,35 @@ int main(int argc, char **argv) {
   if (correct_opt_set && !o.correct_out) { fprintf(stderr, "cfrk: the --correct- options need --correct-out CFILE\n"); return 1; }
   if (o.correct_out && !o.query) { fprintf(stderr, "cfrk: --correct-out and the --correct- options need --query QFILE\n"); return 1; }
   if (o.correct_out && !correct_min_count_set) { fprintf(stderr, "cfrk: --correct-out needs --correct-min-count T\n"); return 1; }
+  // paired-end reads
+  if (o.paired && o.query2) { fprintf(stderr, "cfrk: --paired says the mates are interleaved in one file, --query2 that they are in two: one of them\n"); return 1; }
+  if (o.query2 && o.normalize_out && !o.filter_out && !o.correct_out) {
+    fprintf(stderr, "cfrk: --normalize-out takes ONE input file: mates in two files are not supported, interleave them and say --paired\n");
+    return 1;
+  }
+  if (o.query2 && !o.query) { fprintf(stderr, "cfrk: --query2 needs --query QFILE\n"); return 1; }
+  if (o.paired && o.gpus > 1) { fprintf(stderr, "cfrk: --paired runs on one device: not with --gpus above 1\n"); return 1; }
+  if (o.paired && batch_n >= 0) { fprintf(stderr, "cfrk: --paired reads one file: not with --batch\n"); return 1; }
+  if (o.paired && !o.filter_out && !o.correct_out && !o.normalize_out) {
+    fprintf(stderr, "cfrk: --paired needs --filter-out FFILE, --correct-out CFILE or --normalize-out NFILE\n");
+    return 1;
+  }
+  if (o.query2 && !o.filter_out && !o.correct_out) { fprintf(stderr, "cfrk: --query2 needs --filter-out FFILE or --correct-out CFILE\n"); return 1; }
+  if (o.query2 && o.filter_out && !o.filter_out2) { fprintf(stderr, "cfrk: --query2 needs --filter-out2 FFILE2 beside --filter-out\n"); return 1; }
+  if (o.query2 && o.correct_out && !o.correct_out2) { fprintf(stderr, "cfrk: --query2 needs --correct-out2 CFILE2 beside --correct-out\n"); return 1; }
+  if ((o.filter_out2 && !(o.query2 && o.filter_out)) || (o.correct_out2 && !(o.query2 && o.correct_out))) {
+    fprintf(stderr, "cfrk: --filter-out2 and --correct-out2 receive QFILE2's reads: they need --query2 and --filter-out / --correct-out\n");
+    return 1;
+  }
+  if (o.filter_orphans && !(o.mates() && o.filter_out)) { fprintf(stderr, "cfrk: --filter-orphans needs --paired or --query2, and --filter-out\n"); return 1; }
+  if ((pair_opt_set && !o.mates()) || (pair_mode_set && !(o.paired && o.normalize_out))) {
+    fprintf(stderr, "cfrk: --pair-check needs --paired or --query2; --pair-mode needs --paired with --normalize-out\n");
+    return 1;
+  }
+  if (o.paired && o.normalize_out && (o.normalize_batch & 1)) {
+    fprintf(stderr, "cfrk: --normalize-batch %lld: a round of --paired reads holds whole pairs, an even number\n", o.normalize_batch);
+    return 1;
+  }
   if (o.query && !o.query_out && !o.query_stats && !o.filter_out && !o.correct_out) { fprintf(stderr, "cfrk: --query needs --query-out OFILE, --query-stats SFILE, --filter-out FFILE or --correct-out CFILE\n"); return 1; }
   if (o.correct_out && o.gpus > 1) { fprintf(stderr, "cfrk: --correct-out runs on one device: not with --gpus above 1\n"); return 1; }
   if (o.filter_out && o.gpus > 1) { fprintf(stderr, "cfrk: --filter-out runs on one device: not with --gpus above 1\n"); return 1; }
@@ -1438,7 +1646,17 @@ int main(int argc, char **argv) {
   }
   if (o.query && read_reads(o.query, g_qformat, 0, 0, &g_qreads)) return 1;
   if ((o.filter_names || o.correct_names) && read_whole_file(o.query, g_qtext)) return 1;
-  struct QFree { ~QFree() { if (g_qreads.data) cfrk_host_free_batch(&g_qreads); } } qfree;
+  struct QFree { ~QFree() { for (cfrk_batch *b : {&g_qreads, &g_qreads2}) if (b->data) cfrk_host_free_batch(b); } } qfree;
+  if (o.query2) {
+    if (file_format(o, o.query2) != g_qformat) { fprintf(stderr, "cfrk: %s and %s are not of one format\n", o.query, o.query2); return 1; }
+    if (read_reads(o.query2, g_qformat, 0, 0, &g_qreads2)) return 1;
+    if ((o.filter_names || o.correct_names) && read_whole_file(o.query2, g_qtext2)) return 1;
+    if (g_qreads2.nS != g_qreads.nS) {
+      fprintf(stderr, "cfrk: %s holds %lld records and %s holds %lld: record j of each is a pair\n", o.query, (long long)g_qreads.nS, o.query2, (long long)g_qreads2.nS);
+      return 1;
+    }
+  }
+  if (o.paired && o.query && (o.filter_out || o.correct_out) && odd_records(o.query, g_qreads.nS)) return 1;
   if (o.query_db) return run_query_db(o);
   if (pos.size() < 3) {
     // src/main.cu:239-243

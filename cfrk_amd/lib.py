@@ -52,6 +52,11 @@ CFRK_TEXT_SCAN_TILES = 1024          # tiles per block of its tile scan
 CFRK_EMIT_TILE_BYTES = 16384         # text emitter: bytes of output per workgroup of the copy
 # cfrk_text_record: where a record's header line and quality line lie in its text
 TEXT_RECORD_DTYPE = np.dtype([("head_off", "<i8"), ("qual_off", "<i8"), ("head_len", "<i4"), ("qual_len", "<i4")])
+CFRK_PAIR_BOTH = 0                   # paired reads: a pair is kept iff both mates survive, a lone survivor is an orphan
+CFRK_PAIR_EITHER = 1                 # a pair is kept iff either mate survives (khmer's --paired rule); no orphans
+CFRK_PAIR_NAME_FAST = 256            # mate-name check: bytes of a name a 16-lane group takes (longer: a workgroup)
+# cfrk_pair_counts, 32 bytes
+PAIR_COUNTS_DTYPE = np.dtype([("pairs", "<i8"), ("orphans_a", "<i8"), ("orphans_b", "<i8"), ("dropped", "<i8")])
 CFRK_SKETCH_LOG2M = 14               # distinct sketch: log2 of its registers
 CFRK_SKETCH_REGS = 16384             # one uint8 register per bucket
 CFRK_FASTA_TILE_BYTES = 16384        # device FASTA parser: text bytes per workgroup
@@ -136,6 +141,12 @@ def load_library():
         "cfrk_global_correct_reads_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp, vp], C.c_int),
         "cfrk_global_normalize": ([vp, vp, vp, vp, i64, i64, C.c_uint32, i64, vp, C.POINTER(i64)], C.c_int),
         "cfrk_global_normalize_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, i64, vp, C.POINTER(i64)], C.c_int),
+        "cfrk_global_normalize_pairs": ([vp, vp, vp, vp, i64, i64, C.c_uint32, i64, i32, vp, C.POINTER(i64)], C.c_int),
+        "cfrk_global_normalize_pairs_device": ([vp, vp, vp, vp, i64, i64, C.c_uint32, i64, i32, vp, C.POINTER(i64)], C.c_int),
+        "cfrk_reads_pair_keep": ([vp, i64, i32, i32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "cfrk_reads_pair_keep_device": ([vp, i64, i32, i32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "cfrk_text_pair_check": ([vp, i64, i32, vp, u64, vp, vp, u64, vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "cfrk_text_pair_check_device": ([vp, i64, i32, vp, u64, vp, vp, u64, vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_reads_select": ([vp, vp, vp, vp, i64, i64, vp, vp, C.c_int32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_reads_select_device": ([vp, vp, vp, vp, i64, i64, vp, vp, C.c_int32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_text_index": ([vp, vp, u64, i32, vp, u64, C.POINTER(i64)], C.c_int),
@@ -576,6 +587,78 @@ class Context:
             raise
         return nb.value, ns.value
 
+    # -- paired-end reads: the join of the mates' keep decisions, the mate-name check ---------------
+    def pair_keep(self, keep_a=None, keep_b=None, spans_a=None, spans_b=None, length_a=None, length_b=None, min_len=0,
+                  mode=CFRK_PAIR_BOTH, n_pairs=None):
+        """split layout: one array per side, element j of each is pair j -> (pair uint8[n], orphan_a uint8[n],
+        orphan_b uint8[n], counts: one PAIR_COUNTS_DTYPE row).  A read survives iff its keep byte is non-zero (None:
+        all), its span lies inside the read and span.length >= min_len (spans None: length >= min_len).  BOTH: pair =
+        sA & sB and a lone survivor is an orphan; EITHER: pair = sA | sB, no orphans.  Interleaved arrays are passed as
+        x[0::2], x[1::2].  n_pairs is needed only when every array is None.  Needs no job."""
+        arrs = {"keep_a": (keep_a, np.uint8), "keep_b": (keep_b, np.uint8), "spans_a": (spans_a, READ_SPAN_DTYPE),
+                "spans_b": (spans_b, READ_SPAN_DTYPE), "length_a": (length_a, np.int32), "length_b": (length_b, np.int32)}
+        got = {k: np.ascontiguousarray(a, t) for k, (a, t) in arrs.items() if a is not None}
+        sizes = {len(a) for a in got.values()} | ({int(n_pairs)} if n_pairs is not None else set())
+        if len(sizes) != 1:
+            raise ValueError("the arrays of a pair join differ in size (or none was given and n_pairs is missing)")
+        n = sizes.pop()
+        out = [np.zeros(n, np.uint8) for _ in range(4)]
+        counts = np.zeros(1, PAIR_COUNTS_DTYPE)
+        g = lambda k: _ptr(got.get(k))
+        self.check(self._L.cfrk_reads_pair_keep(self._h, n, 1, int(mode), int(min_len), g("keep_a"), g("keep_b"), g("spans_a"),
+                                                g("spans_b"), g("length_a"), g("length_b"), _ptr(out[0]), _ptr(out[1]),
+                                                _ptr(out[2]), _ptr(out[3]), _ptr(counts)), "cfrk_reads_pair_keep")
+        assert (out[0] == out[1]).all()
+        return out[0], out[2], out[3], counts[0]
+
+    def pair_keep_device(self, n_pairs, stride, mode, min_len, d_keep_a, d_keep_b, d_span_a, d_span_b, d_length_a, d_length_b,
+                         d_pair_a, d_pair_b, d_orphan_a=0, d_orphan_b=0, want_counts=True):
+        """device form: mate A of pair j is element j * stride of the *_a arrays, mate B of the *_b arrays (interleaved:
+        b = a + one element, stride 2; split: stride 1); 0 for an absent array.  The outputs may be the keep arrays (in
+        place).  One launch on the context stream; synchronises only for the counts row (want_counts), which it returns"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        counts = np.zeros(1, PAIR_COUNTS_DTYPE)
+        self.check(self._L.cfrk_reads_pair_keep_device(self._h, n_pairs, int(stride), int(mode), int(min_len), vp(d_keep_a),
+                                                       vp(d_keep_b), vp(d_span_a), vp(d_span_b), vp(d_length_a), vp(d_length_b),
+                                                       vp(d_pair_a), vp(d_pair_b), vp(d_orphan_a), vp(d_orphan_b),
+                                                       _ptr(counts) if want_counts else None), "cfrk_reads_pair_keep_device")
+        return counts[0] if want_counts else None
+
+    def check_pairs(self, text_a, rec_a, text_b=None, rec_b=None):
+        """mate names -> (first_bad, n_bad): first_bad is the smallest index of a pair whose mates do not carry the same
+        identifier (the header up to the first space or tab, a trailing /1 on A with /2 on B dropped), or -1.  With
+        text_b / rec_b None the one text is interleaved (records 2j and 2j + 1); else record j of each text is a pair
+        and the two record arrays must be of one size.  rec = index_text(text, its format).  Needs no job."""
+        as_text = lambda t: np.frombuffer(t, np.uint8) if isinstance(t, (bytes, bytearray, memoryview)) else np.ascontiguousarray(t, np.uint8)
+        text_a = as_text(text_a)
+        rec_a = np.ascontiguousarray(rec_a, TEXT_RECORD_DTYPE)
+        if rec_b is None:
+            if text_b is not None:
+                raise ValueError("text_b without rec_b")
+            if len(rec_a) % 2:
+                raise ValueError(f"{len(rec_a)} interleaved records: an odd number")
+            n, stride, text_b = len(rec_a) // 2, 2, text_a
+            pa, pb = _ptr(rec_a), (rec_a.ctypes.data + TEXT_RECORD_DTYPE.itemsize) if n else None
+        else:
+            text_b = text_a if text_b is None else as_text(text_b)
+            rec_b = np.ascontiguousarray(rec_b, TEXT_RECORD_DTYPE)
+            if len(rec_a) != len(rec_b):
+                raise ValueError(f"{len(rec_a)} and {len(rec_b)} records: the two sides differ in size")
+            n, stride, pa, pb = len(rec_a), 1, _ptr(rec_a), _ptr(rec_b)
+        first, bad = C.c_int64(), C.c_int64()
+        self.check(self._L.cfrk_text_pair_check(self._h, n, stride, _ptr(text_a), text_a.size, pa, _ptr(text_b), text_b.size, pb,
+                                                C.byref(first), C.byref(bad)), "cfrk_text_pair_check")
+        return int(first.value), int(bad.value)
+
+    def check_pairs_device(self, n_pairs, stride, d_text_a, nbytes_a, d_rec_a, d_text_b, nbytes_b, d_rec_b):
+        """device form -> (first_bad, n_bad); never reads outside the two texts; synchronises once"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        first, bad = C.c_int64(), C.c_int64()
+        self.check(self._L.cfrk_text_pair_check_device(self._h, n_pairs, int(stride), vp(d_text_a), nbytes_a, vp(d_rec_a),
+                                                       vp(d_text_b), nbytes_b, vp(d_rec_b), C.byref(first), C.byref(bad)),
+                   "cfrk_text_pair_check_device")
+        return int(first.value), int(bad.value)
+
     def synth_reads_device(self, r0, R, L, Glen, d_data, d_start=None, d_length=None,
                            seedG=1, seedR=2, seedS=3, uniform=False):
         self.check(self._L.cfrk_synth_reads_device(self._h, r0, R, L, Glen, seedG, seedR, seedS,
@@ -908,6 +991,37 @@ class GlobalCounter:
         self.ctx.check(self._L.cfrk_global_normalize_device(self.ctx._h, vp(d_data), vp(d_start), vp(d_length), nN, nS,
                                                             int(cutoff), int(batch_reads), vp(d_keep), C.byref(n)),
                        "cfrk_global_normalize_device")
+        return int(n.value)
+
+    def normalize_pairs(self, data, start, length, cutoff, batch_reads=CFRK_NORMALIZE_BATCH, mode=CFRK_PAIR_EITHER):
+        """normalize() for interleaved paired-end reads (mates 2j and 2j + 1) -> (keep, n_kept): every mate is judged on
+        its own, then the pair is kept or dropped as a whole -- kept if either mate would be (CFRK_PAIR_EITHER, khmer's
+        --paired rule) or only if both would be (CFRK_PAIR_BOTH) -- and every kept read is counted into the job.  The
+        number of reads and batch_reads must be even."""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        nS = len(length)
+        if len(start) != nS:
+            raise ValueError("start and length differ in size")
+        if not 0 <= int(cutoff) <= 0xFFFFFFFF:
+            raise ValueError("cutoff outside 0 .. 2^32 - 1")
+        keep = np.zeros(nS, np.uint8)
+        n = C.c_int64(0)
+        self.ctx.check(self._L.cfrk_global_normalize_pairs(self.ctx._h, _ptr(data), _ptr(start), _ptr(length), len(data), nS,
+                                                           int(cutoff), int(batch_reads), int(mode), _ptr(keep), C.byref(n)),
+                       "cfrk_global_normalize_pairs")
+        return keep, int(n.value)
+
+    def normalize_pairs_device(self, d_data, d_start, d_length, nN, nS, cutoff, d_keep, batch_reads=CFRK_NORMALIZE_BATCH,
+                               mode=CFRK_PAIR_EITHER):
+        """device form of normalize_pairs(): as normalize_device(), one join launch more per round; returns the number of
+        kept reads (even)"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        n = C.c_int64(0)
+        self.ctx.check(self._L.cfrk_global_normalize_pairs_device(self.ctx._h, vp(d_data), vp(d_start), vp(d_length), nN, nS,
+                                                                  int(cutoff), int(batch_reads), int(mode), vp(d_keep), C.byref(n)),
+                       "cfrk_global_normalize_pairs_device")
         return int(n.value)
 
     def export_device(self, d_lo, d_hi, d_cnt, cap, parts=1):

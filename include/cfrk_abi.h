@@ -389,6 +389,24 @@ int cfrk_global_normalize(cfrk_ctx *ctx, const int8_t *data, const int64_t *star
                           int64_t nN, int64_t nS, uint32_t cutoff, int64_t batch_reads,
                           uint8_t *keep, int64_t *n_kept);
 
+/* Paired normalisation: cfrk_global_normalize for interleaved paired-end reads, the mates of pair j being reads 2j and
+ * 2j + 1 (the pairs section below; mode is CFRK_PAIR_EITHER or CFRK_PAIR_BOTH).  Each round
+ *   judges   every mate on its own, exactly as above (the mates of a pair may fall into different size classes);
+ *   joins    the two verdicts of every pair of the round: CFRK_PAIR_EITHER keeps both mates if either would be kept
+ *            (khmer's normalize-by-median --paired), CFRK_PAIR_BOTH keeps both only if both would be; keep[2j] ==
+ *            keep[2j + 1] afterwards;
+ *   inserts  every valid window of every kept read, as above.  A mate without a valid window that is kept through its
+ *            partner inserts nothing.
+ * *n_kept counts reads and is even.  Everything else -- rounds, job state, scheduling independence, errors, the device
+ * form's unchecked ranges, the single synchronisation at the end -- is that of cfrk_global_normalize; in addition an odd
+ * nS or an odd batch_reads is CFRK_ERR_ARG (a round always holds whole pairs), and so is a mode other than the two. */
+int cfrk_global_normalize_pairs_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                       int64_t nN, int64_t nS, uint32_t cutoff, int64_t batch_reads, int mode,
+                                       uint8_t *d_keep /* nS bytes, 0 or 1 */, int64_t *n_kept);
+int cfrk_global_normalize_pairs(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
+                                int64_t nN, int64_t nS, uint32_t cutoff, int64_t batch_reads, int mode,
+                                uint8_t *keep, int64_t *n_kept);
+
 /* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
 
 /* How many DISTINCT k-mers will a job hold?  One streaming pass over the reads answers it to about 1 % before anything
@@ -654,6 +672,81 @@ int cfrk_reads_emit_text(cfrk_ctx *ctx, const int8_t *data, const int64_t *start
                          int32_t min_len, const char *text, uint64_t nbytes,
                          const cfrk_text_record *rec, int out_format, char *out, uint64_t cap_out,
                          uint64_t *nbytes_out, int64_t *nS_out);
+
+/* ---- paired-end reads: the two mates of a pair are kept or dropped together ----------------------------------- */
+
+/* Addressing, for every call of this section: mate A of pair j is element j * stride of the *_a arrays and mate B is
+ * element j * stride of the *_b arrays.  One form serves both layouts a caller has:
+ *   interleaved   one array of 2 * n_pairs elements, b = a + 1, stride = 2 (mates are reads 2j and 2j + 1)
+ *   split         two arrays of n_pairs elements, stride = 1
+ *
+ * Join of keep decisions.  A read SURVIVES iff keep is NULL or its keep byte is non-zero, and
+ *   with a span: the span lies inside the read (0 <= offset, 0 <= length, offset + length <= length[i]) and
+ *                span.length >= min_len;
+ *   with span NULL: length[i] >= min_len (length may be NULL when min_len is 0: nothing is asked of the read then).
+ * This is the rule of cfrk_reads_select and of the emitter WITHOUT their range check of start: neither the data nor
+ * start is an argument here, so a read whose [start, start + length) does not lie inside its buffer survives the join
+ * and is still dropped by the select / the emitter.  The host forms of those refuse such a table; a caller of their
+ * device forms who does not trust start checks it first.
+ * With sA and sB the survival of the two mates of a pair:
+ *   CFRK_PAIR_BOTH     pair = sA & sB;  orphan_a = sA & !sB;  orphan_b = sB & !sA
+ *   CFRK_PAIR_EITHER   pair = sA | sB;  orphan_a = orphan_b = 0   (khmer's --paired rule: a pair stays whole)
+ * pair_a[j * stride] = pair_b[j * stride] = pair; orphan_a / orphan_b (each may be NULL) likewise.  Every byte
+ * written is 0 or 1; with stride 2 the bytes between the addressed ones are not touched.  counts (may be NULL) gets
+ * pairs kept, orphans A, orphans B and pairs dropped (pair = 0 and no orphan): the four sum to n_pairs under
+ * CFRK_PAIR_BOTH, the first and the last do under CFRK_PAIR_EITHER.
+ * The outputs MAY ALIAS the keep inputs (pair_a = keep_a, pair_b = keep_b: the in-place use; every thread reads both
+ * mates before it writes either) and must not overlap anything else, nor each other.
+ * CFRK_ERR_ARG: negative n_pairs or min_len, a stride other than 1 or 2, a mode other than the two, a NULL length_a /
+ * length_b with that side's span or with min_len > 0, NULL pair_a / pair_b with n_pairs > 0.  keep, span and orphan
+ * arrays are NULL or not side by side.  n_pairs = 0 is fine (counts = 0).
+ * Device form: one launch on the context stream, one thread per pair and turn; the counts are reduced per wave, then
+ * per workgroup, and added once per workgroup; it synchronises once, for the counts row, and not at all when counts is NULL.  Nothing is
+ * checked and nothing outside the addressed elements is accessed.
+ * Host form: gathers the addressed elements, runs the device form, scatters the results; synchronous.
+ *
+ * Mate-name check.  The IDENTIFIER of a record is the bytes of its header line behind the marker (head_len - 1 bytes
+ * from head_off + 1) up to but not including the first space or tab; head_len <= 1 gives the empty identifier.  If A's
+ * identifier ends in "/1" and B's ends in "/2", both suffixes are dropped.  A pair is GOOD iff both header ranges lie
+ * inside their text ([0, nbytes], a negative field is outside) and the two identifiers are byte-equal and not empty.
+ * So "name/1" pairs with "name/2" and the Casava-1.8 form "name 1:N:0:.." pairs with "name 2:N:0:.."; "/2" in front of
+ * "/1" is bad.  *first_bad = the smallest bad pair index or -1, *n_bad = the number of bad pairs; CFRK_OK either way.
+ * The mates may live in one text (text_b = text_a) or in two.
+ * CFRK_ERR_ARG: negative n_pairs, a stride other than 1 or 2, NULL outputs, NULL records with n_pairs > 0, a NULL text
+ * with nbytes > 0.  No alignment requirement.
+ * Device form: never reads outside the two texts.  Two launches over all pairs: pairs whose names are both at most
+ * CFRK_PAIR_NAME_FAST bytes go to a group of 16 lanes, a lane comparing one 16-byte piece; a pair with a longer name
+ * goes to a whole workgroup.  Synchronises once, for the two results.
+ * Neither call needs a global job or touches one that is open on the same context. */
+#define CFRK_PAIR_BOTH 0
+#define CFRK_PAIR_EITHER 1
+#define CFRK_PAIR_NAME_FAST 256
+typedef struct cfrk_pair_counts {   /* 32 bytes, no padding */
+  int64_t pairs;       /* pairs kept                                  */
+  int64_t orphans_a;   /* A mates that survive alone (CFRK_PAIR_BOTH) */
+  int64_t orphans_b;   /* B mates that survive alone (CFRK_PAIR_BOTH) */
+  int64_t dropped;     /* pairs of which nothing is kept              */
+} cfrk_pair_counts;
+int cfrk_reads_pair_keep_device(cfrk_ctx *ctx, int64_t n_pairs, int stride, int mode, int32_t min_len,
+                                const uint8_t *d_keep_a, const uint8_t *d_keep_b,
+                                const cfrk_read_span *d_span_a, const cfrk_read_span *d_span_b,
+                                const int32_t *d_length_a, const int32_t *d_length_b,
+                                uint8_t *d_pair_a, uint8_t *d_pair_b, uint8_t *d_orphan_a, uint8_t *d_orphan_b,
+                                cfrk_pair_counts *counts);
+int cfrk_reads_pair_keep(cfrk_ctx *ctx, int64_t n_pairs, int stride, int mode, int32_t min_len,
+                         const uint8_t *keep_a, const uint8_t *keep_b,
+                         const cfrk_read_span *span_a, const cfrk_read_span *span_b,
+                         const int32_t *length_a, const int32_t *length_b,
+                         uint8_t *pair_a, uint8_t *pair_b, uint8_t *orphan_a, uint8_t *orphan_b,
+                         cfrk_pair_counts *counts);
+int cfrk_text_pair_check_device(cfrk_ctx *ctx, int64_t n_pairs, int stride,
+                                const uint8_t *d_text_a, uint64_t nbytes_a, const cfrk_text_record *d_rec_a,
+                                const uint8_t *d_text_b, uint64_t nbytes_b, const cfrk_text_record *d_rec_b,
+                                int64_t *first_bad, int64_t *n_bad);
+int cfrk_text_pair_check(cfrk_ctx *ctx, int64_t n_pairs, int stride,
+                         const char *text_a, uint64_t nbytes_a, const cfrk_text_record *rec_a,
+                         const char *text_b, uint64_t nbytes_b, const cfrk_text_record *rec_b,
+                         int64_t *first_bad, int64_t *n_bad);
 
 /* Unsorted export into device buffers, grouped into `parts` contiguous segments by
  * owner(key) = (mix(key) >> 32) % parts (key-owner partition for the multi-GPU
