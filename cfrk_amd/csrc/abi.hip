@@ -796,6 +796,89 @@ int cfrk_reads_select(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, c
   return download_reads(ctx, o, data_out, start_out, length_out, index_out, *nN_out, *nS_out);
 }
 
+/* ------------------------------------------------------------------ unitigs */
+
+static_assert(sizeof(cfrk_unitig) == 16, "cfrk_unitig is 16 bytes without padding");
+
+int cfrk_global_neighbors_device(cfrk_ctx *ctx, const uint64_t *d_keys_lo, const uint64_t *d_keys_hi, int64_t n,
+                                 uint32_t min_count, uint8_t *d_masks) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = query_check(ctx, n);
+  if (rc || n == 0) return rc;
+  if (!d_keys_lo || !d_masks || (ctx->g_two && !d_keys_hi)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_neighbors_launch(ctx, d_keys_lo, d_keys_hi, n, min_count, d_masks);
+}
+
+int cfrk_global_neighbors(cfrk_ctx *ctx, const uint64_t *keys_lo, const uint64_t *keys_hi, int64_t n, uint32_t min_count,
+                          uint8_t *masks) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = query_check(ctx, n);
+  if (rc || n == 0) return rc;
+  if (!keys_lo || !masks || (ctx->g_two && !keys_hi)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // staged through the query calls' slots: the keys in, the masks out
+  void *d_in, *d_out;
+  const size_t bytes = (size_t)n * 8;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_IN, keys_hi ? 2 * bytes : bytes, &d_in))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, (size_t)n, &d_out))) return rc;
+  uint64_t *d_lo = (uint64_t *)d_in, *d_hi = keys_hi ? d_lo + n : nullptr;
+  HIP_TRY(ctx, hipMemcpyAsync(d_lo, keys_lo, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (keys_hi) HIP_TRY(ctx, hipMemcpyAsync(d_hi, keys_hi, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = cfrk_neighbors_launch(ctx, d_lo, d_hi, n, min_count, (uint8_t *)d_out))) return stage_drain(ctx, rc);
+  return cfrk_memcpy_d2h(ctx, masks, d_out, (size_t)n);
+}
+
+static int unitigs_check(cfrk_ctx *ctx, const void *data_out, uint64_t cap_data, const void *start_out, const void *length_out,
+                         const void *rec_out, uint64_t cap_unitigs, int64_t *nN_out, int64_t *nS_out) {
+  int rc = query_check(ctx, 0);
+  if (rc) return rc;
+  if (!nN_out || !nS_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL size output");
+  if ((cap_data > 0 && !data_out) || (cap_unitigs > 0 && (!start_out || !length_out || !rec_out)))
+    return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL array with a capacity above 0");
+  *nN_out = *nS_out = 0;
+  return CFRK_OK;
+}
+
+int cfrk_global_unitigs_device(cfrk_ctx *ctx, uint32_t min_count, int8_t *d_data_out, uint64_t cap_data, int64_t *d_start_out,
+                               int32_t *d_length_out, cfrk_unitig *d_rec_out, uint64_t cap_unitigs, int64_t *nN_out,
+                               int64_t *nS_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = unitigs_check(ctx, d_data_out, cap_data, d_start_out, d_length_out, d_rec_out, cap_unitigs, nN_out, nS_out);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int64_t nN = 0, nS = 0;
+  uint64_t nseg = 0;
+  if ((rc = cfrk_unitigs_measure(ctx, min_count, &nN, &nS, &nseg))) return rc;
+  const ReadsOut o = {d_data_out, d_start_out, d_length_out, nullptr, cap_data, cap_unitigs, -1, false};
+  if ((rc = reads_out_fit(ctx, "unitigs", o, nN, nS, nN_out, nS_out)) || nS == 0) return rc;
+  return cfrk_unitigs_emit(ctx, d_data_out, d_start_out, d_length_out, d_rec_out, nS, nseg);
+}
+
+int cfrk_global_unitigs(cfrk_ctx *ctx, uint32_t min_count, int8_t *data_out, uint64_t cap_data, int64_t *start_out,
+                        int32_t *length_out, cfrk_unitig *rec_out, uint64_t cap_unitigs, int64_t *nN_out, int64_t *nS_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = unitigs_check(ctx, data_out, cap_data, start_out, length_out, rec_out, cap_unitigs, nN_out, nS_out);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int64_t nN = 0, nS = 0;
+  uint64_t nseg = 0;
+  if ((rc = cfrk_unitigs_measure(ctx, min_count, &nN, &nS, &nseg))) return rc;
+  const ReadsOut fit = {nullptr, nullptr, nullptr, nullptr, cap_data, cap_unitigs, BUF_UNITIG_OUT, false};
+  if ((rc = reads_out_fit(ctx, "unitigs", fit, nN, nS, nN_out, nS_out)) || nS == 0) return rc;
+  // [data | start | length | records] in a slot of their own, then down to the caller's arrays
+  const size_t rec_bytes = (size_t)nS * sizeof(cfrk_unitig);
+  const SlotCarve c((size_t)nN + 16, (uint64_t)nS, true, &rec_bytes, 1);
+  void *p;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_OUT, c.total, &p))) return rc;
+  ReadsOut o = fit;
+  o.data = (int8_t *)p; o.start = carve_at<int64_t>(p, c.o_start); o.length = carve_at<int32_t>(p, c.o_length);
+  cfrk_unitig *d_rec = carve_at<cfrk_unitig>(p, c.o_extra[0]);
+  if ((rc = cfrk_unitigs_emit(ctx, o.data, o.start, o.length, d_rec, nS, nseg))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(rec_out, d_rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  return download_reads(ctx, o, data_out, start_out, length_out, nullptr, nN, nS);
+}
+
 /* ------------------------------------------------------------------ digital normalisation */
 
 static int normalize_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, int64_t batch_reads, const void *data, const void *start,

@@ -48,6 +48,9 @@ enum {  // pool slots
   BUF_NORMALIZE,                              // normalise (normalize.hip): the call's kept-read counter; a paired call's four pair counts behind it
   BUF_PAIRS,                                  // pairs (pairs.hip): the join's four counts, the name check's two results
   BUF_PAIRS_IN,                               // staging of cfrk_reads_pair_keep and cfrk_text_pair_check alone
+  BUF_UNITIG,                                 // unitigs (unitigs.hip): counters, the per-slot bytes, segments, unitig records
+  BUF_UNITIG_AUX,                             // the sort's payload, the lengths and their scan
+  BUF_UNITIG_OUT,                             // staging of cfrk_global_unitigs alone (data, start, length, records out)
   BUF_NSLOTS
 };
 
@@ -99,7 +102,7 @@ struct cfrk_ctx {
   int last_passes;       // passes the most recent add took on a partitioned path (1 unless memory was short)
   uint32_t dbg_flags;    // cfrk_debug_set_flags
   size_t mem_budget;     // 0 = what the device has free; else a cap on the partitioned paths' buffers (diagnostics)
-  double dbg_param[4];   // cfrk_debug_set_param (0 = the library's own choice)
+  double dbg_param[5];   // cfrk_debug_set_param (0 = the library's own choice)
   // query index (query.hip): built on the first query of a job, cleared by every call that changes the result
   bool q_valid;
   int q_log2cap;         // hash index: log2 of its slots (0: the dense array of k <= 12)
@@ -179,6 +182,11 @@ int cfrk_pair_join_launch(cfrk_ctx *ctx, int64_t n_pairs, int stride, int mode, 
                           const uint8_t *d_keep_b, const cfrk_read_span *d_span_a, const cfrk_read_span *d_span_b,
                           const int32_t *d_length_a, const int32_t *d_length_b, uint8_t *d_pair_a, uint8_t *d_pair_b,
                           uint8_t *d_orphan_a, uint8_t *d_orphan_b, unsigned long long *d_counts);
+// unitigs.hip: the neighbour masks of n >= 0 keys from the same index, left enqueued; the unitigs in two steps: the sizes
+// and the segments to emit (synchronises), then order and emit into arrays with room for them, left enqueued (nS >= 1)
+int cfrk_neighbors_launch(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t *d_hi, int64_t n, uint32_t min_count, uint8_t *d_masks);
+int cfrk_unitigs_measure(cfrk_ctx *ctx, uint32_t min_count, int64_t *nN, int64_t *nS, uint64_t *nseg);
+int cfrk_unitigs_emit(cfrk_ctx *ctx, int8_t *d_data, int64_t *d_start, int32_t *d_length, cfrk_unitig *d_rec, int64_t nS, uint64_t nseg);
 // sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
 // enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
 int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,

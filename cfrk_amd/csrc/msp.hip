@@ -2589,12 +2589,13 @@ extern "C" int cfrk_debug_set_mem_budget(cfrk_ctx *ctx, uint64_t bytes) {
 
 extern "C" int cfrk_debug_set_param(cfrk_ctx *ctx, int which, double value) {
   if (!ctx) return CFRK_ERR_ARG;
-  if (which < 0 || which >= 4 || !(value >= 0)) return cfrk_fail(ctx, CFRK_ERR_ARG, "cfrk_debug_set_param: no such parameter / negative value");
+  if (which < 0 || which >= 5 || !(value >= 0)) return cfrk_fail(ctx, CFRK_ERR_ARG, "cfrk_debug_set_param: no such parameter / negative value");
   if (value != 0) {
     if (which == CFRK_PARAM_MSP_CHUNKS && !(value >= 1 && value <= 4096)) return cfrk_fail(ctx, CFRK_ERR_ARG, "chunks: 1 .. 4096");
     if ((which == CFRK_PARAM_L2_SLACK_COMPLETE || which == CFRK_PARAM_L2_SLACK_TRUNCATED) && !(value >= 1.0 && value <= 16.0))
       return cfrk_fail(ctx, CFRK_ERR_ARG, "leaf-stream slack: 1 .. 16");
     if (which == CFRK_PARAM_MSP2_SUBVALUE_BITS && !(value >= 1 && value <= 3)) return cfrk_fail(ctx, CFRK_ERR_ARG, "sub-value bits + 1: 1 .. 3");
+    if (which == CFRK_PARAM_UNITIG_SPLIT_LOG2 && !(value >= 1 && value <= 20)) return cfrk_fail(ctx, CFRK_ERR_ARG, "unitig splitter bits + 1: 1 .. 20");
   }
   ctx->dbg_param[which] = value;
   return CFRK_OK;

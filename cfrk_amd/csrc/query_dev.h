@@ -46,6 +46,29 @@ __device__ __forceinline__ uint32_t q_find2(const uint4 *__restrict__ s, uint64_
   return 0;
 }
 
+// The same probes returning the SLOT of the key, Q_NO_SLOT when it is absent: what a kernel needs that keeps data of
+// its own beside the index, in arrays indexed by slot (unitigs.hip).
+constexpr uint64_t Q_NO_SLOT = ~0ull;
+__device__ __forceinline__ uint64_t q_find1_slot(const uint4 *__restrict__ s, uint64_t mask, uint64_t h, uint64_t key) {
+  for (uint64_t probe = 0; probe <= mask; ++probe) {
+    const uint4 v = s[h];
+    if (v.z == 0) return Q_NO_SLOT;
+    if (q_lo(v) == key) return h;
+    h = (h + 1) & mask;
+  }
+  return Q_NO_SLOT;
+}
+__device__ __forceinline__ uint64_t q_find2_slot(const uint4 *__restrict__ s, uint64_t mask, uint64_t h, uint64_t lo,
+                                                 uint64_t hi) {
+  for (uint64_t probe = 0; probe <= mask; ++probe) {
+    const uint4 a = s[2 * h], b = s[2 * h + 1];
+    if (b.x == 0) return Q_NO_SLOT;
+    if (q_lo(a) == lo && q_hi(a) == hi) return h;
+    h = (h + 1) & mask;
+  }
+  return Q_NO_SLOT;
+}
+
 // window i (bases i .. i+k-1 of the 64-base string hi:lo) as a key, canonical when asked
 template <bool CANON>
 __device__ __forceinline__ uint64_t q_window(uint64_t hi, uint64_t lo, int i, int k) {
@@ -77,6 +100,31 @@ __device__ __forceinline__ uint32_t q_key(const QIndex &q, uint64_t lo, uint64_t
   if (k < 64 && (hi >> (2 * k - 64)) != 0) return 0;
   if (CANON) q_canon2(lo, hi, k);
   return q_find2(static_cast<const uint4 *>(q.p), q.mask, q_slot2(lo, hi, q.shift), lo, hi);
+}
+
+// The index by slot.  Slots: 4^k (MODE 0, the slot is the key), else mask + 1.  q_slot_of takes a key as the index
+// stores it (in range, canonical in a canonical job); the slot of an absent key is Q_NO_SLOT in every mode.
+template <int MODE>
+__device__ __forceinline__ uint64_t q_nslots(const QIndex &q) { return MODE == 0 ? 1ull << (2 * q.k) : q.mask + 1; }
+template <int MODE>
+__device__ __forceinline__ uint32_t q_slot_count(const QIndex &q, uint64_t slot) {
+  if (MODE == 0) return static_cast<const uint32_t *>(q.p)[slot];
+  if (MODE == 1) return static_cast<const uint4 *>(q.p)[slot].z;
+  return static_cast<const uint4 *>(q.p)[2 * slot + 1].x;
+}
+template <int MODE>
+__device__ __forceinline__ void q_slot_key(const QIndex &q, uint64_t slot, uint64_t &lo, uint64_t &hi) {
+  hi = 0;
+  if (MODE == 0) { lo = slot; return; }
+  const uint4 v = static_cast<const uint4 *>(q.p)[MODE == 1 ? slot : 2 * slot];
+  lo = q_lo(v);
+  if (MODE == 2) hi = q_hi(v);
+}
+template <int MODE>
+__device__ __forceinline__ uint64_t q_slot_of(const QIndex &q, uint64_t lo, uint64_t hi) {
+  if (MODE == 0) return static_cast<const uint32_t *>(q.p)[lo] ? lo : Q_NO_SLOT;
+  if (MODE == 1) return q_find1_slot(static_cast<const uint4 *>(q.p), q.mask, q_slot1(lo, q.shift), lo);
+  return q_find2_slot(static_cast<const uint4 *>(q.p), q.mask, q_slot2(lo, hi, q.shift), lo, hi);
 }
 
 }  // namespace

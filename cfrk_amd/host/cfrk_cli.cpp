@@ -40,6 +40,11 @@
 //                    c, for every c with n_c > 0 (`jellyfish histo`'s shape without its upper cut-off)
 //   --histo-only     (global, with --histo) write the spectrum only: the counts are not exported and the output path is
 //                    left untouched
+//   --unitigs-out UFILE [--unitigs-min-count T]  (global, one device) after the count, the compacted de Bruijn graph of
+//                    the k-mers counted T times or more (default 1; 0 reads as 1) as FASTA: the unitigs ascending by
+//                    first k-mer, ">j LN:i:<bases> KC:i:<summed count> km:f:<KC / k-mers>" and " CL:i:1" on a circular
+//                    one, the sequence on one line (cfrk_global_unitigs, cfrk_host_format_unitigs).  Every other output
+//                    is what it is without the option
 //   --min-count N / --max-count N  (global) write only the entries with N_min <= count <= N_max (text and --binary; the
 //                    binary header's n and sum describe the records written)
 //   --query QFILE --query-out OFILE  (global) how often does each k-mer of the reads of QFILE (FASTA, clean parse) occur
@@ -184,6 +189,8 @@ struct Options {
   bool all_chunks = false, native = false, global = false, canonical = false, same_device = false, binary = false, timing = false, sparse = false;
   int device = 0, gpus = 1;
   const char *histo = nullptr;       // --histo FILE
+  const char *unitigs_out = nullptr;  // --unitigs-out UFILE
+  uint32_t unitigs_min_count = 1;     // --unitigs-min-count T
   bool histo_only = false;
   uint32_t min_count = 1, max_count = CFRK_COUNT_MAX;
   const char *query = nullptr, *query_out = nullptr, *query_db = nullptr;   // --query QFILE --query-out OFILE --query-db DB
@@ -444,6 +451,28 @@ int write_histo(const Options &o, const Spectrum &sp) {
   if (!f) { fprintf(stderr, "cfrk: cannot write %s\n", o.histo); return 1; }
   const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
   if (fclose(f) != 0 || !ok) { fprintf(stderr, "cfrk: cannot write %s\n", o.histo); return 1; }
+  return 0;
+}
+
+// --unitigs-out: the unitigs of the finished result through the host form (a sizes-only call, then arrays of that size),
+// formatted on one thread: the text of a compacted graph is small beside the count's input
+int write_unitigs(const Options &o, cfrk_ctx *ctx) {
+  int64_t nN = 0, nS = 0;
+  int rc = cfrk_global_unitigs(ctx, o.unitigs_min_count, nullptr, 0, nullptr, nullptr, nullptr, 0, &nN, &nS);
+  if (rc && rc != CFRK_ERR_SMALL_BUF) return die(ctx, rc, "cfrk_global_unitigs");
+  std::vector<int8_t> data((size_t)nN);
+  std::vector<int64_t> start((size_t)nS);
+  std::vector<int32_t> length((size_t)nS);
+  std::vector<cfrk_unitig> rec((size_t)nS);
+  if (rc && (rc = cfrk_global_unitigs(ctx, o.unitigs_min_count, data.data(), data.size(), start.data(), length.data(), rec.data(),
+                                      rec.size(), &nN, &nS))) return die(ctx, rc, "cfrk_global_unitigs");
+  std::string buf;
+  buf.resize(cfrk_host_format_unitigs(data.data(), start.data(), length.data(), rec.data(), nS, nullptr, 0));
+  cfrk_host_format_unitigs(data.data(), start.data(), length.data(), rec.data(), nS, &buf[0], buf.size());
+  FILE *f = fopen(o.unitigs_out, "wb");
+  if (!f) { fprintf(stderr, "cfrk: cannot write %s\n", o.unitigs_out); return 1; }
+  const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+  if (fclose(f) != 0 || !ok) { fprintf(stderr, "cfrk: cannot write %s\n", o.unitigs_out); return 1; }
   return 0;
 }
 
@@ -943,6 +972,7 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
     if ((rc = result_spectrum(ctx, sp)) || (rc = write_histo(o, sp))) return rc;
   }
   g_timing.histo = now_s() - t2;
+  if (o.unitigs_out && (rc = write_unitigs(o, ctx))) return rc;
   if (o.query) {
     const double q0 = now_s();
     if (o.query_out) {
@@ -1388,6 +1418,7 @@ int main(int argc, char **argv) {
   std::vector<const char *> pos;
   Options o;
   int batch_n = -1;
+  bool unitigs_opt_set = false;
   bool range_set = false, stats_below_set = false, filter_opt_set = false, correct_opt_set = false, correct_min_count_set = false, normalize_opt_set = false, normalize_cutoff_set = false;
   bool pair_opt_set = false, pair_mode_set = false;
   for (int i = 1; i < argc; ++i) {
@@ -1553,9 +1584,21 @@ int main(int argc, char **argv) {
       else o.max_count = x;
       range_set = true;
     }
+    else if (!strcmp(argv[i], "--unitigs-out") || !strcmp(argv[i], "--unitigs-min-count")) {
+      if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
+      const char *opt = argv[i], *v = argv[++i];
+      if (!strcmp(opt, "--unitigs-out")) { o.unitigs_out = v; continue; }
+      if (!parse_count(v, &o.unitigs_min_count)) { fprintf(stderr, "cfrk: %s needs a count (an integer from 0 to 4294967295), not '%s'\n", opt, v); return 1; }
+      unitigs_opt_set = true;
+    }
     else pos.push_back(argv[i]);
   }
   // (refused here: before the input is parsed or a device is opened)
+  if (o.unitigs_out && (!o.global || o.gpus > 1 || batch_n >= 0 || o.sparse)) {
+    fprintf(stderr, "cfrk: --unitigs-out needs --global on one device: not with --gpus above 1, --batch or --sparse\n");
+    return 1;
+  }
+  if (unitigs_opt_set && !o.unitigs_out) { fprintf(stderr, "cfrk: --unitigs-min-count needs --unitigs-out UFILE\n"); return 1; }
   if (o.sparse && (o.global || o.binary || o.histo || o.histo_only || range_set || o.query || o.query_out || o.query_only ||
                    o.query_db || o.query_stats || stats_below_set || o.filter_out || filter_opt_set || o.correct_out || correct_opt_set)) {
     fprintf(stderr, "cfrk: --sparse is a per-read mode: not with --global, --binary, --histo, --query or --min-count / --max-count\n");

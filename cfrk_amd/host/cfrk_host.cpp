@@ -729,6 +729,41 @@ size_t cfrk_host_format_fasta(const int8_t *data, const int64_t *start, const in
   return buf ? (size_t)(p - buf) : s;
 }
 
+size_t cfrk_host_format_unitigs(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
+                                char *buf, size_t cap) {
+  size_t s = 0;
+  char *p = buf;
+  (void)cap;
+  for (int64_t j = 0; j < nS; ++j) {
+    uint64_t kc;
+    uint32_t w[2];                                       // n_kmers, flags
+    memcpy(&kc, (const char *)rec + 16 * j, 8);
+    memcpy(w, (const char *)rec + 16 * j + 8, 8);
+    const uint64_t L = length[j] > 0 ? (uint64_t)length[j] : 0, n = w[0] ? w[0] : 1;
+    // kc / n to one decimal, halves rounded up, in integers (kc * 10 may pass 2^64)
+    const unsigned __int128 tenths = ((unsigned __int128)kc * 10 + n / 2) / n;
+    const uint64_t whole = (uint64_t)(tenths / 10), frac = (uint64_t)(tenths % 10);
+    const bool circ = (w[1] & 1u) != 0;
+    if (!buf) {
+      s += 1 + len_u64((uint64_t)j) + 6 + len_u64(L) + 6 + len_u64(kc) + 6 + len_u64(whole) + 2 + (circ ? 7 : 0) + 1 + (size_t)L + 1;
+      continue;
+    }
+    *p++ = '>';
+    p = put_u64(p, (uint64_t)j);
+    memcpy(p, " LN:i:", 6); p = put_u64(p + 6, L);
+    memcpy(p, " KC:i:", 6); p = put_u64(p + 6, kc);
+    memcpy(p, " km:f:", 6); p = put_u64(p + 6, whole);
+    *p++ = '.';
+    *p++ = (char)('0' + frac);
+    if (circ) { memcpy(p, " CL:i:1", 7); p += 7; }
+    *p++ = '\n';
+    const int8_t *r = data + start[j];
+    for (uint64_t x = 0; x < L; ++x) { const int c = r[x]; *p++ = (c >= 0 && c <= 3) ? "ACGT"[c] : 'N'; }
+    *p++ = '\n';
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
 static void put_le(char *p, uint64_t x, int bytes) { for (int i = 0; i < bytes; ++i) p[i] = (char)(x >> (8 * i)); }
 static uint64_t get_le(const char *p, int bytes) {
   uint64_t x = 0;

@@ -128,6 +128,15 @@ size_t cfrk_host_format_read_stats(const void *stats, int64_t nS, char *buf, siz
 size_t cfrk_host_format_fasta(const int8_t *data, const int64_t *start, const int32_t *length, const int64_t *index,
                               int64_t nS, char *buf, size_t cap);
 
+/* Unitigs as FASTA text (`cfrk --unitigs-out`): rec = nS rows of cfrk_unitig (cfrk_abi.h: 16 bytes -- kc as uint64,
+ * n_kmers and flags as uint32).  One record per unitig j, in order:
+ *   ">" j " LN:i:" length[j] " KC:i:" kc " km:f:" kc / n_kmers with one decimal (halves rounded up)
+ *   and " CL:i:1" when flags has CFRK_UNITIG_CIRCULAR, "\n", then the bases as ACGT (N for any other code) on ONE line.
+ * (The tags are BCALM's.)  One thread: the text is a few bytes per base of a compacted graph.  Returns bytes needed /
+ * written (buf may be NULL to size). */
+size_t cfrk_host_format_unitigs(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
+                                char *buf, size_t cap);
+
 /* Binary global form, little endian, everything in one file:
  *   header, 32 bytes:  char magic[8] = "CFRKGLB1"; uint32 k; uint32 flags (bit 0: canonical counting,
  *                      bit 1: two-word keys, i.e. k > 32); uint64 n (records); uint64 sum of counts

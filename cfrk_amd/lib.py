@@ -67,6 +67,11 @@ CFRK_FASTQ_SCAN_TILES = 1024         # tiles per block of its tile scan
 CFRK_FASTQ_QUAL_BASE = 33            # qualities are Phred+33
 CFRK_FASTQ_MAX_QUAL = 93             # min_qual is 0 .. this
 CFRK_PARAM_MSP_CHUNKS, CFRK_PARAM_L2_SLACK_COMPLETE, CFRK_PARAM_L2_SLACK_TRUNCATED, CFRK_PARAM_MSP2_SUBVALUE_BITS = 0, 1, 2, 3   # cfrk_debug_set_param
+CFRK_PARAM_UNITIG_SPLIT_LOG2 = 4     # s + 1: log2 of the unitig call's splitter period, plus one (0: the default)
+CFRK_UNITIG_CIRCULAR = 0x1           # cfrk_unitig.flags
+CFRK_UNITIG_SPLIT_LOG2_DEFAULT = 10
+# one row per unitig (cfrk_unitig)
+UNITIG_DTYPE = np.dtype([("kc", "<u8"), ("n_kmers", "<u4"), ("flags", "<u4")])
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libcfrk_hip.so")
@@ -131,6 +136,10 @@ def load_library():
         "cfrk_global_histogram": ([vp, vp, C.c_uint32], C.c_int),
         "cfrk_global_query": ([vp, vp, vp, i64, vp], C.c_int),
         "cfrk_global_query_device": ([vp, vp, vp, i64, vp], C.c_int),
+        "cfrk_global_neighbors": ([vp, vp, vp, i64, C.c_uint32, vp], C.c_int),
+        "cfrk_global_neighbors_device": ([vp, vp, vp, i64, C.c_uint32, vp], C.c_int),
+        "cfrk_global_unitigs": ([vp, C.c_uint32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "cfrk_global_unitigs_device": ([vp, C.c_uint32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_global_query_reads": ([vp, vp, vp, vp, i64, i64, vp], C.c_int),
         "cfrk_global_query_reads_device": ([vp, vp, i64, vp], C.c_int),
         "cfrk_global_read_stats": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
@@ -865,6 +874,56 @@ class GlobalCounter:
                                                         C.c_void_p(d_hi) if d_hi else None, n,
                                                         C.c_void_p(d_out) if d_out else None),
                        "cfrk_global_query_device")
+
+    def neighbors(self, keys_lo, keys_hi=None, min_count=1):
+        """neighbour mask of every key, taken as an oriented k-mer exactly as given -> np.uint8[n]: bit b (0..3) is set
+        iff key[1:] + b is present with count >= min_count, bit 4 + b iff b + key[:-1] is (the neighbour is
+        canonicalised in a CFRK_CANONICAL job); 0 for a key with bits at or above 2k"""
+        lo = np.ascontiguousarray(keys_lo, np.uint64)
+        hi = None if keys_hi is None else np.ascontiguousarray(keys_hi, np.uint64)
+        if hi is not None and len(hi) != len(lo):
+            raise ValueError("keys_lo and keys_hi differ in length")
+        out = np.empty(len(lo), np.uint8)
+        self.ctx.check(self._L.cfrk_global_neighbors(self.ctx._h, _ptr(lo), _ptr(hi), len(lo), int(min_count), _ptr(out)),
+                       "cfrk_global_neighbors")
+        return out
+
+    def neighbors_device(self, d_lo, d_hi, n, min_count, d_masks):
+        """device form of neighbors(): returns with the kernel enqueued on the context stream"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self.ctx.check(self._L.cfrk_global_neighbors_device(self.ctx._h, vp(d_lo), vp(d_hi), n, int(min_count), vp(d_masks)),
+                       "cfrk_global_neighbors_device")
+
+    def unitigs(self, min_count=1):
+        """the compacted de Bruijn graph of the keys with count >= min_count -> (data int8[nN], start int64[nS],
+        length int32[nS], rec UNITIG_DTYPE[nS]): the unitigs in the native struct-read layout (codes 0..3, one -1 behind
+        each), ascending by first k-mer; rec: summed count, k-mers, CFRK_UNITIG_CIRCULAR.  A sizes-only call, then the
+        call into arrays of exactly that size."""
+        nN, nS = C.c_int64(), C.c_int64()
+        rc = self._L.cfrk_global_unitigs(self.ctx._h, int(min_count), None, 0, None, None, None, 0, C.byref(nN), C.byref(nS))
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.ctx.check(rc, "cfrk_global_unitigs")
+        data, start = np.empty(nN.value, np.int8), np.empty(nS.value, np.int64)
+        length, rec = np.empty(nS.value, np.int32), np.zeros(nS.value, UNITIG_DTYPE)
+        if rc == CFRK_ERR_SMALL_BUF:
+            self.ctx.check(self._L.cfrk_global_unitigs(self.ctx._h, int(min_count), _ptr(data), data.size, _ptr(start), _ptr(length),
+                                                       _ptr(rec), rec.size, C.byref(nN), C.byref(nS)), "cfrk_global_unitigs")
+        return data, start, length, rec
+
+    def unitigs_device(self, min_count, d_data_out, cap_data, d_start_out, d_length_out, d_rec_out, cap_unitigs):
+        """device form -> (nN, nS); the arrays may be 0 with zero capacities (sizes only).  Raises CfrkError (code
+        CFRK_ERR_SMALL_BUF, with .nN and .nS set, nothing written) when they are too small.  Synchronises once, returns
+        with the emit enqueued on the context stream."""
+        nN, nS = C.c_int64(), C.c_int64()
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_global_unitigs_device(self.ctx._h, int(min_count), vp(d_data_out), cap_data, vp(d_start_out),
+                                                vp(d_length_out), vp(d_rec_out), cap_unitigs, C.byref(nN), C.byref(nS))
+        try:
+            self.ctx.check(rc, "cfrk_global_unitigs_device")
+        except CfrkError as e:
+            e.nN, e.nS = nN.value, nS.value
+            raise
+        return nN.value, nS.value
 
     def query_reads(self, data, start=None, length=None):
         """count of the k-mer starting at every base -> np.uint32[nN]: CFRK_QUERY_NONE where the window holds an

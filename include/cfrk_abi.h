@@ -407,6 +407,68 @@ int cfrk_global_normalize_pairs(cfrk_ctx *ctx, const int8_t *data, const int64_t
                                 int64_t nN, int64_t nS, uint32_t cutoff, int64_t batch_reads, int mode,
                                 uint8_t *keep, int64_t *n_kept);
 
+/* ---- unitigs: the compacted de Bruijn graph of the counted k-mers ---------------------------------------------- */
+
+/* Definitions.  The job has k (1 <= k <= 64) and a strand rule; min_count >= 1 (0 reads as 1).
+ *   Solid keys: the stored keys with count >= min_count.
+ *   Oriented k-mers O: the solid keys; in a CFRK_CANONICAL job every solid key x and rc(x).
+ *   node(a) = a, or min(a, rc(a)) in a canonical job.  a is palindromic iff the job is canonical and a == rc(a).
+ *   succ(a) = { a[1:] + b in O },  pred(a) = { b + a[:-1] in O }.
+ *   LINK a -> b iff succ(a) = {b}, pred(b) = {a}, node(a) != node(b) (no self-loops, no hairpins x -> rc(x)) and neither
+ *   a nor b is palindromic.  Links form disjoint directed paths and cycles over O; in a canonical job every component
+ *   has a distinct mirror image (the two exclusions are exactly what rules out a component that is its own mirror).
+ * A UNITIG is one component, written once:
+ *   path a1 -> ... -> an: as it stands; in a canonical job, of the path and its mirror the one whose first k-mer is
+ *     smaller (a1 < rc(an)); a single palindromic node is written once.
+ *   cycle: cut so that it starts at the smallest oriented k-mer of the cycle (canonical: and of its mirror); flagged
+ *     CFRK_UNITIG_CIRCULAR.
+ *   Sequence = a1 followed by the last base of every further k-mer: n_kmers + k - 1 bases.  kc = the sum of the n_kmers
+ *   stored counts.  Every solid key lies in exactly one unitig, once.
+ *   ORDER: ascending by first k-mer (first base most significant, A < C < G < T).  First k-mers are distinct, so this is
+ *   the ascending lexicographic order of the sequences: one deterministic byte string for a given result.
+ * Output: the struct-read layout of the parsers and of cfrk_reads_select -- codes 0..3, one -1 terminator behind each
+ *   unitig, start_out[j], length_out[j] (bases), rec_out[j] -- so that it goes straight into cfrk_global_add_device,
+ *   cfrk_per_read_sparse_device, the select, or a count at another k.  *nS_out = unitigs, *nN_out = bases + *nS_out.
+ * Capacities: *nS_out <= solid keys and *nN_out <= solid keys * (k + 1) always.  When *nN_out > cap_data or *nS_out >
+ *   cap_unitigs the call returns CFRK_ERR_SMALL_BUF with both sizes complete and nothing written to the arrays; NULL
+ *   arrays with zero capacities are that "sizes only" call.
+ * State: that of cfrk_global_query -- the lookup index is built on demand (and kept), the job is untouched, its digest
+ *   is the same before and after; adds may follow.  CFRK_ERR_STATE: no job, or a CFRK_RUNS_ONLY job.
+ * CFRK_ERR_ARG: NULL size outputs, a NULL array with a capacity above 0, 2^32 unitigs or more, an index of more than
+ *   2^31 slots.  CFRK_ERR_LAYOUT: a unitig of more than 2^31 - 1 bases.  No alignment requirement on data_out.
+ * Device form: seven stages, every one its own launches on the context stream (cfrk_amd/csrc/unitigs.hip): neighbour
+ *   bytes; links, cut at "splitter" nodes (a 2^-s sample of the keys by hash); segments between cuts walked one lane
+ *   each; segments stitched to unitigs one lane per unitig; cycles; the sort by first k-mer and the scan of the
+ *   lengths; the emit, one lane per segment.  No lane's work grows with the longest unitig beyond its number of
+ *   segments (n_kmers / 2^s).  It synchronises ONCE, for the sizes, and returns with the emit enqueued.
+ *   Temporary device memory, kept in the context's pool, per slot of the lookup index (2^ceil(log2(2 * keys)) slots,
+ *   4^k for k <= 12): 11 bytes + per orientation (2 in a canonical job, else 1) 32 bytes (64 for k <= 12) + 20 bytes
+ *   (40 for k <= 12), i.e. 95 bytes per slot for a canonical job of k > 12; 20 bytes per unitig and the sort's scratch.
+ * Host form: stages through the pool; synchronous.
+ *
+ * Neighbour masks.  Key i is taken as an oriented k-mer exactly as given (it need not be present itself):
+ *   bit b (0..3) of masks[i] is set iff key[1:] + b is present with count >= min_count, bit 4 + b iff b + key[:-1] is;
+ *   a canonical job canonicalises the NEIGHBOUR for the lookup; a key with bits at or above 2k gives 0.
+ *   keys_hi may be NULL for k <= 32.  State and errors as cfrk_global_query; the device form returns with the kernel
+ *   enqueued. */
+typedef struct {
+  uint64_t kc;        /* sum of the stored counts of the unitig's k-mers */
+  uint32_t n_kmers;   /* its k-mers: length - k + 1                      */
+  uint32_t flags;     /* CFRK_UNITIG_*                                   */
+} cfrk_unitig;        /* 16 bytes */
+#define CFRK_UNITIG_CIRCULAR 0x1
+#define CFRK_UNITIG_SPLIT_LOG2_DEFAULT 10   /* s: one key in 2^s is a splitter */
+int cfrk_global_neighbors_device(cfrk_ctx *ctx, const uint64_t *d_keys_lo, const uint64_t *d_keys_hi, int64_t n,
+                                 uint32_t min_count, uint8_t *d_masks);
+int cfrk_global_neighbors(cfrk_ctx *ctx, const uint64_t *keys_lo, const uint64_t *keys_hi, int64_t n,
+                          uint32_t min_count, uint8_t *masks);
+int cfrk_global_unitigs_device(cfrk_ctx *ctx, uint32_t min_count, int8_t *d_data_out, uint64_t cap_data,
+                               int64_t *d_start_out, int32_t *d_length_out, cfrk_unitig *d_rec_out, uint64_t cap_unitigs,
+                               int64_t *nN_out, int64_t *nS_out);
+int cfrk_global_unitigs(cfrk_ctx *ctx, uint32_t min_count, int8_t *data_out, uint64_t cap_data, int64_t *start_out,
+                        int32_t *length_out, cfrk_unitig *rec_out, uint64_t cap_unitigs, int64_t *nN_out,
+                        int64_t *nS_out);
+
 /* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
 
 /* How many DISTINCT k-mers will a job hold?  One streaming pass over the reads answers it to about 1 % before anything
@@ -902,6 +964,8 @@ int cfrk_debug_set_flags(cfrk_ctx *ctx, uint32_t flags);
 #define CFRK_PARAM_L2_SLACK_TRUNCATED  2  /* 1 .. 16: the same for truncated runs                                     */
 #define CFRK_PARAM_MSP2_SUBVALUE_BITS  3  /* 1 .. 3: log2(sub-values one workgroup of a shared leaf counts) + 1
                                              (33 <= k <= 64; normally chosen from the expected runs per leaf)         */
+#define CFRK_PARAM_UNITIG_SPLIT_LOG2   4  /* 1 .. 20: s + 1, s = log2 of the unitig call's splitter period (s = 0:
+                                             every node is a splitter); 0 = CFRK_UNITIG_SPLIT_LOG2_DEFAULT            */
 int cfrk_debug_set_param(cfrk_ctx *ctx, int which, double value);
 
 /* ---- synthetic reads, generated on device ----------------------------------- */
