@@ -879,6 +879,68 @@ int cfrk_global_unitigs(cfrk_ctx *ctx, uint32_t min_count, int8_t *data_out, uin
   return download_reads(ctx, o, data_out, start_out, length_out, nullptr, nN, nS);
 }
 
+static_assert(sizeof(cfrk_unitig_link) == 8, "cfrk_unitig_link is 8 bytes without padding");
+
+static int unitig_links_check(cfrk_ctx *ctx, const void *data, const void *start, const void *length, int64_t nN, int64_t nS,
+                              const void *link_ptr, const void *links, uint64_t cap_links, int64_t *n_links_out) {
+  int rc = query_check(ctx, 0);
+  if (rc) return rc;
+  if (nN < 0 || nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (!n_links_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL size output");
+  if (!link_ptr) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL link_ptr");
+  if (nS > 0 && (!data || !start || !length)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (cap_links > 0 && !links) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL array with a capacity above 0");
+  if ((uint64_t)nS >= (1ull << 32)) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld unitigs: a link names its target in 32 bits", (long long)nS);
+  *n_links_out = 0;
+  return CFRK_OK;
+}
+
+static int unitig_links_fit(cfrk_ctx *ctx, int64_t n_links, uint64_t cap_links) {
+  if ((uint64_t)n_links <= cap_links) return CFRK_OK;
+  return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "unitig links: %lld links, room for %llu", (long long)n_links, (unsigned long long)cap_links);
+}
+
+int cfrk_global_unitig_links_device(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d_data, const int64_t *d_start,
+                                    const int32_t *d_length, int64_t nN, int64_t nS, int64_t *d_link_ptr,
+                                    cfrk_unitig_link *d_links, uint64_t cap_links, int64_t *n_links_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = unitig_links_check(ctx, d_data, d_start, d_length, nN, nS, d_link_ptr, d_links, cap_links, n_links_out);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (nS == 0) { HIP_TRY(ctx, hipMemsetAsync(d_link_ptr, 0, 8, ctx->stream)); return CFRK_OK; }
+  if ((rc = cfrk_unitig_links_measure(ctx, min_count, d_data, d_start, d_length, nN, nS, d_link_ptr, n_links_out))) return rc;
+  if ((rc = unitig_links_fit(ctx, *n_links_out, cap_links)) || *n_links_out == 0) return rc;
+  return cfrk_unitig_links_fill(ctx, min_count, d_data, d_start, d_length, nN, nS, d_links);
+}
+
+int cfrk_global_unitig_links(cfrk_ctx *ctx, uint32_t min_count, const int8_t *data, const int64_t *start,
+                             const int32_t *length, int64_t nN, int64_t nS, int64_t *link_ptr, cfrk_unitig_link *links,
+                             uint64_t cap_links, int64_t *n_links_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = unitig_links_check(ctx, data, start, length, nN, nS, link_ptr, links, cap_links, n_links_out);
+  if (rc) return rc;
+  if (nS == 0) { link_ptr[0] = 0; return CFRK_OK; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // staged through the query calls' slots: the unitigs in with room for link_ptr behind them, the rows out
+  const size_t ptr_bytes = ((size_t)nS + 1) * 8;
+  StagePart x[1] = {{nullptr, ptr_bytes, nullptr}};
+  StagedReads d;
+  if ((rc = stage_reads(ctx, BUF_QUERY_IN, data, start, length, nN, nS, STAGE_TABLE, x, 1, &d))) return rc;
+  if ((rc = cfrk_unitig_links_measure(ctx, min_count, d.data, d.start, d.length, nN, nS, (int64_t *)x[0].dev, n_links_out)))
+    return stage_drain(ctx, rc);
+  const int64_t n = *n_links_out;
+  const int fit = unitig_links_fit(ctx, n, cap_links);
+  if (fit || n == 0) {
+    if ((rc = cfrk_memcpy_d2h(ctx, link_ptr, x[0].dev, ptr_bytes))) return rc;
+    return fit;
+  }
+  void *d_links;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, (size_t)n * sizeof *links, &d_links))) return rc;
+  if ((rc = cfrk_unitig_links_fill(ctx, min_count, d.data, d.start, d.length, nN, nS, (cfrk_unitig_link *)d_links))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(link_ptr, x[0].dev, ptr_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  return cfrk_memcpy_d2h(ctx, links, d_links, (size_t)n * sizeof *links);
+}
+
 /* ------------------------------------------------------------------ digital normalisation */
 
 static int normalize_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, int64_t batch_reads, const void *data, const void *start,

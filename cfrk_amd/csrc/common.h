@@ -51,6 +51,7 @@ enum {  // pool slots
   BUF_UNITIG,                                 // unitigs (unitigs.hip): counters, the per-slot bytes, segments, unitig records
   BUF_UNITIG_AUX,                             // the sort's payload, the lengths and their scan
   BUF_UNITIG_OUT,                             // staging of cfrk_global_unitigs alone (data, start, length, records out)
+  BUF_UNITIG_LINKS,                           // unitig links (unitig_links.hip): error / size words, the per-slot tags, the ends' counts and their scan
   BUF_NSLOTS
 };
 
@@ -187,6 +188,13 @@ int cfrk_pair_join_launch(cfrk_ctx *ctx, int64_t n_pairs, int stride, int mode, 
 int cfrk_neighbors_launch(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t *d_hi, int64_t n, uint32_t min_count, uint8_t *d_masks);
 int cfrk_unitigs_measure(cfrk_ctx *ctx, uint32_t min_count, int64_t *nN, int64_t *nS, uint64_t *nseg);
 int cfrk_unitigs_emit(cfrk_ctx *ctx, int8_t *d_data, int64_t *d_start, int32_t *d_length, cfrk_unitig *d_rec, int64_t nS, uint64_t nseg);
+// unitig_links.hip: the links between the unitigs of the job, in two steps: tags, counts and their scan into d_link_ptr
+// (nS + 1 entries), the consistency check (synchronises: *n_links, or CFRK_ERR_LAYOUT); then the rows into d_links (room
+// for *n_links >= 1 of them), left enqueued.  1 <= nS < 2^32.
+int cfrk_unitig_links_measure(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d_data, const int64_t *d_start,
+                              const int32_t *d_length, int64_t nN, int64_t nS, int64_t *d_link_ptr, int64_t *n_links);
+int cfrk_unitig_links_fill(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d_data, const int64_t *d_start,
+                           const int32_t *d_length, int64_t nN, int64_t nS, cfrk_unitig_link *d_links);
 // sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
 // enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
 int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,

@@ -33,14 +33,12 @@
 // Work memory (BUF_UNITIG), per index slot M and with o = 2 orientations in a canonical job, else 1; S = M (k <= 12)
 // or M / 2 (the hash index's load is at most 0.5) bounds the solid nodes: 3 M bytes (adj, link bits, marks) + 8 M (the
 // segment of a head, indexed by v) + 64 o S (segments) + 40 S (unitigs).  Canonical hash index: 95 bytes per slot.
-#include "query_dev.h"
 #include "staging.h"
+#include "unitig_dev.h"
 
 #include <hipcub/hipcub.hpp>
 
 namespace {
-
-typedef unsigned __int128 u128;
 
 constexpr uint32_t U_NONE = 0xFFFFFFFFu;
 enum { L_SOLID = 1, L_OUT = 2, L_IN = 4, L_OUT_CUT = 8, L_IN_CUT = 16, L_PAL = 32 };
@@ -69,15 +67,6 @@ struct UWork {
   unsigned long long *ctr;            // UC_*
 };
 
-// ---- k-mers as 128-bit numbers (first base most significant) ---------------------------------------------------
-__device__ __forceinline__ u128 u_make(uint64_t lo, uint64_t hi) { return ((u128)hi << 64) | lo; }
-__device__ __forceinline__ u128 u_kmask(int k) { return k == 64 ? ~(u128)0 : ((((u128)1) << (2 * k)) - 1); }
-__device__ __forceinline__ u128 u_rc(u128 x, int k) {
-  const u128 r = ((u128)dev_revcomp64((uint64_t)x, 32) << 64) | dev_revcomp64((uint64_t)(x >> 64), 32);
-  return r >> (128 - 2 * k);
-}
-__device__ __forceinline__ u128 u_succ_key(u128 x, int b, int k) { return ((x << 2) | (u128)(unsigned)b) & u_kmask(k); }
-__device__ __forceinline__ u128 u_pred_key(u128 x, int b, int k) { return (x >> 2) | ((u128)(unsigned)b << (2 * (k - 1))); }
 __device__ __forceinline__ bool u_splitter(u128 key, uint64_t split_mask) {
   return (dev_mix64((uint64_t)key ^ dev_mix64((uint64_t)(key >> 64))) & split_mask) == 0;
 }
@@ -91,18 +80,7 @@ __device__ __forceinline__ uint32_t u_lbits(uint32_t l, int o) {
          ((l & L_IN_CUT) ? L_OUT_CUT : 0);
 }
 
-// ---- nodes ------------------------------------------------------------------------------------------------------
-// the slot and the orientation of oriented k-mer z (in range); pal: z is its own reverse complement
-template <int MODE, bool CANON>
-__device__ __forceinline__ uint64_t u_node(const QIndex &q, u128 z, int &o, bool &pal) {
-  o = 0; pal = false;
-  if (CANON) {
-    const u128 r = u_rc(z, q.k);
-    pal = r == z;
-    if (r < z) { z = r; o = 1; }
-  }
-  return q_slot_of<MODE>(q, (uint64_t)z, (uint64_t)(z >> 64));
-}
+// ---- nodes (u_node: unitig_dev.h) -------------------------------------------------------------------------------
 template <int MODE>
 __device__ __forceinline__ u128 u_slot_key(const QIndex &q, uint64_t slot) {
   uint64_t lo, hi;
@@ -446,21 +424,6 @@ __global__ __launch_bounds__(256) void u_emit_kernel(UWork w, uint64_t nseg, con
     }
   }
 }
-
-int u_grid(const cfrk_ctx *ctx, uint64_t items) {
-  const uint64_t want = (items + 255) / 256;
-  return (int)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)ctx->num_cus * 16));
-}
-
-#define U_DISPATCH(KERNEL, grid, ...)                                                                                   \
-  do {                                                                                                                  \
-    if (mode == 0) { if (canon) hipLaunchKernelGGL((KERNEL<0, true>), dim3(grid), dim3(256), 0, ctx->stream, __VA_ARGS__);  \
-                     else hipLaunchKernelGGL((KERNEL<0, false>), dim3(grid), dim3(256), 0, ctx->stream, __VA_ARGS__); }     \
-    else if (mode == 1) { if (canon) hipLaunchKernelGGL((KERNEL<1, true>), dim3(grid), dim3(256), 0, ctx->stream, __VA_ARGS__); \
-                          else hipLaunchKernelGGL((KERNEL<1, false>), dim3(grid), dim3(256), 0, ctx->stream, __VA_ARGS__); }    \
-    else { if (canon) hipLaunchKernelGGL((KERNEL<2, true>), dim3(grid), dim3(256), 0, ctx->stream, __VA_ARGS__);            \
-           else hipLaunchKernelGGL((KERNEL<2, false>), dim3(grid), dim3(256), 0, ctx->stream, __VA_ARGS__); }               \
-  } while (0)
 
 // the parts of BUF_UNITIG for an index of M slots (the same carve in both steps)
 size_t u_carve(void *base, const QIndex &q, bool canon, UWork *w) {

@@ -45,6 +45,12 @@
 //                    first k-mer, ">j LN:i:<bases> KC:i:<summed count> km:f:<KC / k-mers>" and " CL:i:1" on a circular
 //                    one, the sequence on one line (cfrk_global_unitigs, cfrk_host_format_unitigs).  Every other output
 //                    is what it is without the option
+//   --unitigs-links  (with --unitigs-out) BCALM's L tags at the end of every header: " L:<+|->:<v>:<+|->" for every link
+//                    out of the unitig, the links out of its + end first (cfrk_global_unitig_links,
+//                    cfrk_host_format_unitigs_links)
+//   --unitigs-gfa GFILE [--unitigs-min-count T]  (global, one device; with or without --unitigs-out) the same graph as
+//                    GFA 1.0: an S line per unitig with the LN / KC / km tags, an L line per link with the overlap
+//                    <k-1>M (cfrk_host_format_gfa)
 //   --min-count N / --max-count N  (global) write only the entries with N_min <= count <= N_max (text and --binary; the
 //                    binary header's n and sum describe the records written)
 //   --query QFILE --query-out OFILE  (global) how often does each k-mer of the reads of QFILE (FASTA, clean parse) occur
@@ -191,6 +197,8 @@ struct Options {
   const char *histo = nullptr;       // --histo FILE
   const char *unitigs_out = nullptr;  // --unitigs-out UFILE
   uint32_t unitigs_min_count = 1;     // --unitigs-min-count T
+  bool unitigs_links = false;         // --unitigs-links
+  const char *unitigs_gfa = nullptr;  // --unitigs-gfa GFILE
   bool histo_only = false;
   uint32_t min_count = 1, max_count = CFRK_COUNT_MAX;
   const char *query = nullptr, *query_out = nullptr, *query_db = nullptr;   // --query QFILE --query-out OFILE --query-db DB
@@ -455,7 +463,16 @@ int write_histo(const Options &o, const Spectrum &sp) {
 }
 
 // --unitigs-out: the unitigs of the finished result through the host form (a sizes-only call, then arrays of that size),
-// formatted on one thread: the text of a compacted graph is small beside the count's input
+// formatted on one thread: the text of a compacted graph is small beside the count's input.  --unitigs-links and
+// --unitigs-gfa: the links between them as well, the same way.
+int write_text_file(const char *path, const std::string &buf) {
+  FILE *f = fopen(path, "wb");
+  if (!f) { fprintf(stderr, "cfrk: cannot write %s\n", path); return 1; }
+  const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+  if (fclose(f) != 0 || !ok) { fprintf(stderr, "cfrk: cannot write %s\n", path); return 1; }
+  return 0;
+}
+
 int write_unitigs(const Options &o, cfrk_ctx *ctx) {
   int64_t nN = 0, nS = 0;
   int rc = cfrk_global_unitigs(ctx, o.unitigs_min_count, nullptr, 0, nullptr, nullptr, nullptr, 0, &nN, &nS);
@@ -467,12 +484,29 @@ int write_unitigs(const Options &o, cfrk_ctx *ctx) {
   if (rc && (rc = cfrk_global_unitigs(ctx, o.unitigs_min_count, data.data(), data.size(), start.data(), length.data(), rec.data(),
                                       rec.size(), &nN, &nS))) return die(ctx, rc, "cfrk_global_unitigs");
   std::string buf;
-  buf.resize(cfrk_host_format_unitigs(data.data(), start.data(), length.data(), rec.data(), nS, nullptr, 0));
-  cfrk_host_format_unitigs(data.data(), start.data(), length.data(), rec.data(), nS, &buf[0], buf.size());
-  FILE *f = fopen(o.unitigs_out, "wb");
-  if (!f) { fprintf(stderr, "cfrk: cannot write %s\n", o.unitigs_out); return 1; }
-  const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
-  if (fclose(f) != 0 || !ok) { fprintf(stderr, "cfrk: cannot write %s\n", o.unitigs_out); return 1; }
+  if (!o.unitigs_links && !o.unitigs_gfa) {
+    buf.resize(cfrk_host_format_unitigs(data.data(), start.data(), length.data(), rec.data(), nS, nullptr, 0));
+    cfrk_host_format_unitigs(data.data(), start.data(), length.data(), rec.data(), nS, &buf[0], buf.size());
+    return write_text_file(o.unitigs_out, buf);
+  }
+  std::vector<int64_t> link_ptr((size_t)nS + 1);
+  int64_t n_links = 0;
+  rc = cfrk_global_unitig_links(ctx, o.unitigs_min_count, data.data(), start.data(), length.data(), nN, nS, link_ptr.data(), nullptr, 0, &n_links);
+  if (rc && rc != CFRK_ERR_SMALL_BUF) return die(ctx, rc, "cfrk_global_unitig_links");
+  std::vector<cfrk_unitig_link> links((size_t)n_links);
+  if (rc && (rc = cfrk_global_unitig_links(ctx, o.unitigs_min_count, data.data(), start.data(), length.data(), nN, nS, link_ptr.data(),
+                                           links.data(), links.size(), &n_links))) return die(ctx, rc, "cfrk_global_unitig_links");
+  if (o.unitigs_out) {
+    const int64_t *lp = o.unitigs_links ? link_ptr.data() : nullptr;     // (without --unitigs-links: the bytes as they were)
+    buf.resize(cfrk_host_format_unitigs_links(data.data(), start.data(), length.data(), rec.data(), nS, lp, links.data(), nullptr, 0));
+    cfrk_host_format_unitigs_links(data.data(), start.data(), length.data(), rec.data(), nS, lp, links.data(), &buf[0], buf.size());
+    if ((rc = write_text_file(o.unitigs_out, buf))) return rc;
+  }
+  if (o.unitigs_gfa) {
+    buf.resize(cfrk_host_format_gfa(data.data(), start.data(), length.data(), rec.data(), nS, link_ptr.data(), links.data(), o.k, nullptr, 0));
+    cfrk_host_format_gfa(data.data(), start.data(), length.data(), rec.data(), nS, link_ptr.data(), links.data(), o.k, &buf[0], buf.size());
+    if ((rc = write_text_file(o.unitigs_gfa, buf))) return rc;
+  }
   return 0;
 }
 
@@ -972,7 +1006,7 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
     if ((rc = result_spectrum(ctx, sp)) || (rc = write_histo(o, sp))) return rc;
   }
   g_timing.histo = now_s() - t2;
-  if (o.unitigs_out && (rc = write_unitigs(o, ctx))) return rc;
+  if ((o.unitigs_out || o.unitigs_gfa) && (rc = write_unitigs(o, ctx))) return rc;
   if (o.query) {
     const double q0 = now_s();
     if (o.query_out) {
@@ -1584,10 +1618,12 @@ int main(int argc, char **argv) {
       else o.max_count = x;
       range_set = true;
     }
-    else if (!strcmp(argv[i], "--unitigs-out") || !strcmp(argv[i], "--unitigs-min-count")) {
+    else if (!strcmp(argv[i], "--unitigs-links")) o.unitigs_links = true;
+    else if (!strcmp(argv[i], "--unitigs-out") || !strcmp(argv[i], "--unitigs-min-count") || !strcmp(argv[i], "--unitigs-gfa")) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
       const char *opt = argv[i], *v = argv[++i];
       if (!strcmp(opt, "--unitigs-out")) { o.unitigs_out = v; continue; }
+      if (!strcmp(opt, "--unitigs-gfa")) { o.unitigs_gfa = v; continue; }
       if (!parse_count(v, &o.unitigs_min_count)) { fprintf(stderr, "cfrk: %s needs a count (an integer from 0 to 4294967295), not '%s'\n", opt, v); return 1; }
       unitigs_opt_set = true;
     }
@@ -1598,7 +1634,12 @@ int main(int argc, char **argv) {
     fprintf(stderr, "cfrk: --unitigs-out needs --global on one device: not with --gpus above 1, --batch or --sparse\n");
     return 1;
   }
-  if (unitigs_opt_set && !o.unitigs_out) { fprintf(stderr, "cfrk: --unitigs-min-count needs --unitigs-out UFILE\n"); return 1; }
+  if (o.unitigs_gfa && (!o.global || o.gpus > 1 || batch_n >= 0 || o.sparse)) {
+    fprintf(stderr, "cfrk: --unitigs-gfa needs --global on one device: not with --gpus above 1, --batch or --sparse\n");
+    return 1;
+  }
+  if (o.unitigs_links && !o.unitigs_out) { fprintf(stderr, "cfrk: --unitigs-links needs --unitigs-out UFILE\n"); return 1; }
+  if (unitigs_opt_set && !o.unitigs_out && !o.unitigs_gfa) { fprintf(stderr, "cfrk: --unitigs-min-count needs --unitigs-out UFILE\n"); return 1; }
   if (o.sparse && (o.global || o.binary || o.histo || o.histo_only || range_set || o.query || o.query_out || o.query_only ||
                    o.query_db || o.query_stats || stats_below_set || o.filter_out || filter_opt_set || o.correct_out || correct_opt_set)) {
     fprintf(stderr, "cfrk: --sparse is a per-read mode: not with --global, --binary, --histo, --query or --min-count / --max-count\n");

@@ -729,11 +729,33 @@ size_t cfrk_host_format_fasta(const int8_t *data, const int64_t *start, const in
   return buf ? (size_t)(p - buf) : s;
 }
 
+// the FASTA of the unitigs; with link_ptr, the L tags of row j behind its header
+static size_t format_unitigs(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
+                             const int64_t *link_ptr, const void *links, char *buf);
+
 size_t cfrk_host_format_unitigs(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
                                 char *buf, size_t cap) {
+  (void)cap;
+  return format_unitigs(data, start, length, rec, nS, nullptr, nullptr, buf);
+}
+
+size_t cfrk_host_format_unitigs_links(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec,
+                                      int64_t nS, const int64_t *link_ptr, const void *links, char *buf, size_t cap) {
+  (void)cap;
+  return format_unitigs(data, start, length, rec, nS, link_ptr, links, buf);
+}
+
+// row i of cfrk_unitig_link (8 bytes: to, flags as uint32)
+static void get_link(const void *links, int64_t i, uint32_t *to, bool *from_minus, bool *to_minus) {
+  uint32_t w[2];
+  memcpy(w, (const char *)links + 8 * i, 8);
+  *to = w[0]; *from_minus = (w[1] & 1u) != 0; *to_minus = (w[1] & 2u) != 0;
+}
+
+static size_t format_unitigs(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
+                             const int64_t *link_ptr, const void *links, char *buf) {
   size_t s = 0;
   char *p = buf;
-  (void)cap;
   for (int64_t j = 0; j < nS; ++j) {
     uint64_t kc;
     uint32_t w[2];                                       // n_kmers, flags
@@ -744,8 +766,14 @@ size_t cfrk_host_format_unitigs(const int8_t *data, const int64_t *start, const 
     const unsigned __int128 tenths = ((unsigned __int128)kc * 10 + n / 2) / n;
     const uint64_t whole = (uint64_t)(tenths / 10), frac = (uint64_t)(tenths % 10);
     const bool circ = (w[1] & 1u) != 0;
+    const int64_t l0 = link_ptr ? link_ptr[j] : 0, l1 = link_ptr ? link_ptr[j + 1] : 0;
     if (!buf) {
       s += 1 + len_u64((uint64_t)j) + 6 + len_u64(L) + 6 + len_u64(kc) + 6 + len_u64(whole) + 2 + (circ ? 7 : 0) + 1 + (size_t)L + 1;
+      for (int64_t i = l0; i < l1; ++i) {                // " L:<+|->:<v>:<+|->"
+        uint32_t to; bool fm, tm;
+        get_link(links, i, &to, &fm, &tm);
+        s += 7 + len_u64(to);
+      }
       continue;
     }
     *p++ = '>';
@@ -756,11 +784,62 @@ size_t cfrk_host_format_unitigs(const int8_t *data, const int64_t *start, const 
     *p++ = '.';
     *p++ = (char)('0' + frac);
     if (circ) { memcpy(p, " CL:i:1", 7); p += 7; }
+    for (int64_t i = l0; i < l1; ++i) {
+      uint32_t to; bool fm, tm;
+      get_link(links, i, &to, &fm, &tm);
+      memcpy(p, " L:", 3); p[3] = fm ? '-' : '+'; p[4] = ':';
+      p = put_u64(p + 5, to);
+      *p++ = ':'; *p++ = tm ? '-' : '+';
+    }
     *p++ = '\n';
     const int8_t *r = data + start[j];
     for (uint64_t x = 0; x < L; ++x) { const int c = r[x]; *p++ = (c >= 0 && c <= 3) ? "ACGT"[c] : 'N'; }
     *p++ = '\n';
   }
+  return buf ? (size_t)(p - buf) : s;
+}
+
+size_t cfrk_host_format_gfa(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
+                            const int64_t *link_ptr, const void *links, int k, char *buf, size_t cap) {
+  (void)cap;
+  size_t s = 11;                                         // "H\tVN:Z:1.0\n"
+  char *p = buf;
+  if (buf) { memcpy(p, "H\tVN:Z:1.0\n", 11); p += 11; }
+  for (int64_t j = 0; j < nS; ++j) {
+    uint64_t kc;
+    uint32_t w[2];                                       // n_kmers, flags
+    memcpy(&kc, (const char *)rec + 16 * j, 8);
+    memcpy(w, (const char *)rec + 16 * j + 8, 8);
+    const uint64_t L = length[j] > 0 ? (uint64_t)length[j] : 0, n = w[0] ? w[0] : 1;
+    const unsigned __int128 tenths = ((unsigned __int128)kc * 10 + n / 2) / n;      // as in the FASTA header
+    const uint64_t whole = (uint64_t)(tenths / 10), frac = (uint64_t)(tenths % 10);
+    if (!buf) { s += 2 + len_u64((uint64_t)j) + 1 + (size_t)L + 6 + len_u64(L) + 6 + len_u64(kc) + 6 + len_u64(whole) + 2 + 1; continue; }
+    *p++ = 'S'; *p++ = '\t';
+    p = put_u64(p, (uint64_t)j);
+    *p++ = '\t';
+    const int8_t *r = data + start[j];
+    for (uint64_t x = 0; x < L; ++x) { const int c = r[x]; *p++ = (c >= 0 && c <= 3) ? "ACGT"[c] : 'N'; }
+    memcpy(p, "\tLN:i:", 6); p = put_u64(p + 6, L);
+    memcpy(p, "\tKC:i:", 6); p = put_u64(p + 6, kc);
+    memcpy(p, "\tkm:f:", 6); p = put_u64(p + 6, whole);
+    *p++ = '.';
+    *p++ = (char)('0' + frac);
+    *p++ = '\n';
+  }
+  const uint64_t overlap = k > 0 ? (uint64_t)k - 1 : 0;
+  for (int64_t j = 0; j < nS; ++j)
+    for (int64_t i = link_ptr[j]; i < link_ptr[j + 1]; ++i) {
+      uint32_t to; bool fm, tm;
+      get_link(links, i, &to, &fm, &tm);
+      if (!buf) { s += 2 + len_u64((uint64_t)j) + 3 + len_u64(to) + 3 + len_u64(overlap) + 2; continue; }
+      *p++ = 'L'; *p++ = '\t';
+      p = put_u64(p, (uint64_t)j);
+      *p++ = '\t'; *p++ = fm ? '-' : '+'; *p++ = '\t';
+      p = put_u64(p, to);
+      *p++ = '\t'; *p++ = tm ? '-' : '+'; *p++ = '\t';
+      p = put_u64(p, overlap);
+      *p++ = 'M'; *p++ = '\n';
+    }
   return buf ? (size_t)(p - buf) : s;
 }
 

@@ -137,6 +137,20 @@ size_t cfrk_host_format_fasta(const int8_t *data, const int64_t *start, const in
 size_t cfrk_host_format_unitigs(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
                                 char *buf, size_t cap);
 
+/* The same FASTA with BCALM's L tags (`cfrk --unitigs-out UFILE --unitigs-links`): link_ptr = nS + 1 offsets, links =
+ * rows of cfrk_unitig_link (cfrk_abi.h: 8 bytes -- to and flags as uint32; flags bit 0: the link leaves (j,-), bit 1: it
+ * enters (to,-)).  For every link of row j, in row order, " L:<+|->:<to>:<+|->" is appended at the very end of the
+ * header, behind " CL:i:1" where that is present.  Returns bytes needed / written (buf may be NULL to size). */
+size_t cfrk_host_format_unitigs_links(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec,
+                                      int64_t nS, const int64_t *link_ptr, const void *links, char *buf, size_t cap);
+
+/* The graph as GFA 1.0 (`cfrk --unitigs-gfa GFILE`): "H\tVN:Z:1.0\n"; one "S\t<j>\t<SEQ>\tLN:i:<len>\tKC:i:<kc>\tkm:f:<x.y>\n"
+ * per unitig (the mean as in the FASTA header, N for any code outside 0..3); then one
+ * "L\t<u>\t<+|->\t<v>\t<+|->\t<k-1>M\n" per link, in CSR order.  Returns bytes needed / written (buf may be NULL to
+ * size). */
+size_t cfrk_host_format_gfa(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
+                            const int64_t *link_ptr, const void *links, int k, char *buf, size_t cap);
+
 /* Binary global form, little endian, everything in one file:
  *   header, 32 bytes:  char magic[8] = "CFRKGLB1"; uint32 k; uint32 flags (bit 0: canonical counting,
  *                      bit 1: two-word keys, i.e. k > 32); uint64 n (records); uint64 sum of counts

@@ -72,6 +72,10 @@ CFRK_UNITIG_CIRCULAR = 0x1           # cfrk_unitig.flags
 CFRK_UNITIG_SPLIT_LOG2_DEFAULT = 10
 # one row per unitig (cfrk_unitig)
 UNITIG_DTYPE = np.dtype([("kc", "<u8"), ("n_kmers", "<u4"), ("flags", "<u4")])
+CFRK_LINK_FROM_MINUS = 0x1           # cfrk_unitig_link.flags: the link leaves (j,-)
+CFRK_LINK_TO_MINUS = 0x2             # it enters (to,-)
+# one row per link (cfrk_unitig_link)
+UNITIG_LINK_DTYPE = np.dtype([("to", "<u4"), ("flags", "<u4")])
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libcfrk_hip.so")
@@ -140,6 +144,8 @@ def load_library():
         "cfrk_global_neighbors_device": ([vp, vp, vp, i64, C.c_uint32, vp], C.c_int),
         "cfrk_global_unitigs": ([vp, C.c_uint32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_global_unitigs_device": ([vp, C.c_uint32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "cfrk_global_unitig_links": ([vp, C.c_uint32, vp, vp, vp, i64, i64, vp, vp, u64, C.POINTER(i64)], C.c_int),
+        "cfrk_global_unitig_links_device": ([vp, C.c_uint32, vp, vp, vp, i64, i64, vp, vp, u64, C.POINTER(i64)], C.c_int),
         "cfrk_global_query_reads": ([vp, vp, vp, vp, i64, i64, vp], C.c_int),
         "cfrk_global_query_reads_device": ([vp, vp, i64, vp], C.c_int),
         "cfrk_global_read_stats": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
@@ -924,6 +930,40 @@ class GlobalCounter:
             e.nN, e.nS = nN.value, nS.value
             raise
         return nN.value, nS.value
+
+    def unitig_links(self, data, start, length, min_count=1):
+        """the links between the unitigs of this job at this min_count, as unitigs() returned them -> (link_ptr
+        int64[nS + 1], links UNITIG_LINK_DTYPE[n_links]): CSR over unitigs; a row holds the links out of (j,+), then those
+        out of (j,-) (CFRK_LINK_FROM_MINUS), ascending by appended base, target + before - (CFRK_LINK_TO_MINUS).  A
+        sizes-only call, then the call into an array of exactly that size."""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        nS, n = len(length), C.c_int64()
+        link_ptr = np.zeros(nS + 1, np.int64)
+        args = (self.ctx._h, int(min_count), _ptr(data), _ptr(start), _ptr(length), len(data), nS, _ptr(link_ptr))
+        rc = self._L.cfrk_global_unitig_links(*args, None, 0, C.byref(n))
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.ctx.check(rc, "cfrk_global_unitig_links")
+        links = np.zeros(n.value, UNITIG_LINK_DTYPE)
+        if rc == CFRK_ERR_SMALL_BUF:
+            self.ctx.check(self._L.cfrk_global_unitig_links(*args, _ptr(links), links.size, C.byref(n)), "cfrk_global_unitig_links")
+        return link_ptr, links
+
+    def unitig_links_device(self, min_count, d_data, d_start, d_length, nN, nS, d_link_ptr, d_links, cap_links):
+        """device form -> n_links; d_links may be 0 with cap_links 0 (sizes only).  Raises CfrkError (code
+        CFRK_ERR_SMALL_BUF, with .n_links set, d_link_ptr complete, nothing written to d_links) when cap_links is too
+        small.  Synchronises once, returns with the fill pass enqueued on the context stream."""
+        n = C.c_int64()
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_global_unitig_links_device(self.ctx._h, int(min_count), vp(d_data), vp(d_start), vp(d_length), nN, nS,
+                                                     vp(d_link_ptr), vp(d_links), cap_links, C.byref(n))
+        try:
+            self.ctx.check(rc, "cfrk_global_unitig_links_device")
+        except CfrkError as e:
+            e.n_links = n.value
+            raise
+        return n.value
 
     def query_reads(self, data, start=None, length=None):
         """count of the k-mer starting at every base -> np.uint32[nN]: CFRK_QUERY_NONE where the window holds an

@@ -469,6 +469,58 @@ int cfrk_global_unitigs(cfrk_ctx *ctx, uint32_t min_count, int8_t *data_out, uin
                         int32_t *length_out, cfrk_unitig *rec_out, uint64_t cap_unitigs, int64_t *nN_out,
                         int64_t *nS_out);
 
+/* Unitig links: the edges of the compacted graph.  The job, k, the strand rule, min_count, the solid keys, O, rc, succ
+ * and pred are those above.  The input is the unitig list of this job at this min_count as cfrk_global_unitigs wrote
+ * it: unitig j has the sequence s_j of length[j] >= k codes at start[j].
+ *   Orientations: + and - of every unitig in a canonical job, + alone otherwise.
+ *   head(j,+) = s_j[0:k], tail(j,+) = s_j[len-k:len], head(j,-) = rc(tail(j,+)), tail(j,-) = rc(head(j,+)).
+ *   LINK (u,ou) -> (v,ov) iff head(v,ov) is in succ(tail(u,ou)): tail(u,ou)[1:] + b == head(v,ov) for a base b, that
+ *   k-mer being in O.  The overlap is always k - 1 bases.  This is the plain set, with no special cases; it follows that
+ *   - every k-mer of succ(tail(u,ou)) is the head of at least one oriented unitig (a tail has no out-link, so its
+ *     successors have no in-link), and of two only when it is a palindromic single-node unitig: then (v,+) and (v,-)
+ *     are both targets;
+ *   - a CFRK_UNITIG_CIRCULAR unitig has the link (j,+) -> (j,+), in a canonical job (j,-) -> (j,-) as well (GFA's way
+ *     to state a circle); a homopolymer node has (j,+) -> (j,+), a hairpin x -> rc(x) gives (j,+) -> (j,-);
+ *   - in a canonical job the mirror (v,!ov) -> (u,!ou) of every link is a link as well; both are written, as BCALM does;
+ *   - an oriented end has at most 8 links (4 bases x 2): n_links <= 16 nS in a canonical job, <= 4 nS otherwise.
+ * Output: CSR over unitigs.  link_ptr[0] = 0, link_ptr[j + 1] - link_ptr[j] = links out of unitig j, *n_links_out =
+ *   link_ptr[nS]; links[] holds rows of cfrk_unitig_link.  Inside row j the links out of (j,+) come before those out of
+ *   (j,-); within an end they ascend by the appended base b (A < C < G < T); for one b the target + comes before -.
+ *   One byte string for a given result.
+ * Capacity (the select's protocol): when n_links > cap_links the call returns CFRK_ERR_SMALL_BUF with link_ptr and
+ *   *n_links_out complete and nothing written to links; NULL links with cap_links 0 is that "sizes only" call.
+ * State: that of cfrk_global_unitigs -- the index is built on demand and kept, the job is only read (same digest before
+ *   and after), adds may follow.  CFRK_ERR_STATE: no job, or a CFRK_RUNS_ONLY job.
+ * CFRK_ERR_ARG: negative sizes, NULL n_links_out, NULL link_ptr, NULL data / start / length with nS > 0, NULL links with
+ *   cap_links > 0, nS >= 2^32, an index of more than 2^31 slots.  nS = 0 is fine: link_ptr[0] = 0, no links.
+ * Consistency check (cheap; necessary, not sufficient): CFRK_ERR_LAYOUT, cfrk_last_error naming the first offending
+ *   unitig, when some unitig has length < k or a range outside [0, nN), an invalid code in an end window, an end k-mer
+ *   that is not solid at min_count, an end node another unitig end of the input claims as well, or a solid successor of
+ *   a tail that is the head of no oriented unitig of the input: unitigs of another job or threshold, edited sequences.
+ *   Named is the first unitig whose own ends are wrong; when there is none, the first with such a successor.
+ *   The error is found before the sizes are known and wins over CFRK_ERR_SMALL_BUF; after it the arrays are
+ *   unspecified.  For any input whatever nothing outside the buffers is accessed and no loop is unbounded.
+ * Device form (cfrk_amd/csrc/unitig_links.hip): no alignment requirement on d_data, all offsets 64-bit.  A tag pass (one
+ *   lane per unitig end writes the unitig and four end bits at the end node's index slot), a count pass (one lane per
+ *   oriented end: at most 4 successor lookups), a scan into link_ptr, and a fill pass.  No lane's work depends on a
+ *   unitig's length beyond its 2k end bases.  It synchronises ONCE, for n_links and the error word, and returns with
+ *   the fill pass enqueued.  Temporary device memory, kept in the context's pool: 8 bytes per slot of the lookup index
+ *   and 8 bytes per oriented unitig plus the scan's scratch.
+ * Host form: stages through the pool, checks start / length against the terminators as cfrk_global_add does
+ *   (CFRK_ERR_LAYOUT); synchronous. */
+typedef struct cfrk_unitig_link {   /* 8 bytes, no padding */
+  uint32_t to;      /* target unitig v */
+  uint32_t flags;   /* bit 0 (CFRK_LINK_FROM_MINUS): the link leaves (j,-); bit 1 (CFRK_LINK_TO_MINUS): it enters (v,-) */
+} cfrk_unitig_link;
+#define CFRK_LINK_FROM_MINUS 0x1
+#define CFRK_LINK_TO_MINUS 0x2
+int cfrk_global_unitig_links_device(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d_data, const int64_t *d_start,
+                                    const int32_t *d_length, int64_t nN, int64_t nS, int64_t *d_link_ptr /* nS + 1 */,
+                                    cfrk_unitig_link *d_links, uint64_t cap_links, int64_t *n_links_out);
+int cfrk_global_unitig_links(cfrk_ctx *ctx, uint32_t min_count, const int8_t *data, const int64_t *start,
+                             const int32_t *length, int64_t nN, int64_t nS, int64_t *link_ptr /* nS + 1 */,
+                             cfrk_unitig_link *links, uint64_t cap_links, int64_t *n_links_out);
+
 /* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
 
 /* How many DISTINCT k-mers will a job hold?  One streaming pass over the reads answers it to about 1 % before anything

@@ -17,7 +17,13 @@ and per case two yardsticks in the same process: cfrk_global_query_device on 8 x
 absent neighbours' do) and a device copy of the output bytes.  Per-kernel times come from running this under
 `rocprofv3 --kernel-trace --stats`, in a run of its own.
 
-  python tools/bench_unitigs.py [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
+With --links the same cases time cfrk_global_unitig_links_device instead, on the unitigs the default splitter period
+wrote: per case one JSON line (tool "bench_unitig_links") with the sizes-only call (tag, count, scan: `measure`), the
+whole call into an array of exactly n_links rows (`call`), the unitigs call alternating with it in the same repetitions
+(`unitigs_call`), and cfrk_global_query_device on 6 x o x unitigs uniformly random keys (o = 2: the canonical job's
+orientations), the number of probes the passes make: 2 x unitigs in the tag pass, o x 4 x unitigs in the count pass.
+
+  python tools/bench_unitigs.py [--links] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
 """
 import argparse
 import json
@@ -40,6 +46,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--error-rate", type=float, default=0.01)
     ap.add_argument("--max-query-keys", type=int, default=400_000_000)
+    ap.add_argument("--links", action="store_true")
     a = ap.parse_args()
 
     import torch
@@ -98,6 +105,56 @@ def main():
         def full():
             g.unitigs_device(min_count, out[0].data_ptr(), oN, out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), oS)
 
+        if a.links:
+            full()
+            ctx.sync()
+            d_ptr = buf((oS + 1) * 8)
+            unitigs = (out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), oN, oS)
+
+            def link_sizes():
+                try:
+                    return g.unitig_links_device(min_count, *unitigs, d_ptr.data_ptr(), 0, 0)
+                except cfrk_amd.CfrkError as e:
+                    if e.code != cfrk_amd.CFRK_ERR_SMALL_BUF:
+                        raise
+                    return e.n_links
+
+            n_links = link_sizes()
+            d_links = buf(n_links * 8)
+            copy_of = [buf(oN), buf(oS * 8), buf(oS * 4), buf(oS * 16)]     # (the unitigs call beside it writes elsewhere)
+
+            def link_full():
+                g.unitig_links_device(min_count, *unitigs, d_ptr.data_ptr(), d_links.data_ptr(), n_links)
+
+            def unitigs_again():
+                g.unitigs_device(min_count, copy_of[0].data_ptr(), oN, copy_of[1].data_ptr(), copy_of[2].data_ptr(), copy_of[3].data_ptr(), oS)
+
+            nq = max(1, min(12 * oS, a.max_query_keys))
+            with torch.cuda.stream(stream):
+                keys = torch.randint(0, 1 << (2 * k), (nq,), device="cuda", dtype=torch.int64)
+                ans = buf(nq * 4)
+            torch.cuda.synchronize()
+
+            def query():
+                g.query_device(keys.data_ptr(), 0, nq, ans.data_ptr())
+
+            t = {"measure": [], "call": [], "unitigs_call": [], "query_device": []}
+            for rep in range(a.reps + 1):
+                for name, fn in (("measure", link_sizes), ("call", link_full), ("unitigs_call", unitigs_again), ("query_device", query)):
+                    ms = timed(fn)
+                    if rep:                                     # (the first round warms up: code objects, pool buffers)
+                        t[name].append(ms)
+            torch.cuda.synchronize()
+            row = {"tool": "bench_unitig_links", "case": case, "reads": R, "L": L, "glen": a.glen, "k": k, "reps": a.reps,
+                   "error_rate": 0.0 if case == "a" else a.error_rate, "min_count": min_count, "distinct_keys": distinct,
+                   "unitigs": oS, "bytes": oN, "links": n_links, "query_keys": nq}
+            row.update({name: stats(ts) for name, ts in t.items()})
+            row["call_over_unitigs"] = row["call"]["ms"] / row["unitigs_call"]["ms"]
+            row["ns_per_unitig"] = row["call"]["ms"] * 1e6 / max(oS, 1)
+            print(json.dumps(row), flush=True)
+            del g, out, copy_of, keys, ans, d_ptr, d_links, reads
+            torch.cuda.empty_cache()
+            continue
         t_graph, t_call = {s: [] for s in splits}, {s: [] for s in splits}
         for rep in range(a.reps + 1):
             for s in splits:
