@@ -1346,6 +1346,10 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
         const uint32_t n32 = (uint32_t)n1a;                    // (< HUGE_LEAF)
         uint32_t wb = __builtin_amdgcn_readfirstlane((uint32_t)(tid - lane));   // the wave's first record: a scalar
         P3_MARK("P3_PART_LOAD");
+        // (measured and not kept, round 27: the loop one trip ahead of its loads -- 0.05 ms of P3's 6.3 in each of three
+        //  rounds, under the bar of three standard deviations -- and the first trip's records asked for at the kernel's
+        //  entry, in front of the clear of the tables: 0.06 ms on its own, nothing beside the truncated records' early
+        //  loads below.  Sixteen waves per workgroup and two workgroups per CU already hide a record's way from HBM.)
         for (; wb + (uint32_t)P3_THREADS + 64u <= n32; wb += 2u * P3_THREADS) {
           const uint4 rec0 = src[wb + lane], rec1 = src[wb + P3_THREADS + lane];
           home_fast(std::true_type{}, rec0, true);
@@ -1409,6 +1413,32 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
     if (c) drain(std::false_type{}, c);
     if ((v.dbg & CFRK_DEBUG_FORCE_RT_OVERFLOW) && !big_first) rt_fail = 1u;
   }
+  // The first TL_CAP truncated records, TL_PER per thread, are asked for HERE: their addresses were known at entry, and
+  // the cache merge, the clear of the k-mer table and their three barriers need nothing of them -- the HBM round trip
+  // (~1.5 us per leaf, two leaves per CU) runs under that work instead of behind it.  All of a thread's records in
+  // one go and WITHOUT A BRANCH around them (behind one the compiler copies the records into other registers at once,
+  // and waits for them to do so): lanes past the end load the last record again; a leaf without truncated runs, an
+  // exporting leaf, which never looks at them, and a leaf of the pool-wide table load one record that is surely there.
+  // The one-GPU counting kernels only: the shared and the lists forms keep their registers as they were.
+  constexpr bool TREC_EARLY = !SHARED && !LISTS;
+  uint4 trec[TL_PER];
+  auto load_trec = [&](bool early) {
+    if constexpr (TREC_EARLY) {
+      const uint4 *tb = tl ? trunc : v.rec2;
+      // (big_first: the pool-wide table's path asks again behind its own code -- one record here, not four per thread)
+      const uint32_t lim = (tl && !(mode & P3_EXPORT) && !(early && big_first)) ? tl - 1u : 0u;
+#pragma unroll
+      for (int i = 0; i < TL_PER; ++i) trec[i] = tb[min((uint32_t)(i * P3_THREADS + tid), lim)];
+    } else {
+#pragma unroll
+      for (int i = 0; i < TL_PER; ++i) trec[i] = make_uint4(0u, 0u, 0u, 0u);
+      if (tl) {                                      // (uniform)
+#pragma unroll
+        for (int i = 0; i < TL_PER; ++i) trec[i] = ld_t(min((uint32_t)(i * P3_THREADS + tid), tl - 1u));
+      }
+    }
+  };
+  if constexpr (TREC_EARLY) load_trec(true);
   P3_MARK("P3_PART_MERGE");
   __syncthreads();
   if (use_cache) {
@@ -1460,6 +1490,9 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
     for (int s = tid; s < TS; s += P3_THREADS) { keys[s] = CFRK_EMPTY_KEY; cnts[s] = 0; }
     for (int s = tid; s < RT; s += P3_THREADS) rtab[s] = make_uint4(0u, 0u, 0u, RT_EMPTY);
     __syncthreads();
+    // (the rare path: the truncated records are asked for again, so that sixteen registers are not kept alive -- or
+    //  spilled -- across the pool-wide table's code)
+    if constexpr (TREC_EARLY) load_trec(false);
   }
   const bool listed = nd != 0xFFFFFFFFu;
   const bool big = !listed && rt_fail != 0u;
@@ -1481,14 +1514,9 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
     constexpr uint32_t TW_NONE = 0xFFFFFFFFu, TW_TWIN = 0x80000000u;
     uint32_t tw[TL_PER], trank[TL_PER];              // n-1, or TW_TWIN | twin slot << 8 | n
     // (all of a thread's records are asked for before the first is looked up: one HBM round trip instead of
-    //  TL_PER -- the compiler put a full wait behind every load, 4 x ~1.5 us per leaf with two leaves per CU)
-    uint4 trec[TL_PER];
-#pragma unroll
-    for (int i = 0; i < TL_PER; ++i) trec[i] = make_uint4(0u, 0u, 0u, 0u);
-    if (tl) {                                        // (uniform; lanes past the end load the last record again: no
-#pragma unroll                                       //  per-lane branch, so the four loads are in flight together)
-      for (int i = 0; i < TL_PER; ++i) trec[i] = ld_t(min((uint32_t)(i * P3_THREADS + tid), tl - 1u));
-    }
+    //  TL_PER -- the compiler put a full wait behind every load, 4 x ~1.5 us per leaf with two leaves per CU;
+    //  the one-GPU counting kernels have asked in front of the cache merge, see there)
+    if constexpr (!TREC_EARLY) load_trec(false);
 #pragma unroll
     for (int i = 0; i < TL_PER; ++i) {
       const uint32_t g = (uint32_t)(i * P3_THREADS + tid);
@@ -1653,6 +1681,9 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
       }
       // truncated runs: those without a twin (anchored leaf), or all of the sorted list
       const uint32_t ntr = nfl;
+      // (measured and not kept, round 27: these two loops one trip ahead of their loads -- an anchored leaf lists at most
+      //  FL_CAP = one trip of truncated runs, so nothing was hidden; and the first trip's record asked for in front of
+      //  the complete runs' expansion keeps four more registers alive across it: ten spilled)
       for (uint32_t i = tid; i < ((ntr + 63u) & ~63u) && !(v.dbg & CFRK_ABL_P3_NO_TRUNC); i += P3_THREADS) {
         const bool valid = i < ntr;
         uint4 rec = make_uint4(0u, 0u, 0u, 0u);
@@ -1685,29 +1716,59 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
     constexpr int NIT = TS / P3_THREADS;
     uint32_t wbase[NIT];
     if (v.dbg & CFRK_ABL_P3_NO_OUT) continue;
-    auto occupied = [&](int s) { return keys[s] != CFRK_EMPTY_KEY; };
-    wg_rank_slots<NIT, P3_THREADS>(wbase, &wg_total, occupied);
-    __syncthreads();
-    if (tid == 0) {
-      wg_base = atomicAdd((unsigned long long *)&v.stats[ST_CURSOR], (unsigned long long)wg_total);
+    // A thread reads its NIT slots ONCE, keys and counts, into registers; the wave that comes by last (wg_rank_slots_last:
+    // one LDS atomic per wave, no barrier) asks the cursor for the workgroup's places at once, and the counts are read
+    // and the places inside the segment worked out while that atomic is on its way to HBM and back.  One barrier
+    // publishes wg_base; behind it are only the stores.  (Before: ranking, barrier, thread 0's atomic with sixteen
+    // waves parked, barrier, the table read again, stores, barrier.)
+    unsigned long long kk[NIT], occ_m[NIT];
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      kk[i] = keys[i * P3_THREADS + tid];
+      occ_m[i] = __ballot(kk[i] != CFRK_EMPTY_KEY);
+    }
+    const uint32_t total = wg_rank_slots_last<NIT, P3_THREADS>(wbase, &wg_total, occ_m);
+    const bool asks = lane == 0 && total != 0xFFFFFFFFu;         // (every wave has come by: `total` is the workgroup's)
+    unsigned long long got = 0ull;
+    if (asks) {
+      // (the address goes through a vector register the compiler cannot see through: for an address it knows to be
+      //  uniform it rewrites the add into "one lane adds for all, readfirstlane, mad", which waits for the atomic on
+      //  the spot -- the one thing this order is there to avoid)
+      uint32_t opaque0 = 0u;
+      asm volatile("" : "+v"(opaque0));
+      got = atomicAdd((unsigned long long *)&v.stats[ST_CURSOR] + opaque0, (unsigned long long)total);
+    }
+    uint32_t cc[NIT];
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      cc[i] = cnts[i * P3_THREADS + tid];
+      wbase[i] += (uint32_t)__popcll(occ_m[i] & ((1ull << lane) - 1ull));
+    }
+    if (asks) {
+      wg_base = got;
       // a leaf counted in several passes has several segments in the list: no per-leaf index then
       // (a shared leaf: one index entry per sub-value, (leaf << sub_bits) | sub-value)
       uint32_t sg = leaf;
       if (SHARED) sg = (leaf << sub_bits) | rsel;
       if (!LISTS) {                                  // (an owner's result is not kept in leaf form)
-        if (nseg == 0) v.leaf_off[sg] = wg_base;
-        else if (wg_total) v.stats[ST_MULTISEG] = 1;
+        if (nseg == 0) v.leaf_off[sg] = got;
+        else if (total) v.stats[ST_MULTISEG] = 1;
       }
-      if (wg_total) nseg = nseg + 1;
-      leaf_total += wg_total;
+      if (total) nseg = nseg + 1;
+      leaf_total += total;
       if (!LISTS) v.leaf_n[sg] = leaf_total;
     }
     __syncthreads();
-    wg_emit_slots<NIT, P3_THREADS>(wbase, wg_base, occupied, [&](int s, unsigned long long dst) {
-      if (dst < v.out_cap) { v.out_keys[dst] = keys[s]; v.out_cnt[dst] = cnts[s]; }
+    const unsigned long long list_base = wg_base;
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      if (kk[i] == CFRK_EMPTY_KEY) continue;
+      const unsigned long long dst = list_base + wbase[i];
+      if (dst < v.out_cap) { v.out_keys[dst] = kk[i]; v.out_cnt[dst] = cc[i]; }
       else v.stats[ST_OVERFLOW] = 1;
-    });
-    __syncthreads();
+    }
+    // (no barrier here: the table has been read in front of the one above, and two barriers lie between this pass's
+    //  reads of wg_base / sp and the next pass's writes)
   }
 }
 

@@ -127,6 +127,30 @@ __device__ __forceinline__ void wg_rank_slots(uint32_t (&wbase)[NIT], uint32_t *
     wbase[i] = __shfl(b, 0);
   }
 }
+// The leaf kernel's own form of part 1 (msp.hip: p3_body): a wave takes the places of its NIT rows with ONE LDS atomic
+// (the rows' ballots first, their popcounts added; row i starts at the wave's base plus the popcounts of the rows
+// before it), and the same atomic counts the waves that have come by (`*wg_state`: places taken in the low 16 bits,
+// waves in the high 16; must be 0; NIT * NT < 2^16), so the LAST wave knows the workgroup's total without a barrier and
+// its lane 0 can ask the list's cursor for the places at once.  m[i] = the ballot of row i (the caller has the rows'
+// keys in registers).  -> the total in the last wave's lanes, ~0u in the others'.  The order of a workgroup's entries
+// inside its segment is the waves' order of arrival, as with wg_rank_slots.
+template <int NIT, int NT>
+__device__ __forceinline__ uint32_t wg_rank_slots_last(uint32_t (&wbase)[NIT], uint32_t *wg_state, const unsigned long long (&m)[NIT]) {
+  static_assert(NIT * NT < 65536 && NT / 64 < 65536, "places and waves share one word");
+  const int lane = threadIdx.x & 63;
+  uint32_t tot = 0;
+#pragma unroll
+  for (int i = 0; i < NIT; ++i) {
+    wbase[i] = tot;
+    tot += (uint32_t)__popcll(m[i]);
+  }
+  uint32_t old = 0;
+  if (lane == 0) old = atomicAdd(wg_state, tot + (1u << 16));
+  old = __builtin_amdgcn_readfirstlane(old);
+#pragma unroll
+  for (int i = 0; i < NIT; ++i) wbase[i] += old & 0xFFFFu;
+  return ((old >> 16) == (uint32_t)(NT / 64 - 1)) ? (old & 0xFFFFu) + tot : 0xFFFFFFFFu;
+}
 template <int NIT, int NT, class Occ, class Emit>
 __device__ __forceinline__ void wg_emit_slots(const uint32_t (&wbase)[NIT], unsigned long long list_base, Occ occupied, Emit emit) {
   const int tid = threadIdx.x, lane = tid & 63;
