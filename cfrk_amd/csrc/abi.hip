@@ -941,6 +941,125 @@ int cfrk_global_unitig_links(cfrk_ctx *ctx, uint32_t min_count, const int8_t *da
   return cfrk_memcpy_d2h(ctx, links, d_links, (size_t)n * sizeof *links);
 }
 
+static_assert(sizeof(cfrk_unitig_pos) == 8, "cfrk_unitig_pos is 8 bytes without padding");
+static_assert(sizeof(cfrk_read_hit) == 16, "cfrk_read_hit is 16 bytes without padding");
+
+static int unitig_index_check(cfrk_ctx *ctx, const void *data, const void *start, const void *length, int64_t nN, int64_t nS) {
+  int rc = query_check(ctx, 0);
+  if (rc) return rc;
+  if (nN < 0 || nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (nS > 0 && (!data || !start || !length)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if ((uint64_t)nS >= (1ull << 32)) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld unitigs: a position names its unitig in 32 bits", (long long)nS);
+  return CFRK_OK;
+}
+
+int cfrk_global_unitig_index_device(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d_data, const int64_t *d_start,
+                                    const int32_t *d_length, int64_t nN, int64_t nS) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = unitig_index_check(ctx, d_data, d_start, d_length, nN, nS);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_unitig_index_build(ctx, min_count, d_data, d_start, d_length, nN, nS);
+}
+
+int cfrk_global_unitig_index(cfrk_ctx *ctx, uint32_t min_count, const int8_t *data, const int64_t *start,
+                             const int32_t *length, int64_t nN, int64_t nS) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = unitig_index_check(ctx, data, start, length, nN, nS);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (nS == 0) return cfrk_unitig_index_build(ctx, min_count, nullptr, nullptr, nullptr, 0, 0);
+  // staged through the query calls' slot: the unitigs in
+  StagedReads d;
+  if ((rc = stage_reads(ctx, BUF_QUERY_IN, data, start, length, nN, nS, STAGE_TABLE, nullptr, 0, &d))) return rc;
+  return stage_drain(ctx, cfrk_unitig_index_build(ctx, min_count, d.data, d.start, d.length, nN, nS));
+}
+
+int cfrk_global_locate_device(cfrk_ctx *ctx, const uint64_t *d_keys_lo, const uint64_t *d_keys_hi, int64_t n,
+                              cfrk_unitig_pos *d_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = query_check(ctx, n);
+  if (rc) return rc;
+  if (n > 0 && (!d_keys_lo || !d_out || (ctx->g_two && !d_keys_hi))) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_unitig_locate_launch(ctx, d_keys_lo, d_keys_hi, n, d_out);
+}
+
+int cfrk_global_locate(cfrk_ctx *ctx, const uint64_t *keys_lo, const uint64_t *keys_hi, int64_t n, cfrk_unitig_pos *out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = query_check(ctx, n);
+  if (rc) return rc;
+  if (n > 0 && (!keys_lo || !out || (ctx->g_two && !keys_hi))) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (n == 0) return cfrk_unitig_locate_launch(ctx, nullptr, nullptr, 0, nullptr);      // (the state is still checked)
+  // staged through the query calls' slots: the keys in, the positions out
+  void *d_in, *d_out;
+  const size_t bytes = (size_t)n * 8;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_IN, keys_hi ? 2 * bytes : bytes, &d_in))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, bytes, &d_out))) return rc;
+  uint64_t *d_lo = (uint64_t *)d_in, *d_hi = keys_hi ? d_lo + n : nullptr;
+  HIP_TRY(ctx, hipMemcpyAsync(d_lo, keys_lo, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (keys_hi) HIP_TRY(ctx, hipMemcpyAsync(d_hi, keys_hi, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = cfrk_unitig_locate_launch(ctx, d_lo, d_hi, n, (cfrk_unitig_pos *)d_out))) return stage_drain(ctx, rc);
+  return cfrk_memcpy_d2h(ctx, out, d_out, bytes);
+}
+
+static int read_hits_check(cfrk_ctx *ctx, const void *data, const void *start, const void *length, int64_t nN, int64_t nS,
+                           const void *hit_ptr, const void *hits, uint64_t cap_hits, int64_t *n_hits_out) {
+  int rc = query_check(ctx, 0);
+  if (rc) return rc;
+  if (nN < 0 || nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (!n_hits_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL size output");
+  if (!hit_ptr) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL hit_ptr");
+  if (nS > 0 && (!data || !start || !length)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (cap_hits > 0 && !hits) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL array with a capacity above 0");
+  *n_hits_out = 0;
+  return CFRK_OK;
+}
+
+static int read_hits_fit(cfrk_ctx *ctx, int64_t n_hits, uint64_t cap_hits) {
+  if ((uint64_t)n_hits <= cap_hits) return CFRK_OK;
+  return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "read hits: %lld hits, room for %llu", (long long)n_hits, (unsigned long long)cap_hits);
+}
+
+int cfrk_global_read_hits_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                 int64_t nN, int64_t nS, int64_t *d_hit_ptr, cfrk_read_hit *d_hits, uint64_t cap_hits,
+                                 int64_t *n_hits_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = read_hits_check(ctx, d_data, d_start, d_length, nN, nS, d_hit_ptr, d_hits, cap_hits, n_hits_out);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if ((rc = cfrk_read_hits_count(ctx, d_data, d_start, d_length, nN, nS, d_hit_ptr, n_hits_out))) return rc;
+  if ((rc = read_hits_fit(ctx, *n_hits_out, cap_hits)) || *n_hits_out == 0) return rc;
+  return cfrk_read_hits_fill(ctx, d_data, d_start, d_length, nN, nS, d_hit_ptr, d_hits, *n_hits_out);
+}
+
+int cfrk_global_read_hits(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                          int64_t nS, int64_t *hit_ptr, cfrk_read_hit *hits, uint64_t cap_hits, int64_t *n_hits_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = read_hits_check(ctx, data, start, length, nN, nS, hit_ptr, hits, cap_hits, n_hits_out);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // staged through the query calls' slots: the reads in with room for hit_ptr behind them, the rows out
+  const size_t ptr_bytes = ((size_t)nS + 1) * 8;
+  StagePart x[1] = {{nullptr, ptr_bytes, nullptr}};
+  StagedReads d;
+  if ((rc = stage_reads(ctx, BUF_QUERY_IN, data, start, length, nN, nS, STAGE_TABLE, x, 1, &d))) return rc;
+  if ((rc = cfrk_read_hits_count(ctx, d.data, d.start, d.length, nN, nS, (int64_t *)x[0].dev, n_hits_out)))
+    return stage_drain(ctx, rc);
+  const int64_t n = *n_hits_out;
+  const int fit = read_hits_fit(ctx, n, cap_hits);
+  if (fit || n == 0) {
+    if ((rc = cfrk_memcpy_d2h(ctx, hit_ptr, x[0].dev, ptr_bytes))) return rc;
+    return fit;
+  }
+  void *d_hits;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_OUT, (size_t)n * sizeof *hits, &d_hits))) return rc;
+  if ((rc = cfrk_read_hits_fill(ctx, d.data, d.start, d.length, nN, nS, (int64_t *)x[0].dev, (cfrk_read_hit *)d_hits, n))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(hit_ptr, x[0].dev, ptr_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  return cfrk_memcpy_d2h(ctx, hits, d_hits, (size_t)n * sizeof *hits);
+}
+
 /* ------------------------------------------------------------------ digital normalisation */
 
 static int normalize_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, int64_t batch_reads, const void *data, const void *start,

@@ -52,6 +52,9 @@ enum {  // pool slots
   BUF_UNITIG_AUX,                             // the sort's payload, the lengths and their scan
   BUF_UNITIG_OUT,                             // staging of cfrk_global_unitigs alone (data, start, length, records out)
   BUF_UNITIG_LINKS,                           // unitig links (unitig_links.hip): error / size words, the per-slot tags, the ends' counts and their scan
+  BUF_UNITIG_POS,                             // position map (unitig_locate.hip): error words, one cfrk_unitig_pos per slot of the lookup index;
+                                              // valid while ctx->upos_epoch is the index's epoch
+  BUF_READ_HITS,                              // read hits (unitig_locate.hip): the scratch of the hit_ptr scan
   BUF_NSLOTS
 };
 
@@ -107,6 +110,8 @@ struct cfrk_ctx {
   // query index (query.hip): built on the first query of a job, cleared by every call that changes the result
   bool q_valid;
   int q_log2cap;         // hash index: log2 of its slots (0: the dense array of k <= 12)
+  uint64_t q_epoch;      // builds of the index so far: what is kept by slot beside the index names the build it belongs to
+  uint64_t upos_epoch;   // the build the position map of BUF_UNITIG_POS belongs to (0: there is no map)
 };
 
 int cfrk_fail(cfrk_ctx *ctx, int code, const char *fmt, ...);
@@ -195,6 +200,17 @@ int cfrk_unitig_links_measure(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d
                               const int32_t *d_length, int64_t nN, int64_t nS, int64_t *d_link_ptr, int64_t *n_links);
 int cfrk_unitig_links_fill(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d_data, const int64_t *d_start,
                            const int32_t *d_length, int64_t nN, int64_t nS, cfrk_unitig_link *d_links);
+// unitig_locate.hip: the position map of the unitig list into BUF_UNITIG_POS with its consistency check (synchronises:
+// CFRK_ERR_LAYOUT, or the map valid for the index as built); the positions of n >= 0 keys, left enqueued; the hits of
+// nS >= 0 reads in two steps: counts and their scan into d_hit_ptr (nS + 1 entries; synchronises: *n_hits), then the rows
+// into d_hits (room for n_hits >= 1 of them), left enqueued.  The last three are CFRK_ERR_STATE without a valid map.
+int cfrk_unitig_index_build(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d_data, const int64_t *d_start,
+                            const int32_t *d_length, int64_t nN, int64_t nS);
+int cfrk_unitig_locate_launch(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t *d_hi, int64_t n, cfrk_unitig_pos *d_out);
+int cfrk_read_hits_count(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+                         int64_t nS, int64_t *d_hit_ptr, int64_t *n_hits);
+int cfrk_read_hits_fill(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+                        int64_t nS, int64_t *d_hit_ptr, cfrk_read_hit *d_hits, int64_t n_hits);
 // sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
 // enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
 int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,

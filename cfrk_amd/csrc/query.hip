@@ -265,6 +265,7 @@ int cfrk_query_index(cfrk_ctx *ctx, QIndex *q) {
     }
     ctx->q_log2cap = lg;
     ctx->q_valid = true;
+    ++ctx->q_epoch;      // (what is kept by slot beside an earlier build, the position map, is no longer this index's)
   }
   q->p = ctx->pool[BUF_QUERY_INDEX].p;
   q->mask = (1ull << ctx->q_log2cap) - 1;

@@ -8,6 +8,9 @@
 //                                    device memory, one lookup at a time
 // Both call f(w, valid, count) for every window w in ascending order per lane / thread; count is the window's count
 // in the index when valid (all k codes are bases), 0 otherwise.  Inlined into the kernel, as lane_group.h's walkers.
+// A second form, chosen by the policy WinSlot in place of the default WinCount, calls f(w, valid, slot, minus): the
+// window's SLOT in the index (Q_NO_SLOT when the key is absent or the window invalid) for a kernel that keeps an array
+// of its own by slot (unitig_locate.hip), and whether the read spells the reverse complement of the stored key.
 // MODE 0: dense index (k <= 12), 1: one-word hash (k <= 32), 2: two-word hash (k > 32).
 #pragma once
 
@@ -21,6 +24,9 @@ namespace {
 constexpr int READ_STAGE_SLACK = 72;                   // k - 1 <= 63 bytes + skew <= 3 + dword round-up <= 3, a multiple of 8
                                                        // (sparse.hip, k <= 32, stages with a slack of its own)
 constexpr int LONG_CHUNK = 32;                         // windows a thread of the long path rolls in a row
+
+struct WinCount { static constexpr bool SLOT = false; };
+struct WinSlot { static constexpr bool SLOT = true; };
 
 template <bool TWO> struct RsKey { typedef uint64_t type; };
 template <> struct RsKey<true> { typedef unsigned __int128 type; };
@@ -45,6 +51,7 @@ struct Roller {
   }
   __device__ __forceinline__ bool valid() const { return run >= k; }
   __device__ __forceinline__ T key() const { return (CANON && rc < fwd) ? rc : fwd; }
+  __device__ __forceinline__ bool minus() const { return CANON && rc < fwd; }      // key() is the reverse complement
 };
 
 template <int G>
@@ -78,10 +85,20 @@ __device__ __forceinline__ uint32_t rs_lookup(const QIndex &q, T key) {
   return q_find2(static_cast<const uint4 *>(q.p), q.mask, q_slot2(lo, hi, q.shift), lo, hi);
 }
 
+// the same key's slot, Q_NO_SLOT when it is absent
+template <int MODE, class T>
+__device__ __forceinline__ uint64_t rs_lookup_slot(const QIndex &q, T key) {
+  const uint64_t lo = (uint64_t)key;
+  if (MODE == 0) return static_cast<const uint32_t *>(q.p)[lo] ? lo : Q_NO_SLOT;
+  if (MODE == 1) return q_find1_slot(static_cast<const uint4 *>(q.p), q.mask, q_slot1(lo, q.shift), lo);
+  const uint64_t hi = (uint64_t)(key >> (MODE == 2 ? 64 : 0));
+  return q_find2_slot(static_cast<const uint4 *>(q.p), q.mask, q_slot2(lo, hi, q.shift), lo, hi);
+}
+
 // Read (nwin >= 1 windows from byte st on, inside [0, nN)) by the G lanes of a group.  stage_dw: the group's
 // (READ_CAP + READ_STAGE_SLACK) / 4 dwords of LDS.  Lane l takes the windows [t0, t1) = its ceil(nwin / G), set before
 // f is first called (so f may capture them by reference).  The caller puts a wave_sync() before its group's next read.
-template <int G, int MODE, bool CANON, class F>
+template <int G, int MODE, bool CANON, class P = WinCount, class F>
 __device__ __forceinline__ void staged_windows(const int8_t *__restrict__ data, int64_t nN, int64_t st, int nwin,
                                                const QIndex &q, int32_t *stage_dw, int lane, int &t0, int &t1, F f) {
   constexpr bool TWO = MODE == 2;
@@ -104,12 +121,14 @@ __device__ __forceinline__ void staged_windows(const int8_t *__restrict__ data, 
     uint4 v[B], v2[B];
     uint32_t d[B];
     bool ok[B];
+    bool om[B];                                        // (slot form only)
 #pragma unroll
     for (int u = 0; u < B; ++u) {                      // every first-slot load of the batch is issued here ...
       const bool in = w0 + u < t1;
       if (in) R.push((int)stage[w0 + u + k - 1]);
       ok[u] = in && R.valid();
       key[u] = R.key();
+      if constexpr (P::SLOT) om[u] = R.minus();
       if (MODE == 0) {
         d[u] = ok[u] ? dense[(uint64_t)key[u]] : 0u;
       } else if (MODE == 1) {
@@ -123,7 +142,26 @@ __device__ __forceinline__ void staged_windows(const int8_t *__restrict__ data, 
 #pragma unroll
     for (int u = 0; u < B; ++u) {                      // ... before any is resolved
       if (w0 + u >= t1) break;
-      if (ok[u]) {
+      if constexpr (P::SLOT) {
+        uint64_t r = Q_NO_SLOT;
+        if (ok[u]) {
+          const uint64_t lo = (uint64_t)key[u], hi = (uint64_t)(key[u] >> (TWO ? 64 : 0));
+          if (MODE == 0) {
+            if (d[u]) r = lo;
+          } else if (MODE == 1) {
+            const uint64_t h = q_slot1(lo, q.shift);
+            if (v[u].z == 0) r = Q_NO_SLOT;
+            else if (q_lo(v[u]) == lo) r = h;
+            else r = q_find1_slot(slots, q.mask, (h + 1) & q.mask, lo);
+          } else {
+            const uint64_t h = q_slot2(lo, hi, q.shift);
+            if (v2[u].x == 0) r = Q_NO_SLOT;
+            else if (q_lo(v[u]) == lo && q_hi(v[u]) == hi) r = h;
+            else r = q_find2_slot(slots, q.mask, (h + 1) & q.mask, lo, hi);
+          }
+        }
+        f(w0 + u, ok[u], r, ok[u] && om[u]);
+      } else if (ok[u]) {
         uint32_t r;
         const uint64_t lo = (uint64_t)key[u], hi = (uint64_t)(key[u] >> (TWO ? 64 : 0));
         if (MODE == 0) {
@@ -147,7 +185,7 @@ __device__ __forceinline__ void staged_windows(const int8_t *__restrict__ data, 
 
 // the windows [c0, min(c0 + LONG_CHUNK, nwin)) of a read, rolled from its bytes in device memory (st + p <= st +
 // length - 1); nothing when c0 >= nwin
-template <int MODE, bool CANON, class F>
+template <int MODE, bool CANON, class P = WinCount, class F>
 __device__ __forceinline__ void long_chunk(const int8_t *__restrict__ data, int64_t st, int nwin, const QIndex &q,
                                            int64_t c0, F f) {
   if (c0 >= nwin) return;
@@ -157,8 +195,13 @@ __device__ __forceinline__ void long_chunk(const int8_t *__restrict__ data, int6
   for (int64_t p = c0; p < c1 + k - 1; ++p) {
     R.push((int)data[st + p]);
     if (p >= c0 + k - 1) {
-      if (R.valid()) f((int)(p - (k - 1)), true, rs_lookup<MODE>(q, R.key()));
-      else f((int)(p - (k - 1)), false, 0u);
+      if constexpr (P::SLOT) {
+        if (R.valid()) f((int)(p - (k - 1)), true, rs_lookup_slot<MODE>(q, R.key()), R.minus());
+        else f((int)(p - (k - 1)), false, Q_NO_SLOT, false);
+      } else {
+        if (R.valid()) f((int)(p - (k - 1)), true, rs_lookup<MODE>(q, R.key()));
+        else f((int)(p - (k - 1)), false, 0u);
+      }
     }
   }
 }

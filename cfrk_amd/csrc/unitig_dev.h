@@ -1,4 +1,4 @@
-// unitig_dev.h -- what the graph kernels share (unitigs.hip, unitig_links.hip): k-mers as 128-bit numbers, the node
+// unitig_dev.h -- what the graph kernels share (unitigs.hip, unitig_links.hip, unitig_locate.hip): k-mers as 128-bit numbers, the node
 // (index slot and orientation) of an oriented k-mer, the grid size and the dispatch over the three index modes and
 // the two strand rules.
 #pragma once

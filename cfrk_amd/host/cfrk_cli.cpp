@@ -51,6 +51,11 @@
 //   --unitigs-gfa GFILE [--unitigs-min-count T]  (global, one device; with or without --unitigs-out) the same graph as
 //                    GFA 1.0: an S line per unitig with the LN / KC / km tags, an L line per link with the overlap
 //                    <k-1>M (cfrk_host_format_gfa)
+//   --unitigs-map QFILE --unitigs-map-out MFILE [--unitigs-min-count T]  (global, one device; with or without --unitigs-out
+//                    and --unitigs-gfa) where the reads of QFILE (FASTA or FASTQ, sniffed as for --query) lie on that
+//                    graph, as GAF: one line per hit, a maximal stretch of a read's k-mers that step along one unitig on
+//                    one strand, the segment names those of --unitigs-gfa (cfrk_global_unitig_index_device,
+//                    cfrk_global_read_hits, cfrk_host_format_gaf)
 //   --min-count N / --max-count N  (global) write only the entries with N_min <= count <= N_max (text and --binary; the
 //                    binary header's n and sum describe the records written)
 //   --query QFILE --query-out OFILE  (global) how often does each k-mer of the reads of QFILE (FASTA, clean parse) occur
@@ -199,6 +204,8 @@ struct Options {
   uint32_t unitigs_min_count = 1;     // --unitigs-min-count T
   bool unitigs_links = false;         // --unitigs-links
   const char *unitigs_gfa = nullptr;  // --unitigs-gfa GFILE
+  const char *unitigs_map = nullptr;      // --unitigs-map QFILE
+  const char *unitigs_map_out = nullptr;  // --unitigs-map-out MFILE
   bool histo_only = false;
   uint32_t min_count = 1, max_count = CFRK_COUNT_MAX;
   const char *query = nullptr, *query_out = nullptr, *query_db = nullptr;   // --query QFILE --query-out OFILE --query-db DB
@@ -508,6 +515,41 @@ int write_unitigs(const Options &o, cfrk_ctx *ctx) {
     if ((rc = write_text_file(o.unitigs_gfa, buf))) return rc;
   }
   return 0;
+}
+
+// --unitigs-map QFILE --unitigs-map-out MFILE: the unitigs into device arrays (a sizes-only call, then arrays of that
+// size), where they stay; the position map from them (cfrk_global_unitig_index_device); the hits of QFILE's reads
+// (cfrk_global_read_hits) as GAF, the segment names those of --unitigs-gfa (cfrk_host_format_gaf)
+cfrk_batch g_mreads{};     // QFILE, parsed before the input is read
+int write_unitigs_map(const Options &o, cfrk_ctx *ctx) {
+  int64_t nN = 0, nS = 0;
+  int rc = cfrk_global_unitigs_device(ctx, o.unitigs_min_count, nullptr, 0, nullptr, nullptr, nullptr, 0, &nN, &nS);
+  if (rc && rc != CFRK_ERR_SMALL_BUF) return die(ctx, rc, "cfrk_global_unitigs_device");
+  void *d[4] = {nullptr, nullptr, nullptr, nullptr};      // data, start, length, records
+  struct Free { cfrk_ctx *c; void **d; ~Free() { for (int j = 0; j < 4; ++j) if (d[j]) cfrk_device_free(c, d[j]); } } free_d{ctx, d};
+  std::vector<int32_t> ulen((size_t)nS);
+  if (nS > 0) {
+    const size_t bytes[4] = {(size_t)nN, (size_t)nS * 8, (size_t)nS * 4, (size_t)nS * sizeof(cfrk_unitig)};
+    for (int j = 0; j < 4; ++j)
+      if ((rc = cfrk_device_alloc(ctx, bytes[j], &d[j]))) return die(ctx, rc, "cfrk_device_alloc");
+    if ((rc = cfrk_global_unitigs_device(ctx, o.unitigs_min_count, (int8_t *)d[0], (uint64_t)nN, (int64_t *)d[1], (int32_t *)d[2],
+                                         (cfrk_unitig *)d[3], (uint64_t)nS, &nN, &nS))) return die(ctx, rc, "cfrk_global_unitigs_device");
+  }
+  if ((rc = cfrk_global_unitig_index_device(ctx, o.unitigs_min_count, (const int8_t *)d[0], (const int64_t *)d[1], (const int32_t *)d[2],
+                                            nN, nS))) return die(ctx, rc, "cfrk_global_unitig_index_device");
+  if (nS > 0 && (rc = cfrk_memcpy_d2h(ctx, ulen.data(), d[2], (size_t)nS * 4))) return die(ctx, rc, "cfrk_memcpy_d2h");
+  const cfrk_batch &q = g_mreads;
+  std::vector<int64_t> hit_ptr((size_t)q.nS + 1);
+  int64_t n_hits = 0;
+  rc = cfrk_global_read_hits(ctx, q.data, q.start, q.length, q.nN, q.nS, hit_ptr.data(), nullptr, 0, &n_hits);
+  if (rc && rc != CFRK_ERR_SMALL_BUF) return die(ctx, rc, "cfrk_global_read_hits");
+  std::vector<cfrk_read_hit> hits((size_t)n_hits);
+  if (rc && (rc = cfrk_global_read_hits(ctx, q.data, q.start, q.length, q.nN, q.nS, hit_ptr.data(), hits.data(), hits.size(), &n_hits)))
+    return die(ctx, rc, "cfrk_global_read_hits");
+  std::string buf;
+  buf.resize(cfrk_host_format_gaf(q.length, q.nS, hit_ptr.data(), hits.data(), ulen.data(), o.k, nullptr, 0));
+  cfrk_host_format_gaf(q.length, q.nS, hit_ptr.data(), hits.data(), ulen.data(), o.k, &buf[0], buf.size());
+  return write_text_file(o.unitigs_map_out, buf);
 }
 
 // --query: the query reads (parsed once, clean FASTA) and the answers of one result for every window of them
@@ -1007,6 +1049,7 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
   }
   g_timing.histo = now_s() - t2;
   if ((o.unitigs_out || o.unitigs_gfa) && (rc = write_unitigs(o, ctx))) return rc;
+  if (o.unitigs_map && (rc = write_unitigs_map(o, ctx))) return rc;
   if (o.query) {
     const double q0 = now_s();
     if (o.query_out) {
@@ -1619,11 +1662,14 @@ int main(int argc, char **argv) {
       range_set = true;
     }
     else if (!strcmp(argv[i], "--unitigs-links")) o.unitigs_links = true;
-    else if (!strcmp(argv[i], "--unitigs-out") || !strcmp(argv[i], "--unitigs-min-count") || !strcmp(argv[i], "--unitigs-gfa")) {
+    else if (!strcmp(argv[i], "--unitigs-out") || !strcmp(argv[i], "--unitigs-min-count") || !strcmp(argv[i], "--unitigs-gfa") ||
+             !strcmp(argv[i], "--unitigs-map") || !strcmp(argv[i], "--unitigs-map-out")) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
       const char *opt = argv[i], *v = argv[++i];
       if (!strcmp(opt, "--unitigs-out")) { o.unitigs_out = v; continue; }
       if (!strcmp(opt, "--unitigs-gfa")) { o.unitigs_gfa = v; continue; }
+      if (!strcmp(opt, "--unitigs-map")) { o.unitigs_map = v; continue; }
+      if (!strcmp(opt, "--unitigs-map-out")) { o.unitigs_map_out = v; continue; }
       if (!parse_count(v, &o.unitigs_min_count)) { fprintf(stderr, "cfrk: %s needs a count (an integer from 0 to 4294967295), not '%s'\n", opt, v); return 1; }
       unitigs_opt_set = true;
     }
@@ -1638,8 +1684,16 @@ int main(int argc, char **argv) {
     fprintf(stderr, "cfrk: --unitigs-gfa needs --global on one device: not with --gpus above 1, --batch or --sparse\n");
     return 1;
   }
+  if ((o.unitigs_map != nullptr) != (o.unitigs_map_out != nullptr)) {
+    fprintf(stderr, "cfrk: --unitigs-map QFILE and --unitigs-map-out MFILE go together\n");
+    return 1;
+  }
+  if (o.unitigs_map && (!o.global || o.gpus > 1 || batch_n >= 0 || o.sparse)) {
+    fprintf(stderr, "cfrk: --unitigs-map needs --global on one device: not with --gpus above 1, --batch or --sparse\n");
+    return 1;
+  }
   if (o.unitigs_links && !o.unitigs_out) { fprintf(stderr, "cfrk: --unitigs-links needs --unitigs-out UFILE\n"); return 1; }
-  if (unitigs_opt_set && !o.unitigs_out && !o.unitigs_gfa) { fprintf(stderr, "cfrk: --unitigs-min-count needs --unitigs-out UFILE\n"); return 1; }
+  if (unitigs_opt_set && !o.unitigs_out && !o.unitigs_gfa && !o.unitigs_map) { fprintf(stderr, "cfrk: --unitigs-min-count needs --unitigs-out UFILE\n"); return 1; }
   if (o.sparse && (o.global || o.binary || o.histo || o.histo_only || range_set || o.query || o.query_out || o.query_only ||
                    o.query_db || o.query_stats || stats_below_set || o.filter_out || filter_opt_set || o.correct_out || correct_opt_set)) {
     fprintf(stderr, "cfrk: --sparse is a per-read mode: not with --global, --binary, --histo, --query or --min-count / --max-count\n");
@@ -1730,7 +1784,8 @@ int main(int argc, char **argv) {
   }
   if (o.query && read_reads(o.query, g_qformat, 0, 0, &g_qreads)) return 1;
   if ((o.filter_names || o.correct_names) && read_whole_file(o.query, g_qtext)) return 1;
-  struct QFree { ~QFree() { for (cfrk_batch *b : {&g_qreads, &g_qreads2}) if (b->data) cfrk_host_free_batch(b); } } qfree;
+  struct QFree { ~QFree() { for (cfrk_batch *b : {&g_qreads, &g_qreads2, &g_mreads}) if (b->data) cfrk_host_free_batch(b); } } qfree;
+  if (o.unitigs_map && read_reads(o.unitigs_map, file_format(o, o.unitigs_map), 0, 0, &g_mreads)) return 1;
   if (o.query2) {
     if (file_format(o, o.query2) != g_qformat) { fprintf(stderr, "cfrk: %s and %s are not of one format\n", o.query, o.query2); return 1; }
     if (read_reads(o.query2, g_qformat, 0, 0, &g_qreads2)) return 1;

@@ -843,6 +843,47 @@ size_t cfrk_host_format_gfa(const int8_t *data, const int64_t *start, const int3
   return buf ? (size_t)(p - buf) : s;
 }
 
+size_t cfrk_host_format_gaf(const int32_t *read_length, int64_t n_reads, const int64_t *hit_ptr, const void *hits,
+                            const int32_t *unitig_length, int k, char *buf, size_t cap) {
+  (void)cap;
+  size_t s = 0;
+  char *p = buf;
+  const uint64_t k1 = k > 0 ? (uint64_t)k - 1 : 0;
+  for (int64_t i = 0; i < n_reads; ++i) {
+    const uint64_t rl = read_length[i] > 0 ? (uint64_t)read_length[i] : 0;
+    for (int64_t h = hit_ptr[i]; h < hit_ptr[i + 1]; ++h) {
+      uint32_t w[4];                                     // unitig, unitig_at, read_off, n_windows
+      memcpy(w, (const char *)hits + 16 * h, 16);
+      const uint64_t j = w[0], off = w[1] >> 1, a = w[2], m = (uint64_t)w[3] + k1;
+      const bool minus = (w[1] & 1u) != 0;
+      const uint64_t ln = unitig_length[j] > 0 ? (uint64_t)unitig_length[j] : 0;
+      // on the reverse-complemented unitig the hit begins where it ends on the unitig as written
+      const uint64_t ps = minus ? (ln >= off + m ? ln - off - m : 0) : off;
+      if (!buf) {
+        s += len_u64((uint64_t)i) + 1 + len_u64(rl) + 1 + len_u64(a) + 1 + len_u64(a + m) + 3 + 1 + len_u64(j) + 1 + len_u64(ln) + 1 +
+             len_u64(ps) + 1 + len_u64(ps + m) + 1 + 2 * (len_u64(m) + 1) + 4 + 5 + len_u64(m) + 2;
+        continue;
+      }
+      p = put_u64(p, (uint64_t)i); *p++ = '\t';
+      p = put_u64(p, rl); *p++ = '\t';
+      p = put_u64(p, a); *p++ = '\t';
+      p = put_u64(p, a + m); *p++ = '\t';
+      *p++ = '+'; *p++ = '\t';
+      *p++ = minus ? '<' : '>';
+      p = put_u64(p, j); *p++ = '\t';
+      p = put_u64(p, ln); *p++ = '\t';
+      p = put_u64(p, ps); *p++ = '\t';
+      p = put_u64(p, ps + m); *p++ = '\t';
+      p = put_u64(p, m); *p++ = '\t';
+      p = put_u64(p, m); *p++ = '\t';
+      memcpy(p, "255\t", 4); p += 4;
+      memcpy(p, "cg:Z:", 5); p = put_u64(p + 5, m);
+      *p++ = '='; *p++ = '\n';
+    }
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
 static void put_le(char *p, uint64_t x, int bytes) { for (int i = 0; i < bytes; ++i) p[i] = (char)(x >> (8 * i)); }
 static uint64_t get_le(const char *p, int bytes) {
   uint64_t x = 0;

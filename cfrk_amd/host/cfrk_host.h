@@ -151,6 +151,17 @@ size_t cfrk_host_format_unitigs_links(const int8_t *data, const int64_t *start, 
 size_t cfrk_host_format_gfa(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
                             const int64_t *link_ptr, const void *links, int k, char *buf, size_t cap);
 
+/* Read hits as GAF (`cfrk --unitigs-map QFILE --unitigs-map-out MFILE`): hit_ptr = n_reads + 1 offsets, hits = rows of
+ * cfrk_read_hit (cfrk_abi.h: 16 bytes -- unitig, unitig_at = off << 1 | minus, read_off, n_windows as uint32),
+ * unitig_length = the unitig list's lengths (every hit's unitig is an index into it).  One line per hit, in CSR order,
+ * with m = n_windows + k - 1:
+ *   "<read i, 0-based>\t<read_length[i]>\t<read_off>\t<read_off+m>\t+\t<'>' or '<'><j>\t<LN_j>\t<ps>\t<pe>\t<m>\t<m>\t255\tcg:Z:<m>=\n"
+ * '>' (minus clear): ps = off.  '<' (minus set), coordinates on the reverse-complemented unitig: ps = LN_j - off - m.
+ * pe = ps + m.  The segment names are the S names of cfrk_host_format_gfa.  Returns bytes needed / written (buf may be
+ * NULL to size). */
+size_t cfrk_host_format_gaf(const int32_t *read_length, int64_t n_reads, const int64_t *hit_ptr, const void *hits,
+                            const int32_t *unitig_length, int k, char *buf, size_t cap);
+
 /* Binary global form, little endian, everything in one file:
  *   header, 32 bytes:  char magic[8] = "CFRKGLB1"; uint32 k; uint32 flags (bit 0: canonical counting,
  *                      bit 1: two-word keys, i.e. k > 32); uint64 n (records); uint64 sum of counts

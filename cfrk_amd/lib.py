@@ -76,6 +76,11 @@ CFRK_LINK_FROM_MINUS = 0x1           # cfrk_unitig_link.flags: the link leaves (
 CFRK_LINK_TO_MINUS = 0x2             # it enters (to,-)
 # one row per link (cfrk_unitig_link)
 UNITIG_LINK_DTYPE = np.dtype([("to", "<u4"), ("flags", "<u4")])
+CFRK_POS_NONE = 0xFFFFFFFF           # both words of the position of a k-mer that lies on no unitig
+# where a k-mer lies (cfrk_unitig_pos): at = p << 1 | minus
+UNITIG_POS_DTYPE = np.dtype([("unitig", "<u4"), ("at", "<u4")])
+# one row per hit of a read (cfrk_read_hit): unitig_at = off << 1 | minus
+READ_HIT_DTYPE = np.dtype([("unitig", "<u4"), ("unitig_at", "<u4"), ("read_off", "<u4"), ("n_windows", "<u4")])
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libcfrk_hip.so")
@@ -146,6 +151,12 @@ def load_library():
         "cfrk_global_unitigs_device": ([vp, C.c_uint32, vp, u64, vp, vp, vp, u64, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_global_unitig_links": ([vp, C.c_uint32, vp, vp, vp, i64, i64, vp, vp, u64, C.POINTER(i64)], C.c_int),
         "cfrk_global_unitig_links_device": ([vp, C.c_uint32, vp, vp, vp, i64, i64, vp, vp, u64, C.POINTER(i64)], C.c_int),
+        "cfrk_global_unitig_index": ([vp, C.c_uint32, vp, vp, vp, i64, i64], C.c_int),
+        "cfrk_global_unitig_index_device": ([vp, C.c_uint32, vp, vp, vp, i64, i64], C.c_int),
+        "cfrk_global_locate": ([vp, vp, vp, i64, vp], C.c_int),
+        "cfrk_global_locate_device": ([vp, vp, vp, i64, vp], C.c_int),
+        "cfrk_global_read_hits": ([vp, vp, vp, vp, i64, i64, vp, vp, u64, C.POINTER(i64)], C.c_int),
+        "cfrk_global_read_hits_device": ([vp, vp, vp, vp, i64, i64, vp, vp, u64, C.POINTER(i64)], C.c_int),
         "cfrk_global_query_reads": ([vp, vp, vp, vp, i64, i64, vp], C.c_int),
         "cfrk_global_query_reads_device": ([vp, vp, i64, vp], C.c_int),
         "cfrk_global_read_stats": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
@@ -962,6 +973,73 @@ class GlobalCounter:
             self.ctx.check(rc, "cfrk_global_unitig_links_device")
         except CfrkError as e:
             e.n_links = n.value
+            raise
+        return n.value
+
+    def unitig_index(self, data, start, length, min_count=1):
+        """build the position map from the unitigs of this job at this min_count, as unitigs() returned them: afterwards
+        locate() and read_hits() answer until the result changes.  Raises CfrkError (CFRK_ERR_LAYOUT, the message naming
+        the first offending unitig) when the list is not exactly the unitigs of this job at this min_count."""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        self.ctx.check(self._L.cfrk_global_unitig_index(self.ctx._h, int(min_count), _ptr(data), _ptr(start), _ptr(length),
+                                                        len(data), len(length)), "cfrk_global_unitig_index")
+
+    def unitig_index_device(self, min_count, d_data, d_start, d_length, nN, nS):
+        """device form of unitig_index(): synchronises once, for the consistency check"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self.ctx.check(self._L.cfrk_global_unitig_index_device(self.ctx._h, int(min_count), vp(d_data), vp(d_start), vp(d_length),
+                                                               nN, nS), "cfrk_global_unitig_index_device")
+
+    def locate(self, keys_lo, keys_hi=None):
+        """where every key, taken as an oriented k-mer exactly as given, lies on the unitigs -> UNITIG_POS_DTYPE[n]:
+        unitig j and at = p << 1 | minus (minus: the key is the reverse complement of the unitig's k-mer p); both words
+        CFRK_POS_NONE for a key that is not solid or has bits at or above 2k.  Needs unitig_index()."""
+        lo = np.ascontiguousarray(keys_lo, np.uint64)
+        hi = None if keys_hi is None else np.ascontiguousarray(keys_hi, np.uint64)
+        if hi is not None and len(hi) != len(lo):
+            raise ValueError("keys_lo and keys_hi differ in length")
+        out = np.empty(len(lo), UNITIG_POS_DTYPE)
+        self.ctx.check(self._L.cfrk_global_locate(self.ctx._h, _ptr(lo), _ptr(hi), len(lo), _ptr(out)), "cfrk_global_locate")
+        return out
+
+    def locate_device(self, d_lo, d_hi, n, d_out):
+        """device form of locate(): returns with the kernel enqueued on the context stream"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self.ctx.check(self._L.cfrk_global_locate_device(self.ctx._h, vp(d_lo), vp(d_hi), n, vp(d_out)), "cfrk_global_locate_device")
+
+    def read_hits(self, data, start, length):
+        """the hits of every read on the unitigs -> (hit_ptr int64[nS + 1], hits READ_HIT_DTYPE[n_hits]): CSR over reads; a
+        hit is a maximal stretch of windows that step along one unitig on one strand: unitig, unitig_at = off << 1 |
+        minus, read_off, n_windows.  Needs unitig_index().  A sizes-only call, then the call into an array of exactly
+        that size."""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        nS, n = len(length), C.c_int64()
+        hit_ptr = np.zeros(nS + 1, np.int64)
+        args = (self.ctx._h, _ptr(data), _ptr(start), _ptr(length), len(data), nS, _ptr(hit_ptr))
+        rc = self._L.cfrk_global_read_hits(*args, None, 0, C.byref(n))
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.ctx.check(rc, "cfrk_global_read_hits")
+        hits = np.zeros(n.value, READ_HIT_DTYPE)
+        if rc == CFRK_ERR_SMALL_BUF:
+            self.ctx.check(self._L.cfrk_global_read_hits(*args, _ptr(hits), hits.size, C.byref(n)), "cfrk_global_read_hits")
+        return hit_ptr, hits
+
+    def read_hits_device(self, d_data, d_start, d_length, nN, nS, d_hit_ptr, d_hits, cap_hits):
+        """device form -> n_hits; d_hits may be 0 with cap_hits 0 (sizes only).  Raises CfrkError (code
+        CFRK_ERR_SMALL_BUF, with .n_hits set, d_hit_ptr complete, nothing written to d_hits) when cap_hits is too small.
+        Synchronises once, returns with the fill pass enqueued on the context stream."""
+        n = C.c_int64()
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_global_read_hits_device(self.ctx._h, vp(d_data), vp(d_start), vp(d_length), nN, nS, vp(d_hit_ptr),
+                                                  vp(d_hits), cap_hits, C.byref(n))
+        try:
+            self.ctx.check(rc, "cfrk_global_read_hits_device")
+        except CfrkError as e:
+            e.n_hits = n.value
             raise
         return n.value
 

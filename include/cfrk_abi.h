@@ -521,6 +521,77 @@ int cfrk_global_unitig_links(cfrk_ctx *ctx, uint32_t min_count, const int8_t *da
                              const int32_t *length, int64_t nN, int64_t nS, int64_t *link_ptr /* nS + 1 */,
                              cfrk_unitig_link *links, uint64_t cap_links, int64_t *n_links_out);
 
+/* Unitig positions and read hits: where a k-mer, and therefore a read, lies on the graph.  The job, k, the strand rule,
+ * min_count, the solid keys, O, rc and node() are those above; the input of cfrk_global_unitig_index is the unitig list
+ * of this job at this min_count as cfrk_global_unitigs wrote it.  Unitig j has the sequence s_j and n_j = length[j] - k
+ * + 1 k-mers, kmer(j,p) = s_j[p : p+k] for 0 <= p < n_j.
+ *   POSITION of an oriented k-mer x, taken exactly as given: NONE when x is not in O (the key is absent, counted below
+ *   min_count, or has bits at or above 2k).  Otherwise there is exactly one (j,p) with node(kmer(j,p)) = node(x), every
+ *   solid key lying in one unitig once, and the position is (j, p, minus): minus = 0 iff x == kmer(j,p), 1 iff x ==
+ *   rc(kmer(j,p)) != x.  minus is always 0 in a job that is not canonical.  A palindromic k-mer is a single-node unitig
+ *   (links exclude palindromes): p = 0, minus = 0, no special case anywhere.  As cfrk_unitig_pos: at = p << 1 | minus;
+ *   NONE is both words 0xFFFFFFFF (CFRK_POS_NONE).  p < 2^31 because a unitig has at most 2^31 - 1 bases.
+ *   HITS of a read.  The windows w = 0 .. W-1 are those of cfrk_global_read_stats; pos(w) is the position of the
+ *   window's k-mer as the read spells it, NONE when a code is invalid.  Windows w and w+1 are COLINEAR iff both are
+ *   located, on the same unitig with the same minus, and p(w+1) = p(w) + 1 (minus = 0) or p(w) - 1 (minus = 1); there is
+ *   no wrap-around.  A HIT is a maximal stretch a..b of windows in which every two neighbours are colinear; its row is
+ *   cfrk_read_hit with unitig_at = off << 1 | minus, off = min(p(a), p(b)), read_off = a, n_windows = b - a + 1.  So
+ *   read bases [a, a + n + k - 1) equal s_j[off : off + n + k - 1], or its reverse complement when minus is set.  The
+ *   n_windows of a read's hits sum to its windows whose k-mer is in O; hits ascend by read_off and do not overlap in
+ *   windows; a read that crosses the cut of a circular unitig gives two hits; a read of fewer than k bases gives none.
+ * cfrk_global_unitig_index builds the position map: one cfrk_unitig_pos per slot of the lookup index, kept by the
+ *   context.  It is valid until the job's result changes (any add, merge or normalise call, a new job) or it is built
+ *   again; it dies with the lookup index.  The job is only read: same digest before and after.  nS = 0 is fine for a
+ *   job without solid keys.
+ *   Consistency check (necessary and sufficient): CFRK_ERR_LAYOUT, cfrk_last_error naming the first offending unitig,
+ *   when a unitig is shorter than k, lies outside [0, nN) or before the end of its predecessor; has a code outside 0..3;
+ *   has a k-mer that is not solid at min_count; or has a k-mer whose node another k-mer of the input claims as well
+ *   (named is the later of the two claimants).  When none of these holds but a solid key lies in no unitig of the input,
+ *   CFRK_ERR_LAYOUT names no unitig.  After CFRK_OK every x in O has a position.  After an error there is no map.
+ *   CFRK_ERR_ARG: negative sizes, NULL arrays with nS > 0, nS >= 2^32, an index of more than 2^31 slots.
+ *   CFRK_ERR_STATE: no job, or a CFRK_RUNS_ONLY job.  For any input whatever nothing outside the buffers is accessed and
+ *   no loop is unbounded.
+ *   Device form (cfrk_amd/csrc/unitig_locate.hip): one workgroup per tile of 8192 window starts of the unitig bytes, 32
+ *   consecutive starts per lane, so the work is balanced by bases and no lane's work grows with a unitig's length; every
+ *   window finds its slot and claims it with a compare-and-swap; one pass over the slots finds a solid key left out.
+ *   It synchronises ONCE, for the error word.  Temporary device memory: 8 bytes per slot of the lookup index.
+ * cfrk_global_locate: one lane per key, as cfrk_global_neighbors; keys_hi may be NULL for k <= 32.  CFRK_ERR_STATE when
+ *   there is no valid map.  The device form returns with the kernel enqueued.
+ * cfrk_global_read_hits: CSR over reads.  hit_ptr[0] = 0, hit_ptr[i + 1] - hit_ptr[i] = hits of read i in ascending
+ *   read_off, *n_hits_out = hit_ptr[nS].  Capacity (the select's protocol): when n_hits > cap_hits the call returns
+ *   CFRK_ERR_SMALL_BUF with hit_ptr and *n_hits_out complete and nothing written to hits; NULL hits with cap_hits 0 is
+ *   that "sizes only" call; cap_hits = the number of windows is always enough.  1 <= k <= 64, reads of any length.
+ *   CFRK_ERR_STATE without a valid map; CFRK_ERR_ARG: negative sizes, NULL n_hits_out or hit_ptr, NULL data / start /
+ *   length with nS > 0, NULL hits with cap_hits > 0.
+ *   Device form: no alignment requirement on d_data; start and length are not checked: a read outside [0, nN) gets an
+ *   empty row.  A count pass (three launches over the read size classes), the scan of the counts in hit_ptr, ONE
+ *   synchronisation for n_hits, then a fill pass that repeats the lookups and a pass over the rows; it returns with
+ *   those enqueued.  Host form: stages through the pool, checks the layout as cfrk_global_add does; synchronous. */
+typedef struct cfrk_unitig_pos {   /* 8 bytes, no padding */
+  uint32_t unitig;   /* j */
+  uint32_t at;       /* p << 1 | minus */
+} cfrk_unitig_pos;
+#define CFRK_POS_NONE 0xFFFFFFFF   /* both words of the position of a k-mer that is not in O */
+typedef struct cfrk_read_hit {     /* 16 bytes, no padding */
+  uint32_t unitig;      /* j */
+  uint32_t unitig_at;   /* off << 1 | minus: the hit covers s_j[off : off + n_windows + k - 1] */
+  uint32_t read_off;    /* its first window = its first base in the read */
+  uint32_t n_windows;
+} cfrk_read_hit;
+int cfrk_global_unitig_index_device(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d_data, const int64_t *d_start,
+                                    const int32_t *d_length, int64_t nN, int64_t nS);
+int cfrk_global_unitig_index(cfrk_ctx *ctx, uint32_t min_count, const int8_t *data, const int64_t *start,
+                             const int32_t *length, int64_t nN, int64_t nS);
+int cfrk_global_locate_device(cfrk_ctx *ctx, const uint64_t *d_keys_lo, const uint64_t *d_keys_hi /* NULL for k <= 32 */,
+                              int64_t n, cfrk_unitig_pos *d_out);
+int cfrk_global_locate(cfrk_ctx *ctx, const uint64_t *keys_lo, const uint64_t *keys_hi, int64_t n, cfrk_unitig_pos *out);
+int cfrk_global_read_hits_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                 int64_t nN, int64_t nS, int64_t *d_hit_ptr /* nS + 1 */, cfrk_read_hit *d_hits,
+                                 uint64_t cap_hits, int64_t *n_hits_out);
+int cfrk_global_read_hits(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                          int64_t nS, int64_t *hit_ptr /* nS + 1 */, cfrk_read_hit *hits, uint64_t cap_hits,
+                          int64_t *n_hits_out);
+
 /* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
 
 /* How many DISTINCT k-mers will a job hold?  One streaming pass over the reads answers it to about 1 % before anything
