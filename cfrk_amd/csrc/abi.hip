@@ -1060,6 +1060,132 @@ int cfrk_global_read_hits(cfrk_ctx *ctx, const int8_t *data, const int64_t *star
   return cfrk_memcpy_d2h(ctx, hits, d_hits, (size_t)n * sizeof *hits);
 }
 
+/* ------------------------------------------------------------------ graph mask and tips */
+
+int cfrk_global_mask_keys_device(cfrk_ctx *ctx, const uint64_t *d_keys_lo, const uint64_t *d_keys_hi, int64_t n) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = query_check(ctx, n);
+  if (rc) return rc;
+  if (n > 0 && (!d_keys_lo || (ctx->g_two && !d_keys_hi))) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_mask_keys_launch(ctx, d_keys_lo, d_keys_hi, n);
+}
+
+int cfrk_global_mask_keys(cfrk_ctx *ctx, const uint64_t *keys_lo, const uint64_t *keys_hi, int64_t n) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = query_check(ctx, n);
+  if (rc) return rc;
+  if (n > 0 && (!keys_lo || (ctx->g_two && !keys_hi))) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (n == 0) return cfrk_mask_keys_launch(ctx, nullptr, nullptr, 0);
+  // staged through the query calls' slot: the keys in
+  void *d_in;
+  const size_t bytes = (size_t)n * 8;
+  if ((rc = cfrk_pool_get(ctx, BUF_QUERY_IN, keys_hi ? 2 * bytes : bytes, &d_in))) return rc;
+  uint64_t *d_lo = (uint64_t *)d_in, *d_hi = keys_hi ? d_lo + n : nullptr;
+  HIP_TRY(ctx, hipMemcpyAsync(d_lo, keys_lo, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (keys_hi) HIP_TRY(ctx, hipMemcpyAsync(d_hi, keys_hi, bytes, hipMemcpyHostToDevice, ctx->stream));
+  rc = cfrk_mask_keys_launch(ctx, d_lo, d_hi, n);
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
+  return rc;
+}
+
+static int mask_unitigs_check(cfrk_ctx *ctx, const void *data, const void *start, const void *length, int64_t nN, int64_t nS,
+                              const void *drop) {
+  int rc = query_check(ctx, 0);
+  if (rc) return rc;
+  if (nN < 0 || nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (nS > 0 && (!data || !start || !length || !drop)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  return CFRK_OK;
+}
+
+int cfrk_global_mask_unitigs_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                    int64_t nN, int64_t nS, const uint8_t *d_drop) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = mask_unitigs_check(ctx, d_data, d_start, d_length, nN, nS, d_drop);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_mask_unitigs_launch(ctx, d_data, d_start, d_length, nN, nS, d_drop);
+}
+
+int cfrk_global_mask_unitigs(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                             int64_t nS, const uint8_t *drop) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = mask_unitigs_check(ctx, data, start, length, nN, nS, drop);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (nS == 0) return cfrk_mask_unitigs_launch(ctx, nullptr, nullptr, nullptr, 0, 0, nullptr);
+  // staged through the query calls' slot: the unitigs in with the drop bytes behind them
+  StagePart x[1] = {{drop, (size_t)nS, nullptr}};
+  StagedReads d;
+  if ((rc = stage_reads(ctx, BUF_QUERY_IN, data, start, length, nN, nS, STAGE_TABLE, x, 1, &d))) return rc;
+  rc = cfrk_mask_unitigs_launch(ctx, d.data, d.start, d.length, nN, nS, (const uint8_t *)x[0].dev);
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the copies read the caller's buffers)
+  return rc;
+}
+
+int cfrk_global_mask_clear(cfrk_ctx *ctx) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = query_check(ctx, 0);
+  if (rc) return rc;
+  return cfrk_mask_clear_now(ctx);
+}
+
+int cfrk_global_mask_count(cfrk_ctx *ctx, uint64_t *n_masked) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = query_check(ctx, 0);
+  if (rc) return rc;
+  if (!n_masked) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL n_masked");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_mask_count_now(ctx, n_masked);
+}
+
+static int unitig_tips_check(cfrk_ctx *ctx, const void *rec, int64_t nS, const void *link_ptr, const void *links, int64_t n_links,
+                             uint32_t ratio_q8, const void *tip, int64_t *n_tips_out) {
+  if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "unitig tips before begin: the job supplies the strand rule");
+  if (nS < 0 || n_links < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (!n_tips_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL n_tips_out");
+  if (nS > 0 && (!rec || !link_ptr || !tip)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (n_links > 0 && !links) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL links with n_links above 0");
+  if ((uint64_t)nS >= (1ull << 32)) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld unitigs: a link names its target in 32 bits", (long long)nS);
+  if (ratio_q8 > CFRK_TIP_RATIO_Q8_MAX) return cfrk_fail(ctx, CFRK_ERR_ARG, "ratio_q8 %u: at most %d", ratio_q8, CFRK_TIP_RATIO_Q8_MAX);
+  *n_tips_out = 0;
+  return CFRK_OK;
+}
+
+int cfrk_global_unitig_tips_device(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
+                                   const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t ratio_q8,
+                                   uint8_t *d_tip, int64_t *n_tips_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = unitig_tips_check(ctx, d_rec, nS, d_link_ptr, d_links, n_links, ratio_q8, d_tip, n_tips_out);
+  if (rc || nS == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_unitig_tips_launch(ctx, d_rec, nS, d_link_ptr, d_links, n_links, max_kmers, ratio_q8, d_tip, n_tips_out);
+}
+
+int cfrk_global_unitig_tips(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS, const int64_t *link_ptr,
+                            const cfrk_unitig_link *links, int64_t n_links, uint32_t max_kmers, uint32_t ratio_q8, uint8_t *tip,
+                            int64_t *n_tips_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = unitig_tips_check(ctx, rec, nS, link_ptr, links, n_links, ratio_q8, tip, n_tips_out);
+  if (rc || nS == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // [records | link_ptr | links] in a slot of their own, the tip bytes in another
+  Carve c;
+  const size_t rec_bytes = (size_t)nS * sizeof *rec, ptr_bytes = ((size_t)nS + 1) * 8, link_bytes = (size_t)n_links * sizeof *links;
+  const size_t o_rec = c.part(rec_bytes), o_ptr = c.part(ptr_bytes), o_links = c.part(link_bytes);
+  void *d_in, *d_out;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_TIPS_IN, c.end, &d_in))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_TIPS_OUT, (size_t)nS, &d_out))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_rec), rec, rec_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_ptr), link_ptr, ptr_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (n_links) HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_links), links, link_bytes, hipMemcpyHostToDevice, ctx->stream));
+  rc = cfrk_unitig_tips_launch(ctx, carve_at<cfrk_unitig>(d_in, o_rec), nS, carve_at<int64_t>(d_in, o_ptr),
+                               carve_at<cfrk_unitig_link>(d_in, o_links), n_links, max_kmers, ratio_q8, (uint8_t *)d_out, n_tips_out);
+  if (rc) return stage_drain(ctx, rc);
+  return cfrk_memcpy_d2h(ctx, tip, d_out, (size_t)nS);
+}
+
 /* ------------------------------------------------------------------ digital normalisation */
 
 static int normalize_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, int64_t batch_reads, const void *data, const void *start,

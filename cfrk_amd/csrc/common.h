@@ -55,6 +55,11 @@ enum {  // pool slots
   BUF_UNITIG_POS,                             // position map (unitig_locate.hip): error words, one cfrk_unitig_pos per slot of the lookup index;
                                               // valid while ctx->upos_epoch is the index's epoch
   BUF_READ_HITS,                              // read hits (unitig_locate.hip): the scratch of the hit_ptr scan
+  BUF_UNITIG_MASK,                            // graph mask (unitig_mask.hip): one byte per slot of the lookup index; valid while
+                                              // ctx->umask_epoch is the index's epoch
+  BUF_UNITIG_MASK_AUX,                        // the mask count's word
+  BUF_UNITIG_TIPS,                            // tip rule (unitig_tips.hip): error / size words, in-degrees, in-row offsets and rows, the scan's scratch
+  BUF_UNITIG_TIPS_IN, BUF_UNITIG_TIPS_OUT,    // staging of cfrk_global_unitig_tips alone (records, link_ptr, links in; tip bytes out)
   BUF_NSLOTS
 };
 
@@ -112,6 +117,7 @@ struct cfrk_ctx {
   int q_log2cap;         // hash index: log2 of its slots (0: the dense array of k <= 12)
   uint64_t q_epoch;      // builds of the index so far: what is kept by slot beside the index names the build it belongs to
   uint64_t upos_epoch;   // the build the position map of BUF_UNITIG_POS belongs to (0: there is no map)
+  uint64_t umask_epoch;  // the build the graph mask of BUF_UNITIG_MASK belongs to (0: no key is masked)
 };
 
 int cfrk_fail(cfrk_ctx *ctx, int code, const char *fmt, ...);
@@ -211,6 +217,19 @@ int cfrk_read_hits_count(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_s
                          int64_t nS, int64_t *d_hit_ptr, int64_t *n_hits);
 int cfrk_read_hits_fill(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
                         int64_t nS, int64_t *d_hit_ptr, cfrk_read_hit *d_hits, int64_t n_hits);
+// unitig_mask.hip: the graph mask of the index as built (the index is built, the mask created and cleared on demand; the
+// position map is dropped): n >= 0 keys / the k-mers of the dropped reads of a struct-read list added, left enqueued;
+// the mask forgotten; the masked stored keys counted (synchronises).  Arguments are checked by the callers (abi.hip).
+int cfrk_mask_keys_launch(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t *d_hi, int64_t n);
+int cfrk_mask_unitigs_launch(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length, int64_t nN,
+                             int64_t nS, const uint8_t *d_drop);
+int cfrk_mask_clear_now(cfrk_ctx *ctx);
+int cfrk_mask_count_now(cfrk_ctx *ctx, uint64_t *n_masked);
+// unitig_tips.hip: the tip rule over nS >= 1 records and their link rows into d_tip[nS]; synchronises once, for the
+// error word (CFRK_ERR_LAYOUT) and *n_tips
+int cfrk_unitig_tips_launch(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
+                            const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t ratio_q8,
+                            uint8_t *d_tip, int64_t *n_tips);
 // sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
 // enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
 int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,

@@ -40,7 +40,7 @@ struct ULWork {
   const int8_t *data; const int64_t *start; const int32_t *length;
   int64_t nN;
   uint64_t nS;
-  uint32_t min_count;
+  USolid sol;                         // min_count and the graph mask
   unsigned long long *ctr;            // ULC_*
   unsigned long long *tag;            // [slots]
   int64_t *off;                       // [o nS + 1]: an oriented end's links, scanned into its first row
@@ -67,8 +67,8 @@ __device__ __forceinline__ int ul_end_kmer(const ULWork &w, uint64_t j, int end,
 }
 
 // ---- 1 tag ------------------------------------------------------------------------------------------------------
-template <int MODE, bool CANON>
-__global__ __launch_bounds__(256) void ul_tag_kernel(ULWork w) {
+template <int MODE, bool CANON, bool MASKED>
+__device__ __forceinline__ void ul_tag_body(const ULWork &w) {
   const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = tid; i < 2 * w.nS; i += nthreads) {
@@ -81,16 +81,17 @@ __global__ __launch_bounds__(256) void ul_tag_kernel(ULWork w) {
     if (single && end) continue;                                  // (the other lane sets all four bits)
     int o; bool pal;
     const uint64_t slot = u_node<MODE, CANON>(w.q, x, o, pal);
-    if (slot == Q_NO_SLOT || q_slot_count<MODE>(w.q, slot) < w.min_count) { ul_fail(w, j, ULE_ABSENT); continue; }
+    if (!u_solid<MODE, MASKED>(w.q, w.sol, slot)) { ul_fail(w, j, ULE_ABSENT); continue; }
     uint32_t bits = end ? ULB_LAST | (o ? ULB_LAST_RC : 0) : ULB_FIRST | (o ? ULB_FIRST_RC : 0);
     if (single) bits = ULB_FIRST | ULB_LAST | (o ? ULB_FIRST_RC | ULB_LAST_RC : 0);
     if (atomicCAS(&w.tag[slot], UL_EMPTY, (unsigned long long)((j << 4) | bits)) != UL_EMPTY) ul_fail(w, j, ULE_CLAIMED);
   }
 }
+U_SOLID_KERNELS(ul_tag, (ULWork w), (w))
 
 // ---- 2 count, 4 fill --------------------------------------------------------------------------------------------
 // the links out of oriented end i = o j + orientation: counted into off[i], or written from off[i] on
-template <int MODE, bool CANON, bool FILL>
+template <int MODE, bool CANON, bool MASKED, bool FILL>
 __device__ __forceinline__ void ul_links(const ULWork &w, uint64_t i, cfrk_unitig_link *__restrict__ links) {
   const int k = w.q.k;
   const uint64_t j = CANON ? i >> 1 : i;
@@ -103,7 +104,7 @@ __device__ __forceinline__ void ul_links(const ULWork &w, uint64_t i, cfrk_uniti
     for (int b = 0; b < 4; ++b) {
       int oz; bool pal;
       const uint64_t slot = u_node<MODE, CANON>(w.q, u_succ_key(t, b, k), oz, pal);
-      if (slot == Q_NO_SLOT || q_slot_count<MODE>(w.q, slot) < w.min_count) continue;
+      if (!u_solid<MODE, MASKED>(w.q, w.sol, slot)) continue;
       const unsigned long long tag = w.tag[slot];
       const uint32_t bits = tag == UL_EMPTY ? 0u : (uint32_t)tag & 15u;
       // head(v,+) = v's first k-mer: the stored key's orientation must be the successor's; head(v,-) = rc(v's last)
@@ -121,21 +122,23 @@ __device__ __forceinline__ void ul_links(const ULWork &w, uint64_t i, cfrk_uniti
   if (!FILL) w.off[i] = n;
 }
 
-template <int MODE, bool CANON>
-__global__ __launch_bounds__(256) void ul_count_kernel(ULWork w) {
+template <int MODE, bool CANON, bool MASKED>
+__device__ __forceinline__ void ul_count_body(const ULWork &w) {
   const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
   const uint64_t items = (CANON ? 2 : 1) * w.nS;
-  for (uint64_t i = tid; i < items; i += nthreads) ul_links<MODE, CANON, false>(w, i, nullptr);
+  for (uint64_t i = tid; i < items; i += nthreads) ul_links<MODE, CANON, MASKED, false>(w, i, nullptr);
 }
+U_SOLID_KERNELS(ul_count, (ULWork w), (w))
 
-template <int MODE, bool CANON>
-__global__ __launch_bounds__(256) void ul_fill_kernel(ULWork w, cfrk_unitig_link *__restrict__ links) {
+template <int MODE, bool CANON, bool MASKED>
+__device__ __forceinline__ void ul_fill_body(const ULWork &w, cfrk_unitig_link *__restrict__ links) {
   const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
   const uint64_t items = (CANON ? 2 : 1) * w.nS;
-  for (uint64_t i = tid; i < items; i += nthreads) ul_links<MODE, CANON, true>(w, i, links);
+  for (uint64_t i = tid; i < items; i += nthreads) ul_links<MODE, CANON, MASKED, true>(w, i, links);
 }
+U_SOLID_KERNELS(ul_fill, (ULWork w, cfrk_unitig_link *__restrict__ links), (w, links))
 
 // ---- 3 the scanned offsets to the caller ------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ul_ptr_kernel(ULWork w, int o, int64_t *__restrict__ link_ptr) {
@@ -183,14 +186,14 @@ int cfrk_unitig_links_measure(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d
   uint64_t M;
   if ((rc = ul_carve(ctx, q, canon, (uint64_t)nS, true, &w, &tmp, &scan_tmp, &M))) return rc;
   w.data = d_data; w.start = d_start; w.length = d_length; w.nN = nN; w.nS = (uint64_t)nS;
-  w.min_count = min_count ? min_count : 1;
+  w.sol = u_solid_rule(ctx, min_count);
   const uint64_t items = (canon ? 2 : 1) * w.nS;
   HIP_TRY(ctx, hipMemsetAsync(w.ctr, 0xFF, 8, ctx->stream));                  // ULC_ERR: no unitig yet
   HIP_TRY(ctx, hipMemsetAsync(w.ctr + ULC_TOTAL, 0, 8, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(w.tag, 0xFF, M * 8, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(w.off + items, 0, 8, ctx->stream));
-  U_DISPATCH(ul_tag_kernel, u_grid(ctx, 2 * w.nS), w);
-  U_DISPATCH(ul_count_kernel, u_grid(ctx, items), w);
+  U_DISPATCH_SOLID(ul_tag, w.sol, u_grid(ctx, 2 * w.nS), w);
+  U_DISPATCH_SOLID(ul_count, w.sol, u_grid(ctx, items), w);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, scan_tmp, w.off, (size_t)(items + 1), ctx->stream));
   hipLaunchKernelGGL(ul_ptr_kernel, dim3(u_grid(ctx, w.nS + 1)), dim3(256), 0, ctx->stream, w, canon ? 2 : 1, d_link_ptr);
@@ -225,8 +228,8 @@ int cfrk_unitig_links_fill(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d_da
   uint64_t M;
   if ((rc = ul_carve(ctx, q, canon, (uint64_t)nS, false, &w, &tmp, &scan_tmp, &M))) return rc;
   w.data = d_data; w.start = d_start; w.length = d_length; w.nN = nN; w.nS = (uint64_t)nS;
-  w.min_count = min_count ? min_count : 1;
-  U_DISPATCH(ul_fill_kernel, u_grid(ctx, (canon ? 2 : 1) * w.nS), w, d_links);
+  w.sol = u_solid_rule(ctx, min_count);
+  U_DISPATCH_SOLID(ul_fill, w.sol, u_grid(ctx, (canon ? 2 : 1) * w.nS), w, d_links);
   HIP_TRY(ctx, hipGetLastError());
   return CFRK_OK;
 }

@@ -44,7 +44,7 @@ struct UPWork {
   const int8_t *data; const int64_t *start; const int32_t *length;
   int64_t nN;
   uint64_t nS;
-  uint32_t min_count;
+  USolid sol;                         // min_count and the graph mask
   unsigned long long *ctr;            // UPC_*
   unsigned long long *pos;            // [slots]
 };
@@ -80,8 +80,8 @@ __device__ __forceinline__ int64_t up_search(const UPWork &w, int64_t x) {
   return (int64_t)lo - 1;
 }
 
-template <int MODE, bool CANON>
-__global__ __launch_bounds__(256) void up_claim_kernel(UPWork w) {
+template <int MODE, bool CANON, bool MASKED>
+__device__ __forceinline__ void up_claim_body(const UPWork &w) {
   const int k = w.q.k;
   const int64_t nwin = w.nN - k + 1;                    // window starts whose k bytes lie below nN
   const int64_t ntiles = (nwin + UP_TILE - 1) / UP_TILE;
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void up_claim_kernel(UPWork w) {
       if (!R.valid()) { up_fail(w, (uint64_t)j, UPE_CODE); continue; }
       const auto key = R.key();
       const uint64_t slot = q_slot_of<MODE>(w.q, (uint64_t)key, (uint64_t)(key >> (MODE == 2 ? 64 : 0)));
-      if (slot == Q_NO_SLOT || q_slot_count<MODE>(w.q, slot) < w.min_count) { up_fail(w, (uint64_t)j, UPE_ABSENT); continue; }
+      if (!u_solid<MODE, MASKED>(w.q, w.sol, slot)) { up_fail(w, (uint64_t)j, UPE_ABSENT); continue; }
       const unsigned long long at = ((unsigned long long)(ws - s) << 1) | (R.minus() ? 1ull : 0ull);
       const unsigned long long old = atomicCAS(&w.pos[slot], UP_NONE, (at << 32) | (unsigned long long)j);
       // (named is the later of the two claimants: the one that comes second in the list)
@@ -110,18 +110,19 @@ __global__ __launch_bounds__(256) void up_claim_kernel(UPWork w) {
     }
   }
 }
+U_SOLID_KERNELS(up_claim, (UPWork w), (w))
 
 // ---- 3 cover ----------------------------------------------------------------------------------------------------
-template <int MODE, bool CANON>
-__global__ __launch_bounds__(256) void up_cover_kernel(UPWork w) {
+template <int MODE, bool CANON, bool MASKED>
+__device__ __forceinline__ void up_cover_body(const UPWork &w) {
   const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
   const uint64_t M = q_nslots<MODE>(w.q);
   for (uint64_t s = tid; s < M; s += nthreads) {
-    const uint32_t c = q_slot_count<MODE>(w.q, s);
-    if (c != 0 && c >= w.min_count && w.pos[s] == UP_NONE) w.ctr[UPC_MISSING] = 1;
+    if (u_solid<MODE, MASKED>(w.q, w.sol, s) && w.pos[s] == UP_NONE) w.ctr[UPC_MISSING] = 1;      // (a masked key is not one)
   }
 }
+U_SOLID_KERNELS(up_cover, (UPWork w), (w))
 
 // ---- locate -----------------------------------------------------------------------------------------------------
 // the position of oriented k-mer z (in range) exactly as given
@@ -344,7 +345,7 @@ int cfrk_unitig_index_build(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d_d
   w.ctr = carve_at<unsigned long long>(base, 0);
   w.pos = carve_at<unsigned long long>(base, 256);
   w.data = d_data; w.start = d_start; w.length = d_length; w.nN = nN; w.nS = (uint64_t)nS;
-  w.min_count = min_count ? min_count : 1;
+  w.sol = u_solid_rule(ctx, min_count);
   HIP_TRY(ctx, hipMemsetAsync(w.ctr, 0xFF, 8, ctx->stream));                  // UPC_ERR: no unitig yet
   HIP_TRY(ctx, hipMemsetAsync(w.ctr + UPC_MISSING, 0, 8, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(w.pos, 0xFF, M * 8, ctx->stream));
@@ -353,10 +354,10 @@ int cfrk_unitig_index_build(cfrk_ctx *ctx, uint32_t min_count, const int8_t *d_d
     if (nN >= w.q.k) {
       const int64_t ntiles = (nN - w.q.k + 1 + UP_TILE - 1) / UP_TILE;
       const int grid = (int)std::min<int64_t>(ntiles, (int64_t)ctx->num_cus * 16);
-      U_DISPATCH(up_claim_kernel, grid, w);
+      U_DISPATCH_SOLID(up_claim, w.sol, grid, w);
     }
   }
-  U_DISPATCH(up_cover_kernel, u_grid(ctx, M), w);
+  U_DISPATCH_SOLID(up_cover, w.sol, u_grid(ctx, M), w);
   HIP_TRY(ctx, hipGetLastError());
   unsigned long long h[UPC_WORDS];
   HIP_TRY(ctx, hipMemcpyAsync(h, w.ctr, sizeof h, hipMemcpyDeviceToHost, ctx->stream));

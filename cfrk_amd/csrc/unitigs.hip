@@ -57,7 +57,7 @@ static_assert(sizeof(USeg) == 64, "USeg is 64 bytes");
 struct UWork {
   QIndex q;
   uint64_t M, seg_cap, u_cap, split_mask;
-  uint32_t min_count;
+  USolid sol;                         // min_count and the graph mask
   uint8_t *adj, *lk, *vis;
   uint32_t *hid;                      // [2 M]: the segment an oriented node heads
   USeg *seg;
@@ -94,8 +94,8 @@ __device__ __forceinline__ u128 u_okey(const QIndex &q, uint64_t v) {
 }
 
 // the neighbour mask of oriented k-mer x, which need not be present itself
-template <int MODE, bool CANON>
-__device__ __forceinline__ uint32_t u_neighbors(const QIndex &q, u128 x, uint32_t min_count) {
+template <int MODE, bool CANON, bool MASKED>
+__device__ __forceinline__ uint32_t u_neighbors(const QIndex &q, u128 x, const USolid &sol) {
   const int k = q.k;
   uint32_t m = 0;
 #pragma unroll
@@ -103,7 +103,7 @@ __device__ __forceinline__ uint32_t u_neighbors(const QIndex &q, u128 x, uint32_
     const u128 z = j < 4 ? u_succ_key(x, j, k) : u_pred_key(x, j - 4, k);
     int o; bool pal;
     const uint64_t s = u_node<MODE, CANON>(q, z, o, pal);
-    if (s != Q_NO_SLOT && q_slot_count<MODE>(q, s) >= min_count) m |= 1u << j;
+    if (u_solid<MODE, MASKED>(q, sol, s)) m |= 1u << j;
   }
   return m;
 }
@@ -120,10 +120,10 @@ __device__ __forceinline__ uint64_t u_next(const UWork &w, uint64_t v) {
 }
 
 // ---- the public neighbour masks ---------------------------------------------------------------------------------
-template <int MODE, bool CANON>
-__global__ __launch_bounds__(256) void u_neighbors_kernel(QIndex q, const uint64_t *__restrict__ keys_lo,
-                                                          const uint64_t *__restrict__ keys_hi, int64_t n,
-                                                          uint32_t min_count, uint8_t *__restrict__ out) {
+template <int MODE, bool CANON, bool MASKED>
+__device__ __forceinline__ void u_neighbors_body(const QIndex &q, const uint64_t *__restrict__ keys_lo,
+                                                 const uint64_t *__restrict__ keys_hi, int64_t n, const USolid &sol,
+                                                 uint8_t *__restrict__ out) {
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
   const int k = q.k;
@@ -132,22 +132,25 @@ __global__ __launch_bounds__(256) void u_neighbors_kernel(QIndex q, const uint64
     bool in_range;
     if (MODE < 2) in_range = hi == 0 && (k == 32 || (lo >> (2 * k)) == 0);
     else in_range = k == 64 || (hi >> (2 * k - 64)) == 0;
-    out[i] = in_range ? (uint8_t)u_neighbors<MODE, CANON>(q, u_make(lo, hi), min_count) : (uint8_t)0;
+    out[i] = in_range ? (uint8_t)u_neighbors<MODE, CANON, MASKED>(q, u_make(lo, hi), sol) : (uint8_t)0;
   }
 }
+U_SOLID_KERNELS(u_neighbors, (QIndex q, const uint64_t *__restrict__ keys_lo, const uint64_t *__restrict__ keys_hi, int64_t n, USolid sol,
+                              uint8_t *__restrict__ out), (q, keys_lo, keys_hi, n, sol, out))
 
 // ---- 1 adjacency ------------------------------------------------------------------------------------------------
-template <int MODE, bool CANON>
-__global__ __launch_bounds__(256) void u_adj_kernel(UWork w) {
+template <int MODE, bool CANON, bool MASKED>
+__device__ __forceinline__ void u_adj_body(const UWork &w) {
   const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t slot = tid; slot < w.M; slot += nthreads) {
-    const bool solid = q_slot_count<MODE>(w.q, slot) >= w.min_count;    // (an empty slot counts 0, min_count >= 1)
+    const bool solid = u_solid<MODE, MASKED>(w.q, w.sol, slot);
     w.lk[slot] = solid ? L_SOLID : 0;
     w.vis[slot] = 0;
-    w.adj[slot] = solid ? (uint8_t)u_neighbors<MODE, CANON>(w.q, u_slot_key<MODE>(w.q, slot), w.min_count) : (uint8_t)0;
+    w.adj[slot] = solid ? (uint8_t)u_neighbors<MODE, CANON, MASKED>(w.q, u_slot_key<MODE>(w.q, slot), w.sol) : (uint8_t)0;
   }
 }
+U_SOLID_KERNELS(u_adj, (UWork w), (w))
 
 // ---- 2 links ----------------------------------------------------------------------------------------------------
 // A link a -> b (oriented) is cut iff b is a stored key and a splitter, or rc(a) is a stored key and a splitter: the
@@ -458,8 +461,8 @@ int cfrk_neighbors_launch(cfrk_ctx *ctx, const uint64_t *d_lo, const uint64_t *d
   if (rc || n == 0) return rc;
   const bool canon = (ctx->g_flags & CFRK_CANONICAL) != 0;
   const int mode = q.k <= 12 ? 0 : q.k <= 32 ? 1 : 2;
-  if (min_count == 0) min_count = 1;
-  U_DISPATCH(u_neighbors_kernel, u_grid(ctx, (uint64_t)n), q, d_lo, d_hi, n, min_count, d_masks);
+  const USolid sol = u_solid_rule(ctx, min_count);
+  U_DISPATCH_SOLID(u_neighbors, sol, u_grid(ctx, (uint64_t)n), q, d_lo, d_hi, n, sol, d_masks);
   HIP_TRY(ctx, hipGetLastError());
   return CFRK_OK;
 }
@@ -477,11 +480,11 @@ int cfrk_unitigs_measure(cfrk_ctx *ctx, uint32_t min_count, int64_t *nN, int64_t
   void *base;
   if ((rc = cfrk_pool_get(ctx, BUF_UNITIG, bytes, &base))) return rc;
   u_carve(base, q, canon, &w);
-  w.min_count = min_count ? min_count : 1;
+  w.sol = u_solid_rule(ctx, min_count);
   w.split_mask = (1ull << u_split_log2(ctx)) - 1;
   HIP_TRY(ctx, hipMemsetAsync(w.ctr, 0, UC_WORDS * 8, ctx->stream));
   const int gm = u_grid(ctx, w.M), gs = u_grid(ctx, w.seg_cap);
-  U_DISPATCH(u_adj_kernel, gm, w);
+  U_DISPATCH_SOLID(u_adj, w.sol, gm, w);
   U_DISPATCH(u_link_kernel, gm, w);
   if (canon) hipLaunchKernelGGL(u_heads_kernel<true>, dim3(gm), dim3(256), 0, ctx->stream, w);
   else hipLaunchKernelGGL(u_heads_kernel<false>, dim3(gm), dim3(256), 0, ctx->stream, w);

@@ -56,6 +56,14 @@
 //                    graph, as GAF: one line per hit, a maximal stretch of a read's k-mers that step along one unitig on
 //                    one strand, the segment names those of --unitigs-gfa (cfrk_global_unitig_index_device,
 //                    cfrk_global_read_hits, cfrk_host_format_gaf)
+//   --unitigs-clip-tips [--tip-max-kmers M] [--tip-ratio R] [--tip-rounds N] [--tip-report RFILE]  (with --unitigs-out,
+//                    --unitigs-gfa or --unitigs-map) clip tips off the graph before anything is written: up to N rounds
+//                    (default 4) of unitigs, links, the tip rule and a mask of the tips' k-mers, ended by the first
+//                    round without a tip.  A tip has at most M k-mers (default k), one dead end, and at its other end a
+//                    sibling of at least R times its mean coverage (default 2.0, 0 .. 256; 0: topology alone).  UFILE,
+//                    the L tags, the GFA and the GAF then describe the clipped graph; the counts' own output is what
+//                    it is without the option.  RFILE: one line per round, "round<TAB>unitigs<TAB>tips<TAB>masked
+//                    k-mers so far" (cfrk_global_unitig_tips, cfrk_global_mask_unitigs)
 //   --min-count N / --max-count N  (global) write only the entries with N_min <= count <= N_max (text and --binary; the
 //                    binary header's n and sum describe the records written)
 //   --query QFILE --query-out OFILE  (global) how often does each k-mer of the reads of QFILE (FASTA, clean parse) occur
@@ -206,6 +214,11 @@ struct Options {
   const char *unitigs_gfa = nullptr;  // --unitigs-gfa GFILE
   const char *unitigs_map = nullptr;      // --unitigs-map QFILE
   const char *unitigs_map_out = nullptr;  // --unitigs-map-out MFILE
+  bool clip_tips = false;             // --unitigs-clip-tips
+  uint32_t tip_max_kmers = 0;         // --tip-max-kmers M (0: k)
+  uint32_t tip_ratio_q8 = 512;        // --tip-ratio R, in 256ths
+  uint32_t tip_rounds = 4;            // --tip-rounds N
+  const char *tip_report = nullptr;   // --tip-report RFILE
   bool histo_only = false;
   uint32_t min_count = 1, max_count = CFRK_COUNT_MAX;
   const char *query = nullptr, *query_out = nullptr, *query_db = nullptr;   // --query QFILE --query-out OFILE --query-db DB
@@ -478,6 +491,41 @@ int write_text_file(const char *path, const std::string &buf) {
   const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
   if (fclose(f) != 0 || !ok) { fprintf(stderr, "cfrk: cannot write %s\n", path); return 1; }
   return 0;
+}
+
+// --unitigs-clip-tips: rounds of unitigs, links, the tip rule and the mask of the tips' k-mers through the host forms,
+// before anything is written.  The mask stays set, so what write_unitigs and write_unitigs_map compute afterwards is the
+// clipped graph.
+int clip_unitig_tips(const Options &o, cfrk_ctx *ctx) {
+  std::string report;
+  for (uint32_t round = 1; round <= o.tip_rounds; ++round) {
+    int64_t nN = 0, nS = 0, n_links = 0, n_tips = 0;
+    int rc = cfrk_global_unitigs(ctx, o.unitigs_min_count, nullptr, 0, nullptr, nullptr, nullptr, 0, &nN, &nS);
+    if (rc && rc != CFRK_ERR_SMALL_BUF) return die(ctx, rc, "cfrk_global_unitigs");
+    std::vector<int8_t> data((size_t)nN);
+    std::vector<int64_t> start((size_t)nS), link_ptr((size_t)nS + 1);
+    std::vector<int32_t> length((size_t)nS);
+    std::vector<cfrk_unitig> rec((size_t)nS);
+    std::vector<uint8_t> tip((size_t)nS);
+    if (rc && (rc = cfrk_global_unitigs(ctx, o.unitigs_min_count, data.data(), data.size(), start.data(), length.data(), rec.data(),
+                                        rec.size(), &nN, &nS))) return die(ctx, rc, "cfrk_global_unitigs");
+    rc = cfrk_global_unitig_links(ctx, o.unitigs_min_count, data.data(), start.data(), length.data(), nN, nS, link_ptr.data(), nullptr, 0, &n_links);
+    if (rc && rc != CFRK_ERR_SMALL_BUF) return die(ctx, rc, "cfrk_global_unitig_links");
+    std::vector<cfrk_unitig_link> links((size_t)n_links);
+    if (rc && (rc = cfrk_global_unitig_links(ctx, o.unitigs_min_count, data.data(), start.data(), length.data(), nN, nS, link_ptr.data(),
+                                             links.data(), links.size(), &n_links))) return die(ctx, rc, "cfrk_global_unitig_links");
+    if ((rc = cfrk_global_unitig_tips(ctx, rec.data(), nS, link_ptr.data(), links.data(), n_links, o.tip_max_kmers ? o.tip_max_kmers : (uint32_t)o.k,
+                                      o.tip_ratio_q8, tip.data(), &n_tips))) return die(ctx, rc, "cfrk_global_unitig_tips");
+    if (n_tips && (rc = cfrk_global_mask_unitigs(ctx, data.data(), start.data(), length.data(), nN, nS, tip.data())))
+      return die(ctx, rc, "cfrk_global_mask_unitigs");
+    uint64_t masked = 0;
+    if ((rc = cfrk_global_mask_count(ctx, &masked))) return die(ctx, rc, "cfrk_global_mask_count");
+    char line[96];
+    snprintf(line, sizeof line, "%u\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (unsigned long long)masked);
+    report += line;
+    if (!n_tips) break;
+  }
+  return o.tip_report ? write_text_file(o.tip_report, report) : 0;
 }
 
 int write_unitigs(const Options &o, cfrk_ctx *ctx) {
@@ -1048,6 +1096,7 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
     if ((rc = result_spectrum(ctx, sp)) || (rc = write_histo(o, sp))) return rc;
   }
   g_timing.histo = now_s() - t2;
+  if (o.clip_tips && (rc = clip_unitig_tips(o, ctx))) return rc;
   if ((o.unitigs_out || o.unitigs_gfa) && (rc = write_unitigs(o, ctx))) return rc;
   if (o.unitigs_map && (rc = write_unitigs_map(o, ctx))) return rc;
   if (o.query) {
@@ -1496,6 +1545,7 @@ int main(int argc, char **argv) {
   Options o;
   int batch_n = -1;
   bool unitigs_opt_set = false;
+  bool tip_opt_set = false;
   bool range_set = false, stats_below_set = false, filter_opt_set = false, correct_opt_set = false, correct_min_count_set = false, normalize_opt_set = false, normalize_cutoff_set = false;
   bool pair_opt_set = false, pair_mode_set = false;
   for (int i = 1; i < argc; ++i) {
@@ -1662,6 +1712,24 @@ int main(int argc, char **argv) {
       range_set = true;
     }
     else if (!strcmp(argv[i], "--unitigs-links")) o.unitigs_links = true;
+    else if (!strcmp(argv[i], "--unitigs-clip-tips")) o.clip_tips = true;
+    else if (!strcmp(argv[i], "--tip-max-kmers") || !strcmp(argv[i], "--tip-ratio") || !strcmp(argv[i], "--tip-rounds") ||
+             !strcmp(argv[i], "--tip-report")) {
+      if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
+      const char *opt = argv[i], *v = argv[++i];
+      tip_opt_set = true;
+      if (!strcmp(opt, "--tip-report")) { o.tip_report = v; continue; }
+      if (!strcmp(opt, "--tip-ratio")) {
+        char *end = nullptr;
+        const double r = strtod(v, &end);
+        if (end == v || *end || !(r >= 0.0 && r <= 256.0)) { fprintf(stderr, "cfrk: --tip-ratio needs a number from 0 to 256, not '%s'\n", v); return 1; }
+        o.tip_ratio_q8 = (uint32_t)(r * 256.0 + 0.5);
+        continue;
+      }
+      uint32_t x;
+      if (!parse_count(v, &x) || x < 1) { fprintf(stderr, "cfrk: %s needs a count (an integer from 1 to 4294967295), not '%s'\n", opt, v); return 1; }
+      if (!strcmp(opt, "--tip-max-kmers")) o.tip_max_kmers = x; else o.tip_rounds = x;
+    }
     else if (!strcmp(argv[i], "--unitigs-out") || !strcmp(argv[i], "--unitigs-min-count") || !strcmp(argv[i], "--unitigs-gfa") ||
              !strcmp(argv[i], "--unitigs-map") || !strcmp(argv[i], "--unitigs-map-out")) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
@@ -1690,6 +1758,14 @@ int main(int argc, char **argv) {
   }
   if (o.unitigs_map && (!o.global || o.gpus > 1 || batch_n >= 0 || o.sparse)) {
     fprintf(stderr, "cfrk: --unitigs-map needs --global on one device: not with --gpus above 1, --batch or --sparse\n");
+    return 1;
+  }
+  if (o.clip_tips && !o.unitigs_out && !o.unitigs_gfa && !o.unitigs_map) {
+    fprintf(stderr, "cfrk: --unitigs-clip-tips needs --unitigs-out UFILE, --unitigs-gfa GFILE or --unitigs-map QFILE\n");
+    return 1;
+  }
+  if (tip_opt_set && !o.clip_tips) {
+    fprintf(stderr, "cfrk: --tip-max-kmers, --tip-ratio, --tip-rounds and --tip-report need --unitigs-clip-tips\n");
     return 1;
   }
   if (o.unitigs_links && !o.unitigs_out) { fprintf(stderr, "cfrk: --unitigs-links needs --unitigs-out UFILE\n"); return 1; }

@@ -81,6 +81,7 @@ CFRK_POS_NONE = 0xFFFFFFFF           # both words of the position of a k-mer tha
 UNITIG_POS_DTYPE = np.dtype([("unitig", "<u4"), ("at", "<u4")])
 # one row per hit of a read (cfrk_read_hit): unitig_at = off << 1 | minus
 READ_HIT_DTYPE = np.dtype([("unitig", "<u4"), ("unitig_at", "<u4"), ("read_off", "<u4"), ("n_windows", "<u4")])
+CFRK_TIP_RATIO_Q8_MAX = 65536        # tip rule: the largest ratio_q8 (256 = the sibling's mean coverage at least the tip's)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libcfrk_hip.so")
@@ -157,6 +158,14 @@ def load_library():
         "cfrk_global_locate_device": ([vp, vp, vp, i64, vp], C.c_int),
         "cfrk_global_read_hits": ([vp, vp, vp, vp, i64, i64, vp, vp, u64, C.POINTER(i64)], C.c_int),
         "cfrk_global_read_hits_device": ([vp, vp, vp, vp, i64, i64, vp, vp, u64, C.POINTER(i64)], C.c_int),
+        "cfrk_global_mask_keys": ([vp, vp, vp, i64], C.c_int),
+        "cfrk_global_mask_keys_device": ([vp, vp, vp, i64], C.c_int),
+        "cfrk_global_mask_unitigs": ([vp, vp, vp, vp, i64, i64, vp], C.c_int),
+        "cfrk_global_mask_unitigs_device": ([vp, vp, vp, vp, i64, i64, vp], C.c_int),
+        "cfrk_global_mask_clear": ([vp], C.c_int),
+        "cfrk_global_mask_count": ([vp, C.POINTER(u64)], C.c_int),
+        "cfrk_global_unitig_tips": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, vp, C.POINTER(i64)], C.c_int),
+        "cfrk_global_unitig_tips_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, vp, C.POINTER(i64)], C.c_int),
         "cfrk_global_query_reads": ([vp, vp, vp, vp, i64, i64, vp], C.c_int),
         "cfrk_global_query_reads_device": ([vp, vp, i64, vp], C.c_int),
         "cfrk_global_read_stats": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
@@ -1042,6 +1051,101 @@ class GlobalCounter:
             e.n_hits = n.value
             raise
         return n.value
+
+    def mask_keys(self, keys_lo, keys_hi=None):
+        """add keys to the graph mask: a masked key is no longer solid for neighbors(), unitigs(), unitig_links(),
+        unitig_index(), locate() and read_hits(); its count is untouched.  Canonicalised in a CFRK_CANONICAL job; a key
+        that is not stored or has bits at or above 2k is ignored.  Drops the position map."""
+        lo = np.ascontiguousarray(keys_lo, np.uint64)
+        hi = None if keys_hi is None else np.ascontiguousarray(keys_hi, np.uint64)
+        if hi is not None and len(hi) != len(lo):
+            raise ValueError("keys_lo and keys_hi differ in length")
+        self.ctx.check(self._L.cfrk_global_mask_keys(self.ctx._h, _ptr(lo), _ptr(hi), len(lo)), "cfrk_global_mask_keys")
+
+    def mask_keys_device(self, d_lo, d_hi, n):
+        """device form of mask_keys(): returns with the kernel enqueued on the context stream"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self.ctx.check(self._L.cfrk_global_mask_keys_device(self.ctx._h, vp(d_lo), vp(d_hi), n), "cfrk_global_mask_keys_device")
+
+    def mask_unitigs(self, data, start, length, drop):
+        """add every k-mer of every unitig j with drop[j] != 0 to the graph mask (any struct-read list; k-mers that are not
+        stored and windows with an invalid code are skipped).  Drops the position map."""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        drop = np.ascontiguousarray(drop, np.uint8)
+        if len(drop) != len(length):
+            raise ValueError("drop and length differ in length")
+        self.ctx.check(self._L.cfrk_global_mask_unitigs(self.ctx._h, _ptr(data), _ptr(start), _ptr(length), len(data), len(length),
+                                                        _ptr(drop)), "cfrk_global_mask_unitigs")
+
+    def mask_unitigs_device(self, d_data, d_start, d_length, nN, nS, d_drop):
+        """device form of mask_unitigs(): one launch over tiles of the bytes, left enqueued on the context stream"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self.ctx.check(self._L.cfrk_global_mask_unitigs_device(self.ctx._h, vp(d_data), vp(d_start), vp(d_length), nN, nS, vp(d_drop)),
+                       "cfrk_global_mask_unitigs_device")
+
+    def mask_clear(self):
+        """unmask every key; fine without a mask"""
+        self.ctx.check(self._L.cfrk_global_mask_clear(self.ctx._h), "cfrk_global_mask_clear")
+
+    def mask_count(self):
+        """the stored keys that are masked; synchronises"""
+        n = C.c_uint64()
+        self.ctx.check(self._L.cfrk_global_mask_count(self.ctx._h, C.byref(n)), "cfrk_global_mask_count")
+        return n.value
+
+    def unitig_tips(self, rec, link_ptr, links, max_kmers, ratio_q8=512):
+        """the tip rule over the unitigs' records and their links, as unitigs() and unitig_links() returned them ->
+        np.uint8[nS], 1 where unitig j is a tip: not circular, at most max_kmers k-mers, exactly one dead end, and at an
+        attachment a sibling with 256 * mean(sibling) >= ratio_q8 * mean(j) that is no candidate itself or ranks above j.
+        Raises CfrkError (CFRK_ERR_LAYOUT, the message naming the unitig) when the rows are not link rows."""
+        rec = np.ascontiguousarray(rec, UNITIG_DTYPE)
+        link_ptr = np.ascontiguousarray(link_ptr, np.int64)
+        links = np.ascontiguousarray(links, UNITIG_LINK_DTYPE)
+        if len(link_ptr) != len(rec) + 1:
+            raise ValueError("link_ptr has not one entry more than rec")
+        tip, n = np.zeros(len(rec), np.uint8), C.c_int64()
+        self.ctx.check(self._L.cfrk_global_unitig_tips(self.ctx._h, _ptr(rec), len(rec), _ptr(link_ptr), _ptr(links), len(links),
+                                                       int(max_kmers), int(ratio_q8), _ptr(tip), C.byref(n)), "cfrk_global_unitig_tips")
+        assert n.value == int(tip.sum())
+        return tip
+
+    def unitig_tips_device(self, d_rec, nS, d_link_ptr, d_links, n_links, max_kmers, ratio_q8, d_tip):
+        """device form -> n_tips; synchronises once, for n_tips and the check of the rows"""
+        n = C.c_int64()
+        vp = lambda p: C.c_void_p(p) if p else None
+        self.ctx.check(self._L.cfrk_global_unitig_tips_device(self.ctx._h, vp(d_rec), nS, vp(d_link_ptr), vp(d_links), n_links,
+                                                              int(max_kmers), int(ratio_q8), vp(d_tip), C.byref(n)),
+                       "cfrk_global_unitig_tips_device")
+        return n.value
+
+    def clip_tips(self, min_count=1, max_kmers=None, ratio=2.0, rounds=4):
+        """clip tips off the graph: up to `rounds` rounds of unitigs -> links -> tips -> mask_unitigs(tips), stopping at the
+        first round without a tip -> ((data, start, length, rec) of the clipped graph, [(unitigs, tips, masked keys so
+        far) per round]).  max_kmers=None means k; ratio is the mean coverage a sibling must have relative to the tip
+        (Minia's convention; 0: topology alone).  The mask stays set: links, the position map and further rounds see
+        the clipped graph; mask_clear() brings the full one back."""
+        if rounds < 1:
+            raise ValueError("rounds: at least 1")
+        ratio_q8 = int(round(float(ratio) * 256))
+        if not 0 <= ratio_q8 <= CFRK_TIP_RATIO_Q8_MAX:
+            raise ValueError("ratio: 0 .. 256")
+        max_kmers = self.k if max_kmers is None else int(max_kmers)
+        report = []
+        u = self.unitigs(min_count)
+        for _ in range(rounds):
+            data, start, length, rec = u
+            link_ptr, links = self.unitig_links(data, start, length, min_count)
+            tip = self.unitig_tips(rec, link_ptr, links, max_kmers, ratio_q8)
+            n_tips = int(tip.sum())
+            if n_tips:
+                self.mask_unitigs(data, start, length, tip)
+            report.append((len(rec), n_tips, self.mask_count()))
+            if not n_tips:
+                break
+            u = self.unitigs(min_count)
+        return u, report
 
     def query_reads(self, data, start=None, length=None):
         """count of the k-mer starting at every base -> np.uint32[nN]: CFRK_QUERY_NONE where the window holds an

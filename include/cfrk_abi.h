@@ -410,7 +410,8 @@ int cfrk_global_normalize_pairs(cfrk_ctx *ctx, const int8_t *data, const int64_t
 /* ---- unitigs: the compacted de Bruijn graph of the counted k-mers ---------------------------------------------- */
 
 /* Definitions.  The job has k (1 <= k <= 64) and a strand rule; min_count >= 1 (0 reads as 1).
- *   Solid keys: the stored keys with count >= min_count.
+ *   Solid keys: the stored keys with count >= min_count that are not masked ("Graph mask", below; without a mask call
+ *   no key is masked).
  *   Oriented k-mers O: the solid keys; in a CFRK_CANONICAL job every solid key x and rc(x).
  *   node(a) = a, or min(a, rc(a)) in a canonical job.  a is palindromic iff the job is canonical and a == rc(a).
  *   succ(a) = { a[1:] + b in O },  pred(a) = { b + a[:-1] in O }.
@@ -591,6 +592,85 @@ int cfrk_global_read_hits_device(cfrk_ctx *ctx, const int8_t *d_data, const int6
 int cfrk_global_read_hits(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
                           int64_t nS, int64_t *hit_ptr /* nS + 1 */, cfrk_read_hit *hits, uint64_t cap_hits,
                           int64_t *n_hits_out);
+
+/* Graph mask: stored keys that are no longer part of the graph.  A stored key may be MASKED; a masked key is not solid.
+ *   Scope: the mask is seen by the six calls that read solidity -- cfrk_global_neighbors, cfrk_global_unitigs,
+ *   cfrk_global_unitig_links, cfrk_global_unitig_index and, through the position map, cfrk_global_locate and
+ *   cfrk_global_read_hits -- and by nothing else.  Counts are untouched: digest, export, histogram, query, read
+ *   statistics, spans, correction, normalisation and merge never see the mask; a masked key still answers
+ *   cfrk_global_query with its count; the job's digest is the same before and after every call of this section.
+ *   Storage and lifetime: one byte per slot of the lookup index, in the context's pool.  The mask belongs to one build of
+ *   the index, as the position map does: when the result changes (any add, merge or normalise call, a new job) the index
+ *   is rebuilt, the mask is gone and every key is unmasked again.  A mask call on a job without a valid index builds
+ *   the index, as a query does.
+ *   Position map: every change of the mask drops it.  cfrk_global_locate and cfrk_global_read_hits return
+ *   CFRK_ERR_STATE until cfrk_global_unitig_index is called again with the unitigs of the masked graph.
+ *   Without a mask, every byte the six calls write is what it is without this section.
+ * cfrk_global_mask_keys adds keys to the mask.  A key is canonicalised in a CFRK_CANONICAL job; a key that is not stored,
+ *   or has bits at or above 2k, is ignored; duplicates are fine.  keys_hi may be NULL for k <= 32.  One lane per key,
+ *   plain byte stores.
+ * cfrk_global_mask_unitigs adds every k-mer of every unitig j with drop[j] != 0 to the mask.  The list is any
+ *   struct-read list with ascending starts (it is NOT checked to be this job's unitigs); windows with an invalid code,
+ *   and k-mers that are not stored, are skipped; a read outside [0, nN) is skipped.  Balanced by bytes like the claim
+ *   pass of the position map (one workgroup per tile of 8192 window starts of the bytes), so no lane's work grows with a
+ *   unitig's length.  The host form checks start / length against the terminators as cfrk_global_add does
+ *   (CFRK_ERR_LAYOUT).
+ * cfrk_global_mask_clear unmasks everything; fine without a mask.  cfrk_global_mask_count: the stored keys that are
+ *   masked; one pass over the slots; synchronises.
+ * CFRK_ERR_STATE: no job, or a CFRK_RUNS_ONLY job.  CFRK_ERR_ARG: negative sizes, NULL arrays with n or nS above 0, NULL
+ *   n_masked.  CFRK_ERR_TABLE_FULL and CFRK_ERR_NOMEM as for cfrk_global_query.  n = 0 and nS = 0 are fine.  Nothing
+ *   outside the buffers is accessed for any input whatever.  The device forms return with their kernel enqueued; the
+ *   host forms stage through the pool and are synchronous. */
+int cfrk_global_mask_keys_device(cfrk_ctx *ctx, const uint64_t *d_keys_lo, const uint64_t *d_keys_hi /* NULL for k <= 32 */,
+                                 int64_t n);
+int cfrk_global_mask_keys(cfrk_ctx *ctx, const uint64_t *keys_lo, const uint64_t *keys_hi, int64_t n);
+int cfrk_global_mask_unitigs_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                    int64_t nN, int64_t nS, const uint8_t *d_drop /* nS */);
+int cfrk_global_mask_unitigs(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length, int64_t nN,
+                             int64_t nS, const uint8_t *drop /* nS */);
+int cfrk_global_mask_clear(cfrk_ctx *ctx);
+int cfrk_global_mask_count(cfrk_ctx *ctx, uint64_t *n_masked);
+
+/* Unitig tips: short dead-end branches that hang off a better-supported path.  The rule is a pure function of the
+ * compacted graph: the unitigs' records (kc, n_kmers, CFRK_UNITIG_CIRCULAR), the link CSR as cfrk_global_unitig_links
+ * wrote it, and the job's strand rule.  It needs neither sequences nor the index; the job only supplies the strand rule.
+ *   Oriented unitigs: (j,+), and in a canonical job also (j,-).
+ *   out(a) = the links that leave oriented unitig a; in(a) = the links that enter it.  In a canonical job the rows hold
+ *   every link's mirror, so in(j,+) is read off row j: its CFRK_LINK_FROM_MINUS links, mirrored.  In a job that is not
+ *   canonical in() is built from the rows (a count pass, a scan, a fill pass; the order inside an in-row does not matter).
+ *   right(j) = |out(j,+)|, left(j) = |in(j,+)|.  n_j = n_kmers, kc_j = kc.  Means are compared exactly by
+ *   cross-multiplying in 128 bits: mean(w) > mean(j) iff kc_w n_j > kc_j n_w.
+ *   CANDIDATE: j is not CFRK_UNITIG_CIRCULAR, n_j <= max_kmers, and exactly one of left(j), right(j) is 0.  (A unitig
+ *   with both ends dead is isolated, not a tip: it stays.)
+ *   ATTACHMENTS and SIBLINGS of a candidate.  right(j) = 0: every link (u,ou) -> (j,+) of in(j,+) is an attachment, its
+ *   siblings are the targets (w,ow) of out(u,ou) with w != j.  left(j) = 0: every link (j,+) -> (v,ov) of out(j,+) is an
+ *   attachment, its siblings are the sources (w,ow) of in(v,ov) with w != j.
+ *   BEATS: sibling w beats j iff 256 kc_w n_j >= ratio_q8 kc_j n_w, and w is not a candidate, or mean(w) > mean(j), or
+ *   the means are equal and w < j.
+ *   TIP: j is a candidate and, at some attachment, some sibling beats it.  tip[j] = 1 for a tip, else 0; every byte is
+ *   written; *n_tips_out = the tips.
+ *   Every decision reads the input graph only: the result does not depend on any order.  Among candidates that compete
+ *   for one anchor end the best-ranked always survives unless a sibling that is no candidate exists: a fork at the very
+ *   end of a contig keeps one arm.  ratio_q8 = 0 is the purely topological rule, 512 asks the sibling for twice the
+ *   tip's mean coverage; ratio_q8 > CFRK_TIP_RATIO_Q8_MAX (65536) is CFRK_ERR_ARG: the bound keeps every product
+ *   inside 128 bits.  max_kmers = 0 makes nothing a tip.
+ * Untrusted input, checked in a pass before anything is decided: CFRK_ERR_LAYOUT, cfrk_last_error naming the first
+ *   offending unitig, for a link_ptr that does not ascend from 0 to n_links, a row longer than 16 links (4 when not
+ *   canonical), a target >= nS, flag bits beyond the two defined ones or any flag bit in a job that is not canonical, an
+ *   in-degree above 4 when not canonical.  After the check one lane per unitig does at most 8 x 8 comparisons.  No loop
+ *   is unbounded and nothing outside the arrays is accessed.  After an error tip[] is all 0.
+ * CFRK_ERR_STATE: no job.  CFRK_ERR_ARG: NULL n_tips_out, NULL rec / link_ptr / tip with nS > 0, NULL links with n_links
+ *   > 0, negative sizes, nS >= 2^32, ratio_q8 above its bound.  nS = 0 is fine: no tips.
+ * Device form (cfrk_amd/csrc/unitig_tips.hip): n_tips_out is host memory; the call synchronises ONCE, for n_tips and the
+ *   error word.  Temporary device memory, kept in the context's pool: one byte per unitig; not canonical: 12 more bytes
+ *   per unitig, 4 per link and the scan's scratch.  Host form: stages through the pool; synchronous. */
+#define CFRK_TIP_RATIO_Q8_MAX 65536
+int cfrk_global_unitig_tips_device(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr /* nS + 1 */,
+                                   const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t ratio_q8,
+                                   uint8_t *d_tip /* nS bytes, every one written 0 or 1 */, int64_t *n_tips_out);
+int cfrk_global_unitig_tips(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS, const int64_t *link_ptr /* nS + 1 */,
+                            const cfrk_unitig_link *links, int64_t n_links, uint32_t max_kmers, uint32_t ratio_q8,
+                            uint8_t *tip /* nS */, int64_t *n_tips_out);
 
 /* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
 

@@ -23,7 +23,13 @@ whole call into an array of exactly n_links rows (`call`), the unitigs call alte
 (`unitigs_call`), and cfrk_global_query_device on 6 x o x unitigs uniformly random keys (o = 2: the canonical job's
 orientations), the number of probes the passes make: 2 x unitigs in the tag pass, o x 4 x unitigs in the count pass.
 
-  python tools/bench_unitigs.py [--links] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
+With --tips (cases b and c are the ones of interest) the tool "bench_tips" writes, per case: a line "unmasked" with the
+unitigs, links and index calls without a mask, alternating in the same repetitions with the same calls of the library
+given by --parent-lib on the same counted reads, and the verdict whether each median lies inside the parent's own
+run-to-run spread; a line "round1" with the tips call, the mask_unitigs call, and the unitigs, links and index calls with
+the mask of round 1 set, all alternating; and a line "rounds" with nodes, unitigs, tips and masked keys per clip round.
+
+  python tools/bench_unitigs.py [--links | --tips [--parent-lib SO]] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
 """
 import argparse
 import json
@@ -33,6 +39,114 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+class _Graph:
+    """the unitigs, links and position map of a job through the device forms, into buffers of exactly the sizes"""
+
+    def __init__(self, mod, g, min_count, buf):
+        self.mod, self.g, self.mc, self.buf = mod, g, min_count, buf
+        self.resize()
+
+    def resize(self):
+        g, mod = self.g, self.mod
+        try:
+            nN, nS = g.unitigs_device(self.mc, 0, 0, 0, 0, 0, 0)
+        except mod.CfrkError as e:
+            if e.code != mod.CFRK_ERR_SMALL_BUF:
+                raise
+            nN, nS = e.nN, e.nS
+        self.nN, self.nS = nN, nS
+        self.out = [self.buf(nN), self.buf(nS * 8), self.buf(nS * 4), self.buf(nS * 16)]
+        self.unitigs()
+        self.args = (self.out[0].data_ptr(), self.out[1].data_ptr(), self.out[2].data_ptr(), nN, nS)
+        self.ptr = self.buf((nS + 1) * 8)
+        try:
+            self.n_links = g.unitig_links_device(self.mc, *self.args, self.ptr.data_ptr(), 0, 0)
+        except mod.CfrkError as e:
+            if e.code != mod.CFRK_ERR_SMALL_BUF:
+                raise
+            self.n_links = e.n_links
+        self.rows = self.buf(self.n_links * 8)
+        self.links()
+
+    def unitigs(self):
+        o = self.out
+        self.g.unitigs_device(self.mc, o[0].data_ptr(), self.nN, o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), self.nS)
+
+    def links(self):
+        self.g.unitig_links_device(self.mc, *self.args, self.ptr.data_ptr(), self.rows.data_ptr(), self.n_links)
+
+    def index(self):
+        self.g.unitig_index_device(self.mc, *self.args)
+
+    def nodes(self, torch):
+        return int(self.out[3][:self.nS * 16].view(torch.int32).view(self.nS, 4)[:, 2].to(torch.int64).sum()) if self.nS else 0
+
+
+def tips_case(a, torch, cfrk_amd, ctx, g, parent, other, min_count, common, timed, stats, buf):
+    k = a.k
+    ratio_q8 = int(round(a.tip_ratio * 256))
+    new = _Graph(cfrk_amd, g, min_count, buf)
+    ctx.sync()
+    # 1 no mask set: this library and the parent's, alternating
+    series = {"new": new}
+    if other is not None:
+        series["parent"] = _Graph(parent, other, min_count, buf)
+        assert (series["parent"].nN, series["parent"].nS, series["parent"].n_links) == (new.nN, new.nS, new.n_links)
+    t = {(who, call): [] for who in series for call in ("unitigs", "links", "index")}
+    for rep in range(a.reps + 1):
+        for call in ("unitigs", "links", "index"):
+            for who in (("parent", "new") if rep % 2 else ("new", "parent")):
+                if who in series:
+                    ms = timed(getattr(series[who], call))
+                    if rep:                                     # (the first round warms up: code objects, pool buffers)
+                        t[(who, call)].append(ms)
+    row = dict(common, line="unmasked", nodes=new.nodes(torch), unitigs=new.nS, links=new.n_links)
+    for (who, call), ts in t.items():
+        row["%s_%s" % (who, call)] = dict(stats(ts), series=ts)
+    if other is not None:
+        row["inside_parent_spread"] = {call: row["parent_" + call]["min_ms"] <= row["new_" + call]["ms"] <= row["parent_" + call]["max_ms"]
+                                       for call in ("unitigs", "links", "index")}
+        row["new_over_parent"] = {call: row["new_" + call]["ms"] / row["parent_" + call]["ms"] for call in ("unitigs", "links", "index")}
+    print(json.dumps(row), flush=True)
+    series.pop("parent", None)
+    # 2 round 1: the tips call and the mask call, then the three calls with that mask set
+    d_tip = buf(new.nS)
+    tip_args = (new.out[3].data_ptr(), new.nS, new.ptr.data_ptr(), new.rows.data_ptr(), new.n_links, k, ratio_q8, d_tip.data_ptr())
+    n_tips = g.unitig_tips_device(*tip_args)
+    g.mask_unitigs_device(*new.args, d_tip.data_ptr())
+    masked = _Graph(cfrk_amd, g, min_count, buf)
+    ctx.sync()
+    calls = (("tips", lambda: g.unitig_tips_device(*tip_args)), ("mask_unitigs", lambda: g.mask_unitigs_device(*new.args, d_tip.data_ptr())),
+             ("unitigs_masked", masked.unitigs), ("links_masked", masked.links), ("index_masked", masked.index))
+    t = {name: [] for name, _ in calls}
+    for rep in range(a.reps + 1):
+        for name, fn in calls:
+            ms = timed(fn)
+            if rep:
+                t[name].append(ms)
+    row = dict(common, line="round1", unitigs=new.nS, links=new.n_links, tips=n_tips, masked_keys=g.mask_count(),
+               unitigs_after=masked.nS, links_after=masked.n_links, tip_ratio=a.tip_ratio, tip_max_kmers=k)
+    row.update({name: stats(ts) for name, ts in t.items()})
+    print(json.dumps(row), flush=True)
+    # 3 the rounds
+    g.mask_clear()
+    rounds, cur = [], new
+    for r in range(a.tip_rounds):
+        if r:
+            cur = _Graph(cfrk_amd, g, min_count, buf)
+        d_tip = buf(cur.nS)
+        n_tips = g.unitig_tips_device(cur.out[3].data_ptr(), cur.nS, cur.ptr.data_ptr(), cur.rows.data_ptr(), cur.n_links, k, ratio_q8, d_tip.data_ptr())
+        if n_tips:
+            g.mask_unitigs_device(*cur.args, d_tip.data_ptr())
+        rounds.append({"round": r + 1, "nodes": cur.nodes(torch), "unitigs": cur.nS, "tips": n_tips, "masked_keys": g.mask_count()})
+        if not n_tips:
+            break
+    if rounds[-1]["tips"]:
+        last = _Graph(cfrk_amd, g, min_count, buf)
+        rounds.append({"round": len(rounds) + 1, "nodes": last.nodes(torch), "unitigs": last.nS, "tips": None, "masked_keys": g.mask_count()})
+    print(json.dumps(dict(common, line="rounds", tip_ratio=a.tip_ratio, tip_max_kmers=k, rounds=rounds)), flush=True)
 
 
 def main():
@@ -47,12 +161,24 @@ def main():
     ap.add_argument("--error-rate", type=float, default=0.01)
     ap.add_argument("--max-query-keys", type=int, default=400_000_000)
     ap.add_argument("--links", action="store_true")
+    ap.add_argument("--tips", action="store_true")
+    ap.add_argument("--tip-ratio", type=float, default=2.0)
+    ap.add_argument("--tip-rounds", type=int, default=4)
+    ap.add_argument("--parent-lib", help="libcfrk_hip.so of the parent commit: with --tips, the unmasked calls alternate with it")
     a = ap.parse_args()
 
     import torch
     import cfrk_amd
     stream = torch.cuda.Stream()
     ctx = cfrk_amd.Context(0, stream.cuda_stream)
+    parent = pctx = None
+    if a.tips and a.parent_lib:                                 # a second copy of the Python mirror bound to the other library
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("cfrk_parent_lib", cfrk_amd.lib.__file__)
+        parent = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(parent)
+        parent._SO = os.path.abspath(a.parent_lib)
+        pctx = parent.Context(0, stream.cuda_stream)
     R, L, k = a.reads, a.L, a.k
     nN = R * (L + 1)
     splits = [int(s) for s in a.split.split(",")]
@@ -105,6 +231,19 @@ def main():
         def full():
             g.unitigs_device(min_count, out[0].data_ptr(), oN, out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), oS)
 
+        if a.tips:
+            other = None
+            if parent is not None:                              # the same reads counted by the parent's library as well
+                other = parent.GlobalCounter(pctx, k, cfrk_amd.CFRK_CANONICAL, hint)
+                other.add_device(reads.data_ptr(), nN)
+                pctx.sync()
+                assert other.digest()[0] == distinct
+            common = {"tool": "bench_tips", "case": case, "reads": R, "L": L, "glen": a.glen, "k": k, "reps": a.reps,
+                      "error_rate": 0.0 if case == "a" else a.error_rate, "min_count": min_count, "distinct_keys": distinct}
+            tips_case(a, torch, cfrk_amd, ctx, g, parent, other, min_count, common, timed, stats, buf)
+            del g, other, out, reads
+            torch.cuda.empty_cache()
+            continue
         if a.links:
             full()
             ctx.sync()
