@@ -1060,7 +1060,7 @@ int cfrk_global_read_hits(cfrk_ctx *ctx, const int8_t *data, const int64_t *star
   return cfrk_memcpy_d2h(ctx, hits, d_hits, (size_t)n * sizeof *hits);
 }
 
-/* ------------------------------------------------------------------ graph mask and tips */
+/* ------------------------------------------------------------------ graph mask, tips and bubbles */
 
 int cfrk_global_mask_keys_device(cfrk_ctx *ctx, const uint64_t *d_keys_lo, const uint64_t *d_keys_hi, int64_t n) {
   if (!ctx) return CFRK_ERR_ARG;
@@ -1184,6 +1184,60 @@ int cfrk_global_unitig_tips(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS, c
                                carve_at<cfrk_unitig_link>(d_in, o_links), n_links, max_kmers, ratio_q8, (uint8_t *)d_out, n_tips_out);
   if (rc) return stage_drain(ctx, rc);
   return cfrk_memcpy_d2h(ctx, tip, d_out, (size_t)nS);
+}
+
+static int unitig_bubbles_check(cfrk_ctx *ctx, const void *rec, int64_t nS, const void *link_ptr, const void *links, int64_t n_links,
+                                uint32_t ratio_q8, const void *pop, int64_t *n_pop_out) {
+  if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "unitig bubbles before begin: the job supplies the strand rule");
+  if (nS < 0 || n_links < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (!n_pop_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL n_pop_out");
+  if (nS > 0 && (!rec || !link_ptr || !pop)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (n_links > 0 && !links) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL links with n_links above 0");
+  if ((uint64_t)nS >= (1ull << 31)) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld unitigs: a partner names an oriented unitig in 32 bits", (long long)nS);
+  if (ratio_q8 > CFRK_TIP_RATIO_Q8_MAX) return cfrk_fail(ctx, CFRK_ERR_ARG, "ratio_q8 %u: at most %d", ratio_q8, CFRK_TIP_RATIO_Q8_MAX);
+  *n_pop_out = 0;
+  return CFRK_OK;
+}
+
+int cfrk_global_unitig_bubbles_device(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
+                                      const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t max_diff,
+                                      uint32_t ratio_q8, uint8_t *d_pop, uint32_t *d_partner, int64_t *n_pop_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = unitig_bubbles_check(ctx, d_rec, nS, d_link_ptr, d_links, n_links, ratio_q8, d_pop, n_pop_out);
+  if (rc || nS == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_unitig_bubbles_launch(ctx, d_rec, nS, d_link_ptr, d_links, n_links, max_kmers, max_diff, ratio_q8, d_pop, d_partner, n_pop_out);
+}
+
+int cfrk_global_unitig_bubbles(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS, const int64_t *link_ptr,
+                               const cfrk_unitig_link *links, int64_t n_links, uint32_t max_kmers, uint32_t max_diff,
+                               uint32_t ratio_q8, uint8_t *pop, uint32_t *partner, int64_t *n_pop_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = unitig_bubbles_check(ctx, rec, nS, link_ptr, links, n_links, ratio_q8, pop, n_pop_out);
+  if (rc || nS == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // [records | link_ptr | links] in a slot of their own, [pop bytes | partners] in another
+  Carve c, co;
+  const size_t rec_bytes = (size_t)nS * sizeof *rec, ptr_bytes = ((size_t)nS + 1) * 8, link_bytes = (size_t)n_links * sizeof *links;
+  const size_t o_rec = c.part(rec_bytes), o_ptr = c.part(ptr_bytes), o_links = c.part(link_bytes);
+  const size_t o_pop = co.part((size_t)nS), o_partner = co.part(partner ? (size_t)nS * 4 : 0);
+  void *d_in, *d_out;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_BUBBLES_IN, c.end, &d_in))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_BUBBLES_OUT, co.end, &d_out))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_rec), rec, rec_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_ptr), link_ptr, ptr_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (n_links) HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_links), links, link_bytes, hipMemcpyHostToDevice, ctx->stream));
+  uint32_t *d_partner = partner ? carve_at<uint32_t>(d_out, o_partner) : nullptr;
+  rc = cfrk_unitig_bubbles_launch(ctx, carve_at<cfrk_unitig>(d_in, o_rec), nS, carve_at<int64_t>(d_in, o_ptr),
+                                  carve_at<cfrk_unitig_link>(d_in, o_links), n_links, max_kmers, max_diff, ratio_q8,
+                                  carve_at<uint8_t>(d_out, o_pop), d_partner, n_pop_out);
+  if (rc) {                                            // refused: pop all 0, no partner
+    memset(pop, 0, (size_t)nS);
+    if (partner) memset(partner, 0xFF, (size_t)nS * 4);
+    return stage_drain(ctx, rc);
+  }
+  if (partner) HIP_TRY(ctx, hipMemcpyAsync(partner, d_partner, (size_t)nS * 4, hipMemcpyDeviceToHost, ctx->stream));
+  return cfrk_memcpy_d2h(ctx, pop, carve_at<uint8_t>(d_out, o_pop), (size_t)nS);
 }
 
 /* ------------------------------------------------------------------ digital normalisation */

@@ -60,6 +60,8 @@ enum {  // pool slots
   BUF_UNITIG_MASK_AUX,                        // the mask count's word
   BUF_UNITIG_TIPS,                            // tip rule (unitig_tips.hip): error / size words, in-degrees, in-row offsets and rows, the scan's scratch
   BUF_UNITIG_TIPS_IN, BUF_UNITIG_TIPS_OUT,    // staging of cfrk_global_unitig_tips alone (records, link_ptr, links in; tip bytes out)
+  BUF_UNITIG_BUBBLES,                         // bubble rule (unitig_bubbles.hip): error / size words, arm bytes and records, the in-rows, the scan's scratch
+  BUF_UNITIG_BUBBLES_IN, BUF_UNITIG_BUBBLES_OUT,  // staging of cfrk_global_unitig_bubbles alone (records, link_ptr, links in; pop bytes and partners out)
   BUF_NSLOTS
 };
 
@@ -230,6 +232,11 @@ int cfrk_mask_count_now(cfrk_ctx *ctx, uint64_t *n_masked);
 int cfrk_unitig_tips_launch(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
                             const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t ratio_q8,
                             uint8_t *d_tip, int64_t *n_tips);
+// unitig_bubbles.hip: the bubble rule over 1 <= nS < 2^31 records and their link rows into d_pop[nS] and, unless NULL,
+// d_partner[nS]; synchronises once, for the error word (CFRK_ERR_LAYOUT) and *n_pop
+int cfrk_unitig_bubbles_launch(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
+                               const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t max_diff,
+                               uint32_t ratio_q8, uint8_t *d_pop, uint32_t *d_partner, int64_t *n_pop);
 // sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
 // enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
 int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,

@@ -5,98 +5,29 @@
 //
 // The arrays are untrusted.  Passes, each a launch of its own on the context stream; every pass behind the check reads
 // the error word first and does nothing when it is set, so that only checked rows are ever followed:
-//   1 check     one lane per unitig: link_ptr[j] <= link_ptr[j + 1] inside [0, n_links] (0 at j = 0, n_links at the
-//               end), a row of at most 16 links (4 when not canonical), targets below nS, no undefined flag bit (none
-//               at all when not canonical).  Not canonical: a checked row counts its targets' in-degrees.
-//   not canonical only, where in() cannot be read off a unitig's own row:
-//   2 in-degree one lane per unitig: at most 4; hipCUB exclusive sum over the in-degrees, in place
-//   3 in-rows   one lane per unitig: its links' sources into the targets' in-rows, a cursor per target (the order inside
-//               an in-row does not matter: the rule only asks "is there one")
+//   1-3 the check and, not canonical only, the in-rows: unitig_graph_dev.h, shared with the bubble rule
 //   4 candidate one lane per unitig: not circular, n_kmers <= max_kmers, exactly one of left / right is 0 -> which
 //   5 decide    one lane per unitig: a candidate's <= 8 attachments x their <= 8 siblings, BEATS in 128 bits
 //   -- the one synchronisation: the error word and n_tips --
 // In a canonical job the rows hold every link's mirror, so in(j,+) is the row's FROM_MINUS links mirrored, and the
 // sources of in(v,-) are the targets of v's links that leave (v,+).
-#include "staging.h"
-#include "unitig_dev.h"
-
-#include <hipcub/hipcub.hpp>
+#include "unitig_graph_dev.h"
 
 namespace {
 
-constexpr unsigned long long UT_NONE = ~0ull;
-enum { UTC_ERR = 0, UTC_TIPS, UTC_WORDS };
-// error word = unitig << 8 | why, kept with an atomic minimum: the first offending unitig
-enum { UTE_PTR = 1, UTE_ROW, UTE_TARGET, UTE_FLAGS, UTE_INDEG };
+enum { UTC_ERR = UGC_ERR, UTC_TIPS, UTC_WORDS };
 enum { UT_DEAD_RIGHT = 1, UT_DEAD_LEFT = 2 };         // a candidate's cand[] byte: which end has no link
 
-struct UTWork {
-  const cfrk_unitig *rec;
-  const int64_t *ptr;
-  const cfrk_unitig_link *links;
-  uint64_t nS;
-  int64_t n_links;
+struct UTWork : UGraph {
   uint32_t max_kmers, ratio_q8;
-  unsigned long long *ctr;            // UTC_*
   uint8_t *cand;                      // [nS]
-  unsigned long long *in_off;         // [nS + 1], not canonical: in-degrees, scanned into the in-rows' offsets
-  uint32_t *in_cur;                   // [nS]: the fill pass's cursors
-  uint32_t *in_src;                   // [n_links]: the in-rows
   uint8_t *tip;                       // [nS], the caller's
 };
-
-__device__ __forceinline__ void ut_fail(const UTWork &w, uint64_t j, int why) {
-  atomicMin(&w.ctr[UTC_ERR], (unsigned long long)((j << 8) | (uint64_t)why));
-}
-
-// ---- 1 check ----------------------------------------------------------------------------------------------------
-template <bool CANON>
-__global__ __launch_bounds__(256) void ut_check_kernel(UTWork w) {
-  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t j = tid; j < w.nS; j += nthreads) {
-    const int64_t a = w.ptr[j], b = w.ptr[j + 1];
-    int why = 0;
-    if ((j == 0 && a != 0) || (j + 1 == w.nS && b != w.n_links) || a < 0 || b < a || b > w.n_links) why = UTE_PTR;
-    else if (b - a > (CANON ? 16 : 4)) why = UTE_ROW;
-    else
-      for (int64_t t = a; t < b; ++t) {
-        const cfrk_unitig_link l = w.links[t];
-        if (l.to >= w.nS) { why = UTE_TARGET; break; }
-        if (l.flags & ~(CANON ? (uint32_t)(CFRK_LINK_FROM_MINUS | CFRK_LINK_TO_MINUS) : 0u)) { why = UTE_FLAGS; break; }
-      }
-    if (why) { ut_fail(w, j, why); continue; }
-    if (!CANON)
-      for (int64_t t = a; t < b; ++t) atomicAdd(&w.in_off[w.links[t].to], 1ull);
-  }
-}
-
-// ---- 2, 3 the in-rows of a job that is not canonical ------------------------------------------------------------
-__global__ __launch_bounds__(256) void ut_indeg_kernel(UTWork w) {
-  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t j = tid; j < w.nS; j += nthreads)
-    if (w.in_off[j] > 4) ut_fail(w, j, UTE_INDEG);
-}
-
-__global__ __launch_bounds__(256) void ut_in_fill_kernel(UTWork w) {
-  if (w.ctr[UTC_ERR] != UT_NONE) return;
-  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t j = tid; j < w.nS; j += nthreads) {
-    const int64_t a = w.ptr[j], b = w.ptr[j + 1];
-    for (int64_t t = a; t < b; ++t) {
-      const uint32_t v = w.links[t].to;
-      const unsigned long long at = w.in_off[v] + atomicAdd(&w.in_cur[v], 1u);
-      if (at < w.in_off[v + 1]) w.in_src[at] = (uint32_t)j;     // (always: the offsets are the scan of these very counts)
-    }
-  }
-}
 
 // ---- 4 candidates -----------------------------------------------------------------------------------------------
 template <bool CANON>
 __global__ __launch_bounds__(256) void ut_cand_kernel(UTWork w) {
-  if (w.ctr[UTC_ERR] != UT_NONE) return;
+  if (w.ctr[UGC_ERR] != UG_NONE) return;
   const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t j = tid; j < w.nS; j += nthreads) {
@@ -169,7 +100,7 @@ __device__ __forceinline__ bool ut_is_tip(const UTWork &w, uint32_t j, int dead)
 
 template <bool CANON>
 __global__ __launch_bounds__(256) void ut_decide_kernel(UTWork w) {
-  if (w.ctr[UTC_ERR] != UT_NONE) return;
+  if (w.ctr[UGC_ERR] != UG_NONE) return;
   const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
   // (whole waves turn together: the ballot below counts a wave's tips)
   for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < w.nS; base += nthreads) {
@@ -194,7 +125,7 @@ int cfrk_unitig_tips_launch(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS,
   const bool canon = (ctx->g_flags & CFRK_CANONICAL) != 0;
   const uint64_t n = (uint64_t)nS, in_n = canon ? 0 : n;
   size_t scan_tmp = 0;
-  if (!canon) HIP_TRY(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (unsigned long long *)nullptr, (size_t)(n + 1), ctx->stream));
+  if (const int rc = ug_scan_bytes(ctx, canon, n, &scan_tmp)) return rc;
   Carve c;
   const size_t o_ctr = c.part(UTC_WORDS * 8), o_cand = c.part(n), o_off = c.part(canon ? 0 : (in_n + 1) * 8), o_cur = c.part(in_n * 4),
                o_src = c.part(canon ? 0 : (size_t)n_links * 4), o_tmp = c.part(scan_tmp);
@@ -208,22 +139,14 @@ int cfrk_unitig_tips_launch(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS,
   w.in_off = carve_at<unsigned long long>(base, o_off);
   w.in_cur = carve_at<uint32_t>(base, o_cur);
   w.in_src = carve_at<uint32_t>(base, o_src);
-  HIP_TRY(ctx, hipMemsetAsync(w.ctr, 0xFF, 8, ctx->stream));                  // UTC_ERR: no unitig yet
   HIP_TRY(ctx, hipMemsetAsync(w.ctr + UTC_TIPS, 0, 8, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d_tip, 0, n, ctx->stream));                     // every byte is written, whatever is refused
   const int grid = u_grid(ctx, n);
+  if (const int rc = ug_check_launch(ctx, w, canon, grid, carve_at<void>(base, o_tmp), scan_tmp)) return rc;
   if (canon) {
-    hipLaunchKernelGGL(ut_check_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, w);
     hipLaunchKernelGGL(ut_cand_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, w);
     hipLaunchKernelGGL(ut_decide_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, w);
   } else {
-    HIP_TRY(ctx, hipMemsetAsync(w.in_off, 0, (n + 1) * 8, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(w.in_cur, 0, n * 4, ctx->stream));
-    hipLaunchKernelGGL(ut_check_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, w);
-    hipLaunchKernelGGL(ut_indeg_kernel, dim3(grid), dim3(256), 0, ctx->stream, w);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipcub::DeviceScan::ExclusiveSum(carve_at<void>(base, o_tmp), scan_tmp, w.in_off, (size_t)(n + 1), ctx->stream));
-    hipLaunchKernelGGL(ut_in_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream, w);
     hipLaunchKernelGGL(ut_cand_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, w);
     hipLaunchKernelGGL(ut_decide_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, w);
   }
@@ -231,16 +154,7 @@ int cfrk_unitig_tips_launch(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS,
   unsigned long long h[UTC_WORDS];
   HIP_TRY(ctx, hipMemcpyAsync(h, w.ctr, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (h[UTC_ERR] != UT_NONE) {
-    const unsigned long long j = h[UTC_ERR] >> 8;
-    const int why = (int)(h[UTC_ERR] & 255);
-    const char *what = why == UTE_PTR      ? "has a link_ptr that does not ascend from 0 to n_links"
-                       : why == UTE_ROW    ? "has a row of more links than an oriented end can have"
-                       : why == UTE_TARGET ? "has a link to a unitig that is not in the list"
-                       : why == UTE_FLAGS  ? "has a link with an undefined flag bit, or a strand flag in a job that is not canonical"
-                                           : "is entered by more than 4 links";
-    return cfrk_fail(ctx, CFRK_ERR_LAYOUT, "unitig %llu %s: not the links of a unitig list of this strand rule", j, what);
-  }
+  if (h[UTC_ERR] != UG_NONE) return ug_layout_error(ctx, h[UTC_ERR]);
   *n_tips = (int64_t)h[UTC_TIPS];
   return CFRK_OK;
 }

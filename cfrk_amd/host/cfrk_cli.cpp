@@ -64,6 +64,18 @@
 //                    the L tags, the GFA and the GAF then describe the clipped graph; the counts' own output is what
 //                    it is without the option.  RFILE: one line per round, "round<TAB>unitigs<TAB>tips<TAB>masked
 //                    k-mers so far" (cfrk_global_unitig_tips, cfrk_global_mask_unitigs)
+//   --unitigs-pop-bubbles [--bubble-max-kmers M] [--bubble-max-diff D] [--bubble-ratio R] [--bubble-report BFILE]
+//                    [--simplify-rounds N]  (with --unitigs-out, --unitigs-gfa or --unitigs-map) pop simple bubbles before
+//                    anything is written: up to N rounds (default 4) of unitigs, links, the tip rule (iff
+//                    --unitigs-clip-tips is given as well) and the bubble rule on that same graph, then one mask of the
+//                    k-mers of both, ended by the first round that finds neither.  A popped arm has at most M k-mers
+//                    (default k), one link in and one out, and beside it another such unitig between the same two ends,
+//                    at most D k-mers longer or shorter (default 0), of at least R times its mean coverage (default 0:
+//                    the weaker arm always goes -- a choice, not a measured optimum; 2.0 leaves a balanced heterozygous
+//                    site alone).  --tip-rounds is refused here: --simplify-rounds sets the rounds.  --tip-report lines
+//                    get a fifth field, "round<TAB>unitigs<TAB>tips<TAB>bubbles<TAB>masked k-mers so far".  BFILE: one
+//                    line per popped unitig (cfrk_host_format_bubbles: round, popped and kept S names of that round, kept
+//                    strand, lengths, km, snp / mnp / indel, both sequences)  (cfrk_global_unitig_bubbles)
 //   --min-count N / --max-count N  (global) write only the entries with N_min <= count <= N_max (text and --binary; the
 //                    binary header's n and sum describe the records written)
 //   --query QFILE --query-out OFILE  (global) how often does each k-mer of the reads of QFILE (FASTA, clean parse) occur
@@ -219,6 +231,12 @@ struct Options {
   uint32_t tip_ratio_q8 = 512;        // --tip-ratio R, in 256ths
   uint32_t tip_rounds = 4;            // --tip-rounds N
   const char *tip_report = nullptr;   // --tip-report RFILE
+  bool pop_bubbles = false;           // --unitigs-pop-bubbles
+  uint32_t bubble_max_kmers = 0;      // --bubble-max-kmers M (0: k)
+  uint32_t bubble_max_diff = 0;       // --bubble-max-diff D
+  uint32_t bubble_ratio_q8 = 0;       // --bubble-ratio R, in 256ths
+  uint32_t simplify_rounds = 4;       // --simplify-rounds N
+  const char *bubble_report = nullptr;  // --bubble-report BFILE
   bool histo_only = false;
   uint32_t min_count = 1, max_count = CFRK_COUNT_MAX;
   const char *query = nullptr, *query_out = nullptr, *query_db = nullptr;   // --query QFILE --query-out OFILE --query-db DB
@@ -493,13 +511,15 @@ int write_text_file(const char *path, const std::string &buf) {
   return 0;
 }
 
-// --unitigs-clip-tips: rounds of unitigs, links, the tip rule and the mask of the tips' k-mers through the host forms,
-// before anything is written.  The mask stays set, so what write_unitigs and write_unitigs_map compute afterwards is the
-// clipped graph.
-int clip_unitig_tips(const Options &o, cfrk_ctx *ctx) {
-  std::string report;
-  for (uint32_t round = 1; round <= o.tip_rounds; ++round) {
-    int64_t nN = 0, nS = 0, n_links = 0, n_tips = 0;
+// --unitigs-clip-tips, --unitigs-pop-bubbles: rounds of unitigs, links, each enabled rule on that same graph and one mask of
+// the k-mers of the tips and the popped arms through the host forms, before anything is written.  The mask stays set, so
+// what write_unitigs and write_unitigs_map compute afterwards is the simplified graph.  Without --unitigs-pop-bubbles
+// this is the tip loop as it always was, four-field report included.
+int simplify_unitigs(const Options &o, cfrk_ctx *ctx) {
+  std::string report, bubbles;
+  const uint32_t rounds = o.pop_bubbles ? o.simplify_rounds : o.tip_rounds;
+  for (uint32_t round = 1; round <= rounds; ++round) {
+    int64_t nN = 0, nS = 0, n_links = 0, n_tips = 0, n_pop = 0;
     int rc = cfrk_global_unitigs(ctx, o.unitigs_min_count, nullptr, 0, nullptr, nullptr, nullptr, 0, &nN, &nS);
     if (rc && rc != CFRK_ERR_SMALL_BUF) return die(ctx, rc, "cfrk_global_unitigs");
     std::vector<int8_t> data((size_t)nN);
@@ -514,17 +534,37 @@ int clip_unitig_tips(const Options &o, cfrk_ctx *ctx) {
     std::vector<cfrk_unitig_link> links((size_t)n_links);
     if (rc && (rc = cfrk_global_unitig_links(ctx, o.unitigs_min_count, data.data(), start.data(), length.data(), nN, nS, link_ptr.data(),
                                              links.data(), links.size(), &n_links))) return die(ctx, rc, "cfrk_global_unitig_links");
-    if ((rc = cfrk_global_unitig_tips(ctx, rec.data(), nS, link_ptr.data(), links.data(), n_links, o.tip_max_kmers ? o.tip_max_kmers : (uint32_t)o.k,
+    if (o.clip_tips &&
+        (rc = cfrk_global_unitig_tips(ctx, rec.data(), nS, link_ptr.data(), links.data(), n_links, o.tip_max_kmers ? o.tip_max_kmers : (uint32_t)o.k,
                                       o.tip_ratio_q8, tip.data(), &n_tips))) return die(ctx, rc, "cfrk_global_unitig_tips");
-    if (n_tips && (rc = cfrk_global_mask_unitigs(ctx, data.data(), start.data(), length.data(), nN, nS, tip.data())))
+    if (o.pop_bubbles) {
+      std::vector<uint8_t> pop((size_t)nS);
+      std::vector<uint32_t> partner((size_t)nS);
+      if ((rc = cfrk_global_unitig_bubbles(ctx, rec.data(), nS, link_ptr.data(), links.data(), n_links,
+                                           o.bubble_max_kmers ? o.bubble_max_kmers : (uint32_t)o.k, o.bubble_max_diff, o.bubble_ratio_q8,
+                                           pop.data(), partner.data(), &n_pop))) return die(ctx, rc, "cfrk_global_unitig_bubbles");
+      if (o.bubble_report && n_pop) {
+        const size_t at = bubbles.size();
+        bubbles.resize(at + cfrk_host_format_bubbles(round, data.data(), start.data(), length.data(), rec.data(), nS, pop.data(),
+                                                     partner.data(), nullptr, 0));
+        cfrk_host_format_bubbles(round, data.data(), start.data(), length.data(), rec.data(), nS, pop.data(), partner.data(), &bubbles[at],
+                                 bubbles.size() - at);
+      }
+      for (size_t j = 0; j < (size_t)nS; ++j) tip[j] |= pop[j];       // (a popped unitig is never a tip: the rules' sets are disjoint)
+    }
+    if ((n_tips || n_pop) && (rc = cfrk_global_mask_unitigs(ctx, data.data(), start.data(), length.data(), nN, nS, tip.data())))
       return die(ctx, rc, "cfrk_global_mask_unitigs");
     uint64_t masked = 0;
     if ((rc = cfrk_global_mask_count(ctx, &masked))) return die(ctx, rc, "cfrk_global_mask_count");
-    char line[96];
-    snprintf(line, sizeof line, "%u\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (unsigned long long)masked);
+    char line[128];
+    if (o.pop_bubbles)
+      snprintf(line, sizeof line, "%u\t%lld\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (long long)n_pop, (unsigned long long)masked);
+    else
+      snprintf(line, sizeof line, "%u\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (unsigned long long)masked);
     report += line;
-    if (!n_tips) break;
+    if (!n_tips && !n_pop) break;
   }
+  if (o.bubble_report) { if (const int rc = write_text_file(o.bubble_report, bubbles)) return rc; }
   return o.tip_report ? write_text_file(o.tip_report, report) : 0;
 }
 
@@ -1096,7 +1136,7 @@ int run_global(const Options &o, const cfrk_batch &batch, Worker &w, FILE *out, 
     if ((rc = result_spectrum(ctx, sp)) || (rc = write_histo(o, sp))) return rc;
   }
   g_timing.histo = now_s() - t2;
-  if (o.clip_tips && (rc = clip_unitig_tips(o, ctx))) return rc;
+  if ((o.clip_tips || o.pop_bubbles) && (rc = simplify_unitigs(o, ctx))) return rc;
   if ((o.unitigs_out || o.unitigs_gfa) && (rc = write_unitigs(o, ctx))) return rc;
   if (o.unitigs_map && (rc = write_unitigs_map(o, ctx))) return rc;
   if (o.query) {
@@ -1545,7 +1585,7 @@ int main(int argc, char **argv) {
   Options o;
   int batch_n = -1;
   bool unitigs_opt_set = false;
-  bool tip_opt_set = false;
+  bool tip_opt_set = false, tip_rounds_set = false, bubble_opt_set = false;
   bool range_set = false, stats_below_set = false, filter_opt_set = false, correct_opt_set = false, correct_min_count_set = false, normalize_opt_set = false, normalize_cutoff_set = false;
   bool pair_opt_set = false, pair_mode_set = false;
   for (int i = 1; i < argc; ++i) {
@@ -1717,8 +1757,8 @@ int main(int argc, char **argv) {
              !strcmp(argv[i], "--tip-report")) {
       if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
       const char *opt = argv[i], *v = argv[++i];
-      tip_opt_set = true;
       if (!strcmp(opt, "--tip-report")) { o.tip_report = v; continue; }
+      tip_opt_set = true;
       if (!strcmp(opt, "--tip-ratio")) {
         char *end = nullptr;
         const double r = strtod(v, &end);
@@ -1728,7 +1768,31 @@ int main(int argc, char **argv) {
       }
       uint32_t x;
       if (!parse_count(v, &x) || x < 1) { fprintf(stderr, "cfrk: %s needs a count (an integer from 1 to 4294967295), not '%s'\n", opt, v); return 1; }
-      if (!strcmp(opt, "--tip-max-kmers")) o.tip_max_kmers = x; else o.tip_rounds = x;
+      if (!strcmp(opt, "--tip-max-kmers")) o.tip_max_kmers = x; else { o.tip_rounds = x; tip_rounds_set = true; }
+    }
+    else if (!strcmp(argv[i], "--unitigs-pop-bubbles")) o.pop_bubbles = true;
+    else if (!strcmp(argv[i], "--bubble-max-kmers") || !strcmp(argv[i], "--bubble-max-diff") || !strcmp(argv[i], "--bubble-ratio") ||
+             !strcmp(argv[i], "--bubble-report") || !strcmp(argv[i], "--simplify-rounds")) {
+      if (i + 1 >= argc) { fprintf(stderr, "cfrk: %s needs a value\n", argv[i]); return 1; }
+      const char *opt = argv[i], *v = argv[++i];
+      bubble_opt_set = true;
+      if (!strcmp(opt, "--bubble-report")) { o.bubble_report = v; continue; }
+      if (!strcmp(opt, "--bubble-ratio")) {
+        char *end = nullptr;
+        const double r = strtod(v, &end);
+        if (end == v || *end || !(r >= 0.0 && r <= 256.0)) { fprintf(stderr, "cfrk: --bubble-ratio needs a number from 0 to 256, not '%s'\n", v); return 1; }
+        o.bubble_ratio_q8 = (uint32_t)(r * 256.0 + 0.5);
+        continue;
+      }
+      uint32_t x;
+      const uint32_t least = strcmp(opt, "--bubble-max-diff") ? 1u : 0u;
+      if (!parse_count(v, &x) || x < least) {
+        fprintf(stderr, "cfrk: %s needs a count (an integer from %u to 4294967295), not '%s'\n", opt, least, v);
+        return 1;
+      }
+      if (!strcmp(opt, "--bubble-max-kmers")) o.bubble_max_kmers = x;
+      else if (!strcmp(opt, "--bubble-max-diff")) o.bubble_max_diff = x;
+      else o.simplify_rounds = x;
     }
     else if (!strcmp(argv[i], "--unitigs-out") || !strcmp(argv[i], "--unitigs-min-count") || !strcmp(argv[i], "--unitigs-gfa") ||
              !strcmp(argv[i], "--unitigs-map") || !strcmp(argv[i], "--unitigs-map-out")) {
@@ -1764,7 +1828,19 @@ int main(int argc, char **argv) {
     fprintf(stderr, "cfrk: --unitigs-clip-tips needs --unitigs-out UFILE, --unitigs-gfa GFILE or --unitigs-map QFILE\n");
     return 1;
   }
-  if (tip_opt_set && !o.clip_tips) {
+  if (o.pop_bubbles && !o.unitigs_out && !o.unitigs_gfa && !o.unitigs_map) {
+    fprintf(stderr, "cfrk: --unitigs-pop-bubbles needs --unitigs-out UFILE, --unitigs-gfa GFILE or --unitigs-map QFILE\n");
+    return 1;
+  }
+  if (bubble_opt_set && !o.pop_bubbles) {
+    fprintf(stderr, "cfrk: --bubble-max-kmers, --bubble-max-diff, --bubble-ratio, --bubble-report and --simplify-rounds need --unitigs-pop-bubbles\n");
+    return 1;
+  }
+  if (tip_rounds_set && o.pop_bubbles) {
+    fprintf(stderr, "cfrk: --tip-rounds is the tip loop's own: with --unitigs-pop-bubbles the rounds are set by --simplify-rounds N\n");
+    return 1;
+  }
+  if ((tip_opt_set && !o.clip_tips) || (o.tip_report && !o.clip_tips && !o.pop_bubbles)) {
     fprintf(stderr, "cfrk: --tip-max-kmers, --tip-ratio, --tip-rounds and --tip-report need --unitigs-clip-tips\n");
     return 1;
   }

@@ -884,6 +884,59 @@ size_t cfrk_host_format_gaf(const int32_t *read_length, int64_t n_reads, const i
   return buf ? (size_t)(p - buf) : s;
 }
 
+size_t cfrk_host_format_bubbles(uint32_t round, const int8_t *data, const int64_t *start, const int32_t *length, const void *rec,
+                                int64_t nS, const uint8_t *pop, const uint32_t *partner, char *buf, size_t cap) {
+  (void)cap;
+  size_t s = 0;
+  char *p = buf;
+  for (int64_t j = 0; j < nS; ++j) {
+    if (!pop[j] || (int64_t)(partner[j] >> 1) >= nS) continue;          // (a partner that names no unitig: no line)
+    const int64_t t = (int64_t)(partner[j] >> 1);
+    const bool minus = (partner[j] & 1u) != 0;
+    const int64_t at[2] = {j, t};
+    uint64_t L[2], whole[2], frac[2];
+    for (int i = 0; i < 2; ++i) {
+      uint64_t kc;
+      uint32_t n;
+      memcpy(&kc, (const char *)rec + 16 * at[i], 8);
+      memcpy(&n, (const char *)rec + 16 * at[i] + 8, 4);
+      if (!n) n = 1;
+      const unsigned __int128 tenths = ((unsigned __int128)kc * 10 + n / 2) / n;    // as in the S line
+      whole[i] = (uint64_t)(tenths / 10); frac[i] = (uint64_t)(tenths % 10);
+      L[i] = length[at[i]] > 0 ? (uint64_t)length[at[i]] : 0;
+    }
+    const int8_t *a = data + start[j], *b = data + start[t];
+    // the kept unitig's base x, oriented like the popped one: 0..3, or 4 for any other code
+    auto code = [](int c) { return (c >= 0 && c <= 3) ? c : 4; };
+    auto kept = [&](uint64_t x) { const int c = code(minus ? b[L[1] - 1 - x] : b[x]); return (minus && c < 4) ? 3 - c : c; };
+    const char *kind = "indel";
+    if (L[0] == L[1]) {
+      uint64_t differ = 0;
+      for (uint64_t x = 0; x < L[0] && differ < 2; ++x) differ += code(a[x]) != kept(x);
+      kind = differ == 1 ? "snp" : "mnp";
+    }
+    const size_t kind_len = strlen(kind);
+    if (!buf) {
+      s += len_u64(round) + 1 + len_u64((uint64_t)j) + 1 + len_u64((uint64_t)t) + 3 + len_u64(L[0]) + 1 + len_u64(L[1]) + 1 +
+           len_u64(whole[0]) + 3 + len_u64(whole[1]) + 3 + kind_len + 1 + (size_t)L[0] + 1 + (size_t)L[1] + 1;
+      continue;
+    }
+    p = put_u64(p, round); *p++ = '\t';
+    p = put_u64(p, (uint64_t)j); *p++ = '\t';
+    p = put_u64(p, (uint64_t)t); *p++ = '\t';
+    *p++ = minus ? '-' : '+'; *p++ = '\t';
+    p = put_u64(p, L[0]); *p++ = '\t';
+    p = put_u64(p, L[1]); *p++ = '\t';
+    for (int i = 0; i < 2; ++i) { p = put_u64(p, whole[i]); *p++ = '.'; *p++ = (char)('0' + frac[i]); *p++ = '\t'; }
+    memcpy(p, kind, kind_len); p += kind_len; *p++ = '\t';
+    for (uint64_t x = 0; x < L[0]; ++x) *p++ = "ACGTN"[code(a[x])];
+    *p++ = '\t';
+    for (uint64_t x = 0; x < L[1]; ++x) *p++ = "ACGTN"[kept(x)];
+    *p++ = '\n';
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
 static void put_le(char *p, uint64_t x, int bytes) { for (int i = 0; i < bytes; ++i) p[i] = (char)(x >> (8 * i)); }
 static uint64_t get_le(const char *p, int bytes) {
   uint64_t x = 0;

@@ -151,6 +151,18 @@ size_t cfrk_host_format_unitigs_links(const int8_t *data, const int64_t *start, 
 size_t cfrk_host_format_gfa(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
                             const int64_t *link_ptr, const void *links, int k, char *buf, size_t cap);
 
+/* Popped bubbles as text (`cfrk --bubble-report BFILE`): the unitig list of one round (rec = nS rows of cfrk_unitig) with
+ * pop[nS] and partner[nS] as cfrk_global_unitig_bubbles wrote them (partner = s << 1 | p).  One line per unitig j with
+ * pop[j] != 0, in order, eleven fields separated by tabs:
+ *   <round> <j> <s> <'+' or '-': the kept unitig's strand relative to the popped one> <LN_j> <LN_s> <km_j> <km_s> <kind>
+ *   <the popped sequence> <the kept sequence, oriented like the popped one: reverse-complemented when p is set>
+ * km is kc / n_kmers with one decimal as in the S line; the names are the S names of cfrk_host_format_gfa for that
+ * round's list.  kind: "snp" -- equal lengths, Hamming distance 1; "mnp" -- equal lengths, any other distance;
+ * "indel" -- the lengths differ.  A code outside 0..3 prints as N and equals only another such code.  A popped unitig
+ * whose partner names no unitig of the list gives no line.  Returns bytes needed / written (buf may be NULL to size). */
+size_t cfrk_host_format_bubbles(uint32_t round, const int8_t *data, const int64_t *start, const int32_t *length, const void *rec,
+                                int64_t nS, const uint8_t *pop, const uint32_t *partner, char *buf, size_t cap);
+
 /* Read hits as GAF (`cfrk --unitigs-map QFILE --unitigs-map-out MFILE`): hit_ptr = n_reads + 1 offsets, hits = rows of
  * cfrk_read_hit (cfrk_abi.h: 16 bytes -- unitig, unitig_at = off << 1 | minus, read_off, n_windows as uint32),
  * unitig_length = the unitig list's lengths (every hit's unitig is an index into it).  One line per hit, in CSR order,

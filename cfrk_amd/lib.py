@@ -82,6 +82,7 @@ UNITIG_POS_DTYPE = np.dtype([("unitig", "<u4"), ("at", "<u4")])
 # one row per hit of a read (cfrk_read_hit): unitig_at = off << 1 | minus
 READ_HIT_DTYPE = np.dtype([("unitig", "<u4"), ("unitig_at", "<u4"), ("read_off", "<u4"), ("n_windows", "<u4")])
 CFRK_TIP_RATIO_Q8_MAX = 65536        # tip rule: the largest ratio_q8 (256 = the sibling's mean coverage at least the tip's)
+CFRK_BUBBLE_NONE = 0xFFFFFFFF        # bubble rule: the partner of a unitig that is not popped
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libcfrk_hip.so")
@@ -166,6 +167,8 @@ def load_library():
         "cfrk_global_mask_count": ([vp, C.POINTER(u64)], C.c_int),
         "cfrk_global_unitig_tips": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, vp, C.POINTER(i64)], C.c_int),
         "cfrk_global_unitig_tips_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, vp, C.POINTER(i64)], C.c_int),
+        "cfrk_global_unitig_bubbles": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(i64)], C.c_int),
+        "cfrk_global_unitig_bubbles_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(i64)], C.c_int),
         "cfrk_global_query_reads": ([vp, vp, vp, vp, i64, i64, vp], C.c_int),
         "cfrk_global_query_reads_device": ([vp, vp, i64, vp], C.c_int),
         "cfrk_global_read_stats": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
@@ -1146,6 +1149,82 @@ class GlobalCounter:
                 break
             u = self.unitigs(min_count)
         return u, report
+
+    def unitig_bubbles(self, rec, link_ptr, links, max_kmers, max_diff=0, ratio_q8=0):
+        """the bubble rule over the unitigs' records and their links -> (pop np.uint8[nS], partner np.uint32[nS]): pop[j] =
+        1 where unitig j is an arm (not circular, at most max_kmers k-mers, one link in, one link out, neither to itself)
+        and a parallel arm (same source, same target, lengths within max_diff) with 256 * mean(it) >= ratio_q8 * mean(j)
+        ranks above it; partner[j] = s << 1 | p names the best such arm and its orientation relative to (j,+),
+        CFRK_BUBBLE_NONE where pop[j] = 0.  Raises CfrkError (CFRK_ERR_LAYOUT, the message naming the unitig) when the
+        rows are not link rows."""
+        rec = np.ascontiguousarray(rec, UNITIG_DTYPE)
+        link_ptr = np.ascontiguousarray(link_ptr, np.int64)
+        links = np.ascontiguousarray(links, UNITIG_LINK_DTYPE)
+        if len(link_ptr) != len(rec) + 1:
+            raise ValueError("link_ptr has not one entry more than rec")
+        pop, partner, n = np.zeros(len(rec), np.uint8), np.full(len(rec), CFRK_BUBBLE_NONE, np.uint32), C.c_int64()
+        self.ctx.check(self._L.cfrk_global_unitig_bubbles(self.ctx._h, _ptr(rec), len(rec), _ptr(link_ptr), _ptr(links), len(links),
+                                                          int(max_kmers), int(max_diff), int(ratio_q8), _ptr(pop), _ptr(partner),
+                                                          C.byref(n)), "cfrk_global_unitig_bubbles")
+        assert n.value == int(pop.sum())
+        return pop, partner
+
+    def unitig_bubbles_device(self, d_rec, nS, d_link_ptr, d_links, n_links, max_kmers, max_diff, ratio_q8, d_pop, d_partner=0):
+        """device form -> n_pop; d_partner may be 0; synchronises once, for n_pop and the check of the rows"""
+        n = C.c_int64()
+        vp = lambda p: C.c_void_p(p) if p else None
+        self.ctx.check(self._L.cfrk_global_unitig_bubbles_device(self.ctx._h, vp(d_rec), nS, vp(d_link_ptr), vp(d_links), n_links,
+                                                                 int(max_kmers), int(max_diff), int(ratio_q8), vp(d_pop),
+                                                                 vp(d_partner), C.byref(n)),
+                       "cfrk_global_unitig_bubbles_device")
+        return n.value
+
+    def simplify(self, min_count=1, tips=True, bubbles=True, rounds=4, tip_max_kmers=None, tip_ratio=2.0,
+                 bubble_max_kmers=None, bubble_max_diff=0, bubble_ratio=0.0):
+        """simplify the graph: up to `rounds` rounds of unitigs -> links -> each enabled rule on that same graph -> one
+        mask_unitigs(tip | pop), stopping at the first round that finds neither a tip nor a bubble -> ((data, start,
+        length, rec) of the simplified graph, [(unitigs, tips, bubbles, masked keys so far) per round], [(round, popped
+        unitig, partner, popped record, partner's record, popped sequence, partner's sequence oriented like the popped
+        one) per popped unitig]).  tip_* as clip_tips(); bubble_max_kmers=None means k; bubble_ratio is the mean coverage
+        the stronger arm must have relative to the popped one: the default 0 pops the weaker arm whatever the coverages
+        are (a choice, not a measured optimum); 2.0 leaves a balanced heterozygous site alone.  The mask stays set, as
+        after clip_tips()."""
+        if rounds < 1:
+            raise ValueError("rounds: at least 1")
+        tip_q8, bub_q8 = int(round(float(tip_ratio) * 256)), int(round(float(bubble_ratio) * 256))
+        if not 0 <= tip_q8 <= CFRK_TIP_RATIO_Q8_MAX or not 0 <= bub_q8 <= CFRK_TIP_RATIO_Q8_MAX:
+            raise ValueError("ratio: 0 .. 256")
+        tip_max_kmers = self.k if tip_max_kmers is None else int(tip_max_kmers)
+        bubble_max_kmers = self.k if bubble_max_kmers is None else int(bubble_max_kmers)
+        text = lambda data, at, n: "".join("ACGT"[c] for c in data[at:at + n])
+        comp = str.maketrans("ACGT", "TGCA")
+        report, rows = [], []
+        u = self.unitigs(min_count)
+        for rnd in range(1, rounds + 1):
+            data, start, length, rec = u
+            link_ptr, links = self.unitig_links(data, start, length, min_count)
+            drop = np.zeros(len(rec), np.uint8)
+            n_tips = n_pop = 0
+            if tips:
+                tip = self.unitig_tips(rec, link_ptr, links, tip_max_kmers, tip_q8)
+                n_tips = int(tip.sum())
+                drop |= tip
+            if bubbles:
+                pop, partner = self.unitig_bubbles(rec, link_ptr, links, bubble_max_kmers, bubble_max_diff, bub_q8)
+                n_pop = int(pop.sum())
+                drop |= pop
+                for j in np.flatnonzero(pop).tolist():
+                    s, p = int(partner[j]) >> 1, int(partner[j]) & 1
+                    kept = text(data, int(start[s]), int(length[s]))
+                    rows.append((rnd, j, int(partner[j]), tuple(rec[j].tolist()), tuple(rec[s].tolist()),
+                                 text(data, int(start[j]), int(length[j])), kept.translate(comp)[::-1] if p else kept))
+            if n_tips or n_pop:
+                self.mask_unitigs(data, start, length, drop)
+            report.append((len(rec), n_tips, n_pop, self.mask_count()))
+            if not (n_tips or n_pop):
+                break
+            u = self.unitigs(min_count)
+        return u, report, rows
 
     def query_reads(self, data, start=None, length=None):
         """count of the k-mer starting at every base -> np.uint32[nN]: CFRK_QUERY_NONE where the window holds an

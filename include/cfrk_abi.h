@@ -672,6 +672,51 @@ int cfrk_global_unitig_tips(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS, c
                             const cfrk_unitig_link *links, int64_t n_links, uint32_t max_kmers, uint32_t ratio_q8,
                             uint8_t *tip /* nS */, int64_t *n_tips_out);
 
+/* Unitig bubbles: the weaker of two parallel single-unitig paths between the same two oriented unitigs -- what a
+ * substitution or a small indel in the middle of a read leaves behind after compaction, or, with balanced coverage, a
+ * heterozygous site.  Like the tip rule a pure function of the unitigs' records (kc, n_kmers, CFRK_UNITIG_CIRCULAR), the
+ * link CSR as cfrk_global_unitig_links wrote it, and the job's strand rule; no sequence, no index.  Oriented unitigs,
+ * out(), in(), the mirror convention, n_j and kc_j are those of "Unitig tips".
+ *   ARM: oriented unitig x = (j,o) is an arm iff j is not CFRK_UNITIG_CIRCULAR, n_j <= max_kmers, |in(x)| = 1 and
+ *   |out(x)| = 1, and neither the source src(x) of that in-link nor the target dst(x) of that out-link is unitig j in
+ *   either orientation (no self-loop, hairpin or homopolymer node).  In a canonical job (j,-) is an arm iff (j,+) is,
+ *   with src(j,-) = mirror(dst(j,+)) and dst(j,-) = mirror(src(j,+)): one record per unitig suffices.
+ *   PARALLEL: arms x = (j,o) and y = (s,p), s != j, are parallel iff src(x) == src(y) and dst(x) == dst(y) as oriented
+ *   unitigs and |n_j - n_s| <= max_diff.  (max_diff makes this non-transitive: arms of 10, 12 and 14 k-mers with
+ *   max_diff 2 are not all pairwise parallel.  That is intended.)
+ *   BEATS: y beats x iff 256 kc_s n_j >= ratio_q8 kc_j n_s, and s ranks above j: kc_s n_j > kc_j n_s, or they are equal
+ *   and s < j.  All products in 128 bits; ratio_q8 <= CFRK_TIP_RATIO_Q8_MAX as for tips.  Every ratio_q8 <= 256 means
+ *   "the weaker arm always goes"; 512 leaves a balanced heterozygous site alone.
+ *   pop[j] = 1 iff (j,+) is an arm and some parallel arm beats it, else 0.  partner[j] = s << 1 | p for the best-ranked
+ *   arm (s,p) that beats it, p being the partner's orientation when j is read as (j,+); p = 0 when both orientations of
+ *   one s qualify, and always in a job that is not canonical; CFRK_BUBBLE_NONE (0xFFFFFFFF) when pop[j] = 0.
+ *   *n_pop_out = the popped unitigs.  The parallel arms of x are sought among the targets of out(src(x)), which in the
+ *   rows of a real link set are all of them.
+ *   Every decision reads the input graph only: the result depends on no order.  The best-ranked arm of any (src, dst)
+ *   class is never popped, so src and dst stay joined.  A popped unitig has no dead end, so it is never also a tip:
+ *   tip[] and pop[] of one graph are disjoint and may be dropped together.  max_kmers = 0 pops nothing.
+ * Untrusted input: the check of the tip rule runs in front, with the same five CFRK_ERR_LAYOUT reasons naming the first
+ *   offending unitig, and only checked rows are followed.  After the check one lane per unitig looks at the at most 16
+ *   links of one row.  No loop is unbounded, nothing outside the arrays is accessed, every byte of pop and partner is
+ *   written whatever is refused (pop 0, partner NONE after an error).  Rows that pass the check without being a real
+ *   link set (canonical rows that lack their mirrors, say) give CFRK_OK, partners below 2 nS or NONE, and whatever the
+ *   rule says of the rows as given.
+ * CFRK_ERR_STATE: no job.  CFRK_ERR_ARG: NULL n_pop_out, NULL rec / link_ptr / pop with nS > 0, NULL links with n_links
+ *   > 0, negative sizes, nS >= 2^31 (a partner names an oriented unitig in 32 bits), ratio_q8 above its bound.  partner
+ *   may be NULL.  nS = 0 is fine: nothing popped.
+ * Device form (cfrk_amd/csrc/unitig_bubbles.hip): n_pop_out is host memory; the call synchronises ONCE, for n_pop and
+ *   the error word.  Temporary device memory, kept in the context's pool: 9 bytes per unitig; not canonical: 12 more
+ *   bytes per unitig, 4 per link and the scan's scratch.  Host form: stages through the pool; synchronous. */
+#define CFRK_BUBBLE_NONE 0xFFFFFFFF
+int cfrk_global_unitig_bubbles_device(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr /* nS + 1 */,
+                                      const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t max_diff,
+                                      uint32_t ratio_q8, uint8_t *d_pop /* nS bytes, every one written 0 or 1 */,
+                                      uint32_t *d_partner /* nS words, every one written; may be NULL */, int64_t *n_pop_out);
+int cfrk_global_unitig_bubbles(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS, const int64_t *link_ptr /* nS + 1 */,
+                               const cfrk_unitig_link *links, int64_t n_links, uint32_t max_kmers, uint32_t max_diff,
+                               uint32_t ratio_q8, uint8_t *pop /* nS */, uint32_t *partner /* nS; may be NULL */,
+                               int64_t *n_pop_out);
+
 /* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
 
 /* How many DISTINCT k-mers will a job hold?  One streaming pass over the reads answers it to about 1 % before anything

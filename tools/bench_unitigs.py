@@ -29,7 +29,14 @@ given by --parent-lib on the same counted reads, and the verdict whether each me
 run-to-run spread; a line "round1" with the tips call, the mask_unitigs call, and the unitigs, links and index calls with
 the mask of round 1 set, all alternating; and a line "rounds" with nodes, unitigs, tips and masked keys per clip round.
 
-  python tools/bench_unitigs.py [--links | --tips [--parent-lib SO]] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
+With --bubbles (cases b and c) the tool "bench_bubbles" writes, per case: a line "tips_ab" with the tips call on the
+unmasked graph, alternating in the same repetitions with the tips call of the library given by --parent-lib (the check
+and in-rows passes moved to a header the bubble rule shares: the call must be what it was) and the verdict whether its
+median lies inside the parent's own spread; a line "bubbles" with the bubbles call (--bubble-max-diff, --bubble-ratio,
+max_kmers = k) and the tips call alternating, and what both found; and a line "rounds" with nodes, unitigs, tips,
+bubbles and masked keys per round of the combined loop, one mask call per round.
+
+  python tools/bench_unitigs.py [--links | --tips [--parent-lib SO] | --bubbles [--parent-lib SO]] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
 """
 import argparse
 import json
@@ -149,6 +156,77 @@ def tips_case(a, torch, cfrk_amd, ctx, g, parent, other, min_count, common, time
     print(json.dumps(dict(common, line="rounds", tip_ratio=a.tip_ratio, tip_max_kmers=k, rounds=rounds)), flush=True)
 
 
+def bubbles_case(a, torch, cfrk_amd, ctx, g, parent, other, min_count, common, timed, stats, buf):
+    k = a.k
+    tip_q8, bub_q8 = int(round(a.tip_ratio * 256)), int(round(a.bubble_ratio * 256))
+    new = _Graph(cfrk_amd, g, min_count, buf)
+    ctx.sync()
+    d_tip, d_pop, d_partner = buf(new.nS), buf(new.nS), buf(new.nS * 4)
+
+    def graph_args(gr):
+        return (gr.out[3].data_ptr(), gr.nS, gr.ptr.data_ptr(), gr.rows.data_ptr(), gr.n_links)
+
+    # 1 the tips call: this library and the parent's, alternating
+    calls = {"new": lambda: g.unitig_tips_device(*graph_args(new), k, tip_q8, d_tip.data_ptr())}
+    if other is not None:
+        old = _Graph(parent, other, min_count, buf)
+        assert (old.nN, old.nS, old.n_links) == (new.nN, new.nS, new.n_links)
+        d_tip_old = buf(old.nS)
+        calls["parent"] = lambda: other.unitig_tips_device(*graph_args(old), k, tip_q8, d_tip_old.data_ptr())
+    t = {who: [] for who in calls}
+    found = {}
+    for rep in range(2 * a.reps + 1):
+        for who in (("parent", "new") if rep % 2 else ("new", "parent")):
+            if who in calls:
+                box = []
+                ms = timed(lambda: box.append(calls[who]()))
+                found[who] = box[0]
+                if rep:                                         # (the first round warms up: code objects, pool buffers)
+                    t[who].append(ms)
+    row = dict(common, line="tips_ab", nodes=new.nodes(torch), unitigs=new.nS, links=new.n_links, tips=found["new"], tip_ratio=a.tip_ratio)
+    for who, ts in t.items():
+        row[who + "_tips"] = dict(stats(ts), series=ts)
+    if other is not None:
+        assert found["parent"] == found["new"] and bool((d_tip[:new.nS] == d_tip_old[:new.nS]).all())
+        row["inside_parent_spread"] = row["parent_tips"]["min_ms"] <= row["new_tips"]["ms"] <= row["parent_tips"]["max_ms"]
+        row["new_over_parent"] = row["new_tips"]["ms"] / row["parent_tips"]["ms"]
+    print(json.dumps(row), flush=True)
+    # 2 the bubbles call beside the tips call
+    bub = lambda: g.unitig_bubbles_device(*graph_args(new), k, a.bubble_max_diff, bub_q8, d_pop.data_ptr(), d_partner.data_ptr())
+    n_pop = bub()
+    t = {"bubbles": [], "tips": []}
+    for rep in range(a.reps + 1):
+        for name, fn in (("bubbles", bub), ("tips", calls["new"])):
+            ms = timed(fn)
+            if rep:
+                t[name].append(ms)
+    row = dict(common, line="bubbles", unitigs=new.nS, links=new.n_links, bubbles_found=n_pop, tips_found=found["new"], bubble_max_kmers=k,
+               bubble_max_diff=a.bubble_max_diff, bubble_ratio=a.bubble_ratio)
+    row.update({name: stats(ts) for name, ts in t.items()})
+    row["ns_per_unitig"] = row["bubbles"]["ms"] * 1e6 / max(new.nS, 1)
+    print(json.dumps(row), flush=True)
+    # 3 the rounds of the combined loop
+    rounds, cur = [], new
+    for r in range(a.tip_rounds):
+        if r:
+            cur = _Graph(cfrk_amd, g, min_count, buf)
+            d_tip, d_pop = buf(cur.nS), buf(cur.nS)
+        n_tips = g.unitig_tips_device(*graph_args(cur), k, tip_q8, d_tip.data_ptr())
+        n_pop = g.unitig_bubbles_device(*graph_args(cur), k, a.bubble_max_diff, bub_q8, d_pop.data_ptr(), 0)
+        if n_tips or n_pop:
+            d_tip[:cur.nS] |= d_pop[:cur.nS]
+            g.mask_unitigs_device(*cur.args, d_tip.data_ptr())
+        rounds.append({"round": r + 1, "nodes": cur.nodes(torch), "unitigs": cur.nS, "tips": n_tips, "bubbles": n_pop, "masked_keys": g.mask_count()})
+        if not (n_tips or n_pop):
+            break
+    if rounds[-1]["tips"] or rounds[-1]["bubbles"]:
+        last = _Graph(cfrk_amd, g, min_count, buf)
+        rounds.append({"round": len(rounds) + 1, "nodes": last.nodes(torch), "unitigs": last.nS, "tips": None, "bubbles": None,
+                       "masked_keys": g.mask_count()})
+    print(json.dumps(dict(common, line="rounds", tip_ratio=a.tip_ratio, bubble_ratio=a.bubble_ratio, bubble_max_diff=a.bubble_max_diff,
+                          max_kmers=k, rounds=rounds)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="a,b,c")
@@ -164,7 +242,10 @@ def main():
     ap.add_argument("--tips", action="store_true")
     ap.add_argument("--tip-ratio", type=float, default=2.0)
     ap.add_argument("--tip-rounds", type=int, default=4)
-    ap.add_argument("--parent-lib", help="libcfrk_hip.so of the parent commit: with --tips, the unmasked calls alternate with it")
+    ap.add_argument("--bubbles", action="store_true")
+    ap.add_argument("--bubble-ratio", type=float, default=0.0)
+    ap.add_argument("--bubble-max-diff", type=int, default=0)
+    ap.add_argument("--parent-lib", help="libcfrk_hip.so of the parent commit: with --tips the unmasked calls, with --bubbles the tips call alternate with it")
     a = ap.parse_args()
 
     import torch
@@ -172,7 +253,7 @@ def main():
     stream = torch.cuda.Stream()
     ctx = cfrk_amd.Context(0, stream.cuda_stream)
     parent = pctx = None
-    if a.tips and a.parent_lib:                                 # a second copy of the Python mirror bound to the other library
+    if (a.tips or a.bubbles) and a.parent_lib:                                 # a second copy of the Python mirror bound to the other library
         import importlib.util
         spec = importlib.util.spec_from_file_location("cfrk_parent_lib", cfrk_amd.lib.__file__)
         parent = importlib.util.module_from_spec(spec)
@@ -231,16 +312,16 @@ def main():
         def full():
             g.unitigs_device(min_count, out[0].data_ptr(), oN, out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), oS)
 
-        if a.tips:
+        if a.tips or a.bubbles:
             other = None
             if parent is not None:                              # the same reads counted by the parent's library as well
                 other = parent.GlobalCounter(pctx, k, cfrk_amd.CFRK_CANONICAL, hint)
                 other.add_device(reads.data_ptr(), nN)
                 pctx.sync()
                 assert other.digest()[0] == distinct
-            common = {"tool": "bench_tips", "case": case, "reads": R, "L": L, "glen": a.glen, "k": k, "reps": a.reps,
+            common = {"tool": "bench_bubbles" if a.bubbles else "bench_tips", "case": case, "reads": R, "L": L, "glen": a.glen, "k": k, "reps": a.reps,
                       "error_rate": 0.0 if case == "a" else a.error_rate, "min_count": min_count, "distinct_keys": distinct}
-            tips_case(a, torch, cfrk_amd, ctx, g, parent, other, min_count, common, timed, stats, buf)
+            (bubbles_case if a.bubbles else tips_case)(a, torch, cfrk_amd, ctx, g, parent, other, min_count, common, timed, stats, buf)
             del g, other, out, reads
             torch.cuda.empty_cache()
             continue
