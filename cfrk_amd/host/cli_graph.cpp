@@ -1,0 +1,129 @@
+// cli_graph.cpp -- the unitig graph of the finished count, for the `cfrk` command: simplify (--unitigs-clip-tips,
+// --unitigs-pop-bubbles), write (--unitigs-out, --unitigs-links, --unitigs-gfa), map reads onto it (--unitigs-map).
+#include "cli_util.h"
+
+namespace {
+
+// The unitigs of the finished result through the host form (a sizes-only call, then arrays of that size) and, on request,
+// the links between them, the same way.  The text of a compacted graph is small beside the count's input: one thread formats it.
+struct UnitigGraph {
+  int64_t nN = 0, nS = 0, n_links = 0;
+  std::vector<int8_t> data;
+  std::vector<int64_t> start, link_ptr;
+  std::vector<int32_t> length;
+  std::vector<cfrk_unitig> rec;
+  std::vector<cfrk_unitig_link> links;
+  // 0, or the exit status (the error reported)
+  int fetch(cfrk_ctx *ctx, uint32_t min_count, bool with_links) {
+    int rc = sized_call([&] { return cfrk_global_unitigs(ctx, min_count, data.data(), data.size(), start.data(), length.data(), rec.data(), rec.size(), &nN, &nS); },
+                        [&] { data.resize((size_t)nN); start.resize((size_t)nS); length.resize((size_t)nS); rec.resize((size_t)nS); });
+    if (rc) return die(ctx, rc, "cfrk_global_unitigs");
+    if (!with_links) return 0;
+    link_ptr.resize((size_t)nS + 1);
+    rc = sized_call([&] { return cfrk_global_unitig_links(ctx, min_count, data.data(), start.data(), length.data(), nN, nS, link_ptr.data(), links.data(), links.size(), &n_links); },
+                    [&] { links.resize((size_t)n_links); });
+    return rc ? die(ctx, rc, "cfrk_global_unitig_links") : 0;
+  }
+};
+
+}  // namespace
+
+// --unitigs-clip-tips, --unitigs-pop-bubbles: rounds of unitigs, links, each enabled rule on that same graph and one mask of
+// the k-mers of the tips and the popped arms through the host forms, before anything is written.  The mask stays set, so
+// what write_unitigs and write_unitigs_map compute afterwards is the simplified graph.  Without --unitigs-pop-bubbles
+// this is the tip loop as it always was, four-field report included.
+int simplify_unitigs(const Options &o, cfrk_ctx *ctx) {
+  std::string report, bubbles;
+  const uint32_t rounds = o.pop_bubbles ? o.simplify_rounds : o.tip_rounds;
+  for (uint32_t round = 1; round <= rounds; ++round) {
+    int64_t n_tips = 0, n_pop = 0;
+    UnitigGraph g;
+    int rc;
+    if ((rc = g.fetch(ctx, o.unitigs_min_count, true))) return rc;
+    const int64_t nS = g.nS;
+    std::vector<uint8_t> tip((size_t)nS);
+    if (o.clip_tips &&
+        (rc = cfrk_global_unitig_tips(ctx, g.rec.data(), nS, g.link_ptr.data(), g.links.data(), g.n_links, o.tip_max_kmers ? o.tip_max_kmers : (uint32_t)o.k,
+                                      o.tip_ratio_q8, tip.data(), &n_tips))) return die(ctx, rc, "cfrk_global_unitig_tips");
+    if (o.pop_bubbles) {
+      std::vector<uint8_t> pop((size_t)nS);
+      std::vector<uint32_t> partner((size_t)nS);
+      if ((rc = cfrk_global_unitig_bubbles(ctx, g.rec.data(), nS, g.link_ptr.data(), g.links.data(), g.n_links,
+                                           o.bubble_max_kmers ? o.bubble_max_kmers : (uint32_t)o.k, o.bubble_max_diff, o.bubble_ratio_q8,
+                                           pop.data(), partner.data(), &n_pop))) return die(ctx, rc, "cfrk_global_unitig_bubbles");
+      if (o.bubble_report && n_pop)
+        format_into(bubbles, [&](char *out, size_t room) {
+          return cfrk_host_format_bubbles(round, g.data.data(), g.start.data(), g.length.data(), g.rec.data(), nS, pop.data(), partner.data(), out, room);
+        });
+      for (size_t j = 0; j < (size_t)nS; ++j) tip[j] |= pop[j];       // (a popped unitig is never a tip: the rules' sets are disjoint)
+    }
+    if ((n_tips || n_pop) && (rc = cfrk_global_mask_unitigs(ctx, g.data.data(), g.start.data(), g.length.data(), g.nN, nS, tip.data())))
+      return die(ctx, rc, "cfrk_global_mask_unitigs");
+    uint64_t masked = 0;
+    if ((rc = cfrk_global_mask_count(ctx, &masked))) return die(ctx, rc, "cfrk_global_mask_count");
+    char line[128];
+    if (o.pop_bubbles)
+      snprintf(line, sizeof line, "%u\t%lld\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (long long)n_pop, (unsigned long long)masked);
+    else
+      snprintf(line, sizeof line, "%u\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (unsigned long long)masked);
+    report += line;
+    if (!n_tips && !n_pop) break;
+  }
+  if (o.bubble_report) { if (const int rc = write_file(o.bubble_report, bubbles)) return rc; }
+  return o.tip_report ? write_file(o.tip_report, report) : 0;
+}
+
+int write_unitigs(const Options &o, cfrk_ctx *ctx) {
+  UnitigGraph g;
+  const bool with_links = o.unitigs_links || o.unitigs_gfa;
+  int rc;
+  if ((rc = g.fetch(ctx, o.unitigs_min_count, with_links))) return rc;
+  if (o.unitigs_out) {
+    const int64_t *lp = o.unitigs_links ? g.link_ptr.data() : nullptr;     // (without --unitigs-links: the bytes as they were)
+    std::string buf;
+    format_into(buf, [&](char *out, size_t room) {
+      return with_links ? cfrk_host_format_unitigs_links(g.data.data(), g.start.data(), g.length.data(), g.rec.data(), g.nS, lp, g.links.data(), out, room)
+                        : cfrk_host_format_unitigs(g.data.data(), g.start.data(), g.length.data(), g.rec.data(), g.nS, out, room);
+    });
+    if ((rc = write_file(o.unitigs_out, buf))) return rc;
+  }
+  if (o.unitigs_gfa) {
+    std::string buf;
+    format_into(buf, [&](char *out, size_t room) {
+      return cfrk_host_format_gfa(g.data.data(), g.start.data(), g.length.data(), g.rec.data(), g.nS, g.link_ptr.data(), g.links.data(), o.k, out, room);
+    });
+    if ((rc = write_file(o.unitigs_gfa, buf))) return rc;
+  }
+  return 0;
+}
+
+// --unitigs-map QFILE --unitigs-map-out MFILE: the unitigs into device arrays (a sizes-only call, then arrays of that
+// size), where they stay; the position map from them (cfrk_global_unitig_index_device); the hits of QFILE's reads q
+// (cfrk_global_read_hits) as GAF, the segment names those of --unitigs-gfa (cfrk_host_format_gaf)
+int write_unitigs_map(const Options &o, cfrk_ctx *ctx, const cfrk_batch &q) {
+  int64_t nN = 0, nS = 0;
+  int rc = cfrk_global_unitigs_device(ctx, o.unitigs_min_count, nullptr, 0, nullptr, nullptr, nullptr, 0, &nN, &nS);
+  if (rc && rc != CFRK_ERR_SMALL_BUF) return die(ctx, rc, "cfrk_global_unitigs_device");
+  void *d[4] = {nullptr, nullptr, nullptr, nullptr};      // data, start, length, records
+  DeviceBufs bufs(ctx);
+  std::vector<int32_t> ulen((size_t)nS);
+  if (nS > 0) {
+    const size_t bytes[4] = {(size_t)nN, (size_t)nS * 8, (size_t)nS * 4, (size_t)nS * sizeof(cfrk_unitig)};
+    for (int j = 0; j < 4; ++j)
+      if ((rc = bufs.alloc(bytes[j], &d[j]))) return die(ctx, rc, "cfrk_device_alloc");
+    if ((rc = cfrk_global_unitigs_device(ctx, o.unitigs_min_count, (int8_t *)d[0], (uint64_t)nN, (int64_t *)d[1], (int32_t *)d[2],
+                                         (cfrk_unitig *)d[3], (uint64_t)nS, &nN, &nS))) return die(ctx, rc, "cfrk_global_unitigs_device");
+  }
+  if ((rc = cfrk_global_unitig_index_device(ctx, o.unitigs_min_count, (const int8_t *)d[0], (const int64_t *)d[1], (const int32_t *)d[2],
+                                            nN, nS))) return die(ctx, rc, "cfrk_global_unitig_index_device");
+  if (nS > 0 && (rc = cfrk_memcpy_d2h(ctx, ulen.data(), d[2], (size_t)nS * 4))) return die(ctx, rc, "cfrk_memcpy_d2h");
+  std::vector<int64_t> hit_ptr((size_t)q.nS + 1);
+  std::vector<cfrk_read_hit> hits;
+  int64_t n_hits = 0;
+  rc = sized_call([&] { return cfrk_global_read_hits(ctx, q.data, q.start, q.length, q.nN, q.nS, hit_ptr.data(), hits.data(), hits.size(), &n_hits); },
+                  [&] { hits.resize((size_t)n_hits); });
+  if (rc) return die(ctx, rc, "cfrk_global_read_hits");
+  std::string buf;
+  format_into(buf, [&](char *out, size_t room) { return cfrk_host_format_gaf(q.length, q.nS, hit_ptr.data(), hits.data(), ulen.data(), o.k, out, room); });
+  return write_file(o.unitigs_map_out, buf);
+}
