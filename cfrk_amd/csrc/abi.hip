@@ -1240,6 +1240,104 @@ int cfrk_global_unitig_bubbles(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS
   return cfrk_memcpy_d2h(ctx, pop, carve_at<uint8_t>(d_out, o_pop), (size_t)nS);
 }
 
+static_assert(sizeof(cfrk_bulge_stats) == 24, "cfrk_bulge_stats is 24 bytes without padding");
+
+static int unitig_bulges_check(cfrk_ctx *ctx, const void *rec, int64_t nS, const void *link_ptr, const void *links, int64_t n_links,
+                               const cfrk_bulge_params &p, const void *pop, const void *path_ptr, const void *path, uint64_t cap_path,
+                               int64_t *n_path_out, cfrk_bulge_stats *stats) {
+  if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "unitig bulges before begin: the job supplies the strand rule");
+  if (nS < 0 || n_links < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (!stats) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL stats");
+  if (path_ptr && !n_path_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL n_path_out with path_ptr");
+  if (nS > 0 && (!rec || !link_ptr || !pop)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (n_links > 0 && !links) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL links with n_links above 0");
+  if (path_ptr && cap_path > 0 && !path) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL array with a capacity above 0");
+  if ((uint64_t)nS >= (1ull << 31)) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld unitigs: a path names an oriented unitig in 32 bits", (long long)nS);
+  if (p.max_hops > CFRK_BULGE_MAX_HOPS) return cfrk_fail(ctx, CFRK_ERR_ARG, "max_hops %u: at most %d", p.max_hops, CFRK_BULGE_MAX_HOPS);
+  if (p.max_visits > CFRK_BULGE_MAX_VISITS) return cfrk_fail(ctx, CFRK_ERR_ARG, "max_visits %u: at most %d", p.max_visits, CFRK_BULGE_MAX_VISITS);
+  if (p.ratio_q8 > CFRK_TIP_RATIO_Q8_MAX) return cfrk_fail(ctx, CFRK_ERR_ARG, "ratio_q8 %u: at most %d", p.ratio_q8, CFRK_TIP_RATIO_Q8_MAX);
+  if (n_path_out) *n_path_out = 0;
+  stats->arms = stats->popped = stats->undecided = 0;
+  return CFRK_OK;
+}
+
+static int unitig_bulges_fit(cfrk_ctx *ctx, int64_t n_path, uint64_t cap_path) {
+  if ((uint64_t)n_path <= cap_path) return CFRK_OK;
+  return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "unitig bulges: %lld path entries, room for %llu", (long long)n_path, (unsigned long long)cap_path);
+}
+
+int cfrk_global_unitig_bulges_device(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
+                                     const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t max_diff,
+                                     uint32_t max_hops, uint32_t max_visits, uint32_t ratio_q8, uint8_t *d_pop, uint32_t *d_visits,
+                                     int64_t *d_path_ptr, uint32_t *d_path, uint64_t cap_path, int64_t *n_path_out,
+                                     cfrk_bulge_stats *stats) {
+  if (!ctx) return CFRK_ERR_ARG;
+  const cfrk_bulge_params p = {max_kmers, max_diff, max_hops, max_visits, ratio_q8};
+  int rc = unitig_bulges_check(ctx, d_rec, nS, d_link_ptr, d_links, n_links, p, d_pop, d_path_ptr, d_path, cap_path, n_path_out, stats);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (nS == 0) {
+    if (d_path_ptr) HIP_TRY(ctx, hipMemsetAsync(d_path_ptr, 0, 8, ctx->stream));
+    return CFRK_OK;
+  }
+  int64_t n_path = 0;
+  if ((rc = cfrk_unitig_bulges_search(ctx, d_rec, nS, d_link_ptr, d_links, n_links, p, d_pop, d_visits, d_path_ptr, stats, &n_path))) return rc;
+  if (!d_path_ptr) return CFRK_OK;
+  *n_path_out = n_path;
+  if ((rc = unitig_bulges_fit(ctx, n_path, cap_path)) || n_path == 0) return rc;
+  return cfrk_unitig_bulges_fill(ctx, d_rec, nS, d_link_ptr, d_links, n_links, p, stats->popped, d_path_ptr, d_path);
+}
+
+int cfrk_global_unitig_bulges(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS, const int64_t *link_ptr,
+                              const cfrk_unitig_link *links, int64_t n_links, uint32_t max_kmers, uint32_t max_diff,
+                              uint32_t max_hops, uint32_t max_visits, uint32_t ratio_q8, uint8_t *pop, uint32_t *visits,
+                              int64_t *path_ptr, uint32_t *path, uint64_t cap_path, int64_t *n_path_out, cfrk_bulge_stats *stats) {
+  if (!ctx) return CFRK_ERR_ARG;
+  const cfrk_bulge_params p = {max_kmers, max_diff, max_hops, max_visits, ratio_q8};
+  int rc = unitig_bulges_check(ctx, rec, nS, link_ptr, links, n_links, p, pop, path_ptr, path, cap_path, n_path_out, stats);
+  if (rc) return rc;
+  if (nS == 0) {
+    if (path_ptr) path_ptr[0] = 0;
+    return CFRK_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // [records | link_ptr | links] in a slot of their own, [path_ptr | visits | pop] in another, the paths in a third
+  Carve c, co;
+  const size_t rec_bytes = (size_t)nS * sizeof *rec, ptr_bytes = ((size_t)nS + 1) * 8, link_bytes = (size_t)n_links * sizeof *links;
+  const size_t o_rec = c.part(rec_bytes), o_ptr = c.part(ptr_bytes), o_links = c.part(link_bytes);
+  const size_t o_pptr = co.part(path_ptr ? ptr_bytes : 0), o_visits = co.part(visits ? (size_t)nS * 4 : 0), o_pop = co.part((size_t)nS);
+  void *d_in, *d_out;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_BULGES_IN, c.end, &d_in))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_BULGES_OUT, co.end, &d_out))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_rec), rec, rec_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_ptr), link_ptr, ptr_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (n_links) HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_links), links, link_bytes, hipMemcpyHostToDevice, ctx->stream));
+  const cfrk_unitig *d_rec = carve_at<cfrk_unitig>(d_in, o_rec);
+  const int64_t *d_link_ptr = carve_at<int64_t>(d_in, o_ptr);
+  const cfrk_unitig_link *d_links = carve_at<cfrk_unitig_link>(d_in, o_links);
+  uint8_t *d_pop = carve_at<uint8_t>(d_out, o_pop);
+  uint32_t *d_visits = visits ? carve_at<uint32_t>(d_out, o_visits) : nullptr;
+  int64_t *d_path_ptr = path_ptr ? carve_at<int64_t>(d_out, o_pptr) : nullptr;
+  int64_t n_path = 0;
+  rc = cfrk_unitig_bulges_search(ctx, d_rec, nS, d_link_ptr, d_links, n_links, p, d_pop, d_visits, d_path_ptr, stats, &n_path);
+  if (rc) {                                            // refused: everything 0
+    memset(pop, 0, (size_t)nS);
+    if (visits) memset(visits, 0, (size_t)nS * 4);
+    if (path_ptr) memset(path_ptr, 0, ptr_bytes);
+    return stage_drain(ctx, rc);
+  }
+  if (visits) HIP_TRY(ctx, hipMemcpyAsync(visits, d_visits, (size_t)nS * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (path_ptr) HIP_TRY(ctx, hipMemcpyAsync(path_ptr, d_path_ptr, ptr_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = cfrk_memcpy_d2h(ctx, pop, d_pop, (size_t)nS))) return rc;
+  if (!path_ptr) return CFRK_OK;
+  *n_path_out = n_path;
+  if ((rc = unitig_bulges_fit(ctx, n_path, cap_path)) || n_path == 0) return rc;
+  void *d_path;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_BULGES_PATH, (size_t)n_path * 4, &d_path))) return rc;
+  if ((rc = cfrk_unitig_bulges_fill(ctx, d_rec, nS, d_link_ptr, d_links, n_links, p, stats->popped, d_path_ptr, (uint32_t *)d_path))) return rc;
+  return cfrk_memcpy_d2h(ctx, path, d_path, (size_t)n_path * 4);
+}
+
 /* ------------------------------------------------------------------ digital normalisation */
 
 static int normalize_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, int64_t batch_reads, const void *data, const void *start,

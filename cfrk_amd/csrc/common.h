@@ -62,6 +62,9 @@ enum {  // pool slots
   BUF_UNITIG_TIPS_IN, BUF_UNITIG_TIPS_OUT,    // staging of cfrk_global_unitig_tips alone (records, link_ptr, links in; tip bytes out)
   BUF_UNITIG_BUBBLES,                         // bubble rule (unitig_bubbles.hip): error / size words, arm bytes and records, the in-rows, the scan's scratch
   BUF_UNITIG_BUBBLES_IN, BUF_UNITIG_BUBBLES_OUT,  // staging of cfrk_global_unitig_bubbles alone (records, link_ptr, links in; pop bytes and partners out)
+  BUF_UNITIG_BULGES,                          // bulge rule (unitig_bulges.hip): error / size words, the arm list, the popped list, the in-rows, the scans' scratch
+  BUF_UNITIG_BULGES_IN, BUF_UNITIG_BULGES_OUT,  // staging of cfrk_global_unitig_bulges alone (records, link_ptr, links in; pop, visits, path_ptr out)
+  BUF_UNITIG_BULGES_PATH,                     // ... and its paths, sized once n_path is known
   BUF_NSLOTS
 };
 
@@ -237,6 +240,16 @@ int cfrk_unitig_tips_launch(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS,
 int cfrk_unitig_bubbles_launch(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
                                const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t max_diff,
                                uint32_t ratio_q8, uint8_t *d_pop, uint32_t *d_partner, int64_t *n_pop);
+// unitig_bulges.hip: the bulge rule over 1 <= nS < 2^31 records and their link rows.  The search writes d_pop[nS] and,
+// unless NULL, d_visits[nS] and d_path_ptr[nS + 1]; it synchronises once, for the error word (CFRK_ERR_LAYOUT), the
+// counts and *n_path.  The fill pass behind it writes the rows of d_path_ptr into d_path and is left enqueued.
+struct cfrk_bulge_params { uint32_t max_kmers, max_diff, max_hops, max_visits, ratio_q8; };
+int cfrk_unitig_bulges_search(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
+                              const cfrk_unitig_link *d_links, int64_t n_links, const cfrk_bulge_params &p, uint8_t *d_pop,
+                              uint32_t *d_visits, int64_t *d_path_ptr, cfrk_bulge_stats *stats, int64_t *n_path);
+int cfrk_unitig_bulges_fill(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
+                            const cfrk_unitig_link *d_links, int64_t n_links, const cfrk_bulge_params &p, int64_t n_popped,
+                            const int64_t *d_path_ptr, uint32_t *d_path);
 // sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
 // enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
 int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,

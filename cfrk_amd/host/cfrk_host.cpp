@@ -937,6 +937,74 @@ size_t cfrk_host_format_bubbles(uint32_t round, const int8_t *data, const int64_
   return buf ? (size_t)(p - buf) : s;
 }
 
+size_t cfrk_host_format_bulges(uint32_t round, const int8_t *data, const int64_t *start, const int32_t *length, const void *rec,
+                               int64_t nS, const uint8_t *pop, const int64_t *path_ptr, const uint32_t *path, int k, char *buf, size_t cap) {
+  (void)cap;
+  size_t s = 0;
+  char *p = buf;
+  const uint64_t k1 = k > 1 ? (uint64_t)k - 1 : 0;
+  auto code = [](int c) { return (c >= 0 && c <= 3) ? c : 4; };
+  std::string spelled;                                  // the path's sequence as codes 0..4
+  for (int64_t j = 0; j < nS; ++j) {
+    const int64_t a = path_ptr[j], b = path_ptr[j + 1];
+    if (!pop[j] || b <= a) continue;
+    bool named = true;                                  // (a path entry that names no unitig: no line)
+    for (int64_t t = a; t < b; ++t) named = named && (int64_t)(path[t] >> 1) < nS;
+    if (!named) continue;
+    uint64_t kc, path_kmers = 0;
+    uint32_t n;
+    memcpy(&kc, (const char *)rec + 16 * j, 8);
+    memcpy(&n, (const char *)rec + 16 * j + 8, 4);
+    if (!n) n = 1;
+    const unsigned __int128 tenths = ((unsigned __int128)kc * 10 + n / 2) / n;    // as in the S line
+    const uint64_t whole = (uint64_t)(tenths / 10), frac = (uint64_t)(tenths % 10);
+    const uint64_t L = length[j] > 0 ? (uint64_t)length[j] : 0;
+    spelled.clear();
+    size_t names = 0;
+    for (int64_t t = a; t < b; ++t) {
+      const int64_t w = (int64_t)(path[t] >> 1);
+      const bool minus = (path[t] & 1u) != 0;
+      uint32_t wn;
+      memcpy(&wn, (const char *)rec + 16 * w + 8, 4);
+      path_kmers += wn;
+      names += 1 + len_u64((uint64_t)w);
+      const uint64_t wl = length[w] > 0 ? (uint64_t)length[w] : 0;
+      const int8_t *q = data + start[w];
+      for (uint64_t x = (t == a ? 0 : k1); x < wl; ++x) {               // every unitig after the first overlaps k - 1 bases
+        const int c = code(minus ? q[wl - 1 - x] : q[x]);
+        spelled.push_back((char)((minus && c < 4) ? 3 - c : c));
+      }
+    }
+    const int8_t *own = data + start[j];
+    const char *kind = "indel";
+    if (L == spelled.size()) {
+      uint64_t differ = 0;
+      for (uint64_t x = 0; x < L && differ < 2; ++x) differ += code(own[x]) != spelled[x];
+      kind = differ == 1 ? "snp" : "mnp";
+    }
+    const size_t kind_len = strlen(kind);
+    if (!buf) {
+      s += len_u64(round) + 1 + len_u64((uint64_t)j) + 1 + len_u64(L) + 1 + len_u64(whole) + 3 + len_u64((uint64_t)(b - a)) + 1 +
+           len_u64(path_kmers) + 1 + names + 1 + kind_len + 1 + (size_t)L + 1 + spelled.size() + 1;
+      continue;
+    }
+    p = put_u64(p, round); *p++ = '\t';
+    p = put_u64(p, (uint64_t)j); *p++ = '\t';
+    p = put_u64(p, L); *p++ = '\t';
+    p = put_u64(p, whole); *p++ = '.'; *p++ = (char)('0' + frac); *p++ = '\t';
+    p = put_u64(p, (uint64_t)(b - a)); *p++ = '\t';
+    p = put_u64(p, path_kmers); *p++ = '\t';
+    for (int64_t t = a; t < b; ++t) { *p++ = (path[t] & 1u) ? '<' : '>'; p = put_u64(p, (uint64_t)(path[t] >> 1)); }
+    *p++ = '\t';
+    memcpy(p, kind, kind_len); p += kind_len; *p++ = '\t';
+    for (uint64_t x = 0; x < L; ++x) *p++ = "ACGTN"[code(own[x])];
+    *p++ = '\t';
+    for (size_t x = 0; x < spelled.size(); ++x) *p++ = "ACGTN"[(int)spelled[x]];
+    *p++ = '\n';
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
 static void put_le(char *p, uint64_t x, int bytes) { for (int i = 0; i < bytes; ++i) p[i] = (char)(x >> (8 * i)); }
 static uint64_t get_le(const char *p, int bytes) {
   uint64_t x = 0;

@@ -163,6 +163,18 @@ size_t cfrk_host_format_gfa(const int8_t *data, const int64_t *start, const int3
 size_t cfrk_host_format_bubbles(uint32_t round, const int8_t *data, const int64_t *start, const int32_t *length, const void *rec,
                                 int64_t nS, const uint8_t *pop, const uint32_t *partner, char *buf, size_t cap);
 
+/* Popped bulges as text (`cfrk --bulge-report FILE`): the unitig list of one round with pop[nS], path_ptr[nS + 1] and path
+ * as cfrk_global_unitig_bulges wrote them (a path entry = w << 1 | o).  One line per unitig j with pop[j] != 0 and a row
+ * that is not empty, in order, ten fields separated by tabs:
+ *   <round> <j> <LN_j> <km_j> <hops> <the path's k-mers: the sum of its unitigs' n_kmers> <the path in GAF segment
+ *   notation, '>' w for (w,+) and '<' w for (w,-), as in ">3<7>9"> <kind> <the popped sequence> <the path's sequence>
+ * The path's sequence is spelled from s to t, so it is oriented like the popped unitig: the first unitig whole, of every
+ * further one what follows its first k - 1 bases, a unitig entered as (w,-) reverse-complemented.  km, the names and
+ * kind (the popped sequence against the path's) are those of cfrk_host_format_bubbles.  A row with an entry that names
+ * no unitig of the list gives no line.  Returns bytes needed / written (buf may be NULL to size). */
+size_t cfrk_host_format_bulges(uint32_t round, const int8_t *data, const int64_t *start, const int32_t *length, const void *rec,
+                               int64_t nS, const uint8_t *pop, const int64_t *path_ptr, const uint32_t *path, int k, char *buf, size_t cap);
+
 /* Read hits as GAF (`cfrk --unitigs-map QFILE --unitigs-map-out MFILE`): hit_ptr = n_reads + 1 offsets, hits = rows of
  * cfrk_read_hit (cfrk_abi.h: 16 bytes -- unitig, unitig_at = off << 1 | minus, read_off, n_windows as uint32),
  * unitig_length = the unitig list's lengths (every hit's unitig is an index into it).  One line per hit, in CSR order,

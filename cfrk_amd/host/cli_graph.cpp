@@ -1,5 +1,5 @@
 // cli_graph.cpp -- the unitig graph of the finished count, for the `cfrk` command: simplify (--unitigs-clip-tips,
-// --unitigs-pop-bubbles), write (--unitigs-out, --unitigs-links, --unitigs-gfa), map reads onto it (--unitigs-map).
+// --unitigs-pop-bubbles, --unitigs-pop-bulges), write (--unitigs-out, --unitigs-links, --unitigs-gfa), map reads onto it (--unitigs-map).
 #include "cli_util.h"
 
 namespace {
@@ -31,12 +31,13 @@ struct UnitigGraph {
 // --unitigs-clip-tips, --unitigs-pop-bubbles: rounds of unitigs, links, each enabled rule on that same graph and one mask of
 // the k-mers of the tips and the popped arms through the host forms, before anything is written.  The mask stays set, so
 // what write_unitigs and write_unitigs_map compute afterwards is the simplified graph.  Without --unitigs-pop-bubbles
-// this is the tip loop as it always was, four-field report included.
+// this is the tip loop as it always was, four-field report included; --unitigs-pop-bulges adds the bulge rule on that same
+// graph, its pops to the same mask and a field to the report.
 int simplify_unitigs(const Options &o, cfrk_ctx *ctx) {
-  std::string report, bubbles;
-  const uint32_t rounds = o.pop_bubbles ? o.simplify_rounds : o.tip_rounds;
+  std::string report, bubbles, bulges;
+  const uint32_t rounds = (o.pop_bubbles || o.pop_bulges) ? o.simplify_rounds : o.tip_rounds;
   for (uint32_t round = 1; round <= rounds; ++round) {
-    int64_t n_tips = 0, n_pop = 0;
+    int64_t n_tips = 0, n_pop = 0, n_bulges = 0;
     UnitigGraph g;
     int rc;
     if ((rc = g.fetch(ctx, o.unitigs_min_count, true))) return rc;
@@ -57,18 +58,44 @@ int simplify_unitigs(const Options &o, cfrk_ctx *ctx) {
         });
       for (size_t j = 0; j < (size_t)nS; ++j) tip[j] |= pop[j];       // (a popped unitig is never a tip: the rules' sets are disjoint)
     }
-    if ((n_tips || n_pop) && (rc = cfrk_global_mask_unitigs(ctx, g.data.data(), g.start.data(), g.length.data(), g.nN, nS, tip.data())))
+    if (o.pop_bulges) {
+      std::vector<uint8_t> pop((size_t)nS);
+      std::vector<int64_t> path_ptr((size_t)nS + 1);
+      std::vector<uint32_t> path;
+      int64_t n_path = 0;
+      cfrk_bulge_stats stats;
+      const uint32_t max_kmers = o.bulge_max_kmers ? o.bulge_max_kmers : (uint32_t)o.k;
+      const uint64_t reach = (uint64_t)max_kmers + o.bulge_max_diff;
+      const uint32_t max_hops = o.bulge_max_hops ? o.bulge_max_hops : (uint32_t)(reach < CFRK_BULGE_MAX_HOPS ? reach : CFRK_BULGE_MAX_HOPS);
+      rc = sized_call([&] { return cfrk_global_unitig_bulges(ctx, g.rec.data(), nS, g.link_ptr.data(), g.links.data(), g.n_links, max_kmers, o.bulge_max_diff,
+                                                             max_hops, o.bulge_max_visits, o.bulge_ratio_q8, pop.data(), nullptr, path_ptr.data(),
+                                                             path.data(), path.size(), &n_path, &stats); },
+                      [&] { path.resize((size_t)n_path); });
+      if (rc) return die(ctx, rc, "cfrk_global_unitig_bulges");
+      n_bulges = stats.popped;
+      if (o.bulge_report && n_bulges)
+        format_into(bulges, [&](char *out, size_t room) {
+          return cfrk_host_format_bulges(round, g.data.data(), g.start.data(), g.length.data(), g.rec.data(), nS, pop.data(), path_ptr.data(), path.data(),
+                                         o.k, out, room);
+        });
+      for (size_t j = 0; j < (size_t)nS; ++j) tip[j] |= pop[j];       // (disjoint from the tips; a bubble's arm may be popped by both rules)
+    }
+    if ((n_tips || n_pop || n_bulges) && (rc = cfrk_global_mask_unitigs(ctx, g.data.data(), g.start.data(), g.length.data(), g.nN, nS, tip.data())))
       return die(ctx, rc, "cfrk_global_mask_unitigs");
     uint64_t masked = 0;
     if ((rc = cfrk_global_mask_count(ctx, &masked))) return die(ctx, rc, "cfrk_global_mask_count");
     char line[128];
-    if (o.pop_bubbles)
+    if (o.pop_bulges)
+      snprintf(line, sizeof line, "%u\t%lld\t%lld\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (long long)n_pop, (long long)n_bulges,
+               (unsigned long long)masked);
+    else if (o.pop_bubbles)
       snprintf(line, sizeof line, "%u\t%lld\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (long long)n_pop, (unsigned long long)masked);
     else
       snprintf(line, sizeof line, "%u\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (unsigned long long)masked);
     report += line;
-    if (!n_tips && !n_pop) break;
+    if (!n_tips && !n_pop && !n_bulges) break;
   }
+  if (o.bulge_report) { if (const int rc = write_file(o.bulge_report, bulges)) return rc; }
   if (o.bubble_report) { if (const int rc = write_file(o.bubble_report, bubbles)) return rc; }
   return o.tip_report ? write_file(o.tip_report, report) : 0;
 }

@@ -76,6 +76,19 @@
 //                    get a fifth field, "round<TAB>unitigs<TAB>tips<TAB>bubbles<TAB>masked k-mers so far".  BFILE: one
 //                    line per popped unitig (cfrk_host_format_bubbles: round, popped and kept S names of that round, kept
 //                    strand, lengths, km, snp / mnp / indel, both sequences)  (cfrk_global_unitig_bubbles)
+//   --unitigs-pop-bulges [--bulge-max-kmers M] [--bulge-max-diff D] [--bulge-max-hops H] [--bulge-max-visits V]
+//                    [--bulge-ratio R] [--bulge-report FILE] [--simplify-rounds N]  (with --unitigs-out, --unitigs-gfa or
+//                    --unitigs-map) pop arms that run beside a CHAIN of unitigs, in the same loop as --unitigs-clip-tips
+//                    and --unitigs-pop-bubbles and combined with either: every enabled rule sees the same graph of a
+//                    round, one mask takes the k-mers of all of them.  A popped arm has at most M k-mers (default k),
+//                    one link in and one out, and beside it a path of at most H unitigs (default min(M + D, 64), at
+//                    most 64) between the same two ends, each of at least R times its mean coverage (default 0) and
+//                    ranking above it, whose k-mers sum to the arm's within D (default 0).  The depth-first search
+//                    looks at V links at most (default 1024, at most 65536: a choice with headroom, not a measured
+//                    optimum); an arm it cannot decide within V stays.  --tip-report lines get six fields,
+//                    "round<TAB>unitigs<TAB>tips<TAB>bubbles<TAB>bulges<TAB>masked k-mers so far".  FILE: one line per
+//                    popped unitig (cfrk_host_format_bulges: round, S name, LN, km, hops, the path's k-mers, the path
+//                    as >3<7>9, snp / mnp / indel, both sequences)  (cfrk_global_unitig_bulges)
 //   --min-count N / --max-count N  (global) write only the entries with N_min <= count <= N_max (text and --binary; the
 //                    binary header's n and sum describe the records written)
 //   --query QFILE --query-out OFILE  (global) how often does each k-mer of the reads of QFILE (FASTA, clean parse) occur
@@ -223,6 +236,13 @@ struct Options {
   uint32_t bubble_ratio_q8 = 0;       // --bubble-ratio R, in 256ths
   uint32_t simplify_rounds = 4;       // --simplify-rounds N
   const char *bubble_report = nullptr;  // --bubble-report BFILE
+  bool pop_bulges = false;            // --unitigs-pop-bulges
+  uint32_t bulge_max_kmers = 0;       // --bulge-max-kmers M (0: k)
+  uint32_t bulge_max_diff = 0;        // --bulge-max-diff D
+  uint32_t bulge_max_hops = 0;        // --bulge-max-hops H (0: min(M + D, 64))
+  uint32_t bulge_max_visits = 1024;   // --bulge-max-visits V
+  uint32_t bulge_ratio_q8 = 0;        // --bulge-ratio R, in 256ths
+  const char *bulge_report = nullptr; // --bulge-report FILE
   bool histo_only = false;
   uint32_t min_count = 1, max_count = CFRK_COUNT_MAX;
   const char *query = nullptr, *query_out = nullptr, *query_db = nullptr;   // --query QFILE --query-out OFILE --query-db DB
@@ -261,7 +281,7 @@ struct Options {
   int batch_n = -1;                                                 // --batch N (-1: not given)
   std::vector<const char *> pos;                                    // the positional arguments, in order
   // raised by the options that were given: what the cross-option rules ask about
-  bool unitigs_opt_set = false, tip_opt_set = false, tip_rounds_set = false, bubble_opt_set = false, range_set = false, stats_below_set = false;
+  bool unitigs_opt_set = false, tip_opt_set = false, tip_rounds_set = false, bubble_opt_set = false, simplify_rounds_set = false, bulge_opt_set = false, range_set = false, stats_below_set = false;
   bool filter_opt_set = false, correct_opt_set = false, correct_min_count_set = false, normalize_opt_set = false, normalize_cutoff_set = false;
   bool pair_opt_set = false, pair_mode_set = false, min_qual_set = false;
 };

@@ -83,6 +83,10 @@ UNITIG_POS_DTYPE = np.dtype([("unitig", "<u4"), ("at", "<u4")])
 READ_HIT_DTYPE = np.dtype([("unitig", "<u4"), ("unitig_at", "<u4"), ("read_off", "<u4"), ("n_windows", "<u4")])
 CFRK_TIP_RATIO_Q8_MAX = 65536        # tip rule: the largest ratio_q8 (256 = the sibling's mean coverage at least the tip's)
 CFRK_BUBBLE_NONE = 0xFFFFFFFF        # bubble rule: the partner of a unitig that is not popped
+CFRK_BULGE_MAX_HOPS = 64             # bulge rule: the longest path, in unitigs
+CFRK_BULGE_MAX_VISITS = 65536        # the largest search budget, in links looked at
+# what one bulge call found (cfrk_bulge_stats)
+BULGE_STATS_DTYPE = np.dtype([("arms", "<i8"), ("popped", "<i8"), ("undecided", "<i8")])
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libcfrk_hip.so")
@@ -169,6 +173,8 @@ def load_library():
         "cfrk_global_unitig_tips_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, vp, C.POINTER(i64)], C.c_int),
         "cfrk_global_unitig_bubbles": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(i64)], C.c_int),
         "cfrk_global_unitig_bubbles_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(i64)], C.c_int),
+        "cfrk_global_unitig_bulges": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, u64, C.POINTER(i64), vp], C.c_int),
+        "cfrk_global_unitig_bulges_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, u64, C.POINTER(i64), vp], C.c_int),
         "cfrk_global_query_reads": ([vp, vp, vp, vp, i64, i64, vp], C.c_int),
         "cfrk_global_query_reads_device": ([vp, vp, i64, vp], C.c_int),
         "cfrk_global_read_stats": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
@@ -1179,8 +1185,59 @@ class GlobalCounter:
                        "cfrk_global_unitig_bubbles_device")
         return n.value
 
+    def unitig_bulges(self, rec, link_ptr, links, max_kmers, max_diff=0, max_hops=None, max_visits=1024, ratio_q8=0):
+        """the bulge rule over the unitigs' records and their links -> (pop np.uint8[nS], visits np.uint32[nS], path_ptr
+        np.int64[nS + 1], path np.uint32[n_path], stats): pop[j] = 1 where unitig j is an arm of the bubble rule and the
+        depth-first search from its source finds a chain of 1 .. max_hops distinct unitigs to its target, each with 256 *
+        mean(it) >= ratio_q8 * mean(j) and ranking above j, their k-mers summing to n_j within max_diff.  visits[j] = the
+        links the search looked at, max_visits + 1 for an arm it left undecided; row j of the CSR (path_ptr, path) holds
+        the first-found path as w << 1 | o; stats = {"arms", "popped", "undecided"}.  max_hops=None means min(max_kmers
+        + max_diff, 64).  The default of 1024 for max_visits is a choice with headroom over the 55 that small CPU cases
+        needed at k = 31, not a measured optimum.  Raises CfrkError (CFRK_ERR_LAYOUT, the message naming the unitig) when
+        the rows are not link rows.  A sizes-only call, then the call into an array of exactly that size."""
+        rec = np.ascontiguousarray(rec, UNITIG_DTYPE)
+        link_ptr = np.ascontiguousarray(link_ptr, np.int64)
+        links = np.ascontiguousarray(links, UNITIG_LINK_DTYPE)
+        if len(link_ptr) != len(rec) + 1:
+            raise ValueError("link_ptr has not one entry more than rec")
+        max_hops = min(int(max_kmers) + int(max_diff), CFRK_BULGE_MAX_HOPS) if max_hops is None else int(max_hops)
+        nS, n = len(rec), C.c_int64()
+        pop, visits, path_ptr = np.zeros(nS, np.uint8), np.zeros(nS, np.uint32), np.zeros(nS + 1, np.int64)
+        stats = np.zeros(1, BULGE_STATS_DTYPE)
+        args = (self.ctx._h, _ptr(rec), nS, _ptr(link_ptr), _ptr(links), len(links), int(max_kmers), int(max_diff), max_hops,
+                int(max_visits), int(ratio_q8), _ptr(pop), _ptr(visits), _ptr(path_ptr))
+        rc = self._L.cfrk_global_unitig_bulges(*args, None, 0, C.byref(n), _ptr(stats))
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.ctx.check(rc, "cfrk_global_unitig_bulges")
+        path = np.zeros(n.value, np.uint32)
+        if rc == CFRK_ERR_SMALL_BUF:
+            self.ctx.check(self._L.cfrk_global_unitig_bulges(*args, _ptr(path), path.size, C.byref(n), _ptr(stats)),
+                           "cfrk_global_unitig_bulges")
+        assert int(stats["popped"][0]) == int(pop.sum()) and n.value == int(path_ptr[nS])
+        return pop, visits, path_ptr, path, {f: int(stats[f][0]) for f in BULGE_STATS_DTYPE.names}
+
+    def unitig_bulges_device(self, d_rec, nS, d_link_ptr, d_links, n_links, max_kmers, max_diff, max_hops, max_visits, ratio_q8, d_pop,
+                             d_visits=0, d_path_ptr=0, d_path=0, cap_path=0):
+        """device form -> (n_path, stats); d_visits may be 0; d_path_ptr may be 0 (no paths wanted); d_path may be 0 with
+        cap_path 0 (sizes only).  Raises CfrkError (code CFRK_ERR_SMALL_BUF, with .n_path and .stats set, d_pop, d_visits
+        and d_path_ptr complete, nothing written to d_path) when cap_path is too small.  Synchronises once, returns with
+        the pass that writes d_path enqueued on the context stream."""
+        n, stats = C.c_int64(), np.zeros(1, BULGE_STATS_DTYPE)
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_global_unitig_bulges_device(self.ctx._h, vp(d_rec), nS, vp(d_link_ptr), vp(d_links), n_links, int(max_kmers),
+                                                      int(max_diff), int(max_hops), int(max_visits), int(ratio_q8), vp(d_pop),
+                                                      vp(d_visits), vp(d_path_ptr), vp(d_path), cap_path, C.byref(n), _ptr(stats))
+        st = {f: int(stats[f][0]) for f in BULGE_STATS_DTYPE.names}
+        try:
+            self.ctx.check(rc, "cfrk_global_unitig_bulges_device")
+        except CfrkError as e:
+            e.n_path, e.stats = n.value, st
+            raise
+        return n.value, st
+
     def simplify(self, min_count=1, tips=True, bubbles=True, rounds=4, tip_max_kmers=None, tip_ratio=2.0,
-                 bubble_max_kmers=None, bubble_max_diff=0, bubble_ratio=0.0):
+                 bubble_max_kmers=None, bubble_max_diff=0, bubble_ratio=0.0, bulges=False, bulge_max_kmers=None, bulge_max_diff=0,
+                 bulge_max_hops=None, bulge_max_visits=1024, bulge_ratio=0.0):
         """simplify the graph: up to `rounds` rounds of unitigs -> links -> each enabled rule on that same graph -> one
         mask_unitigs(tip | pop), stopping at the first round that finds neither a tip nor a bubble -> ((data, start,
         length, rec) of the simplified graph, [(unitigs, tips, bubbles, masked keys so far) per round], [(round, popped
@@ -1188,23 +1245,31 @@ class GlobalCounter:
         one) per popped unitig]).  tip_* as clip_tips(); bubble_max_kmers=None means k; bubble_ratio is the mean coverage
         the stronger arm must have relative to the popped one: the default 0 pops the weaker arm whatever the coverages
         are (a choice, not a measured optimum); 2.0 leaves a balanced heterozygous site alone.  The mask stays set, as
-        after clip_tips()."""
+        after clip_tips().
+        bulges=True runs the bulge rule on that same graph as well (unitig_bulges(); bulge_max_kmers=None means k,
+        bulge_max_hops=None means min(bulge_max_kmers + bulge_max_diff, 64), bulge_ratio as bubble_ratio; the default of
+        1024 for bulge_max_visits is a choice with headroom, not a measured optimum) and masks tip | pop | bulge in the
+        one call per round.  The per-round tuples are then (unitigs, tips, bubbles, bulges, masked keys so far), and a
+        fourth value is returned: [(round, popped unitig, path as a list of w << 1 | o, popped record, popped sequence,
+        the path's sequence spelled with k - 1 overlaps) per unitig the bulge rule popped]."""
         if rounds < 1:
             raise ValueError("rounds: at least 1")
         tip_q8, bub_q8 = int(round(float(tip_ratio) * 256)), int(round(float(bubble_ratio) * 256))
-        if not 0 <= tip_q8 <= CFRK_TIP_RATIO_Q8_MAX or not 0 <= bub_q8 <= CFRK_TIP_RATIO_Q8_MAX:
+        bulge_q8 = int(round(float(bulge_ratio) * 256))
+        if not 0 <= tip_q8 <= CFRK_TIP_RATIO_Q8_MAX or not 0 <= bub_q8 <= CFRK_TIP_RATIO_Q8_MAX or not 0 <= bulge_q8 <= CFRK_TIP_RATIO_Q8_MAX:
             raise ValueError("ratio: 0 .. 256")
         tip_max_kmers = self.k if tip_max_kmers is None else int(tip_max_kmers)
         bubble_max_kmers = self.k if bubble_max_kmers is None else int(bubble_max_kmers)
+        bulge_max_kmers = self.k if bulge_max_kmers is None else int(bulge_max_kmers)
         text = lambda data, at, n: "".join("ACGT"[c] for c in data[at:at + n])
         comp = str.maketrans("ACGT", "TGCA")
-        report, rows = [], []
+        report, rows, bulge_rows = [], [], []
         u = self.unitigs(min_count)
         for rnd in range(1, rounds + 1):
             data, start, length, rec = u
             link_ptr, links = self.unitig_links(data, start, length, min_count)
             drop = np.zeros(len(rec), np.uint8)
-            n_tips = n_pop = 0
+            n_tips = n_pop = n_bulge = 0
             if tips:
                 tip = self.unitig_tips(rec, link_ptr, links, tip_max_kmers, tip_q8)
                 n_tips = int(tip.sum())
@@ -1218,13 +1283,26 @@ class GlobalCounter:
                     kept = text(data, int(start[s]), int(length[s]))
                     rows.append((rnd, j, int(partner[j]), tuple(rec[j].tolist()), tuple(rec[s].tolist()),
                                  text(data, int(start[j]), int(length[j])), kept.translate(comp)[::-1] if p else kept))
-            if n_tips or n_pop:
+            if bulges:
+                bulge, _, path_ptr, path, _ = self.unitig_bulges(rec, link_ptr, links, bulge_max_kmers, bulge_max_diff, bulge_max_hops,
+                                                                 bulge_max_visits, bulge_q8)
+                n_bulge = int(bulge.sum())
+                drop |= bulge
+                for j in np.flatnonzero(bulge).tolist():
+                    p = path[path_ptr[j]:path_ptr[j + 1]].tolist()
+                    spelled = ""
+                    for w in p:
+                        s = text(data, int(start[w >> 1]), int(length[w >> 1]))
+                        s = s.translate(comp)[::-1] if w & 1 else s
+                        spelled += s[self.k - 1:] if spelled else s
+                    bulge_rows.append((rnd, j, p, tuple(rec[j].tolist()), text(data, int(start[j]), int(length[j])), spelled))
+            if n_tips or n_pop or n_bulge:
                 self.mask_unitigs(data, start, length, drop)
-            report.append((len(rec), n_tips, n_pop, self.mask_count()))
-            if not (n_tips or n_pop):
+            report.append((len(rec), n_tips, n_pop, n_bulge, self.mask_count()) if bulges else (len(rec), n_tips, n_pop, self.mask_count()))
+            if not (n_tips or n_pop or n_bulge):
                 break
             u = self.unitigs(min_count)
-        return u, report, rows
+        return (u, report, rows, bulge_rows) if bulges else (u, report, rows)
 
     def query_reads(self, data, start=None, length=None):
         """count of the k-mer starting at every base -> np.uint32[nN]: CFRK_QUERY_NONE where the window holds an

@@ -717,6 +717,78 @@ int cfrk_global_unitig_bubbles(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS
                                uint32_t ratio_q8, uint8_t *pop /* nS */, uint32_t *partner /* nS; may be NULL */,
                                int64_t *n_pop_out);
 
+/* Unitig bulges: an arm beside a CHAIN of better-supported unitigs between the same two oriented ends.  An error's arm
+ * is one unitig, but the true path beside it is cut by its neighbours' branch points, so the bubble rule, which compares
+ * single unitigs, rarely sees it.  Like the tip and the bubble rule a pure function of the unitigs' records (kc, n_kmers,
+ * CFRK_UNITIG_CIRCULAR), the link CSR as cfrk_global_unitig_links wrote it, and the job's strand rule; no sequence, no
+ * index.  Oriented unitigs, out(), in(), the mirror convention, n_j, kc_j and the 128-bit cross-multiplied means are
+ * those of "Unitig tips".
+ *   ARM: exactly the bubble rule's arm for x = (j,+): j is not CFRK_UNITIG_CIRCULAR, n_j <= max_kmers, |in(x)| = 1 and
+ *   |out(x)| = 1, and neither s = src(x) nor t = dst(x) is unitig j.
+ *   ELIGIBLE: oriented unitig (w,o) is eligible for j iff 256 kc_w n_j >= ratio_q8 kc_j n_w, and w ranks above j:
+ *   kc_w n_j > kc_j n_w, or they are equal and w < j.
+ *   PATH for x: oriented unitigs w_1 .. w_m, 1 <= m <= max_hops, such that the links s -> w_1, w_i -> w_i+1 and w_m -> t
+ *   exist; every w_i is eligible; no w_i is unitig j, unitig(s) or unitig(t) in either orientation; the w_i are pairwise
+ *   distinct as unitigs; n_j - max_diff <= sum of n_w_i <= n_j + max_diff.  A direct link s -> t (m = 0) is no path.
+ *   SEARCH: depth-first and pre-order from s, in one fixed order.  out(cur) is walked in row order: for (u,+) in a
+ *   canonical job the links of row u without CFRK_LINK_FROM_MINUS, for (u,-) those with it, in a job that is not
+ *   canonical row u.  Every link looked at adds 1 to `visits`.  For a link cur -> y: if y == t, the depth (the unitigs
+ *   on the path so far) is >= 1 and the running sum is >= n_j - max_diff, the path is found and the search ends;
+ *   otherwise, if y is eligible, not excluded, the depth is < max_hops and sum + n_y <= n_j + max_diff, the search
+ *   descends into y at once; otherwise it takes the next link.  A row that is done returns to the row above it.  When
+ *   `visits` would exceed max_visits the arm is UNDECIDED: not popped, and visits[j] = max_visits + 1.
+ *   pop[j] = 1 iff (j,+) is an arm and the search found a path, else 0.  visits[j] = the links looked at for an arm, 0
+ *   for a unitig that is no arm.  path_ptr is a CSR over unitigs: path_ptr[0] = 0, path_ptr[j + 1] - path_ptr[j] = m for
+ *   a popped j and 0 otherwise, *n_path_out = path_ptr[nS]; row j of path holds that first-found path as w << 1 | o, in
+ *   order from s to t.  stats: the arms, the popped and the undecided ones.
+ *   Only (j,+) is searched.  In a canonical job the mirrored search, from mirror(t) to mirror(s), decides the same
+ *   whenever neither runs out of budget.
+ *   Every interior unitig of a popped arm's path ranks strictly above the arm, and rank is a total order: by induction
+ *   from the top rank down, in the graph without the popped unitigs there is still a walk from s to t through unpopped
+ *   unitigs.  That holds for all arms popped from one graph at once, and for pop[] of this rule OR-ed with pop[] of the
+ *   bubble rule, since a bubble's partner ranks above it too.  A popped unitig has no dead end, and neither has any
+ *   interior unitig of a path: the result is disjoint from tip[], and all three may go into one mask call.  With equal
+ *   max_kmers, max_diff and ratio_q8 every unitig the bubble rule pops is popped here or undecided.  max_kmers = 0 or
+ *   max_hops = 0 pops nothing.
+ * Capacity (the select's protocol): when n_path > cap_path the call returns CFRK_ERR_SMALL_BUF with pop, visits,
+ *   path_ptr, stats and *n_path_out complete and nothing written to path; NULL path with cap_path 0 is that "sizes only"
+ *   call.  visits may be NULL.  path_ptr may be NULL: then no paths are wanted, no scan runs, path and cap_path are
+ *   ignored and *n_path_out (which may then be NULL as well) is 0.
+ * Untrusted input: the check of the tip rule runs in front, with the same five CFRK_ERR_LAYOUT reasons naming the first
+ *   offending unitig, and only checked rows are followed.  After the check one lane per arm looks at no more than
+ *   max_visits links of rows of at most 16, on a stack of at most max_hops levels.  No loop is unbounded, nothing
+ *   outside the arrays is accessed, every byte of pop, visits and path_ptr is written whatever is refused (all 0 after
+ *   an error, with stats and *n_path_out 0).  Rows that pass the check without being a real link set (canonical rows
+ *   that lack their mirrors, say) give CFRK_OK, path entries below 2 nS, and whatever the rule says of the rows as given.
+ * CFRK_ERR_STATE: no job.  CFRK_ERR_ARG: NULL stats, NULL rec / link_ptr / pop with nS > 0, NULL links with n_links > 0,
+ *   NULL n_path_out with path_ptr given, NULL path with cap_path > 0, negative sizes, nS >= 2^31 (a path names an
+ *   oriented unitig in 32 bits), max_hops > CFRK_BULGE_MAX_HOPS, max_visits > CFRK_BULGE_MAX_VISITS, ratio_q8 above
+ *   CFRK_TIP_RATIO_Q8_MAX.  nS = 0 is fine: nothing popped (path_ptr[0] = 0 in the host form).
+ * Device form (cfrk_amd/csrc/unitig_bulges.hip): stats and n_path_out are host memory; the call synchronises ONCE, for
+ *   the error word, the counts and n_path, and returns with the pass that writes path enqueued.  The search's stack is
+ *   in LDS, 20 KB for the 64 arms of a wave.  Temporary device memory, kept in the context's pool: 16 bytes per unitig
+ *   and the scan's scratch; not canonical: 12 more bytes per unitig and 4 per link.  Host form: stages through the pool;
+ *   synchronous. */
+#define CFRK_BULGE_MAX_HOPS 64
+#define CFRK_BULGE_MAX_VISITS 65536
+typedef struct cfrk_bulge_stats {   /* 24 bytes, no padding */
+  int64_t arms;        /* unitigs j whose (j,+) is an arm      */
+  int64_t popped;      /* arms beside which a path was found   */
+  int64_t undecided;   /* arms whose search ran out of budget  */
+} cfrk_bulge_stats;
+int cfrk_global_unitig_bulges_device(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr /* nS + 1 */,
+                                     const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t max_diff,
+                                     uint32_t max_hops, uint32_t max_visits, uint32_t ratio_q8,
+                                     uint8_t *d_pop /* nS bytes, every one written 0 or 1 */,
+                                     uint32_t *d_visits /* nS words, every one written; may be NULL */,
+                                     int64_t *d_path_ptr /* nS + 1; may be NULL */, uint32_t *d_path, uint64_t cap_path,
+                                     int64_t *n_path_out, cfrk_bulge_stats *stats);
+int cfrk_global_unitig_bulges(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS, const int64_t *link_ptr /* nS + 1 */,
+                              const cfrk_unitig_link *links, int64_t n_links, uint32_t max_kmers, uint32_t max_diff,
+                              uint32_t max_hops, uint32_t max_visits, uint32_t ratio_q8, uint8_t *pop /* nS */,
+                              uint32_t *visits /* nS; may be NULL */, int64_t *path_ptr /* nS + 1; may be NULL */,
+                              uint32_t *path, uint64_t cap_path, int64_t *n_path_out, cfrk_bulge_stats *stats);
+
 /* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
 
 /* How many DISTINCT k-mers will a job hold?  One streaming pass over the reads answers it to about 1 % before anything

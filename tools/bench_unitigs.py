@@ -36,7 +36,13 @@ median lies inside the parent's own spread; a line "bubbles" with the bubbles ca
 max_kmers = k) and the tips call alternating, and what both found; and a line "rounds" with nodes, unitigs, tips,
 bubbles and masked keys per round of the combined loop, one mask call per round.
 
-  python tools/bench_unitigs.py [--links | --tips [--parent-lib SO] | --bubbles [--parent-lib SO]] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
+With --bulges (cases b and c) the tool "bench_bulges" writes, per case: a line "bulges" with the bulges call
+(--bulge-max-diff, --bulge-max-visits, --bulge-ratio, max_kmers = k, max_hops = min(k + max_diff, 64); paths wanted,
+sizes-only call and fill pass included) alternating with the bubbles call in the same repetitions, arms, popped and
+undecided, ns per arm, and the distributions of visits (over arms) and hops (over popped arms); and a line "rounds" with
+nodes, unitigs, tips, bubbles, bulges and masked keys per round of the combined loop, one mask call per round.
+
+  python tools/bench_unitigs.py [--links | --tips [--parent-lib SO] | --bubbles [--parent-lib SO] | --bulges] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
 """
 import argparse
 import json
@@ -227,6 +233,88 @@ def bubbles_case(a, torch, cfrk_amd, ctx, g, parent, other, min_count, common, t
                           max_kmers=k, rounds=rounds)), flush=True)
 
 
+def bulges_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf):
+    k = a.k
+    tip_q8, bub_q8, bulge_q8 = int(round(a.tip_ratio * 256)), int(round(a.bubble_ratio * 256)), int(round(a.bulge_ratio * 256))
+    max_hops = min(k + a.bulge_max_diff, cfrk_amd.CFRK_BULGE_MAX_HOPS)
+    new = _Graph(cfrk_amd, g, min_count, buf)
+    ctx.sync()
+
+    def graph_args(gr):
+        return (gr.out[3].data_ptr(), gr.nS, gr.ptr.data_ptr(), gr.rows.data_ptr(), gr.n_links)
+
+    def outputs(nS):
+        return buf(nS), buf(nS), buf(nS), buf(nS * 4), buf((nS + 1) * 8)     # tip, bubble pop, bulge pop, visits, path_ptr
+
+    def bulges(gr, d_pop, d_visits, d_ptr, d_path=None, cap=0):
+        """-> (n_path, stats): the call with room for `cap` path entries; too little room reads as the sizes-only call"""
+        try:
+            return g.unitig_bulges_device(*graph_args(gr), k, a.bulge_max_diff, max_hops, a.bulge_max_visits, bulge_q8, d_pop.data_ptr(),
+                                          d_visits.data_ptr() if d_visits is not None else 0, d_ptr.data_ptr(),
+                                          d_path.data_ptr() if d_path is not None else 0, cap)
+        except cfrk_amd.CfrkError as e:
+            if e.code != cfrk_amd.CFRK_ERR_SMALL_BUF:
+                raise
+            return e.n_path, e.stats
+
+    d_tip, d_bub, d_pop, d_visits, d_ptr = outputs(new.nS)
+    n_path, st = bulges(new, d_pop, d_visits, d_ptr)
+    d_path = buf(max(n_path, 1) * 4)
+    calls = {"bulges": lambda: bulges(new, d_pop, d_visits, d_ptr, d_path, n_path),
+             "bulges_sizes_only": lambda: bulges(new, d_pop, d_visits, d_ptr),
+             "bubbles": lambda: g.unitig_bubbles_device(*graph_args(new), k, a.bubble_max_diff, bub_q8, d_bub.data_ptr(), 0)}
+    n_bub = calls["bubbles"]()
+    t = {name: [] for name in calls}
+    for rep in range(a.reps + 1):
+        for name, fn in calls.items():
+            ms = timed(fn)
+            if rep:                                             # (the first round warms up: code objects, pool buffers)
+                t[name].append(ms)
+    ctx.sync()
+    visits = d_visits[:new.nS * 4].view(torch.int32)
+    hops = torch.diff(d_ptr[:(new.nS + 1) * 8].view(torch.int64))
+    arms_visits = visits[visits > 0]
+    def quant(x):                                               # median, 90th and 99th percentile, maximum
+        if not x.numel():
+            return []
+        x = x.sort().values
+        return [int(x[min(x.numel() - 1, int(q * x.numel()))]) for q in (0.5, 0.9, 0.99)] + [int(x[-1])]
+
+    row = dict(common, line="bulges", nodes=new.nodes(torch), unitigs=new.nS, links=new.n_links, bubbles_found=n_bub, n_path=n_path, max_kmers=k,
+               max_hops=max_hops, bulge_max_diff=a.bulge_max_diff, bulge_max_visits=a.bulge_max_visits, bulge_ratio=a.bulge_ratio,
+               popped_also_by_bubbles=int((d_pop[:new.nS] & d_bub[:new.nS]).sum()), **st)
+    row.update({name: stats(ts) for name, ts in t.items()})
+    row["ns_per_arm"] = row["bulges"]["ms"] * 1e6 / max(st["arms"], 1)
+    row["visits_p50_p90_p99_max"] = quant(arms_visits)
+    row["visits_sum"] = int(arms_visits.sum())
+    row["hops_p50_p90_p99_max"] = quant(hops[hops > 0])
+    row["hops_histogram"] = torch.bincount(hops[hops > 0], minlength=1).tolist()
+    print(json.dumps(row), flush=True)
+    # the rounds of the combined loop
+    rounds, cur = [], new
+    for r in range(a.tip_rounds):
+        if r:
+            cur = _Graph(cfrk_amd, g, min_count, buf)
+            d_tip, d_bub, d_pop, d_visits, d_ptr = outputs(cur.nS)
+        n_tips = g.unitig_tips_device(*graph_args(cur), k, tip_q8, d_tip.data_ptr())
+        n_bub = g.unitig_bubbles_device(*graph_args(cur), k, a.bubble_max_diff, bub_q8, d_bub.data_ptr(), 0)
+        st = g.unitig_bulges_device(*graph_args(cur), k, a.bulge_max_diff, max_hops, a.bulge_max_visits, bulge_q8, d_pop.data_ptr())[1]
+        if n_tips or n_bub or st["popped"]:
+            d_tip[:cur.nS] |= d_bub[:cur.nS] | d_pop[:cur.nS]
+            g.mask_unitigs_device(*cur.args, d_tip.data_ptr())
+        rounds.append({"round": r + 1, "nodes": cur.nodes(torch), "unitigs": cur.nS, "tips": n_tips, "bubbles": n_bub, "bulges": st["popped"],
+                       "arms": st["arms"], "undecided": st["undecided"], "masked_keys": g.mask_count()})
+        if not (n_tips or n_bub or st["popped"]):
+            break
+    if rounds[-1]["tips"] or rounds[-1]["bubbles"] or rounds[-1]["bulges"]:
+        last = _Graph(cfrk_amd, g, min_count, buf)
+        rounds.append({"round": len(rounds) + 1, "nodes": last.nodes(torch), "unitigs": last.nS, "tips": None, "bubbles": None, "bulges": None,
+                       "masked_keys": g.mask_count()})
+    print(json.dumps(dict(common, line="rounds", tip_ratio=a.tip_ratio, bubble_ratio=a.bubble_ratio, bubble_max_diff=a.bubble_max_diff,
+                          bulge_ratio=a.bulge_ratio, bulge_max_diff=a.bulge_max_diff, bulge_max_visits=a.bulge_max_visits, max_kmers=k,
+                          rounds=rounds)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="a,b,c")
@@ -245,6 +333,10 @@ def main():
     ap.add_argument("--bubbles", action="store_true")
     ap.add_argument("--bubble-ratio", type=float, default=0.0)
     ap.add_argument("--bubble-max-diff", type=int, default=0)
+    ap.add_argument("--bulges", action="store_true")
+    ap.add_argument("--bulge-ratio", type=float, default=0.0)
+    ap.add_argument("--bulge-max-diff", type=int, default=0)
+    ap.add_argument("--bulge-max-visits", type=int, default=1024)
     ap.add_argument("--parent-lib", help="libcfrk_hip.so of the parent commit: with --tips the unmasked calls, with --bubbles the tips call alternate with it")
     a = ap.parse_args()
 
@@ -312,6 +404,13 @@ def main():
         def full():
             g.unitigs_device(min_count, out[0].data_ptr(), oN, out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), oS)
 
+        if a.bulges:
+            common = {"tool": "bench_bulges", "case": case, "reads": R, "L": L, "glen": a.glen, "k": k, "reps": a.reps,
+                      "error_rate": 0.0 if case == "a" else a.error_rate, "min_count": min_count, "distinct_keys": distinct}
+            bulges_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf)
+            del g, out, reads
+            torch.cuda.empty_cache()
+            continue
         if a.tips or a.bubbles:
             other = None
             if parent is not None:                              # the same reads counted by the parent's library as well
