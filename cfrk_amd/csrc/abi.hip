@@ -1338,6 +1338,82 @@ int cfrk_global_unitig_bulges(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS,
   return cfrk_memcpy_d2h(ctx, path, d_path, (size_t)n_path * 4);
 }
 
+static int unitigs_compact_check(cfrk_ctx *ctx, const cfrk_unitigs_in &in, const void *data_out, uint64_t cap_data,
+                                 const void *start_out, const void *length_out, const void *rec_out, uint64_t cap_unitigs,
+                                 int64_t *nN_out, int64_t *nS_out) {
+  if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "unitig compaction before begin: the job supplies k and the strand rule");
+  if (!nN_out || !nS_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL size output");
+  if (in.nN < 0 || in.nS < 0 || in.n_links < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (in.nS > 0 && (!in.data || !in.start || !in.length || !in.rec || !in.link_ptr)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (in.n_links > 0 && !in.links) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL links with n_links above 0");
+  if ((cap_data > 0 && !data_out) || (cap_unitigs > 0 && (!start_out || !length_out || !rec_out)))
+    return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL array with a capacity above 0");
+  if ((uint64_t)in.nS >= (1ull << 31)) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld unitigs: an oriented unitig is named in 32 bits", (long long)in.nS);
+  *nN_out = *nS_out = 0;
+  return CFRK_OK;
+}
+
+int cfrk_global_unitigs_compact_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                       const cfrk_unitig *d_rec, int64_t nN, int64_t nS, const int64_t *d_link_ptr,
+                                       const cfrk_unitig_link *d_links, int64_t n_links, const uint8_t *d_drop, int8_t *d_data_out,
+                                       uint64_t cap_data, int64_t *d_start_out, int32_t *d_length_out, cfrk_unitig *d_rec_out,
+                                       uint64_t cap_unitigs, cfrk_unitig_pos *d_into, int64_t *nN_out, int64_t *nS_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  const cfrk_unitigs_in in = {d_data, d_start, d_length, d_rec, nN, nS, d_link_ptr, d_links, n_links, d_drop};
+  int rc = unitigs_compact_check(ctx, in, d_data_out, cap_data, d_start_out, d_length_out, d_rec_out, cap_unitigs, nN_out, nS_out);
+  if (rc || nS == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int64_t nN_new = 0, nS_new = 0;
+  if ((rc = cfrk_unitigs_compact_measure(ctx, in, &nN_new, &nS_new))) return rc;
+  const ReadsOut o = {d_data_out, d_start_out, d_length_out, nullptr, cap_data, cap_unitigs, -1, false};
+  if ((rc = reads_out_fit(ctx, "unitig compaction", o, nN_new, nS_new, nN_out, nS_out))) return rc;
+  if (nS_new == 0) {                                   // everything dropped
+    if (d_into) HIP_TRY(ctx, hipMemsetAsync(d_into, 0xFF, (size_t)nS * sizeof *d_into, ctx->stream));
+    return CFRK_OK;
+  }
+  return cfrk_unitigs_compact_emit(ctx, in, d_data_out, d_start_out, d_length_out, d_rec_out, d_into, nN_new, nS_new);
+}
+
+int cfrk_global_unitigs_compact(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
+                                const cfrk_unitig *rec, int64_t nN, int64_t nS, const int64_t *link_ptr,
+                                const cfrk_unitig_link *links, int64_t n_links, const uint8_t *drop, int8_t *data_out,
+                                uint64_t cap_data, int64_t *start_out, int32_t *length_out, cfrk_unitig *rec_out,
+                                uint64_t cap_unitigs, cfrk_unitig_pos *into, int64_t *nN_out, int64_t *nS_out) {
+  if (!ctx) return CFRK_ERR_ARG;
+  const cfrk_unitigs_in host = {data, start, length, rec, nN, nS, link_ptr, links, n_links, drop};
+  int rc = unitigs_compact_check(ctx, host, data_out, cap_data, start_out, length_out, rec_out, cap_unitigs, nN_out, nS_out);
+  if (rc || nS == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // [data | start | length | records | link_ptr | links | drop] in a slot of their own
+  StagePart x[4] = {{rec, (size_t)nS * sizeof *rec, nullptr}, {link_ptr, ((size_t)nS + 1) * 8, nullptr},
+                    {links, (size_t)n_links * sizeof *links, nullptr}, {drop, drop ? (size_t)nS : 0, nullptr}};
+  StagedReads d;
+  if ((rc = stage_reads(ctx, BUF_UNITIG_COMPACT_IN, data, start, length, nN, nS, STAGE_TABLE, x, 4, &d))) return rc;
+  const cfrk_unitigs_in in = {d.data, d.start, d.length, (const cfrk_unitig *)x[0].dev, nN, nS, (const int64_t *)x[1].dev,
+                              (const cfrk_unitig_link *)x[2].dev, n_links, (const uint8_t *)x[3].dev};
+  int64_t nN_new = 0, nS_new = 0;
+  if ((rc = cfrk_unitigs_compact_measure(ctx, in, &nN_new, &nS_new))) return stage_drain(ctx, rc);
+  const ReadsOut fit = {nullptr, nullptr, nullptr, nullptr, cap_data, cap_unitigs, BUF_UNITIG_COMPACT_OUT, false};
+  if ((rc = reads_out_fit(ctx, "unitig compaction", fit, nN_new, nS_new, nN_out, nS_out))) return rc;
+  if (nS_new == 0) {
+    if (into) memset(into, 0xFF, (size_t)nS * sizeof *into);
+    return CFRK_OK;
+  }
+  // [data | start | length | records | into] in another, then down to the caller's arrays
+  const size_t xb[2] = {(size_t)nS_new * sizeof(cfrk_unitig), into ? (size_t)nS * sizeof *into : 0};
+  const SlotCarve c((size_t)nN_new + 16, (uint64_t)nS_new, true, xb, 2);
+  void *p;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_COMPACT_OUT, c.total, &p))) return rc;
+  ReadsOut o = fit;
+  o.data = (int8_t *)p; o.start = carve_at<int64_t>(p, c.o_start); o.length = carve_at<int32_t>(p, c.o_length);
+  cfrk_unitig *d_rec = carve_at<cfrk_unitig>(p, c.o_extra[0]);
+  cfrk_unitig_pos *d_into = into ? carve_at<cfrk_unitig_pos>(p, c.o_extra[1]) : nullptr;
+  if ((rc = cfrk_unitigs_compact_emit(ctx, in, o.data, o.start, o.length, d_rec, d_into, nN_new, nS_new))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(rec_out, d_rec, xb[0], hipMemcpyDeviceToHost, ctx->stream));
+  if (into) HIP_TRY(ctx, hipMemcpyAsync(into, d_into, xb[1], hipMemcpyDeviceToHost, ctx->stream));
+  return download_reads(ctx, o, data_out, start_out, length_out, nullptr, nN_new, nS_new);
+}
+
 /* ------------------------------------------------------------------ digital normalisation */
 
 static int normalize_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, int64_t batch_reads, const void *data, const void *start,

@@ -65,6 +65,9 @@ enum {  // pool slots
   BUF_UNITIG_BULGES,                          // bulge rule (unitig_bulges.hip): error / size words, the arm list, the popped list, the in-rows, the scans' scratch
   BUF_UNITIG_BULGES_IN, BUF_UNITIG_BULGES_OUT,  // staging of cfrk_global_unitig_bulges alone (records, link_ptr, links in; pop, visits, path_ptr out)
   BUF_UNITIG_BULGES_PATH,                     // ... and its paths, sized once n_path is known
+  BUF_UNITIG_COMPACT,                         // unitig compaction (unitig_compact.hip): error / size words, links between elements, the rank states, the cycles' minima, the components, the in-rows, the scans' scratch
+  BUF_UNITIG_COMPACT_AUX,                     // the sort's payload, lengths and member counts with their scans, the members' list
+  BUF_UNITIG_COMPACT_IN, BUF_UNITIG_COMPACT_OUT,  // staging of cfrk_global_unitigs_compact alone (the unitigs, records, link_ptr, links, drop in; the unitigs, records, into out)
   BUF_NSLOTS
 };
 
@@ -250,6 +253,16 @@ int cfrk_unitig_bulges_search(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t n
 int cfrk_unitig_bulges_fill(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
                             const cfrk_unitig_link *d_links, int64_t n_links, const cfrk_bulge_params &p, int64_t n_popped,
                             const int64_t *d_path_ptr, uint32_t *d_path);
+// unitig_compact.hip: the compaction of 1 <= nS < 2^31 unitigs, their link rows and drop bytes (NULL: none) in two steps:
+// the checks, the merges, their ranking and the components (synchronises once: CFRK_ERR_LAYOUT, or the sizes); then the
+// order, the members' list, d_into (unless NULL) and the emit into arrays with room for nS_out >= 1 unitigs, left enqueued
+struct cfrk_unitigs_in {
+  const int8_t *data; const int64_t *start; const int32_t *length; const cfrk_unitig *rec; int64_t nN, nS;
+  const int64_t *link_ptr; const cfrk_unitig_link *links; int64_t n_links; const uint8_t *drop;
+};
+int cfrk_unitigs_compact_measure(cfrk_ctx *ctx, const cfrk_unitigs_in &in, int64_t *nN_out, int64_t *nS_out);
+int cfrk_unitigs_compact_emit(cfrk_ctx *ctx, const cfrk_unitigs_in &in, int8_t *d_data, int64_t *d_start, int32_t *d_length,
+                              cfrk_unitig *d_rec, cfrk_unitig_pos *d_into, int64_t nN_out, int64_t nS_out);
 // sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
 // enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
 int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,

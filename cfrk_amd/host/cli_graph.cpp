@@ -18,11 +18,23 @@ struct UnitigGraph {
     int rc = sized_call([&] { return cfrk_global_unitigs(ctx, min_count, data.data(), data.size(), start.data(), length.data(), rec.data(), rec.size(), &nN, &nS); },
                         [&] { data.resize((size_t)nN); start.resize((size_t)nS); length.resize((size_t)nS); rec.resize((size_t)nS); });
     if (rc) return die(ctx, rc, "cfrk_global_unitigs");
-    if (!with_links) return 0;
+    return with_links ? fetch_links(ctx, min_count) : 0;
+  }
+  int fetch_links(cfrk_ctx *ctx, uint32_t min_count) {
+    int rc;
     link_ptr.resize((size_t)nS + 1);
     rc = sized_call([&] { return cfrk_global_unitig_links(ctx, min_count, data.data(), start.data(), length.data(), nN, nS, link_ptr.data(), links.data(), links.size(), &n_links); },
                     [&] { links.resize((size_t)n_links); });
     return rc ? die(ctx, rc, "cfrk_global_unitig_links") : 0;
+  }
+  // --simplify-recompact: the unitigs of this graph without the dropped ones, from the graph itself (this one needs its links)
+  int compact_into(cfrk_ctx *ctx, const uint8_t *drop, UnitigGraph *out) const {
+    UnitigGraph &n = *out;
+    const int rc = sized_call([&] { return cfrk_global_unitigs_compact(ctx, data.data(), start.data(), length.data(), rec.data(), nN, nS, link_ptr.data(),
+                                                                        links.data(), n_links, drop, n.data.data(), n.data.size(), n.start.data(),
+                                                                        n.length.data(), n.rec.data(), n.rec.size(), nullptr, &n.nN, &n.nS); },
+                              [&] { n.data.resize((size_t)n.nN); n.start.resize((size_t)n.nS); n.length.resize((size_t)n.nS); n.rec.resize((size_t)n.nS); });
+    return rc ? die(ctx, rc, "cfrk_global_unitigs_compact") : 0;
   }
 };
 
@@ -36,11 +48,18 @@ struct UnitigGraph {
 int simplify_unitigs(const Options &o, cfrk_ctx *ctx) {
   std::string report, bubbles, bulges;
   const uint32_t rounds = (o.pop_bubbles || o.pop_bulges) ? o.simplify_rounds : o.tip_rounds;
+  UnitigGraph next;                                       // --simplify-recompact: the next round's unitigs, when the last one made them
+  bool have_next = false;
   for (uint32_t round = 1; round <= rounds; ++round) {
     int64_t n_tips = 0, n_pop = 0, n_bulges = 0;
     UnitigGraph g;
     int rc;
-    if ((rc = g.fetch(ctx, o.unitigs_min_count, true))) return rc;
+    if (have_next) {
+      g = std::move(next);
+      next = UnitigGraph();
+      have_next = false;
+      if ((rc = g.fetch_links(ctx, o.unitigs_min_count))) return rc;
+    } else if ((rc = g.fetch(ctx, o.unitigs_min_count, true))) return rc;
     const int64_t nS = g.nS;
     std::vector<uint8_t> tip((size_t)nS);
     if (o.clip_tips &&
@@ -94,6 +113,10 @@ int simplify_unitigs(const Options &o, cfrk_ctx *ctx) {
       snprintf(line, sizeof line, "%u\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (unsigned long long)masked);
     report += line;
     if (!n_tips && !n_pop && !n_bulges) break;
+    if (o.simplify_recompact && round < rounds) {
+      if ((rc = g.compact_into(ctx, tip.data(), &next))) return rc;
+      have_next = true;
+    }
   }
   if (o.bulge_report) { if (const int rc = write_file(o.bulge_report, bulges)) return rc; }
   if (o.bubble_report) { if (const int rc = write_file(o.bubble_report, bubbles)) return rc; }

@@ -111,7 +111,7 @@ const Row TABLE[] = {
   str("--bubble-report", &O::bubble_report, &O::bubble_opt_set), ratio("--bubble-ratio", &O::bubble_ratio_q8, &O::bubble_opt_set),
   count("--bubble-max-kmers", 1, &O::bubble_max_kmers, &O::bubble_opt_set), count("--bubble-max-diff", 0, &O::bubble_max_diff, &O::bubble_opt_set),
   count("--simplify-rounds", 1, &O::simplify_rounds, &O::simplify_rounds_set),
-  flag("--unitigs-pop-bulges", &O::pop_bulges),
+  flag("--unitigs-pop-bulges", &O::pop_bulges), flag("--simplify-recompact", &O::simplify_recompact),
   str("--bulge-report", &O::bulge_report, &O::bulge_opt_set), ratio("--bulge-ratio", &O::bulge_ratio_q8, &O::bulge_opt_set),
   count("--bulge-max-kmers", 1, &O::bulge_max_kmers, &O::bulge_opt_set), count("--bulge-max-diff", 0, &O::bulge_max_diff, &O::bulge_opt_set),
   count("--bulge-max-hops", 1, &O::bulge_max_hops, &O::bulge_opt_set), count("--bulge-max-visits", 0, &O::bulge_max_visits, &O::bulge_opt_set),
@@ -213,6 +213,8 @@ int check_options(const Options &o) {
   if (o.pop_bulges && !graph_out) return refuse("--unitigs-pop-bulges needs --unitigs-out UFILE, --unitigs-gfa GFILE or --unitigs-map QFILE");
   if (o.bulge_opt_set && !o.pop_bulges)
     return refuse("--bulge-max-kmers, --bulge-max-diff, --bulge-max-hops, --bulge-max-visits, --bulge-ratio and --bulge-report need --unitigs-pop-bulges");
+  if (o.simplify_recompact && !o.clip_tips && !o.pop_bubbles && !o.pop_bulges)
+    return refuse("--simplify-recompact needs --unitigs-clip-tips, --unitigs-pop-bubbles or --unitigs-pop-bulges");
   if (o.bulge_max_hops > CFRK_BULGE_MAX_HOPS) return refuse("--bulge-max-hops needs a count from 1 to " TEXT_OF(CFRK_BULGE_MAX_HOPS));
   if (o.bulge_max_visits > CFRK_BULGE_MAX_VISITS) return refuse("--bulge-max-visits needs a count from 0 to " TEXT_OF(CFRK_BULGE_MAX_VISITS));
   if ((o.bubble_opt_set && !o.pop_bubbles) || (o.simplify_rounds_set && !o.pop_bubbles && !o.pop_bulges)) return refuse("--bubble-max-kmers, --bubble-max-diff, --bubble-ratio, --bubble-report and --simplify-rounds need --unitigs-pop-bubbles");

@@ -89,6 +89,10 @@
 //                    "round<TAB>unitigs<TAB>tips<TAB>bubbles<TAB>bulges<TAB>masked k-mers so far".  FILE: one line per
 //                    popped unitig (cfrk_host_format_bulges: round, S name, LN, km, hops, the path's k-mers, the path
 //                    as >3<7>9, snp / mnp / indel, both sequences)  (cfrk_global_unitig_bulges)
+//   --simplify-recompact  (with --unitigs-clip-tips, --unitigs-pop-bubbles or --unitigs-pop-bulges) between two rounds of
+//                    the loop, take the next round's unitigs from the last round's graph and what it dropped
+//                    (cfrk_global_unitigs_compact) and not from the k-mer passes of cfrk_global_unitigs.  Every file
+//                    written is byte for byte the same either way.
 //   --min-count N / --max-count N  (global) write only the entries with N_min <= count <= N_max (text and --binary; the
 //                    binary header's n and sum describe the records written)
 //   --query QFILE --query-out OFILE  (global) how often does each k-mer of the reads of QFILE (FASTA, clean parse) occur
@@ -237,6 +241,7 @@ struct Options {
   uint32_t simplify_rounds = 4;       // --simplify-rounds N
   const char *bubble_report = nullptr;  // --bubble-report BFILE
   bool pop_bulges = false;            // --unitigs-pop-bulges
+  bool simplify_recompact = false;    // --simplify-recompact
   uint32_t bulge_max_kmers = 0;       // --bulge-max-kmers M (0: k)
   uint32_t bulge_max_diff = 0;        // --bulge-max-diff D
   uint32_t bulge_max_hops = 0;        // --bulge-max-hops H (0: min(M + D, 64))

@@ -87,6 +87,7 @@ CFRK_BULGE_MAX_HOPS = 64             # bulge rule: the longest path, in unitigs
 CFRK_BULGE_MAX_VISITS = 65536        # the largest search budget, in links looked at
 # what one bulge call found (cfrk_bulge_stats)
 BULGE_STATS_DTYPE = np.dtype([("arms", "<i8"), ("popped", "<i8"), ("undecided", "<i8")])
+CFRK_COMPACT_TILE_BYTES = 4096       # unitig compaction: bytes of data_out per workgroup of the emit
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libcfrk_hip.so")
@@ -175,6 +176,8 @@ def load_library():
         "cfrk_global_unitig_bubbles_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(i64)], C.c_int),
         "cfrk_global_unitig_bulges": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, u64, C.POINTER(i64), vp], C.c_int),
         "cfrk_global_unitig_bulges_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, u64, C.POINTER(i64), vp], C.c_int),
+        "cfrk_global_unitigs_compact": ([vp, vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, u64, vp, vp, vp, u64, vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "cfrk_global_unitigs_compact_device": ([vp, vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, u64, vp, vp, vp, u64, vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_global_query_reads": ([vp, vp, vp, vp, i64, i64, vp], C.c_int),
         "cfrk_global_query_reads_device": ([vp, vp, i64, vp], C.c_int),
         "cfrk_global_read_stats": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
@@ -1129,12 +1132,13 @@ class GlobalCounter:
                        "cfrk_global_unitig_tips_device")
         return n.value
 
-    def clip_tips(self, min_count=1, max_kmers=None, ratio=2.0, rounds=4):
+    def clip_tips(self, min_count=1, max_kmers=None, ratio=2.0, rounds=4, recompact=False):
         """clip tips off the graph: up to `rounds` rounds of unitigs -> links -> tips -> mask_unitigs(tips), stopping at the
         first round without a tip -> ((data, start, length, rec) of the clipped graph, [(unitigs, tips, masked keys so
         far) per round]).  max_kmers=None means k; ratio is the mean coverage a sibling must have relative to the tip
         (Minia's convention; 0: topology alone).  The mask stays set: links, the position map and further rounds see
-        the clipped graph; mask_clear() brings the full one back."""
+        the clipped graph; mask_clear() brings the full one back.  recompact=True takes the next round's unitigs from
+        compact_unitigs() on this round's graph and tips in place of the unitigs() call; the result is the same."""
         if rounds < 1:
             raise ValueError("rounds: at least 1")
         ratio_q8 = int(round(float(ratio) * 256))
@@ -1153,7 +1157,7 @@ class GlobalCounter:
             report.append((len(rec), n_tips, self.mask_count()))
             if not n_tips:
                 break
-            u = self.unitigs(min_count)
+            u = self.compact_unitigs(data, start, length, rec, link_ptr, links, tip)[:4] if recompact else self.unitigs(min_count)
         return u, report
 
     def unitig_bubbles(self, rec, link_ptr, links, max_kmers, max_diff=0, ratio_q8=0):
@@ -1235,9 +1239,59 @@ class GlobalCounter:
             raise
         return n.value, st
 
+    def compact_unitigs(self, data, start, length, rec, link_ptr, links, drop=None):
+        """the unitigs of the graph without the unitigs j with drop[j] != 0, from the list, its records and its links as
+        unitigs() and unitig_links() returned them -> (data, start, length, rec, into): byte for byte what unitigs()
+        returns after mask_unitigs(drop), without the k-mer passes; into UNITIG_POS_DTYPE[nS] says where input unitig j
+        went: the new index and at = off << 1 | minus (mod n_kmers in a circular unitig), both words CFRK_POS_NONE for a
+        dropped one.  drop=None drops nothing.  The job only supplies k and the strand rule.  Raises CfrkError
+        (CFRK_ERR_LAYOUT, the message naming the unitig) when the arrays are not a unitig list with its links.  A
+        sizes-only call, then the call into arrays of exactly that size."""
+        data = np.ascontiguousarray(data, np.int8)
+        start = np.ascontiguousarray(start, np.int64)
+        length = np.ascontiguousarray(length, np.int32)
+        rec = np.ascontiguousarray(rec, UNITIG_DTYPE)
+        link_ptr = np.ascontiguousarray(link_ptr, np.int64)
+        links = np.ascontiguousarray(links, UNITIG_LINK_DTYPE)
+        drop = None if drop is None else np.ascontiguousarray(drop, np.uint8)
+        nS = len(rec)
+        if len(start) != nS or len(length) != nS or len(link_ptr) != nS + 1 or (drop is not None and len(drop) != nS):
+            raise ValueError("start, length, rec and drop have one entry per unitig, link_ptr one more")
+        into = np.full(nS, CFRK_POS_NONE, UNITIG_POS_DTYPE)      # (both words)
+        head = (self.ctx._h, _ptr(data), _ptr(start), _ptr(length), _ptr(rec), len(data), nS, _ptr(link_ptr), _ptr(links), len(links), _ptr(drop))
+        nN, n = C.c_int64(), C.c_int64()
+        rc = self._L.cfrk_global_unitigs_compact(*head, None, 0, None, None, None, 0, None, C.byref(nN), C.byref(n))
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.ctx.check(rc, "cfrk_global_unitigs_compact")
+        out, ostart = np.empty(nN.value, np.int8), np.empty(n.value, np.int64)
+        olength, orec = np.empty(n.value, np.int32), np.zeros(n.value, UNITIG_DTYPE)
+        if rc == CFRK_ERR_SMALL_BUF:
+            self.ctx.check(self._L.cfrk_global_unitigs_compact(*head, _ptr(out), out.size, _ptr(ostart), _ptr(olength), _ptr(orec), orec.size,
+                                                               _ptr(into), C.byref(nN), C.byref(n)), "cfrk_global_unitigs_compact")
+        return out, ostart, olength, orec, into
+
+    def compact_unitigs_device(self, d_data, d_start, d_length, d_rec, nN, nS, d_link_ptr, d_links, n_links, d_drop, d_data_out, cap_data,
+                               d_start_out, d_length_out, d_rec_out, cap_unitigs, d_into=0):
+        """device form -> (nN, nS) of the result; d_drop may be 0 (nothing dropped), d_into may be 0, the output arrays may be
+        0 with zero capacities (sizes only).  Raises CfrkError (code CFRK_ERR_SMALL_BUF, with .nN and .nS set, nothing
+        written) when they are too small.  Synchronises once, returns with the order and the emit enqueued on the context
+        stream."""
+        nN_out, nS_out = C.c_int64(), C.c_int64()
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_global_unitigs_compact_device(self.ctx._h, vp(d_data), vp(d_start), vp(d_length), vp(d_rec), nN, nS, vp(d_link_ptr),
+                                                        vp(d_links), n_links, vp(d_drop), vp(d_data_out), cap_data, vp(d_start_out),
+                                                        vp(d_length_out), vp(d_rec_out), cap_unitigs, vp(d_into), C.byref(nN_out),
+                                                        C.byref(nS_out))
+        try:
+            self.ctx.check(rc, "cfrk_global_unitigs_compact_device")
+        except CfrkError as e:
+            e.nN, e.nS = nN_out.value, nS_out.value
+            raise
+        return nN_out.value, nS_out.value
+
     def simplify(self, min_count=1, tips=True, bubbles=True, rounds=4, tip_max_kmers=None, tip_ratio=2.0,
                  bubble_max_kmers=None, bubble_max_diff=0, bubble_ratio=0.0, bulges=False, bulge_max_kmers=None, bulge_max_diff=0,
-                 bulge_max_hops=None, bulge_max_visits=1024, bulge_ratio=0.0):
+                 bulge_max_hops=None, bulge_max_visits=1024, bulge_ratio=0.0, recompact=False):
         """simplify the graph: up to `rounds` rounds of unitigs -> links -> each enabled rule on that same graph -> one
         mask_unitigs(tip | pop), stopping at the first round that finds neither a tip nor a bubble -> ((data, start,
         length, rec) of the simplified graph, [(unitigs, tips, bubbles, masked keys so far) per round], [(round, popped
@@ -1251,7 +1305,10 @@ class GlobalCounter:
         1024 for bulge_max_visits is a choice with headroom, not a measured optimum) and masks tip | pop | bulge in the
         one call per round.  The per-round tuples are then (unitigs, tips, bubbles, bulges, masked keys so far), and a
         fourth value is returned: [(round, popped unitig, path as a list of w << 1 | o, popped record, popped sequence,
-        the path's sequence spelled with k - 1 overlaps) per unitig the bulge rule popped]."""
+        the path's sequence spelled with k - 1 overlaps) per unitig the bulge rule popped].
+        recompact=True takes the next round's unitigs from compact_unitigs() on this round's graph and drop bytes in
+        place of the unitigs() call; mask_unitigs() still runs (links and the position map live on the mask).  Every
+        returned value is the same either way."""
         if rounds < 1:
             raise ValueError("rounds: at least 1")
         tip_q8, bub_q8 = int(round(float(tip_ratio) * 256)), int(round(float(bubble_ratio) * 256))
@@ -1301,7 +1358,7 @@ class GlobalCounter:
             report.append((len(rec), n_tips, n_pop, n_bulge, self.mask_count()) if bulges else (len(rec), n_tips, n_pop, self.mask_count()))
             if not (n_tips or n_pop or n_bulge):
                 break
-            u = self.unitigs(min_count)
+            u = self.compact_unitigs(data, start, length, rec, link_ptr, links, drop)[:4] if recompact else self.unitigs(min_count)
         return (u, report, rows, bulge_rows) if bulges else (u, report, rows)
 
     def query_reads(self, data, start=None, length=None):

@@ -789,6 +789,79 @@ int cfrk_global_unitig_bulges(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS,
                               uint32_t *visits /* nS; may be NULL */, int64_t *path_ptr /* nS + 1; may be NULL */,
                               uint32_t *path, uint64_t cap_path, int64_t *n_path_out, cfrk_bulge_stats *stats);
 
+/* Unitig compaction: the unitigs of the graph WITHOUT some of its unitigs, computed from the unitig list itself.  After
+ * a rule has chosen what to drop, the compacted graph of the remaining keys differs from the old one only where a
+ * dropped unitig was the reason two others could not merge.  It is a pure function of the unitigs' sequences and records
+ * as cfrk_global_unitigs wrote them (data, start, length, rec, nN, nS), the link CSR as cfrk_global_unitig_links wrote it
+ * (link_ptr, links, n_links), drop[nS] (a byte per unitig, nonzero: dropped; NULL: nothing is dropped), k and the strand
+ * rule.  It needs neither the index nor the counts; the job only supplies k and the strand rule.
+ *   DEFINING PROPERTY: the output is byte for byte what cfrk_global_unitigs(min_count) returns after
+ *   cfrk_global_mask_unitigs(drop) on the job the inputs came from: sequences, terminators, start, length, kc, n_kmers,
+ *   CFRK_UNITIG_CIRCULAR and the order.
+ * The rule.  Oriented unitigs, head(), tail(), out() and in() are those of "Unitig links" and "Unitig tips", all links
+ *   taken among the SURVIVORS (drop[j] == 0) only.  n_u = n_kmers of u.
+ *   MERGE (u,ou) -> (v,ov) iff out(u,ou) = {(v,ov)} and in(v,ov) = {(u,ou)}; it is not a hairpin (v = u with ov != ou);
+ *   it is not the self-link of a single-node unitig (v = u, ov = ou, n_u = 1); neither u nor v is a palindromic single
+ *   node (a canonical job, n = 1, head = rc(head)); neither is CFRK_UNITIG_CIRCULAR.  A self-link (u,+) -> (u,+) with
+ *   n_u > 1 that has become the only link on both sides IS a merge: the unitig closes to a cycle (a tip fell off it).
+ *   Why this is the k-mer rule: the links inside a surviving unitig stay links, since removing keys only shrinks succ()
+ *   and pred(); at an end, succ(tail(u,ou)) among the remaining keys is exactly the heads of the surviving targets of
+ *   out(u,ou), and the exclusions are node(a) == node(b) and the palindromes of the k-mer rule, stated for ends.
+ *   Merges form disjoint paths and cycles over the oriented unitigs; in a canonical job each has a distinct mirror.  A
+ *   COMPONENT is written once: the members' sequences spelled with their k - 1 overlaps, kc and n_kmers summed.
+ *   path: as it stands; in a canonical job, of the path and its mirror the one whose first k-mer is smaller.
+ *   cycle (also one that closes only now): cut at the smallest oriented k-mer of the cycle (canonical: and of its
+ *     mirror), flagged CFRK_UNITIG_CIRCULAR.  A cycle of fewer than k k-mers is legal.
+ *   A CFRK_UNITIG_CIRCULAR input is a component of its own and is copied.  ORDER: ascending by first k-mer.
+ * Output: a unitig list in the layout of cfrk_global_unitigs (data_out / cap_data, start_out, length_out, rec_out /
+ *   cap_unitigs, *nN_out, *nS_out), and, unless NULL, into[nS]: where input unitig j went, as cfrk_unitig_pos.  unitig =
+ *   the index in the output, at = off << 1 | minus: input j covers s_new[off : off + length[j]], or that is its reverse
+ *   complement when minus is set (always 0 in a job that is not canonical).  In a circular output the positions are
+ *   taken mod n_kmers: a member that the cut splits wraps around the end.  A dropped unitig has CFRK_POS_NONE in both
+ *   words.
+ * Capacities: *nS_out <= the survivors and *nN_out <= the sum of their lengths plus their number, always.  The select's
+ *   protocol: when *nN_out > cap_data or *nS_out > cap_unitigs the call returns CFRK_ERR_SMALL_BUF with both sizes
+ *   complete and nothing written to the arrays (into included); NULL arrays with zero capacities are that "sizes only"
+ *   call.  Outputs must not overlap inputs.  No alignment requirement on data or data_out.
+ * Untrusted input.  The rows go through the check of "Unitig tips" (the same five CFRK_ERR_LAYOUT reasons).  Beyond it,
+ *   CFRK_ERR_LAYOUT, cfrk_last_error naming the first offending unitig (dropped ones are checked like the others), for a
+ *   unitig with length < k, with length != n_kmers + k - 1, with a range outside [0, nN) or a start before the end of
+ *   its predecessor; for a merge whose k - 1 overlap does not match in the two end windows (named is the lower of the
+ *   two unitigs); for a component of more than 2^31 - 1 bases (named is the unitig it begins with).  A merge is taken
+ *   only when the out-condition read off u's row and the in-condition read off v's row (not canonical: off v's in-row,
+ *   built from all rows) name each other, so rows that pass the check without being a link set still give well-formed
+ *   paths and cycles, every survivor in exactly one written component.  Interior codes are not checked: the check is
+ *   necessary, not sufficient; cfrk_global_unitig_index on the result is the sufficient one.  For any input whatever
+ *   nothing outside the buffers is accessed and no loop is unbounded.  An error wins over CFRK_ERR_SMALL_BUF; after it
+ *   the arrays are unspecified and the sizes are 0.
+ * CFRK_ERR_STATE: no job.  CFRK_ERR_ARG: NULL size outputs, negative sizes, NULL data / start / length / rec / link_ptr
+ *   with nS > 0, NULL links with n_links > 0, a NULL output array with a capacity above 0, nS >= 2^31.  nS = 0 is fine:
+ *   both sizes 0.
+ * Device form (cfrk_amd/csrc/unitig_compact.hip): after the checks one lane per oriented unitig finds its merge from two
+ *   rows of at most 16 links and the 2k end bases; the chains are ranked by pointer doubling, ceil(log2 nS) launches of
+ *   one lane per oriented unitig, so no lane's work grows with the members of a chain; the smallest k-mer of a cycle is
+ *   found one window per lane over the cycles' members only; the components are sorted by first k-mer; the emit runs one
+ *   workgroup per CFRK_COMPACT_TILE_BYTES of OUTPUT bytes, so one member of 10^6 bases among short ones costs what its
+ *   bytes cost.  It synchronises ONCE, for the sizes and the error word, and returns with the order, into and the emit
+ *   enqueued.  Temporary device memory, kept in the context's pool: 140 bytes per oriented unitig (2 nS of them in a
+ *   canonical job, else nS), 52 per unitig, 44 per output unitig, the sort's and the scans' scratch; not canonical: 12
+ *   more bytes per unitig and 4 per link.  16 bytes of LDS in the emit, no scratch.
+ * Host form: stages through the pool, checks start / length against the terminators as cfrk_global_add does
+ *   (CFRK_ERR_LAYOUT); synchronous. */
+#define CFRK_COMPACT_TILE_BYTES 4096
+int cfrk_global_unitigs_compact_device(cfrk_ctx *ctx, const int8_t *d_data, const int64_t *d_start, const int32_t *d_length,
+                                       const cfrk_unitig *d_rec, int64_t nN, int64_t nS, const int64_t *d_link_ptr /* nS + 1 */,
+                                       const cfrk_unitig_link *d_links, int64_t n_links, const uint8_t *d_drop /* nS; may be NULL */,
+                                       int8_t *d_data_out, uint64_t cap_data, int64_t *d_start_out, int32_t *d_length_out,
+                                       cfrk_unitig *d_rec_out, uint64_t cap_unitigs, cfrk_unitig_pos *d_into /* nS; may be NULL */,
+                                       int64_t *nN_out, int64_t *nS_out);
+int cfrk_global_unitigs_compact(cfrk_ctx *ctx, const int8_t *data, const int64_t *start, const int32_t *length,
+                                const cfrk_unitig *rec, int64_t nN, int64_t nS, const int64_t *link_ptr /* nS + 1 */,
+                                const cfrk_unitig_link *links, int64_t n_links, const uint8_t *drop /* nS; may be NULL */,
+                                int8_t *data_out, uint64_t cap_data, int64_t *start_out, int32_t *length_out,
+                                cfrk_unitig *rec_out, uint64_t cap_unitigs, cfrk_unitig_pos *into /* nS; may be NULL */,
+                                int64_t *nN_out, int64_t *nS_out);
+
 /* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
 
 /* How many DISTINCT k-mers will a job hold?  One streaming pass over the reads answers it to about 1 % before anything

@@ -42,7 +42,15 @@ sizes-only call and fill pass included) alternating with the bubbles call in the
 undecided, ns per arm, and the distributions of visits (over arms) and hops (over popped arms); and a line "rounds" with
 nodes, unitigs, tips, bubbles, bulges and masked keys per round of the combined loop, one mask call per round.
 
-  python tools/bench_unitigs.py [--links | --tips [--parent-lib SO] | --bubbles [--parent-lib SO] | --bulges] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
+With --compact (cases b and c) the tool "bench_compact" writes, per case: a line "compact" with the compaction call
+(cfrk_global_unitigs_compact_device on the unmasked graph and the drop bytes of round 1 of tips + bubbles + bulges, into
+arrays of exactly the sizes) alternating in the same repetitions with the unitigs call under the mask of those drop bytes
+-- the yardstick: the two results are asserted byte-equal first --, with the compaction's sizes-only call (everything up
+to its synchronisation; the difference to the whole call is the sort, the scans, the members' list and the emit) and with
+a device copy of the output bytes; and a line "loop" with the whole loop of --tip-rounds rounds, every round's graph made
+by the unitigs call or by the compaction, the two alternating over --loop-reps repetitions, the rounds asserted equal.
+
+  python tools/bench_unitigs.py [--links | --tips [--parent-lib SO] | --bubbles [--parent-lib SO] | --bulges | --compact] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
 """
 import argparse
 import json
@@ -315,6 +323,115 @@ def bulges_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf
                           rounds=rounds)), flush=True)
 
 
+def compact_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf, stream):
+    k = a.k
+    tip_q8, bub_q8, bulge_q8 = int(round(a.tip_ratio * 256)), int(round(a.bubble_ratio * 256)), int(round(a.bulge_ratio * 256))
+    max_hops = min(k + a.bulge_max_diff, cfrk_amd.CFRK_BULGE_MAX_HOPS)
+
+    def graph_args(gr):
+        return (gr.out[3].data_ptr(), gr.nS, gr.ptr.data_ptr(), gr.rows.data_ptr(), gr.n_links)
+
+    def drop_of(gr):
+        """round 1 of tips + bubbles + bulges on this graph -> (drop bytes, what each rule found)"""
+        d_tip, d_bub, d_pop = buf(gr.nS), buf(gr.nS), buf(gr.nS)
+        n_tips = g.unitig_tips_device(*graph_args(gr), k, tip_q8, d_tip.data_ptr())
+        n_bub = g.unitig_bubbles_device(*graph_args(gr), k, a.bubble_max_diff, bub_q8, d_bub.data_ptr(), 0)
+        st = g.unitig_bulges_device(*graph_args(gr), k, a.bulge_max_diff, max_hops, a.bulge_max_visits, bulge_q8, d_pop.data_ptr())[1]
+        ctx.sync()
+        d_tip[:gr.nS] |= d_bub[:gr.nS] | d_pop[:gr.nS]
+        torch.cuda.synchronize()
+        return d_tip, (n_tips, n_bub, st["popped"])
+
+    def compact(gr, d_drop, out=None, sizes=(0, 0)):
+        """-> (nN, nS) of the compaction of gr; without `out` the sizes-only call"""
+        o = [x.data_ptr() for x in out] if out else [0, 0, 0, 0]
+        try:
+            return g.compact_unitigs_device(gr.out[0].data_ptr(), gr.out[1].data_ptr(), gr.out[2].data_ptr(), gr.out[3].data_ptr(), gr.nN, gr.nS,
+                                            gr.ptr.data_ptr(), gr.rows.data_ptr(), gr.n_links, d_drop.data_ptr(), o[0], sizes[0], o[1], o[2], o[3], sizes[1])
+        except cfrk_amd.CfrkError as e:
+            if e.code != cfrk_amd.CFRK_ERR_SMALL_BUF:
+                raise
+            return e.nN, e.nS
+
+    new = _Graph(cfrk_amd, g, min_count, buf)
+    d_drop, found = drop_of(new)
+    cN, cS = compact(new, d_drop)
+    cout = [buf(cN), buf(cS * 8), buf(cS * 4), buf(cS * 16)]
+    assert compact(new, d_drop, cout, (cN, cS)) == (cN, cS)
+    g.mask_unitigs_device(*new.args, d_drop.data_ptr())
+    masked = _Graph(cfrk_amd, g, min_count, buf)                 # the yardstick: the unitigs call under the mask of round 1
+    ctx.sync()
+    assert (masked.nN, masked.nS) == (cN, cS), ((masked.nN, masked.nS), (cN, cS))
+    for got, want, n in zip(cout, masked.out, (cN, cS * 8, cS * 4, cS * 16)):
+        assert bool((got[:n] == want[:n]).all()), "the compaction is not the masked unitigs call byte for byte"
+    dst = buf(cN)
+
+    def copy():
+        with torch.cuda.stream(stream):
+            dst[:cN].copy_(cout[0][:cN])
+
+    calls = {"compact": lambda: compact(new, d_drop, cout, (cN, cS)), "unitigs_masked": masked.unitigs,
+             "compact_sizes_only": lambda: compact(new, d_drop), "copy_output": copy}
+    t = {name: [] for name in calls}
+    for rep in range(a.reps + 1):
+        for name, fn in calls.items():                          # alternating in one process
+            ms = timed(fn)
+            if rep:                                             # (the first round warms up: code objects, pool buffers)
+                t[name].append(ms)
+    row = dict(common, line="compact", nodes=new.nodes(torch), unitigs=new.nS, links=new.n_links, tips=found[0], bubbles=found[1], bulges=found[2],
+               dropped=int(d_drop[:new.nS].ne(0).sum()), unitigs_after=cS, bytes_after=cN, byte_equal=True)
+    row.update({name: dict(stats(ts), series=ts) for name, ts in t.items()})
+    row["order_and_emit_ms"] = row["compact"]["ms"] - row["compact_sizes_only"]["ms"]
+    row["unitigs_over_compact"] = row["unitigs_masked"]["ms"] / row["compact"]["ms"]
+    row["outside_yardstick_spread"] = row["compact"]["max_ms"] < row["unitigs_masked"]["min_ms"]
+    print(json.dumps(row), flush=True)
+    # the whole loop, with and without recompaction, from an unmasked graph each time; the two alternate
+    def loop(recompact):
+        g.mask_clear()
+        cur, rounds = _Graph(cfrk_amd, g, min_count, buf), []
+        for r in range(a.tip_rounds):
+            d, found = drop_of(cur)
+            if any(found):
+                g.mask_unitigs_device(*cur.args, d.data_ptr())
+            rounds.append((cur.nS,) + found)
+            if not any(found):
+                break                                           # (else: the next graph, after the last round the loop's result)
+            if recompact:
+                nN, nS = compact(cur, d)
+                nxt = _Graph.__new__(_Graph)
+                nxt.mod, nxt.g, nxt.mc, nxt.buf, nxt.nN, nxt.nS = cfrk_amd, g, min_count, buf, nN, nS
+                nxt.out = [buf(nN), buf(nS * 8), buf(nS * 4), buf(nS * 16)]
+                assert compact(cur, d, nxt.out, (nN, nS)) == (nN, nS)
+                nxt.args = (nxt.out[0].data_ptr(), nxt.out[1].data_ptr(), nxt.out[2].data_ptr(), nN, nS)
+                nxt.ptr = buf((nS + 1) * 8)
+                try:
+                    nxt.n_links = g.unitig_links_device(min_count, *nxt.args, nxt.ptr.data_ptr(), 0, 0)
+                except cfrk_amd.CfrkError as e:
+                    if e.code != cfrk_amd.CFRK_ERR_SMALL_BUF:
+                        raise
+                    nxt.n_links = e.n_links
+                nxt.rows = buf(nxt.n_links * 8)
+                nxt.links()
+                cur = nxt
+            else:
+                cur = _Graph(cfrk_amd, g, min_count, buf)
+        return rounds
+
+    t, seen = {False: [], True: []}, {}
+    for rep in range(a.loop_reps + 1):
+        for recompact in ((False, True) if rep % 2 else (True, False)):
+            box = []
+            ms = timed(lambda: box.append(loop(recompact)))
+            seen[recompact] = box[0]
+            if rep:
+                t[recompact].append(ms)
+    assert seen[False] == seen[True], (seen[False], seen[True])
+    row = dict(common, line="loop", rounds=[dict(zip(("unitigs", "tips", "bubbles", "bulges"), r)) for r in seen[True]],
+               loop=dict(stats(t[False]), series=t[False]), loop_recompact=dict(stats(t[True]), series=t[True]))
+    row["loop_over_recompact"] = row["loop"]["ms"] / row["loop_recompact"]["ms"]
+    print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="a,b,c")
@@ -337,6 +454,8 @@ def main():
     ap.add_argument("--bulge-ratio", type=float, default=0.0)
     ap.add_argument("--bulge-max-diff", type=int, default=0)
     ap.add_argument("--bulge-max-visits", type=int, default=1024)
+    ap.add_argument("--compact", action="store_true")
+    ap.add_argument("--loop-reps", type=int, default=3)
     ap.add_argument("--parent-lib", help="libcfrk_hip.so of the parent commit: with --tips the unmasked calls, with --bubbles the tips call alternate with it")
     a = ap.parse_args()
 
@@ -404,6 +523,13 @@ def main():
         def full():
             g.unitigs_device(min_count, out[0].data_ptr(), oN, out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), oS)
 
+        if a.compact:
+            common = {"tool": "bench_compact", "case": case, "reads": R, "L": L, "glen": a.glen, "k": k, "reps": a.reps,
+                      "error_rate": 0.0 if case == "a" else a.error_rate, "min_count": min_count, "distinct_keys": distinct}
+            compact_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf, stream)
+            del g, out, reads
+            torch.cuda.empty_cache()
+            continue
         if a.bulges:
             common = {"tool": "bench_bulges", "case": case, "reads": R, "L": L, "glen": a.glen, "k": k, "reps": a.reps,
                       "error_rate": 0.0 if case == "a" else a.error_rate, "min_count": min_count, "distinct_keys": distinct}
