@@ -22,6 +22,10 @@ struct TableView;
 #define CFRK_ABL_P1_NO_EMIT    CFRK_ABL_BIT(0x1000u)    // partition kernel: front end only, no records built
 #define CFRK_ABL_P2_NO_ATOMIC  CFRK_ABL_BIT(0x2000u)    // second-level kernel: no cursor atomics (every tile's segments land at the stream starts)
 #define CFRK_ABL_P2_LINEAR_OUT CFRK_ABL_BIT(0x4000u)    // second-level kernel: sorted tiles written back to back (what the scatter into 512 streams per bin costs)
+// (these two count RIGHT.  OLD_CEXP: the expansion of the distinct complete runs as it was before round 32.  PATHS: the leaf kernel
+//  counts the paths its expansion takes, tools/p3_paths.py -- global atomics and a look-up pass per leaf, so NOT beside a timing run)
+#define CFRK_ABL_P3_OLD_CEXP   CFRK_ABL_BIT(0x8000u)    // leaf kernel: lanes per run by the number of runs (3, 2 or 1) in every instantiation
+#define CFRK_ABL_P3_PATHS      CFRK_ABL_BIT(0x800000u)  // leaf kernel: path counters on (cfrk_debug_p3_paths)
 #define CFRK_ABL_RX3_NO_CURSOR CFRK_ABL_BIT(0x10000u)   // radix leaf kernel: no atomic on the result cursor (workgroup b writes from entry b * 16384)
 #define CFRK_ABL_RX3_NO_COUNT  CFRK_ABL_BIT(0x20000u)   // radix leaf kernel: keys are loaded but not counted
 #define CFRK_ABL_RX2_NO_OUT    CFRK_ABL_BIT(0x40000u)   // radix second-level kernel: the sorted tile is not written out
@@ -32,7 +36,7 @@ struct TableView;
 #define CFRK_ABL_SK_ALWAYS     CFRK_ABL_BIT(0x400000u)  // sketch: one LDS word per register, atomic max for every window
 // every bit cfrk_debug_set_flags accepts: the documented test switches of include/cfrk_abi.h, plus the ablations of an ablation build
 #ifdef CFRK_ABLATIONS
-#define CFRK_DEBUG_KNOWN_BITS (0xFFu | 0x7F00u | 0x7F0000u)
+#define CFRK_DEBUG_KNOWN_BITS (0xFFu | 0xFF00u | 0xFF0000u)
 #else
 #define CFRK_DEBUG_KNOWN_BITS 0xFFu
 #endif

@@ -135,6 +135,7 @@ __device__ __forceinline__ void l1_put(const MspView &v, uint32_t reg, uint32_t 
 // wave: two workgroups per CU instead of three.
 #define P1_MARK(text) asm volatile("; " text)
 // the same for the parts of the leaf kernel's scan of the complete stream (p3_body, phase 1a; tools/p3_isa_account.py)
+// ... and of its phase 2
 #define P3_MARK(text) asm volatile("; " text)
 template <int P1B_TR, bool SUB = false>
 struct P1Lds {
@@ -713,7 +714,21 @@ constexpr int KT_TRIPS_SPLIT = 16;          // (buckets of two slots)
 // SAT: the count saturates at CFRK_COUNT_MAX (table.h: sat_add) -- the merge of lists whose counts nothing bounds;
 // the leaf kernel's own counts cannot overflow (HUGE_LEAF)
 constexpr uint32_t KT_DONE = 0x80000000u;
-template <bool SAT = false>
+// Path counters of the leaf kernel, in an ABLATION BUILD only and there only with CFRK_ABL_P3_PATHS set (msp.h; read by
+// cfrk_debug_p3_paths, tools/p3_paths.py): how often the expansion of the distinct complete runs takes which way.  The
+// product build has none of it, and the timing ablations run without it (the counters are global atomics).
+enum { P3C_LEAVES_1 = 0, P3C_LEAVES_2, P3C_LEAVES_3,   // leaves whose record table is listed, by the lanes per run 1024 threads gave before every leaf took three
+       P3C_CEXP_WAVES, P3C_CEXP_SLOW,                  // wave-calls of the complete runs' expansion with notes / those that leave the one-walk path
+       P3C_KT_CLAIMED, P3C_KT_MATCHED,                 // k-mer table: keys of that expansion that claimed an empty slot / found their key
+       P3C_RT_ENTRIES, P3C_RT_TWINNED, P3C_RT_PALIN,   // record-table entries / whose reverse complement is an entry too / that are their own
+       P3C_N };
+#ifdef CFRK_ABLATIONS
+__device__ unsigned long long p3_paths[P3C_N];
+#define P3_COUNT(i, n) atomicAdd(&p3_paths[i], (unsigned long long)(n))
+#else
+#define P3_COUNT(i, n) ((void)0)
+#endif
+template <bool SAT = false, bool PATHS = false>
 __device__ __forceinline__ void kt_try(unsigned long long *keys, uint32_t *cnts, uint64_t key, uint32_t &b,
                                        uint32_t add) {
   const bool p = (int32_t)b >= 0;
@@ -729,6 +744,15 @@ __device__ __forceinline__ void kt_try(unsigned long long *keys, uint32_t *cnts,
     won = (old == CFRK_EMPTY_KEY || old == key) ? 1u : 0u;      // lost to another key: same bucket again
   }
   const bool ok = hit || won != 0u;
+#ifdef CFRK_ABLATIONS
+  if (PATHS) {
+    const unsigned long long mh = __ballot(p && hit), mw = __ballot(p && !hit && won != 0u);
+    if ((threadIdx.x & 63) == 0) {
+      if (mh) P3_COUNT(P3C_KT_MATCHED, __popcll(mh));
+      if (mw) P3_COUNT(P3C_KT_CLAIMED, __popcll(mw));
+    }
+  }
+#endif
   if (SAT) {
     if (p && ok) {
       const uint32_t old = atomicAdd(&cnts[s], add);
@@ -761,18 +785,25 @@ __device__ __forceinline__ bool in_subset(uint64_t key, KeySubset ss) {
 // Only keys of subset `ss` are counted.  A key that finds no room is counted in the HBM table when
 // ovf == nullptr; otherwise *ovf (an LDS flag) is raised and the caller redoes the subset in
 // halves -- and waves that see the flag up stop working on a pass that is lost anyway.
-template <bool CANON>
+// PATHS (an ablation build's caller with CFRK_ABL_P3_PATHS set, for the complete runs' expansion): count the paths taken.
+template <bool CANON, bool PATHS = false>
 __device__ __forceinline__ void count_record_v2(unsigned long long *keys, uint32_t *cnts, uint4 rec, uint32_t add,
                                                 bool valid, int k, uint64_t kmask, int rcsh,
                                                 const TableView &t, KeySubset ss = KeySubset{0u, 0u},
                                                 uint32_t *ovf = nullptr, int part = 0, int parts = 1,
-                                                const uint8_t *tb = nullptr, uint32_t tb_n = 0u) {
+                                                const uint8_t *tb = nullptr, uint32_t tb_n = 0u,
+                                                const uint8_t *tb2 = nullptr, uint32_t tb2_n = 0u) {
   // tb[0 .. tb_n): lengths (in k-mers) of the truncated runs that are prefixes of this record: k-mer J
   // of the record is counted once more for every one of them that is longer than J
+  // tb2[0 .. tb2_n) (canonical, with tb): the same lengths noted with the record's STRAND TWIN, whose k-mers are this
+  // record's in reverse order: k-mer J of n is counted once more for every one of them with t >= n - J
   if (ovf && *(volatile uint32_t *)ovf) return;
-  // a record may be shared by `parts` lanes, each expanding a contiguous share of its k-mers
+  P3_MARK("P3_PART_XSETUP");
+  // a record may be shared by `parts` lanes (1 .. 6), each expanding a contiguous share of its k-mers
   const int nall = valid ? (int)(rec.w & 63u) + 1 : 0;
-  const int per = (parts == 1) ? nall : (parts == 2) ? ((nall + 1) >> 1) : ((nall + 2) / 3);
+  // (ceil(nall / parts), nall <= 64, by a multiply: `parts` is uniform and the reciprocal a scalar)
+  const int per = (parts <= 3) ? ((parts == 1) ? nall : (parts == 2) ? ((nall + 1) >> 1) : ((nall + 2) / 3))
+                               : (int)(((uint32_t)(nall + parts - 1) * (65536u / (uint32_t)parts + 1u)) >> 16);
   const int j0 = part * per;
   const int nk = max(min(nall, j0 + per) - j0, 0);
   uint64_t hi = ((uint64_t)rec.x << 32) | rec.y;
@@ -791,8 +822,15 @@ __device__ __forceinline__ void count_record_v2(unsigned long long *keys, uint32
   // The forward-strand instantiation keeps the loop per k-mer pair: it is out of registers.
   unsigned long long exq = 0ull;
   const bool tb_fast = CANON && tb && !__ballot(valid && (nk > 8 || tb_n > 127u));
+  if (tb) {
+    P3_MARK("P3_PART_XWALK");
+#ifdef CFRK_ABLATIONS
+    if (PATHS && (threadIdx.x & 63) == 0) { P3_COUNT(P3C_CEXP_WAVES, 1); if (!tb_fast) P3_COUNT(P3C_CEXP_SLOW, 1); }
+#endif
+  }
   if (tb_fast) exq = noted_counts8(tb, tb_n, j0);
   for (int j = 0; __ballot(j < nk); j += 2) {
+    P3_MARK("P3_PART_XSTEP");
     uint32_t add0 = add, add1 = add;
     if (tb_fast) {
       add0 += (uint32_t)(exq >> (8 * (j & 7))) & 255u;
@@ -829,8 +867,8 @@ __device__ __forceinline__ void count_record_v2(unsigned long long *keys, uint32
     //  index, which the export by leaf needs: at C3's size a handful of the 65 536 leaves were split)
     const int trips = ovf ? (ss.mask == 0u ? KT_TRIPS : KT_TRIPS_SPLIT) : KT_TRIPS;
     for (int it = 0; it < trips && __ballot((int32_t)(b0 & b1) >= 0); ++it) {
-      kt_try(keys, cnts, key0, b0, add0);
-      kt_try(keys, cnts, key1, b1, add1);
+      kt_try<false, PATHS>(keys, cnts, key0, b0, add0);
+      kt_try<false, PATHS>(keys, cnts, key1, b1, add1);
     }
     if (ovf) {
       if ((int32_t)(b0 & b1) >= 0) *ovf = 1u;
@@ -1506,8 +1544,45 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
   bool use_anchors = false;
   {
     // (a) record table: occupied slots, longest first (not when the leaf is counted from its streams)
+    P3_MARK("P3_PART_LIST");
     const uint4 e = rtab[tid];                       // RT == P3_THREADS
     const bool occ = !big && e.w != RT_EMPTY;
+    // STRAND TWINS.  The table is keyed by a run's bases as read, and reads come from both strands: a locus sits in it
+    // twice, as a run and as its reverse complement, and both expansions roll, canonicalise, hash and count the SAME
+    // canonical k-mers (the second one's every key a match: on C3 every entry has its twin, and 44 % of the expansion's
+    // keys are matches).  MEASURED AND NOT KEPT (round 32, profiles/r32): every entry looked its reverse complement up
+    // here, of a pair the one with the smaller bases was expanded with both multiplicities and both lists of noted
+    // lengths (the twin's mirrored), the other left out of the list.  On top of three lanes per run that made the
+    // kernel SLOWER in every round: +0.25 / +0.20 ms of P3's 5.7 with the twin's notes in a walk of their own,
+    // +0.08 / +0.13 ms with both walks in one loop, within +-0.07 ms of it without the pass's barrier; four and six
+    // lanes per merged run were slower still (+0.36 ... +0.43 / +0.28 ... +0.35 ms).  The expansion is not issue-bound:
+    // a wave takes its three steps and its walk whether eight or sixteen waves of the workgroup do so beside it, and
+    // the look-up pass and the second list are added to every leaf's critical path.
+#ifdef CFRK_ABLATIONS
+    if constexpr (CANON && !SHARED && !LISTS) {
+      if (anchors_on && (v.dbg & CFRK_ABL_P3_PATHS)) {     // (uniform) the look-up alone, to count the twins
+        const uint4 r = revcomp_record(e, (int)(e.w & 31u) + k);
+        const bool palin = rtab_diff(r, e) == 0u;          // its own reverse complement
+        uint32_t h = (occ && !palin) ? rtab_slot_k(r, k, RT_LOG) : RT_DONE;
+        bool found = false;
+        // (an entry of the table is always found from its home slot: the twins see each other or neither does)
+        for (int it = 0; it < RT && __ballot((int32_t)h >= 0); ++it) {
+          const bool p = (int32_t)h >= 0;
+          const uint32_t hh = h & (uint32_t)(RT - 1);
+          const uint4 e2 = rtab[hh];
+          const bool hit = p && rtab_diff(e2, r) == 0u;
+          found = found || hit;
+          h = (p && !hit && e2.w != RT_EMPTY) ? ((hh + 1u) & (uint32_t)(RT - 1)) : (h | RT_DONE);
+        }
+        const unsigned long long mo = __ballot(occ), mt = __ballot(found), mp = __ballot(occ && palin);
+        if (lane == 0) {
+          if (mo) P3_COUNT(P3C_RT_ENTRIES, __popcll(mo));
+          if (mt) P3_COUNT(P3C_RT_TWINNED, __popcll(mt));
+          if (mp) P3_COUNT(P3C_RT_PALIN, __popcll(mp));
+        }
+      }
+    }
+#endif
     uint32_t rank = 0;
     if (occ) rank = atomicAdd(&nhist[e.w & 31u], 1u);
     // (b) truncated runs: the first TL_CAP of the stream, by position
@@ -1517,6 +1592,7 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
     //  TL_PER -- the compiler put a full wait behind every load, 4 x ~1.5 us per leaf with two leaves per CU;
     //  the one-GPU counting kernels have asked in front of the cache merge, see there)
     if constexpr (!TREC_EARLY) load_trec(false);
+    P3_MARK("P3_PART_ANCHOR");
 #pragma unroll
     for (int i = 0; i < TL_PER; ++i) {
       const uint32_t g = (uint32_t)(i * P3_THREADS + tid);
@@ -1548,6 +1624,7 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
         if (lane == 0 && fb) atomicAdd(&nfb, (uint32_t)__popcll(fb));
       }
     }
+    P3_MARK("P3_PART_GROUP");
     __syncthreads();
     use_anchors = anchors_on && nfb <= (uint32_t)FL_CAP;
     if (use_anchors) {
@@ -1652,24 +1729,49 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
         // ~320 distinct runs for 1024 lanes, and a wave works for as many steps as its longest run
         // has k-mers: up to three lanes share a record, each expanding a share of its k-mers
         const uint32_t nlist = (v.dbg & CFRK_ABL_P3_NO_CEXP) ? 0u : nocc;
-        const int parts = (nlist * 3u <= (uint32_t)P3_THREADS) ? 3 : (nlist * 2u <= (uint32_t)P3_THREADS) ? 2 : 1;
+        // lanes per run before every canonical leaf took three (the forward-strand instantiation's still: it is out of
+        // registers and walks its notes per k-mer pair whatever a lane's share)
+        const int parts_by_n = (nlist * 3u <= (uint32_t)P3_THREADS) ? 3 : (nlist * 2u <= (uint32_t)P3_THREADS) ? 2 : 1;
+#ifdef CFRK_ABLATIONS
+        if (tid == 0 && nlist && (v.dbg & CFRK_ABL_P3_PATHS)) P3_COUNT(P3C_LEAVES_1 + parts_by_n - 1, 1);
+#endif
+        // Canonical counting: THREE lanes per run however many runs (the list is sorted by length: more than 1024 items
+        // take a second trip, of the shortest runs).  With two, the longest runs' lanes hold nine k-mers: their waves
+        // miss the one-walk path of the notes (tb_fast: <= 8) and take five steps instead of three.  On C3 a quarter
+        // of the leaves list more than 341 runs and 7 % of the expansion's wave-calls walked their notes per k-mer
+        // pair: 6.07 -> 5.78 ms per launch (round 32, profiles/r32).  (Four and six lanes for a short list, measured
+        // beside the twin merge, lose against three: a setup is issued per lane, and two k-mers make a step.)
+        // (The shared-leaf instantiation keeps the lanes it had, like the forward-strand one: with three always it
+        //  spilled 18 scratch instructions, over the 16 that tests/test_kernel_resources.py allows; as it stands 13.)
+        constexpr bool LANES3 = CANON && !SHARED;
+        const int parts = (LANES3 && !(v.dbg & CFRK_ABL_P3_OLD_CEXP)) ? 3 : parts_by_n;
         const uint32_t nitems = nlist * (uint32_t)parts;
-        for (uint32_t i = tid; i < ((nitems + 63u) & ~63u); i += P3_THREADS) {
-          const bool valid = i < nitems;
-          const uint32_t ri = (parts == 1) ? i : (parts == 2) ? (i >> 1) : (i / 3u);
-          uint4 rec = make_uint4(0u, 0u, 0u, 0u);
-          uint32_t slot = 0;
-          if (valid) { slot = occ_list[ri]; rec = rtab[slot]; }
-          if (use_anchors) {
-            // ... plus one for every truncated run of this locus that reaches the k-mer
-            const uint32_t g0 = th[slot];
-            count_record_v2<CANON>(keys, cnts, rec, rec.w >> 6, valid, k, kmask, rcsh, t, ss, ovf,
-                                   (int)(i - ri * (uint32_t)parts), parts, tbytes + g0, valid ? th[slot + 1] - g0 : 0u);
-          } else {
-            count_record_v2<CANON>(keys, cnts, rec, rec.w >> 6, valid, k, kmask, rcsh, t, ss, ovf,
-                                   (int)(i - ri * (uint32_t)parts), parts);
+        const uint32_t prcp = (1u << 20) / (uint32_t)parts + 1u;        // (i / parts for i < 2^12 by a multiply)
+        P3_MARK("P3_PART_CEXP");
+        // (PATHS: count_record_v2 counts the paths it takes -- an ablation build with CFRK_ABL_P3_PATHS set)
+        auto expand = [&](auto paths_) {
+          constexpr bool PATHS = decltype(paths_)::value;
+          for (uint32_t i = tid; i < ((nitems + 63u) & ~63u); i += P3_THREADS) {
+            const bool valid = i < nitems;
+            const uint32_t ri = LANES3 ? ((i * prcp) >> 20) : ((parts == 1) ? i : (parts == 2) ? (i >> 1) : (i / 3u));
+            uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+            uint32_t slot = 0;
+            if (valid) { slot = occ_list[ri]; rec = rtab[slot]; }
+            if (use_anchors) {
+              // ... plus one for every truncated run of this locus that reaches the k-mer
+              const uint32_t g0 = th[slot];
+              count_record_v2<CANON, PATHS>(keys, cnts, rec, rec.w >> 6, valid, k, kmask, rcsh, t, ss, ovf,
+                                            (int)(i - ri * (uint32_t)parts), parts, tbytes + g0, valid ? th[slot + 1] - g0 : 0u);
+            } else {
+              count_record_v2<CANON, PATHS>(keys, cnts, rec, rec.w >> 6, valid, k, kmask, rcsh, t, ss, ovf,
+                                            (int)(i - ri * (uint32_t)parts), parts);
+            }
           }
-        }
+        };
+#ifdef CFRK_ABLATIONS
+        if (v.dbg & CFRK_ABL_P3_PATHS) expand(std::true_type{}); else
+#endif
+        expand(std::false_type{});
       } else {
         // the complete runs straight from their stream, weight 1 each
         for (uint64_t i = tid; i < ((n1 + 63) & ~63ull); i += P3_THREADS) {
@@ -1681,6 +1783,7 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
       }
       // truncated runs: those without a twin (anchored leaf), or all of the sorted list
       const uint32_t ntr = nfl;
+      P3_MARK("P3_PART_TRUNC");
       // (measured and not kept, round 27: these two loops one trip ahead of their loads -- an anchored leaf lists at most
       //  FL_CAP = one trip of truncated runs, so nothing was hidden; and the first trip's record asked for in front of
       //  the complete runs' expansion keeps four more registers alive across it: ten spilled)
@@ -1698,6 +1801,7 @@ __device__ __forceinline__ void p3_body(int k, uint32_t mode, const MspView &v, 
         count_record_v2<CANON>(keys, cnts, rec, 1u, valid && mine(rec.w), k, kmask, rcsh, t, ss, ovf);
       }
     }
+    P3_MARK("P3_PART_OUT");
     __syncthreads();
     if (kovf) {
       // this subset does not fit the table either: its two halves replace it (the table is discarded)
@@ -2668,6 +2772,23 @@ extern "C" int cfrk_debug_set_flags(cfrk_ctx *ctx, uint32_t flags) {
   ctx->dbg_flags = flags;
   return CFRK_OK;
 }
+
+#ifdef CFRK_ABLATIONS
+// ablation build only (tools/p3_paths.py): the leaf kernel's path counters since the last reset, out[0 .. n) in the
+// order of P3C_*, of the current device; synchronises it (no context: the counters outlive the ones that counted)
+extern "C" int cfrk_debug_p3_paths(uint64_t *out, int n, int reset) {
+  if (!out || n < 0 || n > P3C_N) return CFRK_ERR_ARG;
+  unsigned long long h[P3C_N] = {};
+  if (hipDeviceSynchronize() != hipSuccess) return CFRK_ERR_HIP;
+  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(p3_paths), sizeof(h)) != hipSuccess) return CFRK_ERR_HIP;
+  for (int i = 0; i < n; ++i) out[i] = h[i];
+  if (reset) {
+    const unsigned long long z[P3C_N] = {};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(p3_paths), z, sizeof(z)) != hipSuccess) return CFRK_ERR_HIP;
+  }
+  return CFRK_OK;
+}
+#endif
 
 extern "C" int cfrk_debug_last_add_passes(cfrk_ctx *ctx, int *out_passes) {
   if (!ctx || !out_passes) return CFRK_ERR_ARG;

@@ -110,6 +110,48 @@ __device__ __forceinline__ unsigned long long noted_counts8(const uint8_t *tb, u
   }
   return exq;
 }
+// The same for the notes of a record's STRAND TWIN (the other strand's run of the locus, msp.hip: p3_body): a noted
+// length t there is a SUFFIX here -- of a record of n k-mers it covers the k-mers J >= n - t.  k-mer j0 + q is counted
+// once more for every entry with t >= n - j0 - q: the same nine fields by d = clamp(t - (n - j0 - 8), 0, 8), and byte
+// q is the fields' sum over d >= 8 - q.  Needs tb_n <= 127; the bytes of both forms may be added (<= 254).
+__device__ __forceinline__ unsigned long long noted_counts8_twin(const uint8_t *tb, uint32_t tb_n, int j0, int n) {
+  unsigned long long hist = 0ull;
+  const int base = n - j0 - 8;
+  for (uint32_t e = 0; __ballot(e < tb_n); ++e) {
+    if (e < tb_n) {
+      const int d = min(max((int)tb[e] - base, 0), 8);
+      hist += 1ull << (7 * d);
+    }
+  }
+  unsigned long long exq = 0ull;
+  uint32_t run = 0;
+#pragma unroll
+  for (int d = 8; d >= 1; --d) {
+    run += (uint32_t)(hist >> (7 * d)) & 127u;
+    exq |= (unsigned long long)run << (8 * (8 - d));
+  }
+  return exq;
+}
+
+// both walks in one loop (the two lists' loads in flight together): noted_counts8(tb, ..) + noted_counts8_twin(tb2, ..)
+__device__ __forceinline__ unsigned long long noted_counts8_both(const uint8_t *tb, uint32_t tb_n, const uint8_t *tb2, uint32_t tb2_n, int j0, int n) {
+  unsigned long long hist = 0ull, hist2 = 0ull;
+  const int base = n - j0 - 8;
+  for (uint32_t e = 0; __ballot(e < max(tb_n, tb2_n)); ++e) {
+    const int a = (e < tb_n) ? (int)tb[e] : 0, b = (e < tb2_n) ? (int)tb2[e] : -64;
+    hist += 1ull << (7 * min(max(a - j0, 0), 8));            // (an entry that is not there lands in field 0, which nobody reads)
+    hist2 += 1ull << (7 * min(max(b - base, 0), 8));
+  }
+  unsigned long long exq = 0ull;
+  uint32_t run = 0, run2 = 0;
+#pragma unroll
+  for (int d = 8; d >= 1; --d) {
+    run += (uint32_t)(hist >> (7 * d)) & 127u;
+    run2 += (uint32_t)(hist2 >> (7 * d)) & 127u;
+    exq += ((unsigned long long)run << (8 * (d - 1))) + ((unsigned long long)run2 << (8 * (8 - d)));
+  }
+  return exq;
+}
 
 // Epilogue of the leaf and merge kernels: the occupied slots of a workgroup's LDS table (slot s = i * NT +
 // tid, i < NIT, per thread) go to consecutive places of the result list with ONE cursor atomic per

@@ -15,7 +15,14 @@ The parts.  p3_body marks the parts of the scan with assembly comments (P3_MARK:
 
 A marker opens a SEGMENT that runs, in the order of the kernel's text, to the next marker; `before` is everything in
 front of the first marker (prologue, table clear) and `after` everything behind P3_PART_END (skeleton, expansion,
-copy-out).  The scan is inlined several times (two steps per trip of the main loop, the peeled tail, the general loop
+copy-out).  `after` is marked too and listed part by part in a second table (JSON: "phase2"):
+
+  LIST    occupied slots of the record table ranked            ANCHOR  truncated runs look their complete twin up
+  GROUP   notes grouped, lists written                         CEXP    loop over the listed runs
+  XSETUP / XWALK / XSTEP   count_record_v2: a lane's share and first k-mer / walk over the notes / a step of two k-mers
+  TRUNC   truncated runs without a twin                        OUT     copy-out
+
+The scan is inlined several times (two steps per trip of the main loop, the peeled tail, the general loop
 next to the specialised one), so a part has several segments: the table gives their number, the sum and the SMALLEST and
 LARGEST segment.  What one call of a part issues is about one segment, not the sum.
 
@@ -38,7 +45,9 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "cfrk_amd", "csrc", "msp.hip")
-PARTS = ["before", "SEED", "LOAD", "HOME", "CACHE", "APPEND", "DRAIN", "MERGE", "after"]
+PARTS = ["before", "SEED", "LOAD", "HOME", "CACHE", "APPEND", "DRAIN", "MERGE", "after",
+         "LIST", "ANCHOR", "GROUP", "CEXP", "XSETUP", "XWALK", "XSTEP", "TRUNC", "OUT"]
+PHASE2 = PARTS[PARTS.index("after"):]              # behind P3_PART_END: not part of the scan
 PART_NAMES = {
     "before": "prologue, stream bounds, table clear",
     "SEED": "warm-up: first records straight into the probe loop",
@@ -48,7 +57,16 @@ PART_NAMES = {
     "APPEND": "leftover append",
     "DRAIN": "drain / insert loop (+ cache install)",
     "MERGE": "cache merge after the scan",
-    "after": "skeleton, expansion, copy-out",
+    "after": "skeleton, expansion, copy-out (second table: up to phase 2's first marker -- export, pool-wide table)",
+    "LIST": "phase 2: the record table's occupied slots read and ranked by length",
+    "ANCHOR": "phase 2: truncated runs look their complete twin up",
+    "GROUP": "phase 2: notes grouped by slot, lists written, key subsets",
+    "CEXP": "phase 2: loop over the listed runs (list and table reads)",
+    "XSETUP": "expansion: a lane's share of a record, first k-mer, reverse complement",
+    "XWALK": "expansion: the walk(s) over the noted lengths",
+    "XSTEP": "expansion: one step of two k-mers (roll, canonicalise, hash, k-mer table)",
+    "TRUNC": "phase 2: truncated runs without a twin / of the sorted list",
+    "OUT": "copy-out to the result list",
 }
 CLASSES = ("vector", "scalar", "lds", "global")
 
@@ -122,18 +140,21 @@ def segments(body):
 
 
 def account(segs):
-    per = {}
+    """-> (the scan's parts with `before` and `after`, the parts `after` is made of)"""
+    per, per2 = {}, {}
     for part, cnt in segs:
         if part not in PARTS:
             raise SystemExit("unknown marker P3_PART_%s" % part)
-        q = per.setdefault(part, dict(segments=0, smallest=None, largest=None, **dict.fromkeys(CLASSES, 0)))
-        q["segments"] += 1
-        for c in CLASSES:
-            q[c] += cnt[c]
-        issue = cnt["vector"] + cnt["scalar"] + cnt["lds"] + cnt["global"]
-        q["smallest"] = issue if q["smallest"] is None else min(q["smallest"], issue)
-        q["largest"] = issue if q["largest"] is None else max(q["largest"], issue)
-    return per
+        # a part of phase 2 counts as `after` in the scan's table, and under its own name in phase 2's
+        for table, name in ((per, "after" if part in PHASE2 else part),) + (((per2, part),) if part in PHASE2 else ()):
+            q = table.setdefault(name, dict(segments=0, smallest=None, largest=None, **dict.fromkeys(CLASSES, 0)))
+            q["segments"] += 1
+            for c in CLASSES:
+                q[c] += cnt[c]
+            issue = cnt["vector"] + cnt["scalar"] + cnt["lds"] + cnt["global"]
+            q["smallest"] = issue if q["smallest"] is None else min(q["smallest"], issue)
+            q["largest"] = issue if q["largest"] is None else max(q["largest"], issue)
+    return per, per2
 
 
 def main():
@@ -156,7 +177,7 @@ def main():
             compile_asm(hipcc, out, a.define)
             text = open(out).read()
     body, meta = cut_kernel(text, a.canon, a.shared)
-    per = account(segments(body))
+    per, per2 = account(segments(body))
     scan_parts = [p for p in PARTS if p in per and p not in ("before", "after")]
     scan = {c: sum(per[p][c] for p in scan_parts) for c in CLASSES}
     scratch_ops = sum(1 for ln in body if ln.strip().startswith("scratch_"))
@@ -164,7 +185,7 @@ def main():
                   vgprs=meta.get("vgpr_count"), sgprs=meta.get("sgpr_count"), lds_bytes=meta.get("group_segment_fixed_size"),
                   scratch_bytes=meta.get("private_segment_fixed_size"), scratch_instructions=scratch_ops,
                   vgpr_spills=meta.get("vgpr_spill_count", 0), sgpr_spills=meta.get("sgpr_spill_count", 0),
-                  parts=per, scan=scan)
+                  parts=per, scan=scan, phase2=per2)
     if a.json:
         print(json.dumps(result))
         return 0
@@ -181,6 +202,13 @@ def main():
               (p, q["segments"], q["vector"], q["scalar"], q["lds"], q["global"], q["smallest"], q["largest"], PART_NAMES[p]))
     print("scan (all parts but before / after): %d vector, %d scalar, %d LDS, %d global instructions of text" %
           (scan["vector"], scan["scalar"], scan["lds"], scan["global"]))
+    print("`after`, part by part (phase 2: count_record_v2 is inlined at every call, so XSETUP / XWALK / XSTEP have a segment"
+          " per call site)")
+    for p in PHASE2:
+        if p in per2:
+            q = per2[p]
+            print("%-7s %4d %7d %7d %5d %7d %9d %8d  %s" %
+                  (p, q["segments"], q["vector"], q["scalar"], q["lds"], q["global"], q["smallest"], q["largest"], PART_NAMES[p]))
     return 0
 
 
