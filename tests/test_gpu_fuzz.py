@@ -1,11 +1,14 @@
 """Randomised parity of the global paths against the oracle: random k, read lengths (including
 reads shorter than k and empty reads), invalid-base densities, homopolymer / tandem-repeat
-stretches, buffer sizes around the 32-byte chunk and wave-tile edges, one or two adds."""
+stretches, one or two adds; and (test_random_seam_ladders_match_oracle) random features of tests/seam_cases.py on random
+wave and tile seams, with buffer sizes around the 32-byte chunk and wave-tile edges."""
 import numpy as np
 import pytest
 
 from . import oracle_lib as orc
+from . import msp_ref
 from . import refsem
+from . import seam_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -58,6 +61,38 @@ def test_random_inputs_match_oracle(ctx, seed):
     lo, hi, cnt = g.export()
     wlo, whi, wcnt = orc.global_count(data, k, orc.ORC_CANONICAL if canonical else 0)
     assert len(lo) == len(wlo)
+    assert (lo == wlo).all() and (hi == whi).all() and (cnt.astype(np.uint64) == wcnt).all()
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_random_seam_ladders_match_oracle(ctx, seed):
+    """a random k, ~20 features of the seam ladder drawn at random on random seams (a third of them tile seams) of the
+    path's own period, the buffer cut at a random size around a chunk, wave or tile edge; one add or two (the second
+    buffer: the first one shifted by a random pad, which moves every feature off its seam and the tie tags with it)"""
+    import cfrk_amd
+    rng = np.random.default_rng(3000 + seed)
+    k = int(rng.choice([8, 12, 15, 16, 17, 20, 23, 26, 29, 30, 31, 32, 33, 40, 47, 64]))
+    canonical = bool(rng.integers(0, 2))
+    period = sc.PERIOD64 if k < 16 else sc.PERIOD1 if k <= 32 else sc.PERIOD2
+    W = msp_ref.params(k).W if k >= 16 else 1
+    items = sc.items_for(rng, k, W)
+    items = [items[i] for i in rng.choice(len(items), 20, replace=False)]
+    seams = sorted({int(8 * rng.integers(1, 13)) if rng.random() < 0.33 else int(rng.integers(1, 100)) for _ in items})
+    lad = sc.ladder(period, items[:len(seams)], seams=seams)
+    unit = int(rng.choice([32, period, 8 * period]))                       # a chunk, wave or tile edge somewhere behind the first feature
+    first = (seams[0] * period + 700) // unit + 1
+    edge = unit * int(rng.integers(first, max(first, len(lad.data) // unit) + 1))
+    data = lad.data[:min(len(lad.data), edge + int(rng.integers(-33, 34)))]
+    g = cfrk_amd.GlobalCounter(ctx, k, cfrk_amd.CFRK_CANONICAL if canonical else 0, 0)
+    g.add(data)
+    whole = data
+    if rng.random() < 0.4:
+        second = np.concatenate([sc.padding(int(rng.integers(1, 32))), data, sc.padding(1)])
+        g.add(second)
+        whole = np.concatenate([data, sc.padding(1), second])
+    lo, hi, cnt = g.export()
+    wlo, whi, wcnt = orc.global_count(whole, k, orc.ORC_CANONICAL if canonical else 0)
+    assert len(lo) == len(wlo) and len(lo) > 0
     assert (lo == wlo).all() and (hi == whi).all() and (cnt.astype(np.uint64) == wcnt).all()
 
 
