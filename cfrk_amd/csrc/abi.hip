@@ -1414,6 +1414,91 @@ int cfrk_global_unitigs_compact(cfrk_ctx *ctx, const int8_t *data, const int64_t
   return download_reads(ctx, o, data_out, start_out, length_out, nullptr, nN_new, nS_new);
 }
 
+static_assert(sizeof(cfrk_read_path) == 16, "cfrk_read_path is 16 bytes without padding");
+static_assert(sizeof(cfrk_path_stats) == 32, "cfrk_path_stats is 32 bytes without padding");
+
+static int read_paths_check(cfrk_ctx *ctx, const cfrk_read_paths_in &in, const void *path_ptr, const void *paths, uint64_t cap_paths,
+                            int64_t *n_paths_out, cfrk_path_stats *stats) {
+  if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "read paths before begin: the job supplies the strand rule");
+  if (in.nR < 0 || in.n_hits < 0 || in.nS < 0 || in.n_links < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (!n_paths_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL n_paths_out");
+  if (!stats) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL stats");
+  if (!in.d_hit_ptr || !path_ptr) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL hit_ptr or path_ptr");
+  if (in.n_hits > 0 && !in.d_hits) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL hits with n_hits above 0");
+  if (in.nS > 0 && (!in.d_rec || !in.d_link_ptr)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (in.n_links > 0 && !in.d_links) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL links with n_links above 0");
+  if (cap_paths > 0 && !paths) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL array with a capacity above 0");
+  if ((uint64_t)in.nS >= (1ull << 32)) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld unitigs: a hit names its unitig in 32 bits", (long long)in.nS);
+  if ((uint64_t)in.n_hits >= (1ull << 32)) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld hits: support counts in 32 bits", (long long)in.n_hits);
+  *n_paths_out = 0;
+  stats->n_paths = stats->n_steps = stats->n_gaps = stats->n_unlinked = 0;
+  return CFRK_OK;
+}
+
+static int read_paths_fit(cfrk_ctx *ctx, int64_t n_paths, uint64_t cap_paths) {
+  if ((uint64_t)n_paths <= cap_paths) return CFRK_OK;
+  return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "read paths: %lld paths, room for %llu", (long long)n_paths, (unsigned long long)cap_paths);
+}
+
+int cfrk_global_read_paths_device(cfrk_ctx *ctx, const int64_t *d_hit_ptr, int64_t nR, const cfrk_read_hit *d_hits, int64_t n_hits,
+                                  const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr, const cfrk_unitig_link *d_links,
+                                  int64_t n_links, int64_t *d_path_ptr, cfrk_read_path *d_paths, uint64_t cap_paths,
+                                  int64_t *n_paths_out, uint32_t *d_support, cfrk_path_stats *stats) {
+  if (!ctx) return CFRK_ERR_ARG;
+  const cfrk_read_paths_in in = {d_hit_ptr, nR, d_hits, n_hits, d_rec, nS, d_link_ptr, d_links, n_links};
+  int rc = read_paths_check(ctx, in, d_path_ptr, d_paths, cap_paths, n_paths_out, stats);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int64_t n_paths = 0;
+  if ((rc = cfrk_read_paths_measure(ctx, in, d_path_ptr, d_support, &n_paths, stats))) return rc;
+  *n_paths_out = n_paths;
+  if ((rc = read_paths_fit(ctx, n_paths, cap_paths)) || n_paths == 0) return rc;
+  return cfrk_read_paths_fill(ctx, in, d_paths, n_paths);
+}
+
+int cfrk_global_read_paths(cfrk_ctx *ctx, const int64_t *hit_ptr, int64_t nR, const cfrk_read_hit *hits, int64_t n_hits,
+                           const cfrk_unitig *rec, int64_t nS, const int64_t *link_ptr, const cfrk_unitig_link *links,
+                           int64_t n_links, int64_t *path_ptr, cfrk_read_path *paths, uint64_t cap_paths, int64_t *n_paths_out,
+                           uint32_t *support, cfrk_path_stats *stats) {
+  if (!ctx) return CFRK_ERR_ARG;
+  const cfrk_read_paths_in host = {hit_ptr, nR, hits, n_hits, rec, nS, link_ptr, links, n_links};
+  int rc = read_paths_check(ctx, host, path_ptr, paths, cap_paths, n_paths_out, stats);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // [hit_ptr | hits | records | link_ptr | links | support] in a slot of their own, [path_ptr | paths] in another
+  Carve c;
+  const size_t hptr_bytes = ((size_t)nR + 1) * 8, hit_bytes = (size_t)n_hits * sizeof *hits, rec_bytes = (size_t)nS * sizeof *rec,
+               lptr_bytes = nS ? ((size_t)nS + 1) * 8 : 0, link_bytes = (size_t)n_links * sizeof *links,
+               sup_bytes = support ? (size_t)n_links * 4 : 0;
+  const size_t o_hptr = c.part(hptr_bytes), o_hits = c.part(hit_bytes), o_rec = c.part(rec_bytes), o_lptr = c.part(lptr_bytes),
+               o_links = c.part(link_bytes), o_sup = c.part(sup_bytes);
+  void *d_in, *d_out;
+  if ((rc = cfrk_pool_get(ctx, BUF_READ_PATHS_IN, c.end, &d_in))) return rc;
+  const struct { size_t off, bytes; const void *src; } up[6] = {{o_hptr, hptr_bytes, hit_ptr}, {o_hits, hit_bytes, hits}, {o_rec, rec_bytes, rec},
+                                                               {o_lptr, lptr_bytes, link_ptr}, {o_links, link_bytes, links},
+                                                               {o_sup, sup_bytes, support}};
+  for (const auto &u : up)
+    if (u.bytes) HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, u.off), u.src, u.bytes, hipMemcpyHostToDevice, ctx->stream));
+  const cfrk_read_paths_in in = {carve_at<int64_t>(d_in, o_hptr), nR, carve_at<cfrk_read_hit>(d_in, o_hits), n_hits,
+                                 carve_at<cfrk_unitig>(d_in, o_rec), nS, carve_at<int64_t>(d_in, o_lptr),
+                                 carve_at<cfrk_unitig_link>(d_in, o_links), n_links};
+  uint32_t *d_support = sup_bytes ? carve_at<uint32_t>(d_in, o_sup) : nullptr;
+  if ((rc = cfrk_pool_get(ctx, BUF_READ_PATHS_OUT, hptr_bytes, &d_out))) return stage_drain(ctx, rc);
+  int64_t n_paths = 0;
+  if ((rc = cfrk_read_paths_measure(ctx, in, (int64_t *)d_out, d_support, &n_paths, stats))) {
+    memset(path_ptr, 0, hptr_bytes);                   // refused: everything 0, support as it was
+    return stage_drain(ctx, rc);
+  }
+  *n_paths_out = n_paths;
+  if (sup_bytes) HIP_TRY(ctx, hipMemcpyAsync(support, d_support, sup_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = cfrk_memcpy_d2h(ctx, path_ptr, d_out, hptr_bytes))) return rc;
+  if ((rc = read_paths_fit(ctx, n_paths, cap_paths)) || n_paths == 0) return rc;
+  // (the rows go where path_ptr was: it is down already)
+  if ((rc = cfrk_pool_get(ctx, BUF_READ_PATHS_OUT, (size_t)n_paths * sizeof *paths, &d_out))) return rc;
+  if ((rc = cfrk_read_paths_fill(ctx, in, (cfrk_read_path *)d_out, n_paths))) return rc;
+  return cfrk_memcpy_d2h(ctx, paths, d_out, (size_t)n_paths * sizeof *paths);
+}
+
 /* ------------------------------------------------------------------ digital normalisation */
 
 static int normalize_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, int64_t batch_reads, const void *data, const void *start,

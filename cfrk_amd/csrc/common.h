@@ -68,6 +68,8 @@ enum {  // pool slots
   BUF_UNITIG_COMPACT,                         // unitig compaction (unitig_compact.hip): error / size words, links between elements, the rank states, the cycles' minima, the components, the in-rows, the scans' scratch
   BUF_UNITIG_COMPACT_AUX,                     // the sort's payload, lengths and member counts with their scans, the members' list
   BUF_UNITIG_COMPACT_IN, BUF_UNITIG_COMPACT_OUT,  // staging of cfrk_global_unitigs_compact alone (the unitigs, records, link_ptr, links, drop in; the unitigs, records, into out)
+  BUF_READ_PATHS,                             // read paths (read_paths.hip): error / size words, the start flags and their scan, the in-rows, the scans' scratch
+  BUF_READ_PATHS_IN, BUF_READ_PATHS_OUT,      // staging of cfrk_global_read_paths alone (hit_ptr, hits, records, link_ptr, links, support in; path_ptr, paths out)
   BUF_NSLOTS
 };
 
@@ -263,6 +265,16 @@ struct cfrk_unitigs_in {
 int cfrk_unitigs_compact_measure(cfrk_ctx *ctx, const cfrk_unitigs_in &in, int64_t *nN_out, int64_t *nS_out);
 int cfrk_unitigs_compact_emit(cfrk_ctx *ctx, const cfrk_unitigs_in &in, int8_t *d_data, int64_t *d_start, int32_t *d_length,
                               cfrk_unitig *d_rec, cfrk_unitig_pos *d_into, int64_t nN_out, int64_t nS_out);
+// read_paths.hip: the paths of nR >= 0 reads through the link rows in two steps: the checks, the join, support (unless
+// NULL), the scan and d_path_ptr (synchronises once: CFRK_ERR_LAYOUT, or *n_paths and *stats); then the rows into
+// d_paths (room for n_paths >= 1 of them), left enqueued.  The fill step reads what the measure step left in the pool.
+struct cfrk_read_paths_in {
+  const int64_t *d_hit_ptr; int64_t nR; const cfrk_read_hit *d_hits; int64_t n_hits;
+  const cfrk_unitig *d_rec; int64_t nS; const int64_t *d_link_ptr; const cfrk_unitig_link *d_links; int64_t n_links;
+};
+int cfrk_read_paths_measure(cfrk_ctx *ctx, const cfrk_read_paths_in &in, int64_t *d_path_ptr, uint32_t *d_support,
+                            int64_t *n_paths, cfrk_path_stats *stats);
+int cfrk_read_paths_fill(cfrk_ctx *ctx, const cfrk_read_paths_in &in, cfrk_read_path *d_paths, int64_t n_paths);
 // sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
 // enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
 int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,

@@ -94,18 +94,21 @@ int ug_scan_bytes(cfrk_ctx *ctx, bool canon, uint64_t n, size_t *bytes) {
   return CFRK_OK;
 }
 
-// the error word set to "no unitig yet", then the check; not canonical: the in-degrees, their scan and the in-rows
-int ug_check_launch(cfrk_ctx *ctx, const UGraph &g, bool canon, int grid, void *scan_tmp, size_t scan_bytes) {
+// the error word set to "no unitig yet", then the check; not canonical: the in-degrees, their scan and the in-rows.
+// in_rows false: a caller that never reads in() gets the check and the in-degree refusal alone (in_off holds counts,
+// in_cur, in_src and the scan's scratch are not touched)
+int ug_check_launch(cfrk_ctx *ctx, const UGraph &g, bool canon, int grid, void *scan_tmp, size_t scan_bytes, bool in_rows = true) {
   HIP_TRY(ctx, hipMemsetAsync(g.ctr, 0xFF, 8, ctx->stream));
   if (canon) {
     hipLaunchKernelGGL(ut_check_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, g);
     return CFRK_OK;
   }
   HIP_TRY(ctx, hipMemsetAsync(g.in_off, 0, (g.nS + 1) * 8, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(g.in_cur, 0, g.nS * 4, ctx->stream));
+  if (in_rows) HIP_TRY(ctx, hipMemsetAsync(g.in_cur, 0, g.nS * 4, ctx->stream));
   hipLaunchKernelGGL(ut_check_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, g);
   hipLaunchKernelGGL(ut_indeg_kernel, dim3(grid), dim3(256), 0, ctx->stream, g);
   HIP_TRY(ctx, hipGetLastError());
+  if (!in_rows) return CFRK_OK;
   HIP_TRY(ctx, hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, g.in_off, (size_t)(g.nS + 1), ctx->stream));
   hipLaunchKernelGGL(ut_in_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream, g);
   return CFRK_OK;

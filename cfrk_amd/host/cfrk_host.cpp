@@ -799,9 +799,9 @@ static size_t format_unitigs(const int8_t *data, const int64_t *start, const int
   return buf ? (size_t)(p - buf) : s;
 }
 
-size_t cfrk_host_format_gfa(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
-                            const int64_t *link_ptr, const void *links, int k, char *buf, size_t cap) {
-  (void)cap;
+// the GFA text; with `support`, "\tRC:i:<c>" behind every L line (cfrk_host_format_gfa_support has the rule for c)
+static size_t format_gfa(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
+                         const int64_t *link_ptr, const void *links, const uint32_t *support, bool canonical, int k, char *buf) {
   size_t s = 11;                                         // "H\tVN:Z:1.0\n"
   char *p = buf;
   if (buf) { memcpy(p, "H\tVN:Z:1.0\n", 11); p += 11; }
@@ -831,16 +831,43 @@ size_t cfrk_host_format_gfa(const int8_t *data, const int64_t *start, const int3
     for (int64_t i = link_ptr[j]; i < link_ptr[j + 1]; ++i) {
       uint32_t to; bool fm, tm;
       get_link(links, i, &to, &fm, &tm);
-      if (!buf) { s += 2 + len_u64((uint64_t)j) + 3 + len_u64(to) + 3 + len_u64(overlap) + 2; continue; }
+      uint64_t c = 0;
+      if (support) {
+        c = support[i];
+        if (canonical && (int64_t)to < nS)               // the mirror (to,!tm) -> (j,!fm), where it is another row
+          for (int64_t x = link_ptr[to]; x < link_ptr[to + 1]; ++x) {
+            uint32_t mt; bool mfm, mtm;
+            get_link(links, x, &mt, &mfm, &mtm);
+            if (mt != (uint32_t)j || mfm == tm || mtm == fm) continue;
+            if (x != i) c += support[x];
+            break;
+          }
+      }
+      if (!buf) { s += 2 + len_u64((uint64_t)j) + 3 + len_u64(to) + 3 + len_u64(overlap) + 2 + (support ? 6 + len_u64(c) : 0); continue; }
       *p++ = 'L'; *p++ = '\t';
       p = put_u64(p, (uint64_t)j);
       *p++ = '\t'; *p++ = fm ? '-' : '+'; *p++ = '\t';
       p = put_u64(p, to);
       *p++ = '\t'; *p++ = tm ? '-' : '+'; *p++ = '\t';
       p = put_u64(p, overlap);
-      *p++ = 'M'; *p++ = '\n';
+      *p++ = 'M';
+      if (support) { memcpy(p, "\tRC:i:", 6); p = put_u64(p + 6, c); }
+      *p++ = '\n';
     }
   return buf ? (size_t)(p - buf) : s;
+}
+
+size_t cfrk_host_format_gfa(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
+                            const int64_t *link_ptr, const void *links, int k, char *buf, size_t cap) {
+  (void)cap;
+  return format_gfa(data, start, length, rec, nS, link_ptr, links, nullptr, false, k, buf);
+}
+
+size_t cfrk_host_format_gfa_support(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
+                                    const int64_t *link_ptr, const void *links, const uint32_t *support, int canonical, int k,
+                                    char *buf, size_t cap) {
+  (void)cap;
+  return format_gfa(data, start, length, rec, nS, link_ptr, links, support, canonical != 0, k, buf);
 }
 
 size_t cfrk_host_format_gaf(const int32_t *read_length, int64_t n_reads, const int64_t *hit_ptr, const void *hits,
@@ -872,6 +899,62 @@ size_t cfrk_host_format_gaf(const int32_t *read_length, int64_t n_reads, const i
       *p++ = minus ? '<' : '>';
       p = put_u64(p, j); *p++ = '\t';
       p = put_u64(p, ln); *p++ = '\t';
+      p = put_u64(p, ps); *p++ = '\t';
+      p = put_u64(p, ps + m); *p++ = '\t';
+      p = put_u64(p, m); *p++ = '\t';
+      p = put_u64(p, m); *p++ = '\t';
+      memcpy(p, "255\t", 4); p += 4;
+      memcpy(p, "cg:Z:", 5); p = put_u64(p + 5, m);
+      *p++ = '='; *p++ = '\n';
+    }
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
+size_t cfrk_host_format_gaf_paths(const int32_t *read_length, int64_t n_reads, const int64_t *hit_ptr, const void *hits,
+                                  const int64_t *path_ptr, const void *paths, const int32_t *unitig_length, int k, char *buf, size_t cap) {
+  (void)cap;
+  size_t s = 0;
+  char *p = buf;
+  const uint64_t k1 = k > 0 ? (uint64_t)k - 1 : 0;
+  for (int64_t i = 0; i < n_reads; ++i) {
+    const uint64_t rl = read_length[i] > 0 ? (uint64_t)read_length[i] : 0;
+    for (int64_t t = path_ptr[i]; t < path_ptr[i + 1]; ++t) {
+      uint32_t w[4];                                     // hit_first, n_hits, read_off, n_windows
+      memcpy(w, (const char *)paths + 16 * t, 16);
+      const int64_t h0 = hit_ptr[i] + (int64_t)w[0], h1 = h0 + (int64_t)w[1];
+      const uint64_t a = w[2], m = (uint64_t)w[3] + k1;
+      uint64_t pl = 0, ps = 0;
+      size_t names = 0;
+      for (int64_t h = h0; h < h1; ++h) {
+        uint32_t x[4];                                   // unitig, unitig_at, read_off, n_windows
+        memcpy(x, (const char *)hits + 16 * h, 16);
+        const uint64_t ln = unitig_length[x[0]] > 0 ? (uint64_t)unitig_length[x[0]] : 0;
+        pl += h == h0 ? ln : (ln >= k1 ? ln - k1 : 0);   // every segment after the first overlaps k - 1 bases
+        names += 1 + len_u64(x[0]);
+        if (h == h0) {                                   // ps of cfrk_host_format_gaf, for the first hit
+          const uint64_t off = x[1] >> 1, hm = (uint64_t)x[3] + k1;
+          ps = (x[1] & 1u) ? (ln >= off + hm ? ln - off - hm : 0) : off;
+        }
+      }
+      if (!buf) {
+        s += len_u64((uint64_t)i) + 1 + len_u64(rl) + 1 + len_u64(a) + 1 + len_u64(a + m) + 3 + names + 1 + len_u64(pl) + 1 +
+             len_u64(ps) + 1 + len_u64(ps + m) + 1 + 2 * (len_u64(m) + 1) + 4 + 5 + len_u64(m) + 2;
+        continue;
+      }
+      p = put_u64(p, (uint64_t)i); *p++ = '\t';
+      p = put_u64(p, rl); *p++ = '\t';
+      p = put_u64(p, a); *p++ = '\t';
+      p = put_u64(p, a + m); *p++ = '\t';
+      *p++ = '+'; *p++ = '\t';
+      for (int64_t h = h0; h < h1; ++h) {
+        uint32_t x[2];
+        memcpy(x, (const char *)hits + 16 * h, 8);
+        *p++ = (x[1] & 1u) ? '<' : '>';
+        p = put_u64(p, x[0]);
+      }
+      *p++ = '\t';
+      p = put_u64(p, pl); *p++ = '\t';
       p = put_u64(p, ps); *p++ = '\t';
       p = put_u64(p, ps + m); *p++ = '\t';
       p = put_u64(p, m); *p++ = '\t';

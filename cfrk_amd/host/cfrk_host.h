@@ -186,6 +186,30 @@ size_t cfrk_host_format_bulges(uint32_t round, const int8_t *data, const int64_t
 size_t cfrk_host_format_gaf(const int32_t *read_length, int64_t n_reads, const int64_t *hit_ptr, const void *hits,
                             const int32_t *unitig_length, int k, char *buf, size_t cap);
 
+/* Read paths as GAF (`cfrk --unitigs-map QFILE --unitigs-map-out MFILE --unitigs-map-paths`): the arguments of
+ * cfrk_host_format_gaf and path_ptr = n_reads + 1 offsets, paths = rows of cfrk_read_path (cfrk_abi.h: 16 bytes --
+ * hit_first inside the read's hit row, n_hits, read_off, n_windows as uint32) as cfrk_global_read_paths wrote them.  One
+ * line per path, in CSR order, with m = n_windows + k - 1:
+ *   "<read i>\t<read_length[i]>\t<read_off>\t<read_off+m>\t+\t<path>\t<PL>\t<ps>\t<ps+m>\t<m>\t<m>\t255\tcg:Z:<m>=\n"
+ * <path> is its hits' segments in GAF notation as cfrk_host_format_bulges spells them (">3<7>9"); PL is the sum of the
+ * segments' LN minus (n_hits - 1)(k - 1); ps is the first hit's ps as cfrk_host_format_gaf defines it.  A path of one hit
+ * gives exactly the line cfrk_host_format_gaf gives for that hit.  Returns bytes needed / written (buf may be NULL to
+ * size). */
+size_t cfrk_host_format_gaf_paths(const int32_t *read_length, int64_t n_reads, const int64_t *hit_ptr, const void *hits,
+                                  const int64_t *path_ptr, const void *paths, const int32_t *unitig_length, int k, char *buf, size_t cap);
+
+/* The GFA of cfrk_host_format_gfa with the reads that walk every link (`cfrk --unitigs-gfa GFILE --unitigs-map QFILE
+ * --unitigs-link-support`): the same text with "\tRC:i:<c>" appended to every L line; support = n_links counters as
+ * cfrk_global_read_paths left them (must not be NULL).  Not canonical, or the link is its own mirror: c = support[r].
+ * Canonical: c = support[r] + support[r'] where r' is the mirror row (v,!ov) -> (u,!ou) of r = (u,ou) -> (v,ov), when
+ * that row exists and is another row; a read and its reverse complement then tag the same two lines alike.  The one
+ * exception: at even k, rows into or out of a palindromic single-node unitig keep per-strand numbers, because its hits
+ * are always '+': a read and its reverse complement enter it through different rows that are not each other's mirror.
+ * Returns bytes needed / written (buf may be NULL to size). */
+size_t cfrk_host_format_gfa_support(const int8_t *data, const int64_t *start, const int32_t *length, const void *rec, int64_t nS,
+                                    const int64_t *link_ptr, const void *links, const uint32_t *support, int canonical, int k,
+                                    char *buf, size_t cap);
+
 /* Binary global form, little endian, everything in one file:
  *   header, 32 bytes:  char magic[8] = "CFRKGLB1"; uint32 k; uint32 flags (bit 0: canonical counting,
  *                      bit 1: two-word keys, i.e. k > 32); uint64 n (records); uint64 sum of counts

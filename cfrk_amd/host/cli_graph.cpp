@@ -1,5 +1,6 @@
 // cli_graph.cpp -- the unitig graph of the finished count, for the `cfrk` command: simplify (--unitigs-clip-tips,
-// --unitigs-pop-bubbles, --unitigs-pop-bulges), write (--unitigs-out, --unitigs-links, --unitigs-gfa), map reads onto it (--unitigs-map).
+// --unitigs-pop-bubbles, --unitigs-pop-bulges), write (--unitigs-out, --unitigs-links, --unitigs-gfa), map reads onto it (--unitigs-map)
+// and thread them through it (--unitigs-map-paths, --unitigs-link-support, --unitigs-map-stats).
 #include "cli_util.h"
 
 namespace {
@@ -124,6 +125,7 @@ int simplify_unitigs(const Options &o, cfrk_ctx *ctx) {
 }
 
 int write_unitigs(const Options &o, cfrk_ctx *ctx) {
+  if (!o.unitigs_out && o.link_support) return 0;         // (GFILE alone, with the RC tags: write_unitigs_map fetches the graph and writes it)
   UnitigGraph g;
   const bool with_links = o.unitigs_links || o.unitigs_gfa;
   int rc;
@@ -137,7 +139,7 @@ int write_unitigs(const Options &o, cfrk_ctx *ctx) {
     });
     if ((rc = write_file(o.unitigs_out, buf))) return rc;
   }
-  if (o.unitigs_gfa) {
+  if (o.unitigs_gfa && !o.link_support) {                 // (--unitigs-link-support: write_unitigs_map writes GFILE, with the RC tags)
     std::string buf;
     format_into(buf, [&](char *out, size_t room) {
       return cfrk_host_format_gfa(g.data.data(), g.start.data(), g.length.data(), g.rec.data(), g.nS, g.link_ptr.data(), g.links.data(), o.k, out, room);
@@ -149,7 +151,10 @@ int write_unitigs(const Options &o, cfrk_ctx *ctx) {
 
 // --unitigs-map QFILE --unitigs-map-out MFILE: the unitigs into device arrays (a sizes-only call, then arrays of that
 // size), where they stay; the position map from them (cfrk_global_unitig_index_device); the hits of QFILE's reads q
-// (cfrk_global_read_hits) as GAF, the segment names those of --unitigs-gfa (cfrk_host_format_gaf)
+// (cfrk_global_read_hits) as GAF, the segment names those of --unitigs-gfa (cfrk_host_format_gaf).
+// --unitigs-map-paths, --unitigs-link-support, --unitigs-map-stats: the hits joined across the links of that same graph
+// (cfrk_global_read_paths); MFILE then holds one line per path (cfrk_host_format_gaf_paths), GFILE the RC:i: tags
+// (cfrk_host_format_gfa_support), SFILE "reads hits paths steps gaps unlinked"
 int write_unitigs_map(const Options &o, cfrk_ctx *ctx, const cfrk_batch &q) {
   int64_t nN = 0, nS = 0;
   int rc = cfrk_global_unitigs_device(ctx, o.unitigs_min_count, nullptr, 0, nullptr, nullptr, nullptr, 0, &nN, &nS);
@@ -174,6 +179,46 @@ int write_unitigs_map(const Options &o, cfrk_ctx *ctx, const cfrk_batch &q) {
                   [&] { hits.resize((size_t)n_hits); });
   if (rc) return die(ctx, rc, "cfrk_global_read_hits");
   std::string buf;
-  format_into(buf, [&](char *out, size_t room) { return cfrk_host_format_gaf(q.length, q.nS, hit_ptr.data(), hits.data(), ulen.data(), o.k, out, room); });
-  return write_file(o.unitigs_map_out, buf);
+  if (!o.map_paths && !o.link_support && !o.map_stats) {
+    format_into(buf, [&](char *out, size_t room) { return cfrk_host_format_gaf(q.length, q.nS, hit_ptr.data(), hits.data(), ulen.data(), o.k, out, room); });
+    return write_file(o.unitigs_map_out, buf);
+  }
+  UnitigGraph g;
+  if ((rc = g.fetch(ctx, o.unitigs_min_count, true))) return rc;
+  std::vector<int64_t> path_ptr((size_t)q.nS + 1);
+  std::vector<cfrk_read_path> paths;
+  std::vector<uint32_t> support(o.link_support ? (size_t)g.n_links : 0);
+  int64_t n_paths = 0;
+  cfrk_path_stats stats;
+  // a sizes-only call without support, then the call that fits: the steps are counted once
+  auto call = [&](uint32_t *sup) {
+    return cfrk_global_read_paths(ctx, hit_ptr.data(), q.nS, hits.data(), n_hits, g.rec.data(), g.nS, g.link_ptr.data(), g.links.data(), g.n_links,
+                                  path_ptr.data(), paths.data(), paths.size(), &n_paths, sup, &stats);
+  };
+  rc = call(nullptr);
+  if (!rc || rc == CFRK_ERR_SMALL_BUF) {
+    paths.resize((size_t)n_paths);
+    rc = call(o.link_support ? support.data() : nullptr);
+  }
+  if (rc) return die(ctx, rc, "cfrk_global_read_paths");
+  format_into(buf, [&](char *out, size_t room) {
+    return o.map_paths ? cfrk_host_format_gaf_paths(q.length, q.nS, hit_ptr.data(), hits.data(), path_ptr.data(), paths.data(), ulen.data(), o.k, out, room)
+                       : cfrk_host_format_gaf(q.length, q.nS, hit_ptr.data(), hits.data(), ulen.data(), o.k, out, room);
+  });
+  if ((rc = write_file(o.unitigs_map_out, buf))) return rc;
+  if (o.link_support) {
+    buf.clear();
+    format_into(buf, [&](char *out, size_t room) {
+      return cfrk_host_format_gfa_support(g.data.data(), g.start.data(), g.length.data(), g.rec.data(), g.nS, g.link_ptr.data(), g.links.data(),
+                                          support.data(), o.canonical ? 1 : 0, o.k, out, room);
+    });
+    if ((rc = write_file(o.unitigs_gfa, buf))) return rc;
+  }
+  if (o.map_stats) {
+    char line[160];
+    snprintf(line, sizeof line, "%lld\t%lld\t%llu\t%llu\t%llu\t%llu\n", (long long)q.nS, (long long)n_hits, (unsigned long long)stats.n_paths,
+             (unsigned long long)stats.n_steps, (unsigned long long)stats.n_gaps, (unsigned long long)stats.n_unlinked);
+    if ((rc = write_file(o.map_stats, line))) return rc;
+  }
+  return 0;
 }

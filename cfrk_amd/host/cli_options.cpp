@@ -117,6 +117,7 @@ const Row TABLE[] = {
   count("--bulge-max-hops", 1, &O::bulge_max_hops, &O::bulge_opt_set), count("--bulge-max-visits", 0, &O::bulge_max_visits, &O::bulge_opt_set),
   str("--unitigs-out", &O::unitigs_out), str("--unitigs-gfa", &O::unitigs_gfa), str("--unitigs-map", &O::unitigs_map),
   str("--unitigs-map-out", &O::unitigs_map_out), count("--unitigs-min-count", 0, &O::unitigs_min_count, &O::unitigs_opt_set),
+  flag("--unitigs-map-paths", &O::map_paths), flag("--unitigs-link-support", &O::link_support), str("--unitigs-map-stats", &O::map_stats),
 };
 
 // the value v of row r into o; 1 (the refusal printed) when it is not one the kind takes
@@ -208,6 +209,9 @@ int check_options(const Options &o) {
   if (o.unitigs_gfa && not_global_on_one) return needs_global_on_one("--unitigs-gfa");
   if ((o.unitigs_map != nullptr) != (o.unitigs_map_out != nullptr)) return refuse("--unitigs-map QFILE and --unitigs-map-out MFILE go together");
   if (o.unitigs_map && not_global_on_one) return needs_global_on_one("--unitigs-map");
+  if (o.map_paths && !o.unitigs_map) return refuse("--unitigs-map-paths needs --unitigs-map QFILE");
+  if (o.link_support && !(o.unitigs_map && o.unitigs_gfa)) return refuse("--unitigs-link-support needs --unitigs-map QFILE and --unitigs-gfa GFILE");
+  if (o.map_stats && !o.unitigs_map) return refuse("--unitigs-map-stats needs --unitigs-map QFILE");
   if (o.clip_tips && !graph_out) return refuse("--unitigs-clip-tips needs --unitigs-out UFILE, --unitigs-gfa GFILE or --unitigs-map QFILE");
   if (o.pop_bubbles && !graph_out) return refuse("--unitigs-pop-bubbles needs --unitigs-out UFILE, --unitigs-gfa GFILE or --unitigs-map QFILE");
   if (o.pop_bulges && !graph_out) return refuse("--unitigs-pop-bulges needs --unitigs-out UFILE, --unitigs-gfa GFILE or --unitigs-map QFILE");

@@ -56,6 +56,17 @@
 //                    graph, as GAF: one line per hit, a maximal stretch of a read's k-mers that step along one unitig on
 //                    one strand, the segment names those of --unitigs-gfa (cfrk_global_unitig_index_device,
 //                    cfrk_global_read_hits, cfrk_host_format_gaf)
+//   --unitigs-map-paths  (with --unitigs-map) MFILE gets one line per PATH, not per hit: a read's consecutive hits that
+//                    leave one oriented unitig at its end and enter the next at its head one window later, across a
+//                    link of the graph that is written, are one walk, spelled >3<7>9 (cfrk_global_read_paths,
+//                    cfrk_host_format_gaf_paths).  A path of one hit is the line it was
+//   --unitigs-link-support  (with --unitigs-map and --unitigs-gfa) every L line of GFILE gets "\tRC:i:<c>": the reads of
+//                    QFILE that walk across the link, in a --canonical run together with those that walk across its
+//                    mirror (cfrk_host_format_gfa_support)
+//   --unitigs-map-stats SFILE  (with --unitigs-map) one line of six tab-separated numbers: reads, hits, paths, steps
+//                    (joined pairs of hits), gaps (pairs that are not window-adjacent) and unlinked (adjacent pairs
+//                    without a link: 0 on the graph's own complete links).  All three act on the graph that is
+//                    written, after any tip, bubble or bulge loop; without them every byte written is what it was
 //   --unitigs-clip-tips [--tip-max-kmers M] [--tip-ratio R] [--tip-rounds N] [--tip-report RFILE]  (with --unitigs-out,
 //                    --unitigs-gfa or --unitigs-map) clip tips off the graph before anything is written: up to N rounds
 //                    (default 4) of unitigs, links, the tip rule and a mask of the tips' k-mers, ended by the first
@@ -229,6 +240,9 @@ struct Options {
   const char *unitigs_gfa = nullptr;  // --unitigs-gfa GFILE
   const char *unitigs_map = nullptr;      // --unitigs-map QFILE
   const char *unitigs_map_out = nullptr;  // --unitigs-map-out MFILE
+  bool map_paths = false;             // --unitigs-map-paths
+  bool link_support = false;          // --unitigs-link-support
+  const char *map_stats = nullptr;    // --unitigs-map-stats SFILE
   bool clip_tips = false;             // --unitigs-clip-tips
   uint32_t tip_max_kmers = 0;         // --tip-max-kmers M (0: k)
   uint32_t tip_ratio_q8 = 512;        // --tip-ratio R, in 256ths

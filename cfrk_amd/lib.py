@@ -88,6 +88,9 @@ CFRK_BULGE_MAX_VISITS = 65536        # the largest search budget, in links looke
 # what one bulge call found (cfrk_bulge_stats)
 BULGE_STATS_DTYPE = np.dtype([("arms", "<i8"), ("popped", "<i8"), ("undecided", "<i8")])
 CFRK_COMPACT_TILE_BYTES = 4096       # unitig compaction: bytes of data_out per workgroup of the emit
+# cfrk_read_path / cfrk_path_stats: a read's walk through the graph as a range of its hits; what a read_paths call counted
+READ_PATH_DTYPE = np.dtype([("hit_first", "<u4"), ("n_hits", "<u4"), ("read_off", "<u4"), ("n_windows", "<u4")])
+PATH_STATS_DTYPE = np.dtype([("n_paths", "<u8"), ("n_steps", "<u8"), ("n_gaps", "<u8"), ("n_unlinked", "<u8")])
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libcfrk_hip.so")
@@ -178,6 +181,8 @@ def load_library():
         "cfrk_global_unitig_bulges_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, u64, C.POINTER(i64), vp], C.c_int),
         "cfrk_global_unitigs_compact": ([vp, vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, u64, vp, vp, vp, u64, vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "cfrk_global_unitigs_compact_device": ([vp, vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, u64, vp, vp, vp, u64, vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "cfrk_global_read_paths": ([vp, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, vp, u64, C.POINTER(i64), vp, vp], C.c_int),
+        "cfrk_global_read_paths_device": ([vp, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, vp, u64, C.POINTER(i64), vp, vp], C.c_int),
         "cfrk_global_query_reads": ([vp, vp, vp, vp, i64, i64, vp], C.c_int),
         "cfrk_global_query_reads_device": ([vp, vp, i64, vp], C.c_int),
         "cfrk_global_read_stats": ([vp, vp, vp, vp, i64, i64, C.c_uint32, vp], C.c_int),
@@ -1063,6 +1068,60 @@ class GlobalCounter:
             e.n_hits = n.value
             raise
         return n.value
+
+    def read_paths(self, hit_ptr, hits, rec, link_ptr, links, support=None):
+        """the hits of every read (read_hits()) joined across the links -> (path_ptr int64[nR + 1], paths
+        READ_PATH_DTYPE[n_paths], support uint32[n_links], stats): CSR over reads; a path is a maximal chain of
+        consecutive hits of a read in which each leaves its oriented unitig at the end, the next enters its own at the
+        head one window later, and a link of (link_ptr, links) joins the two: hit_first (inside the read's hit row),
+        n_hits, read_off, n_windows.  links may be any sub-CSR of unitig_links(): the reads then break where rows are
+        missing.  support[r] is INCREMENTED by the steps across link r: pass the array of an earlier batch to
+        accumulate, None starts from zero.  stats = {"n_paths", "n_steps", "n_gaps", "n_unlinked"}.  Raises CfrkError
+        (CFRK_ERR_LAYOUT, the message naming the unitig or the read) when the rows are not link rows or the hits not
+        hits on these unitigs; support is then untouched.  A sizes-only call, then the call into an array of exactly
+        that size."""
+        hit_ptr = np.ascontiguousarray(hit_ptr, np.int64)
+        hits = np.ascontiguousarray(hits, READ_HIT_DTYPE)
+        rec = np.ascontiguousarray(rec, UNITIG_DTYPE)
+        link_ptr = np.ascontiguousarray(link_ptr, np.int64)
+        links = np.ascontiguousarray(links, UNITIG_LINK_DTYPE)
+        if len(hit_ptr) < 1 or len(link_ptr) != len(rec) + 1:
+            raise ValueError("hit_ptr is empty, or link_ptr has not one entry more than rec")
+        if support is None:
+            support = np.zeros(len(links), np.uint32)
+        if support.dtype != np.uint32 or not support.flags.c_contiguous or len(support) != len(links):
+            raise ValueError("support is not a contiguous uint32 array with one entry per link")
+        nR, n = len(hit_ptr) - 1, C.c_int64()
+        path_ptr, stats = np.zeros(nR + 1, np.int64), np.zeros(1, PATH_STATS_DTYPE)
+        args = (self.ctx._h, _ptr(hit_ptr), nR, _ptr(hits), len(hits), _ptr(rec), len(rec), _ptr(link_ptr), _ptr(links), len(links),
+                _ptr(path_ptr))
+        rc = self._L.cfrk_global_read_paths(*args, None, 0, C.byref(n), None, _ptr(stats))       # (no support: counted below)
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.ctx.check(rc, "cfrk_global_read_paths")
+        paths = np.zeros(n.value, READ_PATH_DTYPE)
+        self.ctx.check(self._L.cfrk_global_read_paths(*args, _ptr(paths), paths.size, C.byref(n), _ptr(support), _ptr(stats)),
+                       "cfrk_global_read_paths")
+        assert n.value == int(path_ptr[nR]) == int(stats["n_paths"][0])
+        return path_ptr, paths, support, {f: int(stats[f][0]) for f in PATH_STATS_DTYPE.names}
+
+    def read_paths_device(self, d_hit_ptr, nR, d_hits, n_hits, d_rec, nS, d_link_ptr, d_links, n_links, d_path_ptr, d_paths, cap_paths,
+                          d_support=0):
+        """device form -> (n_paths, stats); d_paths may be 0 with cap_paths 0 (sizes only); d_support may be 0 (no
+        support wanted), else its n_links words are added to.  Raises CfrkError (code CFRK_ERR_SMALL_BUF, with .n_paths
+        and .stats set, d_path_ptr and d_support complete, nothing written to d_paths) when cap_paths is too small.
+        Synchronises once, returns with the passes that write d_paths enqueued on the context stream."""
+        n, stats = C.c_int64(), np.zeros(1, PATH_STATS_DTYPE)
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_global_read_paths_device(self.ctx._h, vp(d_hit_ptr), nR, vp(d_hits), n_hits, vp(d_rec), nS, vp(d_link_ptr),
+                                                   vp(d_links), n_links, vp(d_path_ptr), vp(d_paths), cap_paths, C.byref(n),
+                                                   vp(d_support), _ptr(stats))
+        st = {f: int(stats[f][0]) for f in PATH_STATS_DTYPE.names}
+        try:
+            self.ctx.check(rc, "cfrk_global_read_paths_device")
+        except CfrkError as e:
+            e.n_paths, e.stats = n.value, st
+            raise
+        return n.value, st
 
     def mask_keys(self, keys_lo, keys_hi=None):
         """add keys to the graph mask: a masked key is no longer solid for neighbors(), unitigs(), unitig_links(),

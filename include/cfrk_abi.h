@@ -862,6 +862,81 @@ int cfrk_global_unitigs_compact(cfrk_ctx *ctx, const int8_t *data, const int64_t
                                 cfrk_unitig *rec_out, uint64_t cap_unitigs, cfrk_unitig_pos *into /* nS; may be NULL */,
                                 int64_t *nN_out, int64_t *nS_out);
 
+/* Read paths and link support: the hits of a read joined across links into walks through the graph, and how many reads
+ * walk across every link.  A pure function of the hit CSR as cfrk_global_read_hits wrote it for nR reads (hit_ptr[nR + 1],
+ * hits[n_hits]), the unitigs' records (rec[nS]; only n_kmers is read), a link CSR (link_ptr[nS + 1], links[n_links]) and
+ * the job's strand rule, which is used for the row check alone.  It needs no sequence, no index, no position map and no
+ * counts.  The link CSR is the one cfrk_global_unitig_links wrote OR ANY SUB-CSR of it: a caller may have removed rows;
+ * the call then says where reads break.
+ *   ENDS of a hit (j, off, m, n), m = unitig_at & 1, off = unitig_at >> 1, n = n_windows, N = rec[j].n_kmers: its first
+ *   window lies at pf = m ? off + n - 1 : off, its last at pl = m ? off : off + n - 1.  It ENTERS AT THE HEAD of (j,m) iff
+ *   pf == (m ? N - 1 : 0) and LEAVES AT THE END of (j,m) iff pl == (m ? 0 : N - 1).
+ *   STEP: two consecutive hits h, h' of one read are JOINED iff (a) h'.read_off == h.read_off + h.n_windows, (b) h leaves
+ *   at the end of (j,m), (c) h' enters at the head of (j',m'), and (d) row j of the link CSR holds a link whose
+ *   CFRK_LINK_FROM_MINUS bit equals m, whose `to` equals j' and whose CFRK_LINK_TO_MINUS bit equals m'.  The first such
+ *   row in CSR order is the step's link r, an index into links.  Everything is read literally: a read across the cut of
+ *   a circular unitig joins through (j,+) -> (j,+), a hairpin through (j,+) -> (j,-); a palindromic single-node unitig is
+ *   always entered and left as (v,+), because its hits have minus = 0.
+ *   PATH: a maximal chain of joined hits of one read, so a range of consecutive hits.  path_ptr[nR + 1] and
+ *   paths[n_paths] are a CSR over reads, path_ptr[0] = 0, *n_paths_out = path_ptr[nR]; a row is cfrk_read_path: hit_first
+ *   (index inside the read's hit row), n_hits, read_off, n_windows (the sum of its hits' windows, which are contiguous by
+ *   (a)).  Paths ascend by hit_first; the n_hits of a read's paths sum to its hits.
+ *   LINK SUPPORT: support[r] is INCREMENTED by the number of steps whose link is r.  The call adds and never clears: the
+ *   caller zeroes support[n_links] once, batches of reads then accumulate.  NULL support skips the output.  Counting is
+ *   directional, as the read spells it; nothing is mirrored here.  n_hits < 2^32, so one call cannot overflow a counter
+ *   it found at zero.
+ *   STATISTICS (cfrk_path_stats): n_paths; n_steps = joined pairs; n_gaps = consecutive hits of a read that fail (a);
+ *   n_unlinked = pairs that pass (a) but fail (b), (c) or (d).  Sum of support added = n_steps.
+ *   CONSEQUENCE: with the library's own hits and its own complete link CSR of the same graph n_unlinked is 0, and a
+ *   read's paths are its maximal runs of located windows: two located neighbouring windows that are not colinear are the
+ *   tail of one oriented unitig and a solid successor of it, and that is a link; the hit before the break therefore
+ *   leaves at an end, the one behind it enters at a head.
+ * Capacity (the select's protocol): when n_paths > cap_paths the call returns CFRK_ERR_SMALL_BUF with path_ptr,
+ *   *n_paths_out, stats and support complete and nothing written to paths; NULL paths with cap_paths 0 is that "sizes
+ *   only" call (give it a NULL support, or the exact call adds the steps a second time); cap_paths = n_hits is always
+ *   enough.
+ * Untrusted input.  The row check of "Unitig tips" runs in front (the same five CFRK_ERR_LAYOUT reasons naming the first
+ *   offending unitig).  Then the hits: CFRK_ERR_LAYOUT, cfrk_last_error naming the first offending read, when hit_ptr
+ *   does not start at 0, descends or leaves [0, n_hits] (hit_ptr[nR] may lie below n_hits: the hits behind it belong to
+ *   no read and are not looked at); when a hit's unitig is >= nS, its n_windows is 0, or off + n_windows > n_kmers.  A
+ *   refused row wins over a refused hit_ptr, that over a refused hit.  After an error path_ptr is all 0, the sizes and
+ *   stats are 0 and support is UNTOUCHED: the hits are checked in a pass of their own in front of the one that counts.
+ *   For any input whatever nothing outside the buffers is accessed and no loop is unbounded.
+ * CFRK_ERR_ARG: negative sizes, NULL n_paths_out / stats / hit_ptr / path_ptr, NULL hits with n_hits > 0, NULL rec /
+ *   link_ptr with nS > 0, NULL links with n_links > 0, NULL paths with cap_paths > 0, nS >= 2^32, n_hits >= 2^32.
+ *   CFRK_ERR_STATE: no job.  nR = 0 and n_hits = 0 are fine.  The job, the index, the position map and the mask are
+ *   neither read nor changed: same digest before and after.
+ * Device form (cfrk_amd/csrc/read_paths.hip): balanced by HITS, one lane per hit in the check, the join (at most 16
+ *   links of one row, one atomic add on support[r]) and the pass that writes the rows, so a read of 10^5 hits costs what
+ *   its hits cost; a hipCUB exclusive sum over the start flags numbers the paths.  No alignment requirement on any array
+ *   beyond that of its element type (4 bytes for hits, paths and support).  n_paths_out and stats are host memory; the
+ *   call synchronises ONCE, for n_paths, the statistics and the error words, and returns with the passes that write
+ *   paths enqueued.  Temporary device memory, kept in the context's pool: 4 bytes per hit and the scan's scratch; not
+ *   canonical: 8 bytes per unitig for the in-degrees the row check counts (the in-rows are not built: nothing here
+ *   reads them).  Host form: stages through the pool; synchronous. */
+typedef struct cfrk_read_path {    /* 16 bytes, no padding */
+  uint32_t hit_first;   /* index inside the read's hit row */
+  uint32_t n_hits;
+  uint32_t read_off;    /* its first window = its first base in the read */
+  uint32_t n_windows;   /* the path covers read bases [read_off, read_off + n_windows + k - 1) */
+} cfrk_read_path;
+typedef struct cfrk_path_stats {   /* 32 bytes, no padding */
+  uint64_t n_paths;
+  uint64_t n_steps;      /* joined pairs of consecutive hits            */
+  uint64_t n_gaps;       /* consecutive hits of a read that fail (a)    */
+  uint64_t n_unlinked;   /* pairs that pass (a) but fail (b), (c) or (d) */
+} cfrk_path_stats;
+int cfrk_global_read_paths_device(cfrk_ctx *ctx, const int64_t *d_hit_ptr /* nR + 1 */, int64_t nR, const cfrk_read_hit *d_hits,
+                                  int64_t n_hits, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr /* nS + 1 */,
+                                  const cfrk_unitig_link *d_links, int64_t n_links, int64_t *d_path_ptr /* nR + 1 */,
+                                  cfrk_read_path *d_paths, uint64_t cap_paths, int64_t *n_paths_out,
+                                  uint32_t *d_support /* n_links, added to; may be NULL */, cfrk_path_stats *stats);
+int cfrk_global_read_paths(cfrk_ctx *ctx, const int64_t *hit_ptr /* nR + 1 */, int64_t nR, const cfrk_read_hit *hits,
+                           int64_t n_hits, const cfrk_unitig *rec, int64_t nS, const int64_t *link_ptr /* nS + 1 */,
+                           const cfrk_unitig_link *links, int64_t n_links, int64_t *path_ptr /* nR + 1 */,
+                           cfrk_read_path *paths, uint64_t cap_paths, int64_t *n_paths_out,
+                           uint32_t *support /* n_links, added to; may be NULL */, cfrk_path_stats *stats);
+
 /* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
 
 /* How many DISTINCT k-mers will a job hold?  One streaming pass over the reads answers it to about 1 % before anything

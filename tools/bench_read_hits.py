@@ -18,9 +18,20 @@ repetition.  Per case one JSON line, appended to --out as well:
   spans          cfrk_global_read_spans_device (longest run, min_count as the case's) on the same reads
   hits_over_spans = hits / spans
 
+With --paths the same three cases measure cfrk_global_read_paths_device on the hits and the links of the case (appended
+to profiles/r32/bench_read_paths.jsonl):
+
+  hits           the yardstick: the cfrk_global_read_hits_device call that produces the hits
+  paths_sizes    cfrk_global_read_paths_device, sizes only, no support: checks, join, scan, path_ptr, the synchronisation
+  paths          the whole call into an array of exactly n_paths rows, with support
+  paths_plain    the same without support: what the atomics on support[] cost is paths - paths_plain
+  copy_hits      the byte floor: a device copy of the hit array's bytes (16 B per hit in; 16 B per path and path_ptr out
+                 are less)
+  and paths_per_read, n_steps, n_gaps, n_unlinked, one_path_share (reads that are exactly one path) and max_support
+
 Per-kernel times come from running this under `rocprofv3 --kernel-trace --stats`, in a run of its own.
 
-  python tools/bench_read_hits.py [--cases a,b,c] [--reads R] [--L L] [--glen G] [--k K] [--reps N] [--out FILE]
+  python tools/bench_read_hits.py [--paths] [--cases a,b,c] [--reads R] [--L L] [--glen G] [--k K] [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -41,8 +52,11 @@ def main():
     ap.add_argument("--k", type=int, default=31)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--error-rate", type=float, default=0.01)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r27", "bench_read_hits.jsonl"))
+    ap.add_argument("--paths", action="store_true")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "r32", "bench_read_paths.jsonl") if a.paths else os.path.join(ROOT, "profiles", "r27", "bench_read_hits.jsonl")
 
     import torch
     import cfrk_amd
@@ -108,6 +122,56 @@ def main():
         d_hptr = buf((R + 1) * 8)
         n_hits = small_buf(lambda: g.read_hits_device(*rd, d_hptr.data_ptr(), 0, 0), "n_hits")
         d_hits = buf(n_hits * 16)
+        if a.paths:
+            g.unitig_links_device(min_count, *unitigs, d_lptr.data_ptr(), d_links.data_ptr(), n_links)
+            g.read_hits_device(*rd, d_hptr.data_ptr(), d_hits.data_ptr(), n_hits)
+            ctx.sync()
+            graph = (d_hptr.data_ptr(), R, d_hits.data_ptr(), n_hits, u[3].data_ptr(), oS, d_lptr.data_ptr(), d_links.data_ptr(), n_links)
+            d_pptr = buf((R + 1) * 8)
+            n_paths, pstats = small_buf(lambda: g.read_paths_device(*graph, d_pptr.data_ptr(), 0, 0), ("n_paths", "stats"))
+            d_paths, dst = buf(n_paths * 16), buf(n_hits * 16)
+            with torch.cuda.stream(stream):
+                support = torch.zeros(max(n_links, 1), dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+
+            def copy_hits():
+                with torch.cuda.stream(stream):
+                    dst[:n_hits * 16].copy_(d_hits[:n_hits * 16])
+
+            # one call into the zeroed support: what a caller gets (the timed calls below add to it again)
+            g.read_paths_device(*graph, d_pptr.data_ptr(), d_paths.data_ptr(), n_paths, support.data_ptr())
+            ctx.sync()
+            max_support = int(support.max()) if n_links else 0
+            rows = d_pptr[:(R + 1) * 8].view(torch.int64)
+            one_path = int(((rows[1:] - rows[:-1]) == 1).sum())
+            calls = (("hits", lambda: g.read_hits_device(*rd, d_hptr.data_ptr(), d_hits.data_ptr(), n_hits)),
+                     ("paths_sizes", lambda: small_buf(lambda: g.read_paths_device(*graph, d_pptr.data_ptr(), 0, 0), "n_paths")),
+                     ("paths", lambda: g.read_paths_device(*graph, d_pptr.data_ptr(), d_paths.data_ptr(), n_paths, support.data_ptr())),
+                     ("paths_plain", lambda: g.read_paths_device(*graph, d_pptr.data_ptr(), d_paths.data_ptr(), n_paths)),
+                     ("copy_hits", copy_hits))
+            t = {name: [] for name, _ in calls}
+            for rep in range(a.reps + 1):
+                for name, fn in calls:
+                    ms = timed(fn)
+                    if rep:
+                        t[name].append(ms)
+            torch.cuda.synchronize()
+            row = {"tool": "bench_read_hits --paths", "case": case, "reads": R, "L": L, "glen": a.glen, "k": k, "reps": a.reps,
+                   "error_rate": 0.0 if case == "a" else a.error_rate, "min_count": min_count, "unitigs": oS, "n_links": n_links,
+                   "n_hits": n_hits, "n_paths": n_paths, "paths_per_read": n_paths / R, "n_steps": pstats["n_steps"],
+                   "n_gaps": pstats["n_gaps"], "n_unlinked": pstats["n_unlinked"], "one_path_share": one_path / R,
+                   "max_support": max_support, "steps_per_link": pstats["n_steps"] / max(n_links, 1)}
+            row.update({name: stats(ts) for name, ts in t.items()})
+            row["paths_over_hits"] = row["paths"]["ms"] / row["hits"]["ms"]
+            row["paths_over_copy"] = row["paths"]["ms"] / row["copy_hits"]["ms"]
+            line = json.dumps(row)
+            print(line, flush=True)
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+            del g, u, reads, r_start, r_length, d_lptr, d_links, d_hptr, d_hits, d_pptr, d_paths, dst, support, rows
+            torch.cuda.empty_cache()
+            continue
         d_spans = buf(R * 8)
         with torch.cuda.stream(stream):
             keys = torch.randint(0, 1 << (2 * k), (max(nodes, 1),), device="cuda", dtype=torch.int64)
