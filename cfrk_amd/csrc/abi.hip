@@ -1749,4 +1749,14 @@ int cfrk_synth_reads_device(cfrk_ctx *ctx, int64_t r0, int64_t R, int L, int64_t
   return cfrk_launch_synth(ctx, r0, R, L, Glen, seedG, seedR, seedS, uniform, d_data, d_start, d_length);
 }
 
+/* ------------------------------------------------------------------ the radix path's shape (tests) */
+
+// Read-only: the shape radix.hip's host code chooses for (k, nN) -- the very function cfrk_radix_count lays its buffers
+// out by -- and four host-side values the context's most recent radix add left behind.
+int cfrk_debug_radix_info(const cfrk_ctx *ctx, int k, int64_t nN, uint64_t out[12]) {
+  if (!out || nN < 0) return CFRK_ERR_ARG;
+  cfrk_radix_info(ctx, k, nN, out);
+  return CFRK_OK;
+}
+
 }  // extern "C"

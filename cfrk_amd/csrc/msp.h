@@ -93,6 +93,8 @@ struct cfrk_msp {
   double dens_scale;
   uint64_t list_n;     // entries in the list (valid after resolve)
   bool list_n_valid;
+  uint32_t rx_last[4]; // radix.hip, the most recent add: attempts of the layout loop, level 1 laid out again, the leaves
+                       // laid out again, grid of the leaf kernel (cfrk_debug_radix_info)
   MspView view;
   alignas(16) unsigned char view2[256];   // msp2.hip: the View2 of a CFRK_RUNS_ONLY job (its leaf streams hold the runs)
 };
@@ -122,4 +124,5 @@ int  cfrk_msp2_merge_runs_group(cfrk_ctx *ctx, const void *d_recv, const uint64_
 bool cfrk_radix_usable(const cfrk_ctx *ctx);
 bool cfrk_radix_prefers(const cfrk_ctx *ctx, int64_t nN);   // ... or k = 16 and a batch small enough for its leaves (radix.hip)
 int  cfrk_radix_count(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN);
+void cfrk_radix_info(const cfrk_ctx *ctx, int k, int64_t nN, uint64_t out[12]);   // cfrk_debug_radix_info
 

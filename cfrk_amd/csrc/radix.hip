@@ -10,7 +10,7 @@
 //   RX3  persistent workgroups walk the leaves: an LDS array of counters addressed by the low idx bits, then the
 //        non-zero counters are un-scrambled and appended to the result list through an LDS buffer (one cursor
 //        atomic per ~10 leaves).
-//   Leaf shape, chosen on the HOST from k and the batch size (cfrk_radix_count):
+//   Leaf shape, chosen on the HOST from k and the batch size (rx_shape):
 //     8 <= k <= 12: idx = 2k - 11 (5..13) counters of 32 bits, replicated when there are fewer than 2^13;
 //     13 <= k <= 15: idx = 14 -- 2^14 keys per leaf as PACKED 16-bit counters in 2^13 words -- while a leaf is
 //        expected to stay well under 2^16 elements (exact below that: no half can carry; a leaf that turns out
@@ -638,11 +638,70 @@ bool cfrk_radix_usable(const cfrk_ctx *ctx) {
 // counters), i.e. up to ~4e9 bases per add.  Not for CFRK_RUNS_ONLY jobs (the runs exchange is msp.hip's).
 constexpr int RX16_IDX = 15, RX16_B2 = 9;
 static double rx_pad2(int b2) { return 1.0 + 3.5 * (double)(1u << b2) / (double)RX2_KEYS; }
+
+// THE SHAPE of a radix add, from k and the batch size alone: the one place where it is chosen (cfrk_radix_count lays its
+// buffers out by it, cfrk_radix_prefers asks it whether k = 16 comes here at all, cfrk_debug_radix_info shows it to the
+// tests, which restate it in tests/radix_ref.py).
+struct RxShape {
+  int b1, b2, idx;            // level-1 bits, level-2 bits, counter-address bits of a leaf (all 0: k <= 7, no partition)
+  uint32_t hi8;               // level 1 keeps an 8-bit plane beside the 16-bit one
+  uint32_t mul, inv, kmask;   // scramble: x * mul mod 4^k, and back
+  uint64_t cap1, cap2;        // fixed strides: elements per level-1 region, per leaf
+  bool direct;                // k <= 7: rxs_count_kernel
+  bool takes;                 // a batch of this size at this k is counted here (k <= 15 always; k = 16 while its leaves stay small)
+};
+static RxShape rx_shape(int k, int64_t nN) {
+  RxShape s;
+  memset(&s, 0, sizeof s);
+  if (k < 1 || k > 16) return s;
+  s.takes = true;
+  if (k <= 7) { s.direct = true; return s; }
+  // at least 2048 leaves (one workgroup each in RX3), at most 2^13 counter words per leaf (k = 16: 2^14)
+  s.b1 = 8;
+  if (k == 16) {
+    s.idx = RX16_IDX;
+    const double per_leaf = (double)nN / (double)(1u << (8 + RX16_B2)) * rx_pad2(RX16_B2);
+    s.takes = per_leaf * 1.5 <= 49152.0;
+  } else if (2 * k - 11 > RX_IDX_MAX) {
+    // k >= 13: 2^14 keys per leaf as packed 16-bit counters (half the leaves, half RX2's fan-out) pay while a leaf
+    // stays under 2^16 elements; a leaf above that is counted in two passes over its stream, so a batch whose MEAN
+    // leaf comes near it (k = 13 from ~2e8 bases, k = 14 from ~8e8, k = 15 from ~3e9) keeps 2^13 keys per leaf and
+    // 32-bit counters instead (ADVICE r4; measured at configs[1]'s size: profiles/r05/ksweep_*)
+    const int b2w = 2 * k - s.b1 - (RX_IDX_MAX + 1);
+    const double per_leaf = (double)nN / (double)(1ull << (s.b1 + b2w)) * rx_pad2(b2w);
+    s.idx = (per_leaf * 1.5 <= 49152.0) ? RX_IDX_MAX + 1 : RX_IDX_MAX;
+  } else s.idx = std::max(0, 2 * k - 11);
+  s.b2 = 2 * k - s.b1 - s.idx;
+  s.kmask = (uint32_t)((1ull << (2 * k)) - 1ull);
+  s.mul = 0x9E3779B1u;
+  s.inv = inv_odd32(s.mul);
+  const uint64_t nb1 = 1ull << s.b1, nleaf = 1ull << (s.b1 + s.b2);
+  // (a tile of RX2 rounds each of its <= 512 segments up to eight elements, ~3.5 pads each; level-1 regions start on
+  //  multiples of 16 elements, leaf streams on multiples of 8)
+  const double pad2 = rx_pad2(s.b2);
+  s.cap1 = ((uint64_t)((double)nN / (double)(nb1 * RX_NREG) * 1.3) + 4096 + 15) & ~15ull;
+  s.cap2 = ((uint64_t)((double)nN / (double)nleaf * 1.5 * pad2) + 1024 + 7) & ~7ull;
+  // the 8-bit plane also exists when the level's keys fill the 16-bit plane exactly (k = 12): a pad must not look like a key
+  // (RX2 has since come to tell a region's elements by their index, not their value: profiles/r34/README.md)
+  s.hi8 = (2 * k - s.b1 >= 16) ? 1u : 0u;
+  return s;
+}
+
 bool cfrk_radix_prefers(const cfrk_ctx *ctx, int64_t nN) {
   if (cfrk_radix_usable(ctx)) return true;
   if (ctx->g_two || ctx->g_k != 16 || (ctx->g_flags & (CFRK_FORCE_HASH | CFRK_RUNS_ONLY)) || (ctx->dbg_flags & CFRK_DEBUG_NO_RADIX16)) return false;
-  const double per_leaf = (double)nN / (double)(1u << (8 + RX16_B2)) * rx_pad2(RX16_B2);
-  return per_leaf * 1.5 <= 49152.0;
+  return rx_shape(16, nN).takes;
+}
+
+// cfrk_debug_radix_info (abi.hip): the shape as the host would choose it, and what the last radix add of the context did
+void cfrk_radix_info(const cfrk_ctx *ctx, int k, int64_t nN, uint64_t out[12]) {
+  const RxShape s = rx_shape(k, nN);
+  out[0] = (uint64_t)s.b1; out[1] = (uint64_t)s.b2; out[2] = (uint64_t)s.idx;
+  out[3] = s.mul; out[4] = s.inv;
+  out[5] = s.cap1; out[6] = s.cap2;
+  out[7] = (s.takes ? 1u : 0u) | (s.direct ? 2u : 0u) | (s.hi8 ? 4u : 0u);
+  const cfrk_msp *ms = ctx ? ctx->msp : nullptr;
+  for (int i = 0; i < 4; ++i) out[8 + i] = ms ? (uint64_t)ms->rx_last[i] : 0;
 }
 
 int cfrk_radix_count(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN) {
@@ -678,33 +737,15 @@ int cfrk_radix_count(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN) {
     ms->pending = true;
     ms->leaf_form = false;
     ms->list_n_valid = false;
+    ms->rx_last[0] = 0; ms->rx_last[1] = 0; ms->rx_last[2] = 0; ms->rx_last[3] = (uint32_t)grid;
     return CFRK_OK;
   }
-  // at least 2048 leaves (one workgroup each in RX3), at most 2^13 counter words per leaf (k = 16: 2^14)
-  v.b1 = 8;
-  if (k == 16) v.idx = RX16_IDX;
-  else if (2 * k - 11 > RX_IDX_MAX) {
-    // k >= 13: 2^14 keys per leaf as packed 16-bit counters (half the leaves, half RX2's fan-out) pay while a leaf
-    // stays under 2^16 elements; a leaf above that is counted in two passes over its stream, so a batch whose MEAN
-    // leaf comes near it (k = 13 from ~2e8 bases, k = 14 from ~8e8, k = 15 from ~3e9) keeps 2^13 keys per leaf and
-    // 32-bit counters instead (ADVICE r4; measured at configs[1]'s size: profiles/r05/ksweep_*)
-    const int b2w = 2 * k - v.b1 - (RX_IDX_MAX + 1);
-    const double per_leaf = (double)nN / (double)(1ull << (v.b1 + b2w)) * rx_pad2(b2w);
-    v.idx = (per_leaf * 1.5 <= 49152.0) ? RX_IDX_MAX + 1 : RX_IDX_MAX;
-  } else v.idx = std::max(0, 2 * k - 11);
-  v.b2 = 2 * k - v.b1 - v.idx;
-  v.kmask = (uint32_t)((1ull << (2 * k)) - 1ull);
-  v.mul = 0x9E3779B1u;
+  const RxShape sh = rx_shape(k, nN);
+  v.b1 = sh.b1; v.b2 = sh.b2; v.idx = sh.idx;
+  v.kmask = sh.kmask; v.mul = sh.mul; v.inv = sh.inv; v.hi8 = sh.hi8;
   v.dbg = ctx->dbg_flags;
-  v.inv = inv_odd32(v.mul);
   const uint64_t nb1 = 1ull << v.b1, nleaf = 1ull << (v.b1 + v.b2);
-  // (a tile of RX2 rounds each of its <= 512 segments up to eight elements, ~3.5 pads each; level-1 regions start on
-  //  multiples of 16 elements, leaf streams on multiples of 8)
-  const double pad2 = rx_pad2(v.b2);
-  const uint64_t cap1 = ((uint64_t)((double)nN / (double)(nb1 * RX_NREG) * 1.3) + 4096 + 15) & ~15ull;
-  const uint64_t cap2 = ((uint64_t)((double)nN / (double)nleaf * 1.5 * pad2) + 1024 + 7) & ~7ull;
-  // the 8-bit plane also exists when the level's keys fill the 16-bit plane exactly (k = 12): a pad must not look like a key
-  v.hi8 = (2 * k - v.b1 >= 16) ? 1u : 0u;
+  const uint64_t cap1 = sh.cap1, cap2 = sh.cap2;
   const size_t l1_elems = (size_t)nb1 * RX_NREG * cap1;
   const size_t need = l1_elems * 3 + (size_t)nleaf * cap2 * 2 + (size_t)ctx->g_cap * 12;
   const size_t have = ctx->pool[BUF_MSP_L1].cap + ctx->pool[BUF_MSP_L2].cap + ctx->pool[BUF_MSP_OUTK].cap + ctx->pool[BUF_MSP_OUTC].cap;
@@ -743,7 +784,9 @@ int cfrk_radix_count(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN) {
   // demand: the level is laid out back to back (all keys together never exceed the buffer) and its
   // kernel runs again (see msp.hip).
   bool run_rx1 = true, settled = false;
+  uint32_t attempts = 0;
   for (int attempt = 0; attempt < 4 && !settled; ++attempt) {
+    ++attempts;
     if (run_rx1) {
       HIP_TRY(ctx, hipMemsetAsync(ctx->g_stats + ST_L1OVF, 0, sizeof(uint64_t), ctx->stream));
       const dim3 g1((unsigned)tiles), b1d(RX1_THREADS);
@@ -795,10 +838,13 @@ int cfrk_radix_count(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN) {
     settled = true;
   }
   if (!settled) return cfrk_fail(ctx, CFRK_ERR_STATE, "the key regions did not settle after an exact layout");
-  // persistent: four workgroups (32 KB of counters each) per CU walk the leaves
-  if (k == 16) hipLaunchKernelGGL((rx3_kernel<14, 512>), dim3((unsigned)std::min<uint64_t>(nleaf, (uint64_t)std::max(1, ctx->num_cus) * 2)), dim3(512), 0, ctx->stream, v, (uint32_t)nleaf);
-  else hipLaunchKernelGGL((rx3_kernel<RX_IDX_MAX, 256>), dim3((unsigned)std::min<uint64_t>(nleaf, (uint64_t)std::max(1, ctx->num_cus) * 4)), dim3(256), 0, ctx->stream, v, (uint32_t)nleaf);
+  // persistent: four workgroups (32 KB of counters each) per CU walk the leaves (k = 16: two of 64 KB)
+  const unsigned g3 = (unsigned)std::min<uint64_t>(nleaf, (uint64_t)std::max(1, ctx->num_cus) * (k == 16 ? 2 : 4));
+  if (k == 16) hipLaunchKernelGGL((rx3_kernel<14, 512>), dim3(g3), dim3(512), 0, ctx->stream, v, (uint32_t)nleaf);
+  else hipLaunchKernelGGL((rx3_kernel<RX_IDX_MAX, 256>), dim3(g3), dim3(256), 0, ctx->stream, v, (uint32_t)nleaf);
   HIP_TRY(ctx, hipGetLastError());
+  // (cfrk_debug_radix_info: what this add did)
+  ms->rx_last[0] = attempts; ms->rx_last[1] = v.exact1; ms->rx_last[2] = v.exact; ms->rx_last[3] = g3;
   // the result list lives where msp.hip keeps its own: digest / export / fold are shared
   ms->view.out_keys = v.out_keys; ms->view.out_cnt = v.out_cnt; ms->view.out_cap = v.out_cap;
   ms->view.stats = v.stats;

@@ -221,6 +221,7 @@ def load_library():
         "cfrk_debug_set_mem_budget": ([vp, u64], C.c_int),
         "cfrk_debug_device_bytes": ([vp, C.POINTER(u64)], C.c_int),
         "cfrk_debug_hash_info": ([vp, u64, u64, C.POINTER(u64)], C.c_int),
+        "cfrk_debug_radix_info": ([vp, C.c_int, i64, C.POINTER(u64)], C.c_int),
         "cfrk_debug_set_flags": ([vp, C.c_uint32], C.c_int),
         "cfrk_debug_set_param": ([vp, C.c_int, C.c_double], C.c_int),
         "cfrk_debug_last_add_passes": ([vp, C.POINTER(C.c_int)], C.c_int),
@@ -268,6 +269,21 @@ def hash_info(lo, hi=0, ctx=None):
     if rc != 0:
         raise CfrkError(rc, "cfrk_debug_hash_info")
     return tuple(int(x) for x in out)
+
+
+def radix_info(k, nN, ctx=None):
+    """cfrk_debug_radix_info -> dict: the shape radix.hip's host code chooses for a global add of nN bytes at k (b1, b2,
+    idx, mul, inv, cap1, cap2; takes: the radix path counts such a batch; direct: k <= 7; hi8: level 1 keeps an 8-bit
+    plane) -- pure host arithmetic, no device needed -- and, with a Context, what its most recent radix add did
+    (attempts of the layout loop, relaid1 / relaid2: level 1 / the leaves were laid out again, grid of the leaf kernel)."""
+    out = (C.c_uint64 * 12)()
+    rc = load_library().cfrk_debug_radix_info(ctx._h if ctx is not None else None, int(k), int(nN), out)
+    if rc != 0:
+        raise CfrkError(rc, "cfrk_debug_radix_info")
+    o = [int(x) for x in out]
+    return {"b1": o[0], "b2": o[1], "idx": o[2], "mul": o[3], "inv": o[4], "cap1": o[5], "cap2": o[6],
+            "takes": bool(o[7] & 1), "direct": bool(o[7] & 2), "hi8": bool(o[7] & 4),
+            "attempts": o[8], "relaid1": bool(o[9]), "relaid2": bool(o[10]), "grid": o[11]}
 
 
 def _sketch_regs(regs):

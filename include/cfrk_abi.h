@@ -1390,6 +1390,23 @@ int cfrk_debug_last_add_passes(cfrk_ctx *ctx, int *out_passes);
  * no context: ctx may be NULL (out[0] = out[1] = 0).  Touches nothing; never synchronises. */
 int cfrk_debug_hash_info(const cfrk_ctx *ctx, uint64_t lo, uint64_t hi, uint64_t out[4]);
 
+/* Read-only introspection of the radix path (global jobs with k <= 16), so that a test can craft keys for a chosen
+ * leaf and counter, and notices when the scramble or a sizing rule changes.  The shape is evaluated on the host by the
+ * very function the add chooses it with, from k and the batch size nN (bytes of reads) alone; it needs no device and no
+ * context: ctx may be NULL.  out[0] = b1, out[1] = b2 (bits of the two partition levels), out[2] = idx (bits that
+ * address a leaf's counters: a scrambled key is bin : sub-bin : counter, top to bottom); out[3] = the odd multiplier
+ * of the scramble x * mul mod 4^k, out[4] = its inverse mod 2^32; out[5] = cap1, out[6] = cap2 (elements a level-1
+ * region and a leaf hold before the level is laid out again with exact sizes); out[7] = flags: bit 0 a batch of nN at
+ * this k is counted by the radix path (every k <= 15; k = 16 up to ~3.5e9 bases; the job's flags and debug bits, which
+ * can also keep k = 16 away from it, are not looked at), bit 1 k <= 7 (no partition: one dense table in LDS; out[0..6]
+ * are 0), bit 2 level 1 keeps an 8-bit plane beside its 16-bit plane.  k outside 1..16: all of out[0..7] are 0.
+ * With a context, out[8..11] tell what its most recent radix add did (0 without one, or before the first): out[8] =
+ * attempts of the layout loop (1: every region and leaf fitted its fixed stride; 0 for k <= 7), out[9] = 1 when level 1
+ * was laid out again, out[10] = 1 when the leaves were, out[11] = workgroups of the leaf kernel (k <= 7: of the
+ * counting kernel) -- workgroup w walks leaves w, w + out[11], ...  Host-side values the add had in hand: touches
+ * nothing, never synchronises. */
+int cfrk_debug_radix_info(const cfrk_ctx *ctx, int k, int64_t nN, uint64_t out[12]);
+
 /* Test switches for rarely taken device paths (0 = normal operation).  Bit 0: every leaf of the
  * one-word partitioned path (16 <= k <= 32) is treated as if its complete runs had overflowed the
  * record table, i.e. takes the second-chance deduplication over the whole LDS pool. */
