@@ -1338,6 +1338,58 @@ int cfrk_global_unitig_bulges(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS,
   return cfrk_memcpy_d2h(ctx, path, d_path, (size_t)n_path * 4);
 }
 
+static_assert(sizeof(cfrk_weak_stats) == 24, "cfrk_weak_stats is 24 bytes without padding");
+
+static int unitig_weak_check(cfrk_ctx *ctx, const void *rec, int64_t nS, const void *link_ptr, const void *links, int64_t n_links,
+                             uint32_t ratio_q8, const void *weak, cfrk_weak_stats *stats) {
+  if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "weak unitigs before begin: the job supplies the strand rule");
+  if (nS < 0 || n_links < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (!stats) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL stats");
+  if (nS > 0 && (!rec || !link_ptr || !weak)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (n_links > 0 && !links) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL links with n_links above 0");
+  if ((uint64_t)nS >= (1ull << 32)) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld unitigs: a link names its target in 32 bits", (long long)nS);
+  if (ratio_q8 > CFRK_TIP_RATIO_Q8_MAX) return cfrk_fail(ctx, CFRK_ERR_ARG, "ratio_q8 %u: at most %d", ratio_q8, CFRK_TIP_RATIO_Q8_MAX);
+  stats->connections = stats->isolated = stats->candidates = 0;
+  return CFRK_OK;
+}
+
+int cfrk_global_unitig_weak_device(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
+                                   const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t ratio_q8,
+                                   uint32_t iso_max_kmers, uint32_t iso_mean_q8, uint8_t *d_weak, cfrk_weak_stats *stats) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = unitig_weak_check(ctx, d_rec, nS, d_link_ptr, d_links, n_links, ratio_q8, d_weak, stats);
+  if (rc || nS == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_unitig_weak_launch(ctx, d_rec, nS, d_link_ptr, d_links, n_links, max_kmers, ratio_q8, iso_max_kmers, iso_mean_q8, d_weak, stats);
+}
+
+int cfrk_global_unitig_weak(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS, const int64_t *link_ptr,
+                            const cfrk_unitig_link *links, int64_t n_links, uint32_t max_kmers, uint32_t ratio_q8,
+                            uint32_t iso_max_kmers, uint32_t iso_mean_q8, uint8_t *weak, cfrk_weak_stats *stats) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = unitig_weak_check(ctx, rec, nS, link_ptr, links, n_links, ratio_q8, weak, stats);
+  if (rc || nS == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // [records | link_ptr | links] in a slot of their own, the weak bytes in another
+  Carve c;
+  const size_t rec_bytes = (size_t)nS * sizeof *rec, ptr_bytes = ((size_t)nS + 1) * 8, link_bytes = (size_t)n_links * sizeof *links;
+  const size_t o_rec = c.part(rec_bytes), o_ptr = c.part(ptr_bytes), o_links = c.part(link_bytes);
+  void *d_in, *d_out;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_WEAK_IN, c.end, &d_in))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_WEAK_OUT, (size_t)nS, &d_out))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_rec), rec, rec_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_ptr), link_ptr, ptr_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (n_links) HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_links), links, link_bytes, hipMemcpyHostToDevice, ctx->stream));
+  rc = cfrk_unitig_weak_launch(ctx, carve_at<cfrk_unitig>(d_in, o_rec), nS, carve_at<int64_t>(d_in, o_ptr),
+                               carve_at<cfrk_unitig_link>(d_in, o_links), n_links, max_kmers, ratio_q8, iso_max_kmers, iso_mean_q8,
+                               (uint8_t *)d_out, stats);
+  if (rc) {                                            // refused: weak all 0
+    memset(weak, 0, (size_t)nS);
+    return stage_drain(ctx, rc);
+  }
+  return cfrk_memcpy_d2h(ctx, weak, d_out, (size_t)nS);
+}
+
 static int unitigs_compact_check(cfrk_ctx *ctx, const cfrk_unitigs_in &in, const void *data_out, uint64_t cap_data,
                                  const void *start_out, const void *length_out, const void *rec_out, uint64_t cap_unitigs,
                                  int64_t *nN_out, int64_t *nS_out) {

@@ -70,6 +70,8 @@ enum {  // pool slots
   BUF_UNITIG_COMPACT_IN, BUF_UNITIG_COMPACT_OUT,  // staging of cfrk_global_unitigs_compact alone (the unitigs, records, link_ptr, links, drop in; the unitigs, records, into out)
   BUF_READ_PATHS,                             // read paths (read_paths.hip): error / size words, the start flags and their scan, the in-rows, the scans' scratch
   BUF_READ_PATHS_IN, BUF_READ_PATHS_OUT,      // staging of cfrk_global_read_paths alone (hit_ptr, hits, records, link_ptr, links, support in; path_ptr, paths out)
+  BUF_UNITIG_WEAK,                            // weak rule (unitig_weak.hip): error / count words, the in-rows, the scan's scratch
+  BUF_UNITIG_WEAK_IN, BUF_UNITIG_WEAK_OUT,    // staging of cfrk_global_unitig_weak alone (records, link_ptr, links in; weak bytes out)
   BUF_NSLOTS
 };
 
@@ -245,6 +247,11 @@ int cfrk_unitig_tips_launch(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS,
 int cfrk_unitig_bubbles_launch(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
                                const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t max_diff,
                                uint32_t ratio_q8, uint8_t *d_pop, uint32_t *d_partner, int64_t *n_pop);
+// unitig_weak.hip: the weak rule over 1 <= nS < 2^32 records and their link rows into d_weak[nS]; synchronises once, for
+// the error word (CFRK_ERR_LAYOUT) and *stats
+int cfrk_unitig_weak_launch(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
+                            const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t ratio_q8,
+                            uint32_t iso_max_kmers, uint32_t iso_mean_q8, uint8_t *d_weak, cfrk_weak_stats *stats);
 // unitig_bulges.hip: the bulge rule over 1 <= nS < 2^31 records and their link rows.  The search writes d_pop[nS] and,
 // unless NULL, d_visits[nS] and d_path_ptr[nS + 1]; it synchronises once, for the error word (CFRK_ERR_LAYOUT), the
 // counts and *n_path.  The fill pass behind it writes the rows of d_path_ptr into d_path and is left enqueued.

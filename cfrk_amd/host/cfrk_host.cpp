@@ -1088,6 +1088,40 @@ size_t cfrk_host_format_bulges(uint32_t round, const int8_t *data, const int64_t
   return buf ? (size_t)(p - buf) : s;
 }
 
+size_t cfrk_host_format_weak(uint32_t round, const int8_t *data, const int64_t *start, const int32_t *length, const void *rec,
+                             int64_t nS, const uint8_t *weak, char *buf, size_t cap) {
+  (void)cap;
+  size_t s = 0;
+  char *p = buf;
+  for (int64_t j = 0; j < nS; ++j) {
+    if (weak[j] != 1 && weak[j] != 2) continue;         // CFRK_WEAK_CONNECTION, CFRK_WEAK_ISOLATED; any other byte: no line
+    const char *kind = weak[j] == 1 ? "connection" : "isolated";
+    const size_t kind_len = strlen(kind);
+    uint64_t kc;
+    uint32_t n;
+    memcpy(&kc, (const char *)rec + 16 * j, 8);
+    memcpy(&n, (const char *)rec + 16 * j + 8, 4);
+    if (!n) n = 1;
+    const unsigned __int128 tenths = ((unsigned __int128)kc * 10 + n / 2) / n;      // as in the S line
+    const uint64_t whole = (uint64_t)(tenths / 10), frac = (uint64_t)(tenths % 10);
+    const uint64_t L = length[j] > 0 ? (uint64_t)length[j] : 0;
+    if (!buf) {
+      s += len_u64(round) + 1 + len_u64((uint64_t)j) + 1 + kind_len + 1 + len_u64(L) + 1 + len_u64(kc) + 1 + len_u64(whole) + 3 + (size_t)L + 1;
+      continue;
+    }
+    p = put_u64(p, round); *p++ = '\t';
+    p = put_u64(p, (uint64_t)j); *p++ = '\t';
+    memcpy(p, kind, kind_len); p += kind_len; *p++ = '\t';
+    p = put_u64(p, L); *p++ = '\t';
+    p = put_u64(p, kc); *p++ = '\t';
+    p = put_u64(p, whole); *p++ = '.'; *p++ = (char)('0' + frac); *p++ = '\t';
+    const int8_t *a = data + start[j];
+    for (uint64_t x = 0; x < L; ++x) { const int c = a[x]; *p++ = "ACGTN"[(c >= 0 && c <= 3) ? c : 4]; }
+    *p++ = '\n';
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
 static void put_le(char *p, uint64_t x, int bytes) { for (int i = 0; i < bytes; ++i) p[i] = (char)(x >> (8 * i)); }
 static uint64_t get_le(const char *p, int bytes) {
   uint64_t x = 0;

@@ -175,6 +175,16 @@ size_t cfrk_host_format_bubbles(uint32_t round, const int8_t *data, const int64_
 size_t cfrk_host_format_bulges(uint32_t round, const int8_t *data, const int64_t *start, const int32_t *length, const void *rec,
                                int64_t nS, const uint8_t *pop, const int64_t *path_ptr, const uint32_t *path, int k, char *buf, size_t cap);
 
+/* Dropped weak unitigs as text (`cfrk --weak-report FILE`): the unitig list of one round with weak[nS] as
+ * cfrk_global_unitig_weak wrote it.  One line per unitig j with weak[j] = 1 (CFRK_WEAK_CONNECTION) or 2
+ * (CFRK_WEAK_ISOLATED), in order, seven fields separated by tabs:
+ *   <round> <j> <"connection" or "isolated"> <LN_j> <KC_j> <km_j> <the sequence>
+ * LN, KC and km are those of the S line of cfrk_host_format_gfa for that round's list (km = kc / n_kmers with one decimal);
+ * a code outside 0..3 prints as N.  Any other byte of weak gives no line.  Returns bytes needed / written (buf may be
+ * NULL to size). */
+size_t cfrk_host_format_weak(uint32_t round, const int8_t *data, const int64_t *start, const int32_t *length, const void *rec,
+                             int64_t nS, const uint8_t *weak, char *buf, size_t cap);
+
 /* Read hits as GAF (`cfrk --unitigs-map QFILE --unitigs-map-out MFILE`): hit_ptr = n_reads + 1 offsets, hits = rows of
  * cfrk_read_hit (cfrk_abi.h: 16 bytes -- unitig, unitig_at = off << 1 | minus, read_off, n_windows as uint32),
  * unitig_length = the unitig list's lengths (every hit's unitig is an index into it).  One line per hit, in CSR order,

@@ -1,5 +1,5 @@
 // cli_graph.cpp -- the unitig graph of the finished count, for the `cfrk` command: simplify (--unitigs-clip-tips,
-// --unitigs-pop-bubbles, --unitigs-pop-bulges), write (--unitigs-out, --unitigs-links, --unitigs-gfa), map reads onto it (--unitigs-map)
+// --unitigs-pop-bubbles, --unitigs-pop-bulges, --unitigs-drop-weak), write (--unitigs-out, --unitigs-links, --unitigs-gfa), map reads onto it (--unitigs-map)
 // and thread them through it (--unitigs-map-paths, --unitigs-link-support, --unitigs-map-stats).
 #include "cli_util.h"
 
@@ -45,14 +45,16 @@ struct UnitigGraph {
 // the k-mers of the tips and the popped arms through the host forms, before anything is written.  The mask stays set, so
 // what write_unitigs and write_unitigs_map compute afterwards is the simplified graph.  Without --unitigs-pop-bubbles
 // this is the tip loop as it always was, four-field report included; --unitigs-pop-bulges adds the bulge rule on that same
-// graph, its pops to the same mask and a field to the report.
+// graph, its pops to the same mask and a field to the report; --unitigs-drop-weak adds the weak rule the same way, with two
+// fields at the end of the report's lines.
 int simplify_unitigs(const Options &o, cfrk_ctx *ctx) {
-  std::string report, bubbles, bulges;
-  const uint32_t rounds = (o.pop_bubbles || o.pop_bulges) ? o.simplify_rounds : o.tip_rounds;
+  std::string report, bubbles, bulges, weaks;
+  const uint32_t rounds = (o.pop_bubbles || o.pop_bulges || o.drop_weak) ? o.simplify_rounds : o.tip_rounds;
   UnitigGraph next;                                       // --simplify-recompact: the next round's unitigs, when the last one made them
   bool have_next = false;
   for (uint32_t round = 1; round <= rounds; ++round) {
-    int64_t n_tips = 0, n_pop = 0, n_bulges = 0;
+    int64_t n_tips = 0, n_pop = 0, n_bulges = 0, n_weak = 0;
+    cfrk_weak_stats weak_stats = {0, 0, 0};
     UnitigGraph g;
     int rc;
     if (have_next) {
@@ -100,25 +102,41 @@ int simplify_unitigs(const Options &o, cfrk_ctx *ctx) {
         });
       for (size_t j = 0; j < (size_t)nS; ++j) tip[j] |= pop[j];       // (disjoint from the tips; a bubble's arm may be popped by both rules)
     }
-    if ((n_tips || n_pop || n_bulges) && (rc = cfrk_global_mask_unitigs(ctx, g.data.data(), g.start.data(), g.length.data(), g.nN, nS, tip.data())))
+    if (o.drop_weak) {
+      std::vector<uint8_t> weak((size_t)nS);
+      if ((rc = cfrk_global_unitig_weak(ctx, g.rec.data(), nS, g.link_ptr.data(), g.links.data(), g.n_links, o.weak_max_kmers ? o.weak_max_kmers : (uint32_t)o.k,
+                                        o.weak_ratio_q8, o.weak_iso_max_set ? o.weak_iso_max_kmers : 2u * (uint32_t)o.k, o.weak_iso_mean_q8, weak.data(),
+                                        &weak_stats))) return die(ctx, rc, "cfrk_global_unitig_weak");
+      n_weak = weak_stats.connections + weak_stats.isolated;
+      if (o.weak_report && n_weak)
+        format_into(weaks, [&](char *out, size_t room) {
+          return cfrk_host_format_weak(round, g.data.data(), g.start.data(), g.length.data(), g.rec.data(), nS, weak.data(), out, room);
+        });
+      for (size_t j = 0; j < (size_t)nS; ++j) tip[j] |= weak[j] ? 1 : 0;    // (disjoint from the tips; a bubble's arm may be a connection too)
+    }
+    if ((n_tips || n_pop || n_bulges || n_weak) && (rc = cfrk_global_mask_unitigs(ctx, g.data.data(), g.start.data(), g.length.data(), g.nN, nS, tip.data())))
       return die(ctx, rc, "cfrk_global_mask_unitigs");
     uint64_t masked = 0;
     if ((rc = cfrk_global_mask_count(ctx, &masked))) return die(ctx, rc, "cfrk_global_mask_count");
-    char line[128];
+    char line[192];
+    int at;
     if (o.pop_bulges)
-      snprintf(line, sizeof line, "%u\t%lld\t%lld\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (long long)n_pop, (long long)n_bulges,
+      at = snprintf(line, sizeof line, "%u\t%lld\t%lld\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (long long)n_pop, (long long)n_bulges,
                (unsigned long long)masked);
     else if (o.pop_bubbles)
-      snprintf(line, sizeof line, "%u\t%lld\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (long long)n_pop, (unsigned long long)masked);
+      at = snprintf(line, sizeof line, "%u\t%lld\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (long long)n_pop, (unsigned long long)masked);
     else
-      snprintf(line, sizeof line, "%u\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (unsigned long long)masked);
+      at = snprintf(line, sizeof line, "%u\t%lld\t%lld\t%llu\n", round, (long long)nS, (long long)n_tips, (unsigned long long)masked);
+    if (o.drop_weak)                                      // (over the line's '\n': two fields more)
+      snprintf(line + at - 1, sizeof line - (size_t)(at - 1), "\t%lld\t%lld\n", (long long)weak_stats.connections, (long long)weak_stats.isolated);
     report += line;
-    if (!n_tips && !n_pop && !n_bulges) break;
+    if (!n_tips && !n_pop && !n_bulges && !n_weak) break;
     if (o.simplify_recompact && round < rounds) {
       if ((rc = g.compact_into(ctx, tip.data(), &next))) return rc;
       have_next = true;
     }
   }
+  if (o.weak_report) { if (const int rc = write_file(o.weak_report, weaks)) return rc; }
   if (o.bulge_report) { if (const int rc = write_file(o.bulge_report, bulges)) return rc; }
   if (o.bubble_report) { if (const int rc = write_file(o.bubble_report, bubbles)) return rc; }
   return o.tip_report ? write_file(o.tip_report, report) : 0;

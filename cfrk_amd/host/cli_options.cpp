@@ -115,6 +115,11 @@ const Row TABLE[] = {
   str("--bulge-report", &O::bulge_report, &O::bulge_opt_set), ratio("--bulge-ratio", &O::bulge_ratio_q8, &O::bulge_opt_set),
   count("--bulge-max-kmers", 1, &O::bulge_max_kmers, &O::bulge_opt_set), count("--bulge-max-diff", 0, &O::bulge_max_diff, &O::bulge_opt_set),
   count("--bulge-max-hops", 1, &O::bulge_max_hops, &O::bulge_opt_set), count("--bulge-max-visits", 0, &O::bulge_max_visits, &O::bulge_opt_set),
+  flag("--unitigs-drop-weak", &O::drop_weak),
+  str("--weak-report", &O::weak_report, &O::weak_opt_set), ratio("--weak-ratio", &O::weak_ratio_q8, &O::weak_opt_set),
+  count("--weak-max-kmers", 1, &O::weak_max_kmers, &O::weak_opt_set),
+  count("--weak-iso-max-kmers", 0, &O::weak_iso_max_kmers, &O::weak_opt_set, [](O &o) { o.weak_iso_max_set = true; }),
+  ratio("--weak-iso-mean", &O::weak_iso_mean_q8, &O::weak_opt_set),
   str("--unitigs-out", &O::unitigs_out), str("--unitigs-gfa", &O::unitigs_gfa), str("--unitigs-map", &O::unitigs_map),
   str("--unitigs-map-out", &O::unitigs_map_out), count("--unitigs-min-count", 0, &O::unitigs_min_count, &O::unitigs_opt_set),
   flag("--unitigs-map-paths", &O::map_paths), flag("--unitigs-link-support", &O::link_support), str("--unitigs-map-stats", &O::map_stats),
@@ -215,16 +220,20 @@ int check_options(const Options &o) {
   if (o.clip_tips && !graph_out) return refuse("--unitigs-clip-tips needs --unitigs-out UFILE, --unitigs-gfa GFILE or --unitigs-map QFILE");
   if (o.pop_bubbles && !graph_out) return refuse("--unitigs-pop-bubbles needs --unitigs-out UFILE, --unitigs-gfa GFILE or --unitigs-map QFILE");
   if (o.pop_bulges && !graph_out) return refuse("--unitigs-pop-bulges needs --unitigs-out UFILE, --unitigs-gfa GFILE or --unitigs-map QFILE");
+  if (o.drop_weak && !graph_out) return refuse("--unitigs-drop-weak needs --unitigs-out UFILE, --unitigs-gfa GFILE or --unitigs-map QFILE");
+  if (o.weak_opt_set && !o.drop_weak)
+    return refuse("--weak-max-kmers, --weak-ratio, --weak-iso-max-kmers, --weak-iso-mean and --weak-report need --unitigs-drop-weak");
   if (o.bulge_opt_set && !o.pop_bulges)
     return refuse("--bulge-max-kmers, --bulge-max-diff, --bulge-max-hops, --bulge-max-visits, --bulge-ratio and --bulge-report need --unitigs-pop-bulges");
-  if (o.simplify_recompact && !o.clip_tips && !o.pop_bubbles && !o.pop_bulges)
+  if (o.simplify_recompact && !o.clip_tips && !o.pop_bubbles && !o.pop_bulges && !o.drop_weak)
     return refuse("--simplify-recompact needs --unitigs-clip-tips, --unitigs-pop-bubbles or --unitigs-pop-bulges");
   if (o.bulge_max_hops > CFRK_BULGE_MAX_HOPS) return refuse("--bulge-max-hops needs a count from 1 to " TEXT_OF(CFRK_BULGE_MAX_HOPS));
   if (o.bulge_max_visits > CFRK_BULGE_MAX_VISITS) return refuse("--bulge-max-visits needs a count from 0 to " TEXT_OF(CFRK_BULGE_MAX_VISITS));
-  if ((o.bubble_opt_set && !o.pop_bubbles) || (o.simplify_rounds_set && !o.pop_bubbles && !o.pop_bulges)) return refuse("--bubble-max-kmers, --bubble-max-diff, --bubble-ratio, --bubble-report and --simplify-rounds need --unitigs-pop-bubbles");
+  if ((o.bubble_opt_set && !o.pop_bubbles) || (o.simplify_rounds_set && !o.pop_bubbles && !o.pop_bulges && !o.drop_weak)) return refuse("--bubble-max-kmers, --bubble-max-diff, --bubble-ratio, --bubble-report and --simplify-rounds need --unitigs-pop-bubbles");
   if (o.tip_rounds_set && o.pop_bubbles) return refuse("--tip-rounds is the tip loop's own: with --unitigs-pop-bubbles the rounds are set by --simplify-rounds N");
   if (o.tip_rounds_set && o.pop_bulges) return refuse("--tip-rounds is the tip loop's own: with --unitigs-pop-bulges the rounds are set by --simplify-rounds N");
-  if ((o.tip_opt_set && !o.clip_tips) || (o.tip_report && !o.clip_tips && !o.pop_bubbles && !o.pop_bulges)) return refuse("--tip-max-kmers, --tip-ratio, --tip-rounds and --tip-report need --unitigs-clip-tips");
+  if (o.tip_rounds_set && o.drop_weak) return refuse("--tip-rounds is the tip loop's own: with --unitigs-drop-weak the rounds are set by --simplify-rounds N");
+  if ((o.tip_opt_set && !o.clip_tips) || (o.tip_report && !o.clip_tips && !o.pop_bubbles && !o.pop_bulges && !o.drop_weak)) return refuse("--tip-max-kmers, --tip-ratio, --tip-rounds and --tip-report need --unitigs-clip-tips");
   if (o.unitigs_links && !o.unitigs_out) return refuse("--unitigs-links needs --unitigs-out UFILE");
   if (o.unitigs_opt_set && !graph_out) return refuse("--unitigs-min-count needs --unitigs-out UFILE");
   if (o.sparse && (o.global || o.binary || o.histo || o.histo_only || o.range_set || o.query || o.query_out || o.query_only || o.query_db ||

@@ -100,7 +100,21 @@
 //                    "round<TAB>unitigs<TAB>tips<TAB>bubbles<TAB>bulges<TAB>masked k-mers so far".  FILE: one line per
 //                    popped unitig (cfrk_host_format_bulges: round, S name, LN, km, hops, the path's k-mers, the path
 //                    as >3<7>9, snp / mnp / indel, both sequences)  (cfrk_global_unitig_bulges)
-//   --simplify-recompact  (with --unitigs-clip-tips, --unitigs-pop-bubbles or --unitigs-pop-bulges) between two rounds of
+//   --unitigs-drop-weak [--weak-max-kmers M] [--weak-ratio R] [--weak-iso-max-kmers I] [--weak-iso-mean A]
+//                    [--weak-report FILE] [--simplify-rounds N]  (with --unitigs-out, --unitigs-gfa or --unitigs-map) drop
+//                    erroneous connections and isolated low-coverage unitigs, in the same loop as the three rules above
+//                    and combined with any of them: every enabled rule sees the same graph of a round, one mask takes
+//                    the k-mers of all of them, the first round in which no enabled rule finds anything ends the loop.
+//                    A connection has at most M k-mers (default k), links at both ends and none to itself, and at EVERY
+//                    one of those links a sibling -- another way out of the same neighbour's end -- of at least R times
+//                    its mean coverage (default 4.0, 0 .. 256) that ranks above it.  At an equal ratio that contains
+//                    everything --unitigs-pop-bubbles pops, hence the high default.  An isolated unitig has no link at
+//                    all, at most I k-mers (default 2 k; 0: none) and a mean coverage below A (default 2.0, 0 .. 256;
+//                    0: none).  All four defaults are choices, not measured optima.  --tip-rounds is refused here:
+//                    --simplify-rounds sets the rounds.  --tip-report lines get two further fields at their end,
+//                    "...<TAB>connections<TAB>isolated".  FILE: one line per dropped unitig (cfrk_host_format_weak: round,
+//                    S name, connection / isolated, LN, KC, km, the sequence)  (cfrk_global_unitig_weak)
+//   --simplify-recompact  (with --unitigs-clip-tips, --unitigs-pop-bubbles, --unitigs-pop-bulges or --unitigs-drop-weak) between two rounds of
 //                    the loop, take the next round's unitigs from the last round's graph and what it dropped
 //                    (cfrk_global_unitigs_compact) and not from the k-mer passes of cfrk_global_unitigs.  Every file
 //                    written is byte for byte the same either way.
@@ -262,6 +276,12 @@ struct Options {
   uint32_t bulge_max_visits = 1024;   // --bulge-max-visits V
   uint32_t bulge_ratio_q8 = 0;        // --bulge-ratio R, in 256ths
   const char *bulge_report = nullptr; // --bulge-report FILE
+  bool drop_weak = false;             // --unitigs-drop-weak
+  uint32_t weak_max_kmers = 0;        // --weak-max-kmers M (0: k)
+  uint32_t weak_ratio_q8 = 1024;      // --weak-ratio R, in 256ths
+  uint32_t weak_iso_max_kmers = 0;    // --weak-iso-max-kmers I (without weak_iso_max_set: 2 k)
+  uint32_t weak_iso_mean_q8 = 512;    // --weak-iso-mean A, in 256ths
+  const char *weak_report = nullptr;  // --weak-report FILE
   bool histo_only = false;
   uint32_t min_count = 1, max_count = CFRK_COUNT_MAX;
   const char *query = nullptr, *query_out = nullptr, *query_db = nullptr;   // --query QFILE --query-out OFILE --query-db DB
@@ -300,7 +320,7 @@ struct Options {
   int batch_n = -1;                                                 // --batch N (-1: not given)
   std::vector<const char *> pos;                                    // the positional arguments, in order
   // raised by the options that were given: what the cross-option rules ask about
-  bool unitigs_opt_set = false, tip_opt_set = false, tip_rounds_set = false, bubble_opt_set = false, simplify_rounds_set = false, bulge_opt_set = false, range_set = false, stats_below_set = false;
+  bool unitigs_opt_set = false, tip_opt_set = false, tip_rounds_set = false, bubble_opt_set = false, simplify_rounds_set = false, bulge_opt_set = false, weak_opt_set = false, weak_iso_max_set = false, range_set = false, stats_below_set = false;
   bool filter_opt_set = false, correct_opt_set = false, correct_min_count_set = false, normalize_opt_set = false, normalize_cutoff_set = false;
   bool pair_opt_set = false, pair_mode_set = false, min_qual_set = false;
 };

@@ -87,6 +87,10 @@ CFRK_BULGE_MAX_HOPS = 64             # bulge rule: the longest path, in unitigs
 CFRK_BULGE_MAX_VISITS = 65536        # the largest search budget, in links looked at
 # what one bulge call found (cfrk_bulge_stats)
 BULGE_STATS_DTYPE = np.dtype([("arms", "<i8"), ("popped", "<i8"), ("undecided", "<i8")])
+CFRK_WEAK_CONNECTION = 1             # weak rule: weak[j] of an erroneous connection
+CFRK_WEAK_ISOLATED = 2               # ... and of an isolated low-coverage unitig
+# what one weak call found (cfrk_weak_stats)
+WEAK_STATS_DTYPE = np.dtype([("connections", "<i8"), ("isolated", "<i8"), ("candidates", "<i8")])
 CFRK_COMPACT_TILE_BYTES = 4096       # unitig compaction: bytes of data_out per workgroup of the emit
 # cfrk_read_path / cfrk_path_stats: a read's walk through the graph as a range of its hits; what a read_paths call counted
 READ_PATH_DTYPE = np.dtype([("hit_first", "<u4"), ("n_hits", "<u4"), ("read_off", "<u4"), ("n_windows", "<u4")])
@@ -177,6 +181,8 @@ def load_library():
         "cfrk_global_unitig_tips_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, vp, C.POINTER(i64)], C.c_int),
         "cfrk_global_unitig_bubbles": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(i64)], C.c_int),
         "cfrk_global_unitig_bubbles_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(i64)], C.c_int),
+        "cfrk_global_unitig_weak": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp], C.c_int),
+        "cfrk_global_unitig_weak_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp], C.c_int),
         "cfrk_global_unitig_bulges": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, u64, C.POINTER(i64), vp], C.c_int),
         "cfrk_global_unitig_bulges_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, u64, C.POINTER(i64), vp], C.c_int),
         "cfrk_global_unitigs_compact": ([vp, vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, u64, vp, vp, vp, u64, vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
@@ -1314,6 +1320,38 @@ class GlobalCounter:
             raise
         return n.value, st
 
+    def unitig_weak(self, rec, link_ptr, links, max_kmers, ratio_q8=1024, iso_max_kmers=0, iso_mean_q8=0):
+        """the weak rule over the unitigs' records and their links -> (weak np.uint8[nS], stats): weak[j] =
+        CFRK_WEAK_CONNECTION where unitig j is not circular, has at most max_kmers k-mers, a link at both ends and none
+        to itself, and at every one of those links a sibling (another way out of the same neighbour's end) with 256 *
+        mean(it) >= ratio_q8 * mean(j) that ranks above j; CFRK_WEAK_ISOLATED where it is not circular, has no link at
+        all, at most iso_max_kmers k-mers and 256 * mean(j) < iso_mean_q8; 0 elsewhere.  stats = {"connections",
+        "isolated", "candidates"}.  At equal max_kmers and ratio_q8 this contains everything unitig_bubbles() pops, so the
+        default ratio_q8 of 1024 (four times the coverage) is deliberately high; like the isolated thresholds' default of
+        0 (off) it is a choice, not a measured optimum.  Raises CfrkError (CFRK_ERR_LAYOUT, the message naming the unitig)
+        when the rows are not link rows."""
+        rec = np.ascontiguousarray(rec, UNITIG_DTYPE)
+        link_ptr = np.ascontiguousarray(link_ptr, np.int64)
+        links = np.ascontiguousarray(links, UNITIG_LINK_DTYPE)
+        if len(link_ptr) != len(rec) + 1:
+            raise ValueError("link_ptr has not one entry more than rec")
+        weak, stats = np.zeros(len(rec), np.uint8), np.zeros(1, WEAK_STATS_DTYPE)
+        self.ctx.check(self._L.cfrk_global_unitig_weak(self.ctx._h, _ptr(rec), len(rec), _ptr(link_ptr), _ptr(links), len(links),
+                                                       int(max_kmers), int(ratio_q8), int(iso_max_kmers), int(iso_mean_q8), _ptr(weak),
+                                                       _ptr(stats)), "cfrk_global_unitig_weak")
+        st = {f: int(stats[f][0]) for f in WEAK_STATS_DTYPE.names}
+        assert st["connections"] == int((weak == CFRK_WEAK_CONNECTION).sum()) and st["isolated"] == int((weak == CFRK_WEAK_ISOLATED).sum())
+        return weak, st
+
+    def unitig_weak_device(self, d_rec, nS, d_link_ptr, d_links, n_links, max_kmers, ratio_q8, iso_max_kmers, iso_mean_q8, d_weak):
+        """device form -> stats; synchronises once, for the counts and the check of the rows"""
+        stats = np.zeros(1, WEAK_STATS_DTYPE)
+        vp = lambda p: C.c_void_p(p) if p else None
+        self.ctx.check(self._L.cfrk_global_unitig_weak_device(self.ctx._h, vp(d_rec), nS, vp(d_link_ptr), vp(d_links), n_links,
+                                                              int(max_kmers), int(ratio_q8), int(iso_max_kmers), int(iso_mean_q8),
+                                                              vp(d_weak), _ptr(stats)), "cfrk_global_unitig_weak_device")
+        return {f: int(stats[f][0]) for f in WEAK_STATS_DTYPE.names}
+
     def compact_unitigs(self, data, start, length, rec, link_ptr, links, drop=None):
         """the unitigs of the graph without the unitigs j with drop[j] != 0, from the list, its records and its links as
         unitigs() and unitig_links() returned them -> (data, start, length, rec, into): byte for byte what unitigs()
@@ -1366,7 +1404,8 @@ class GlobalCounter:
 
     def simplify(self, min_count=1, tips=True, bubbles=True, rounds=4, tip_max_kmers=None, tip_ratio=2.0,
                  bubble_max_kmers=None, bubble_max_diff=0, bubble_ratio=0.0, bulges=False, bulge_max_kmers=None, bulge_max_diff=0,
-                 bulge_max_hops=None, bulge_max_visits=1024, bulge_ratio=0.0, recompact=False):
+                 bulge_max_hops=None, bulge_max_visits=1024, bulge_ratio=0.0, recompact=False, weak=False, weak_max_kmers=None,
+                 weak_ratio=4.0, weak_iso_max_kmers=None, weak_iso_mean=2.0):
         """simplify the graph: up to `rounds` rounds of unitigs -> links -> each enabled rule on that same graph -> one
         mask_unitigs(tip | pop), stopping at the first round that finds neither a tip nor a bubble -> ((data, start,
         length, rec) of the simplified graph, [(unitigs, tips, bubbles, masked keys so far) per round], [(round, popped
@@ -1381,6 +1420,14 @@ class GlobalCounter:
         one call per round.  The per-round tuples are then (unitigs, tips, bubbles, bulges, masked keys so far), and a
         fourth value is returned: [(round, popped unitig, path as a list of w << 1 | o, popped record, popped sequence,
         the path's sequence spelled with k - 1 overlaps) per unitig the bulge rule popped].
+        weak=True runs the weak rule on that same graph as well (unitig_weak(); weak_max_kmers=None means k,
+        weak_iso_max_kmers=None means 2 k, weak_ratio is the mean coverage a sibling must have relative to the
+        connection, weak_iso_mean the mean coverage below which an isolated unitig goes) and masks tip | pop | bulge |
+        (weak != 0) in the one call per round.  The rule contains the bubble rule at an equal ratio, hence the high default
+        of 4.0; that, 2.0 and 2 k are choices, not measured optima.  The per-round tuples then end in two more counts,
+        (..., masked keys so far, connections, isolated), the loop stops at the first round in which no enabled rule
+        finds anything, and one more value is returned last: [(round, unitig, CFRK_WEAK_CONNECTION or CFRK_WEAK_ISOLATED,
+        record, sequence) per unitig the weak rule dropped].
         recompact=True takes the next round's unitigs from compact_unitigs() on this round's graph and drop bytes in
         place of the unitigs() call; mask_unitigs() still runs (links and the position map live on the mask).  Every
         returned value is the same either way."""
@@ -1388,6 +1435,11 @@ class GlobalCounter:
             raise ValueError("rounds: at least 1")
         tip_q8, bub_q8 = int(round(float(tip_ratio) * 256)), int(round(float(bubble_ratio) * 256))
         bulge_q8 = int(round(float(bulge_ratio) * 256))
+        weak_q8, weak_iso_q8 = int(round(float(weak_ratio) * 256)), int(round(float(weak_iso_mean) * 256))
+        if weak and (not 0 <= weak_q8 <= CFRK_TIP_RATIO_Q8_MAX or not 0 <= weak_iso_q8 <= 0xFFFFFFFF):
+            raise ValueError("weak_ratio: 0 .. 256; weak_iso_mean: 0 .. 2^24")
+        weak_max_kmers = self.k if weak_max_kmers is None else int(weak_max_kmers)
+        weak_iso_max_kmers = 2 * self.k if weak_iso_max_kmers is None else int(weak_iso_max_kmers)
         if not 0 <= tip_q8 <= CFRK_TIP_RATIO_Q8_MAX or not 0 <= bub_q8 <= CFRK_TIP_RATIO_Q8_MAX or not 0 <= bulge_q8 <= CFRK_TIP_RATIO_Q8_MAX:
             raise ValueError("ratio: 0 .. 256")
         tip_max_kmers = self.k if tip_max_kmers is None else int(tip_max_kmers)
@@ -1395,13 +1447,13 @@ class GlobalCounter:
         bulge_max_kmers = self.k if bulge_max_kmers is None else int(bulge_max_kmers)
         text = lambda data, at, n: "".join("ACGT"[c] for c in data[at:at + n])
         comp = str.maketrans("ACGT", "TGCA")
-        report, rows, bulge_rows = [], [], []
+        report, rows, bulge_rows, weak_rows = [], [], [], []
         u = self.unitigs(min_count)
         for rnd in range(1, rounds + 1):
             data, start, length, rec = u
             link_ptr, links = self.unitig_links(data, start, length, min_count)
             drop = np.zeros(len(rec), np.uint8)
-            n_tips = n_pop = n_bulge = 0
+            n_tips = n_pop = n_bulge = n_conn = n_iso = 0
             if tips:
                 tip = self.unitig_tips(rec, link_ptr, links, tip_max_kmers, tip_q8)
                 n_tips = int(tip.sum())
@@ -1428,13 +1480,22 @@ class GlobalCounter:
                         s = s.translate(comp)[::-1] if w & 1 else s
                         spelled += s[self.k - 1:] if spelled else s
                     bulge_rows.append((rnd, j, p, tuple(rec[j].tolist()), text(data, int(start[j]), int(length[j])), spelled))
-            if n_tips or n_pop or n_bulge:
+            if weak:
+                wk, st = self.unitig_weak(rec, link_ptr, links, weak_max_kmers, weak_q8, weak_iso_max_kmers, weak_iso_q8)
+                n_conn, n_iso = st["connections"], st["isolated"]
+                drop |= (wk != 0).astype(np.uint8)
+                for j in np.flatnonzero(wk).tolist():
+                    weak_rows.append((rnd, j, int(wk[j]), tuple(rec[j].tolist()), text(data, int(start[j]), int(length[j]))))
+            found = n_tips or n_pop or n_bulge or n_conn or n_iso
+            if found:
                 self.mask_unitigs(data, start, length, drop)
-            report.append((len(rec), n_tips, n_pop, n_bulge, self.mask_count()) if bulges else (len(rec), n_tips, n_pop, self.mask_count()))
-            if not (n_tips or n_pop or n_bulge):
+            row = (len(rec), n_tips, n_pop, n_bulge, self.mask_count()) if bulges else (len(rec), n_tips, n_pop, self.mask_count())
+            report.append(row + (n_conn, n_iso) if weak else row)
+            if not found:
                 break
             u = self.compact_unitigs(data, start, length, rec, link_ptr, links, drop)[:4] if recompact else self.unitigs(min_count)
-        return (u, report, rows, bulge_rows) if bulges else (u, report, rows)
+        out = (u, report, rows, bulge_rows) if bulges else (u, report, rows)
+        return out + (weak_rows,) if weak else out
 
     def query_reads(self, data, start=None, length=None):
         """count of the k-mer starting at every base -> np.uint32[nN]: CFRK_QUERY_NONE where the window holds an

@@ -789,6 +789,68 @@ int cfrk_global_unitig_bulges(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS,
                               uint32_t *visits /* nS; may be NULL */, int64_t *path_ptr /* nS + 1; may be NULL */,
                               uint32_t *path, uint64_t cap_path, int64_t *n_path_out, cfrk_bulge_stats *stats);
 
+/* Weak unitigs: erroneous connections and isolated low-coverage pieces.  An erroneous connection is a short, thin
+ * unitig that is linked at both ends (so it is no tip), possibly by several links at an end (so it is no arm of the
+ * bubble or the bulge rule), and that at each of those links sits beside a much better-covered way out of the same
+ * neighbour: what a chimeric read or an error whose own neighbours are errors leaves behind.  An isolated piece is a
+ * short, thin unitig without any link, as clipping leaves them floating.  Like the other three rules a pure function of
+ * the unitigs' records (kc, n_kmers, CFRK_UNITIG_CIRCULAR), the link CSR as cfrk_global_unitig_links wrote it, and the
+ * job's strand rule; no sequence, no index.  Oriented unitigs, out(), in(), the mirror convention, left(j), right(j),
+ * n_j, kc_j and the 128-bit cross-multiplied means are exactly those of "Unitig tips".
+ *   SELF-FREE: no link of row j has target j, in either orientation; in a job that is not canonical no link of j's
+ *   in-row has source j either (no self-loop, hairpin or homopolymer node).
+ *   ISOLATED: j is not CFRK_UNITIG_CIRCULAR, left(j) = right(j) = 0, n_j <= iso_max_kmers and 256 kc_j < iso_mean_q8 n_j
+ *   (mean coverage below iso_mean_q8 / 256).  Then weak[j] = CFRK_WEAK_ISOLATED.
+ *   CANDIDATE: j is not CFRK_UNITIG_CIRCULAR, n_j <= max_kmers, left(j) >= 1 and right(j) >= 1, and j is self-free.
+ *   ATTACHMENTS and SIBLINGS of a candidate, at BOTH ends.  Right end: every link (j,+) -> (v,ov) of out(j,+) is an
+ *   attachment, its siblings are the sources (w,ow) of in(v,ov) with w != j.  Left end: every link (u,ou) -> (j,+) of
+ *   in(j,+) is an attachment, its siblings are the targets (w,ow) of out(u,ou) with w != j.  In a canonical job the left
+ *   end of (j,+) is the right end of (j,-): every link of row j is an attachment of one end or the other, and at its
+ *   target (v,ov) the siblings are the targets of v's links that leave (v,!ov).
+ *   BEATS (the bubble rule's): w beats j iff 256 kc_w n_j >= ratio_q8 kc_j n_w, and w ranks above j: kc_w n_j > kc_j n_w,
+ *   or they are equal and w < j.  ratio_q8 <= CFRK_TIP_RATIO_Q8_MAX as for tips.
+ *   WEAK CONNECTION: j is a candidate and at EVERY attachment of BOTH ends some sibling beats it.  Then weak[j] =
+ *   CFRK_WEAK_CONNECTION.
+ *   Everything else is 0; every byte is written.  stats: the connections, the isolated ones, and the candidates.
+ *   max_kmers = 0 makes no connection; iso_max_kmers = 0 or iso_mean_q8 = 0 makes nothing isolated (a unitig's record has
+ *   n_kmers >= 1).
+ *   Every decision reads the input graph only: the result depends on no order.
+ *   The best-ranked neighbour at any oriented end is never a weak connection through that end, because "every
+ *   attachment" includes this one and no sibling there ranks above it.  So the rule alone never leaves a neighbour with a
+ *   new dead end: an oriented end that had a link keeps one.
+ *   weak[] and tip[] of one graph are disjoint: a tip has exactly one dead end, a connection none, an isolated unitig two.
+ *   All four rules' results may go into one mask call.
+ *   At equal max_kmers and ratio_q8 every unitig the bubble rule pops (whatever its max_diff) is a weak connection: an
+ *   arm is self-free, and its one in-link and its one out-link each have the parallel arm, which beats it, as a sibling.
+ *   The converse is false.  That superset is why a caller wants a HIGH ratio here (the Python and CLI default is 4.0,
+ *   against 0 for bubbles): at a low one the rule eats a heterozygous site's weaker arm and more.
+ * Untrusted input: the check of the tip rule runs in front, with the same five CFRK_ERR_LAYOUT reasons naming the first
+ *   offending unitig, and only checked rows are followed.  After the check one lane per unitig looks at the at most 16
+ *   links of its row and, at each target, at that row's at most 16 links, of which in a real link set at most 8 are on
+ *   the entering side: 128 comparisons.  No loop is unbounded, nothing outside the arrays is accessed, every byte of
+ *   weak is written whatever is refused (all 0 after an error, with stats 0).  Rows that pass the check without being a
+ *   real link set (canonical rows that lack their mirrors, say) give CFRK_OK and whatever the rule says of the rows as
+ *   given, in() of a canonical job being read off the rows by the mirror convention.
+ * CFRK_ERR_STATE: no job.  CFRK_ERR_ARG: NULL stats, NULL rec / link_ptr / weak with nS > 0, NULL links with n_links > 0,
+ *   negative sizes, nS >= 2^32, ratio_q8 above its bound.  nS = 0 is fine: nothing found.
+ * Device form (cfrk_amd/csrc/unitig_weak.hip): stats is host memory; the call synchronises ONCE, for the counts and the
+ *   error word.  Temporary device memory, kept in the context's pool: four words; not canonical: 12 bytes per unitig, 4
+ *   per link and the scan's scratch.  Host form: stages through the pool; synchronous. */
+#define CFRK_WEAK_CONNECTION 1
+#define CFRK_WEAK_ISOLATED 2
+typedef struct cfrk_weak_stats {   /* 24 bytes, no padding */
+  int64_t connections;   /* weak[j] == CFRK_WEAK_CONNECTION */
+  int64_t isolated;      /* weak[j] == CFRK_WEAK_ISOLATED   */
+  int64_t candidates;    /* the candidates for a connection */
+} cfrk_weak_stats;
+int cfrk_global_unitig_weak_device(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr /* nS + 1 */,
+                                   const cfrk_unitig_link *d_links, int64_t n_links, uint32_t max_kmers, uint32_t ratio_q8,
+                                   uint32_t iso_max_kmers, uint32_t iso_mean_q8, uint8_t *d_weak /* nS bytes, every one written */,
+                                   cfrk_weak_stats *stats);
+int cfrk_global_unitig_weak(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS, const int64_t *link_ptr /* nS + 1 */,
+                            const cfrk_unitig_link *links, int64_t n_links, uint32_t max_kmers, uint32_t ratio_q8,
+                            uint32_t iso_max_kmers, uint32_t iso_mean_q8, uint8_t *weak /* nS */, cfrk_weak_stats *stats);
+
 /* Unitig compaction: the unitigs of the graph WITHOUT some of its unitigs, computed from the unitig list itself.  After
  * a rule has chosen what to drop, the compacted graph of the remaining keys differs from the old one only where a
  * dropped unitig was the reason two others could not merge.  It is a pure function of the unitigs' sequences and records

@@ -50,7 +50,18 @@ to its synchronisation; the difference to the whole call is the sort, the scans,
 a device copy of the output bytes; and a line "loop" with the whole loop of --tip-rounds rounds, every round's graph made
 by the unitigs call or by the compaction, the two alternating over --loop-reps repetitions, the rounds asserted equal.
 
-  python tools/bench_unitigs.py [--links | --tips [--parent-lib SO] | --bubbles [--parent-lib SO] | --bulges | --compact] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
+With --weak (cases b and c) the tool "bench_weak" writes, per case: a line "weak" with the weak call (--weak-ratio,
+--weak-iso-mean, max_kmers = k, iso_max_kmers = 2k) alternating in the same repetitions with the tips call, the bubbles
+call and the links call that feeds all three, the candidates, connections and isolated unitigs found, and how many of the
+connections the bubble rule pops as well; and two lines "rounds", for the combined loop without the rule (tips + bubbles +
+bulges) and with it, each with nodes, unitigs and what every rule found per round and after the loop, and, on the graph
+the loop leaves, the hits and paths (read_hits, read_paths) of the reads that were counted and of the same reads without
+their substitutions: reads, reads in one path, reads in several, reads without a hit, gaps and unlinked steps.  A read
+with an error breaks where the error's k-mers were dropped, as it should; an error-free read that breaks is true sequence
+eaten -- the check on the rule's default ratio.  A third "rounds" line with
+no rule at all gives the same numbers on the graph as counted.
+
+  python tools/bench_unitigs.py [--links | --tips [--parent-lib SO] | --bubbles [--parent-lib SO] | --bulges | --compact | --weak] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
 """
 import argparse
 import json
@@ -323,6 +334,108 @@ def bulges_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf
                           rounds=rounds)), flush=True)
 
 
+def weak_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf, rd, rd_clean):
+    k = a.k
+    tip_q8, bub_q8, bulge_q8 = int(round(a.tip_ratio * 256)), int(round(a.bubble_ratio * 256)), int(round(a.bulge_ratio * 256))
+    weak_q8, iso_q8 = int(round(a.weak_ratio * 256)), int(round(a.weak_iso_mean * 256))
+    max_hops = min(k + a.bulge_max_diff, cfrk_amd.CFRK_BULGE_MAX_HOPS)
+    R = rd[4]
+
+    def graph_args(gr):
+        return (gr.out[3].data_ptr(), gr.nS, gr.ptr.data_ptr(), gr.rows.data_ptr(), gr.n_links)
+
+    def small_buf(call, field):
+        try:
+            return call()
+        except cfrk_amd.CfrkError as e:
+            if e.code != cfrk_amd.CFRK_ERR_SMALL_BUF:
+                raise
+            return getattr(e, field) if isinstance(field, str) else tuple(getattr(e, f) for f in field)
+
+    new = _Graph(cfrk_amd, g, min_count, buf)
+    ctx.sync()
+    d_tip, d_bub, d_weak = buf(new.nS), buf(new.nS), buf(new.nS)
+    weak = lambda: g.unitig_weak_device(*graph_args(new), k, weak_q8, 2 * k, iso_q8, d_weak.data_ptr())
+    calls = {"weak": weak, "tips": lambda: g.unitig_tips_device(*graph_args(new), k, tip_q8, d_tip.data_ptr()),
+             "bubbles": lambda: g.unitig_bubbles_device(*graph_args(new), k, a.bubble_max_diff, bub_q8, d_bub.data_ptr(), 0), "links_call": new.links}
+    st, n_tips, n_bub = weak(), calls["tips"](), calls["bubbles"]()
+    t = {name: [] for name in calls}
+    for rep in range(a.reps + 1):
+        for name, fn in calls.items():                          # alternating in one process
+            ms = timed(fn)
+            if rep:                                             # (the first round warms up: code objects, pool buffers)
+                t[name].append(ms)
+    ctx.sync()
+    torch.cuda.synchronize()
+    row = dict(common, line="weak", nodes=new.nodes(torch), unitigs=new.nS, links=new.n_links, tips_found=n_tips, bubbles_found=n_bub,
+               max_kmers=k, weak_ratio=a.weak_ratio, iso_max_kmers=2 * k, weak_iso_mean=a.weak_iso_mean,
+               connections_also_popped_by_bubbles=int(((d_weak[:new.nS] == 1) & (d_bub[:new.nS] != 0)).sum()), **st)
+    row.update({name: dict(stats(ts), series=ts) for name, ts in t.items()})
+    row["weak_over_tips"] = row["weak"]["ms"] / row["tips"]["ms"]
+    row["weak_over_links"] = row["weak"]["ms"] / row["links_call"]["ms"]
+    row["ns_per_unitig"] = row["weak"]["ms"] * 1e6 / max(new.nS, 1)
+    print(json.dumps(row), flush=True)
+    del new, d_tip, d_bub, d_weak
+
+    def paths_on(gr, rd):
+        """the hits and paths of the reads `rd` on the graph the mask leaves"""
+        g.unitig_index_device(min_count, *gr.args)
+        d_hptr = buf((R + 1) * 8)
+        n_hits = small_buf(lambda: g.read_hits_device(*rd, d_hptr.data_ptr(), 0, 0), "n_hits")
+        d_hits = buf(max(n_hits, 1) * 16)
+        if n_hits:
+            g.read_hits_device(*rd, d_hptr.data_ptr(), d_hits.data_ptr(), n_hits)
+        ctx.sync()
+        d_pptr = buf((R + 1) * 8)
+        n_paths, pst = small_buf(lambda: g.read_paths_device(d_hptr.data_ptr(), R, d_hits.data_ptr(), n_hits, *graph_args(gr), d_pptr.data_ptr(), 0, 0),
+                                 ("n_paths", "stats"))
+        ctx.sync()
+        torch.cuda.synchronize()
+        per_read = torch.diff(d_pptr[:(R + 1) * 8].view(torch.int64))
+        return {"reads": R, "hits": n_hits, "paths": n_paths, "reads_in_one_path": int((per_read == 1).sum()),
+                "reads_in_several_paths": int((per_read > 1).sum()), "reads_without_a_hit": int((per_read == 0).sum()),
+                "gaps": pst["n_gaps"], "unlinked": pst["n_unlinked"], "steps": pst["n_steps"]}
+
+    for rules in ("none", "tips+bubbles+bulges", "tips+bubbles+bulges+weak"):
+        g.mask_clear()
+        rounds, cur = [], _Graph(cfrk_amd, g, min_count, buf)
+        for r in range(a.tip_rounds if rules != "none" else 0):
+            if r:
+                cur = _Graph(cfrk_amd, g, min_count, buf)
+            d_tip, d_bub, d_pop, d_weak = buf(cur.nS), buf(cur.nS), buf(cur.nS), buf(cur.nS)
+            n_tips = g.unitig_tips_device(*graph_args(cur), k, tip_q8, d_tip.data_ptr())
+            n_bub = g.unitig_bubbles_device(*graph_args(cur), k, a.bubble_max_diff, bub_q8, d_bub.data_ptr(), 0)
+            bst = g.unitig_bulges_device(*graph_args(cur), k, a.bulge_max_diff, max_hops, a.bulge_max_visits, bulge_q8, d_pop.data_ptr())[1]
+            wst = {"connections": 0, "isolated": 0, "candidates": 0}
+            if rules.endswith("weak"):
+                wst = g.unitig_weak_device(*graph_args(cur), k, weak_q8, 2 * k, iso_q8, d_weak.data_ptr())
+            found = n_tips or n_bub or bst["popped"] or wst["connections"] or wst["isolated"]
+            if found:
+                ctx.sync()
+                d_tip[:cur.nS] |= d_bub[:cur.nS] | d_pop[:cur.nS]
+                if rules.endswith("weak"):
+                    d_tip[:cur.nS] |= d_weak[:cur.nS].ne(0).to(torch.uint8)
+                torch.cuda.synchronize()
+                g.mask_unitigs_device(*cur.args, d_tip.data_ptr())
+            rounds.append({"round": r + 1, "nodes": cur.nodes(torch), "unitigs": cur.nS, "tips": n_tips, "bubbles": n_bub, "bulges": bst["popped"],
+                           "undecided": bst["undecided"], "connections": wst["connections"], "isolated": wst["isolated"],
+                           "weak_candidates": wst["candidates"], "masked_keys": g.mask_count()})
+            del d_tip, d_bub, d_pop, d_weak
+            if not found:
+                break
+        if rounds and any(rounds[-1][f] for f in ("tips", "bubbles", "bulges", "connections", "isolated")):
+            cur = _Graph(cfrk_amd, g, min_count, buf)
+        ctx.sync()
+        after = {"nodes": cur.nodes(torch), "unitigs": cur.nS, "links": cur.n_links, "masked_keys": g.mask_count()}
+        print(json.dumps(dict(common, line="rounds", rules=rules, tip_ratio=a.tip_ratio, bubble_ratio=a.bubble_ratio, bubble_max_diff=a.bubble_max_diff,
+                              bulge_ratio=a.bulge_ratio, bulge_max_diff=a.bulge_max_diff, bulge_max_visits=a.bulge_max_visits, weak_ratio=a.weak_ratio,
+                              weak_iso_mean=a.weak_iso_mean, max_kmers=k, rounds=rounds, after=after, read_paths=paths_on(cur, rd),
+                              error_free_read_paths=paths_on(cur, rd_clean))), flush=True)
+        del cur
+        torch.cuda.empty_cache()
+    g.mask_clear()
+
+
 def compact_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf, stream):
     k = a.k
     tip_q8, bub_q8, bulge_q8 = int(round(a.tip_ratio * 256)), int(round(a.bubble_ratio * 256)), int(round(a.bulge_ratio * 256))
@@ -455,6 +568,9 @@ def main():
     ap.add_argument("--bulge-max-diff", type=int, default=0)
     ap.add_argument("--bulge-max-visits", type=int, default=1024)
     ap.add_argument("--compact", action="store_true")
+    ap.add_argument("--weak", action="store_true")
+    ap.add_argument("--weak-ratio", type=float, default=4.0)
+    ap.add_argument("--weak-iso-mean", type=float, default=2.0)
     ap.add_argument("--loop-reps", type=int, default=3)
     ap.add_argument("--parent-lib", help="libcfrk_hip.so of the parent commit: with --tips the unmasked calls, with --bubbles the tips call alternate with it")
     a = ap.parse_args()
@@ -492,7 +608,8 @@ def main():
     for case in a.cases.split(","):
         with torch.cuda.stream(stream):
             reads = buf(nN)
-            ctx.synth_reads_device(0, R, L, a.glen, reads.data_ptr())
+            r_start, r_length = (buf(R * 8), buf(R * 4)) if a.weak else (None, None)   # (the reads as a list: --weak maps them back)
+            ctx.synth_reads_device(0, R, L, a.glen, reads.data_ptr(), r_start.data_ptr() if a.weak else None, r_length.data_ptr() if a.weak else None)
             ctx.sync()
             if case != "a":                                     # substitutions: another base, never a terminator
                 gen = torch.Generator(device="cuda").manual_seed(25)
@@ -523,6 +640,19 @@ def main():
         def full():
             g.unitigs_device(min_count, out[0].data_ptr(), oN, out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), oS)
 
+        if a.weak:
+            common = {"tool": "bench_weak", "case": case, "reads": R, "L": L, "glen": a.glen, "k": k, "reps": a.reps,
+                      "error_rate": 0.0 if case == "a" else a.error_rate, "min_count": min_count, "distinct_keys": distinct}
+            with torch.cuda.stream(stream):
+                clean = buf(nN)                                 # the same reads without the substitutions
+                ctx.synth_reads_device(0, R, L, a.glen, clean.data_ptr())
+                ctx.sync()
+            torch.cuda.synchronize()
+            weak_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf, (reads.data_ptr(), r_start.data_ptr(), r_length.data_ptr(), nN, R),
+                      (clean.data_ptr(), r_start.data_ptr(), r_length.data_ptr(), nN, R))
+            del g, out, reads, clean, r_start, r_length
+            torch.cuda.empty_cache()
+            continue
         if a.compact:
             common = {"tool": "bench_compact", "case": case, "reads": R, "L": L, "glen": a.glen, "k": k, "reps": a.reps,
                       "error_rate": 0.0 if case == "a" else a.error_rate, "min_count": min_count, "distinct_keys": distinct}
