@@ -1551,6 +1551,130 @@ int cfrk_global_read_paths(cfrk_ctx *ctx, const int64_t *hit_ptr, int64_t nR, co
   return cfrk_memcpy_d2h(ctx, paths, d_out, (size_t)n_paths * sizeof *paths);
 }
 
+static_assert(sizeof(cfrk_unitig_component) == 32, "cfrk_unitig_component is 32 bytes without padding");
+static_assert(sizeof(cfrk_component_stats) == 32, "cfrk_component_stats is 32 bytes without padding");
+static_assert(sizeof(cfrk_read_component) == 16, "cfrk_read_component is 16 bytes without padding");
+static_assert(sizeof(cfrk_read_component_stats) == 32, "cfrk_read_component_stats is 32 bytes without padding");
+
+static int unitig_components_check(cfrk_ctx *ctx, const cfrk_unitig_components_in &in, const void *comp, const void *comps,
+                                   uint64_t cap_comps, int64_t *n_comps_out, cfrk_component_stats *stats) {
+  if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "unitig components before begin: the job supplies the strand rule");
+  if (in.nS < 0 || in.n_links < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (!n_comps_out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL n_comps_out");
+  if (!stats) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL stats");
+  if (in.nS > 0 && (!in.d_rec || !in.d_link_ptr || !comp)) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL buffer");
+  if (in.n_links > 0 && !in.d_links) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL links with n_links above 0");
+  if (cap_comps > 0 && !comps) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL array with a capacity above 0");
+  if ((uint64_t)in.nS >= (1ull << 32)) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld unitigs: a link names its target in 32 bits", (long long)in.nS);
+  *n_comps_out = 0;
+  stats->n_components = stats->n_unitigs = stats->n_kmers = stats->n_links = 0;
+  return CFRK_OK;
+}
+
+static int unitig_components_fit(cfrk_ctx *ctx, int64_t n_comps, uint64_t cap_comps) {
+  if ((uint64_t)n_comps <= cap_comps) return CFRK_OK;
+  return cfrk_fail(ctx, CFRK_ERR_SMALL_BUF, "unitig components: %lld components, room for %llu", (long long)n_comps, (unsigned long long)cap_comps);
+}
+
+int cfrk_global_unitig_components_device(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr,
+                                         const cfrk_unitig_link *d_links, int64_t n_links, const uint8_t *d_drop, uint32_t *d_comp,
+                                         cfrk_unitig_component *d_comps, uint64_t cap_comps, int64_t *n_comps_out,
+                                         cfrk_component_stats *stats) {
+  if (!ctx) return CFRK_ERR_ARG;
+  const cfrk_unitig_components_in in = {d_rec, nS, d_link_ptr, d_links, n_links, d_drop};
+  int rc = unitig_components_check(ctx, in, d_comp, d_comps, cap_comps, n_comps_out, stats);
+  if (rc || nS == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int64_t n_comps = 0;
+  if ((rc = cfrk_unitig_components_measure(ctx, in, d_comp, &n_comps, stats))) return rc;
+  *n_comps_out = n_comps;
+  if ((rc = unitig_components_fit(ctx, n_comps, cap_comps)) || n_comps == 0) return rc;
+  return cfrk_unitig_components_fill(ctx, in, d_comp, d_comps, n_comps);
+}
+
+int cfrk_global_unitig_components(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS, const int64_t *link_ptr,
+                                  const cfrk_unitig_link *links, int64_t n_links, const uint8_t *drop, uint32_t *comp,
+                                  cfrk_unitig_component *comps, uint64_t cap_comps, int64_t *n_comps_out, cfrk_component_stats *stats) {
+  if (!ctx) return CFRK_ERR_ARG;
+  const cfrk_unitig_components_in host = {rec, nS, link_ptr, links, n_links, drop};
+  int rc = unitig_components_check(ctx, host, comp, comps, cap_comps, n_comps_out, stats);
+  if (rc || nS == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // [records | link_ptr | links | drop] in a slot of their own, comp and then the table in another
+  Carve c;
+  const size_t rec_bytes = (size_t)nS * sizeof *rec, ptr_bytes = ((size_t)nS + 1) * 8, link_bytes = (size_t)n_links * sizeof *links,
+               drop_bytes = drop ? (size_t)nS : 0, comp_bytes = (size_t)nS * 4;
+  const size_t o_rec = c.part(rec_bytes), o_ptr = c.part(ptr_bytes), o_links = c.part(link_bytes), o_drop = c.part(drop_bytes),
+               o_comp = c.part(comp_bytes);
+  void *d_in, *d_out;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_COMP_IN, c.end, &d_in))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_rec), rec, rec_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_ptr), link_ptr, ptr_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (n_links) HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_links), links, link_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (drop) HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_drop), drop, drop_bytes, hipMemcpyHostToDevice, ctx->stream));
+  const cfrk_unitig_components_in in = {carve_at<cfrk_unitig>(d_in, o_rec), nS, carve_at<int64_t>(d_in, o_ptr),
+                                        carve_at<cfrk_unitig_link>(d_in, o_links), n_links, drop ? carve_at<uint8_t>(d_in, o_drop) : nullptr};
+  uint32_t *d_comp = carve_at<uint32_t>(d_in, o_comp);    // (stays on the device for the table pass)
+  int64_t n_comps = 0;
+  if ((rc = cfrk_unitig_components_measure(ctx, in, d_comp, &n_comps, stats))) {
+    memset(comp, 0xFF, comp_bytes);                    // refused: all CFRK_COMP_NONE
+    return stage_drain(ctx, rc);
+  }
+  *n_comps_out = n_comps;
+  if ((rc = cfrk_memcpy_d2h(ctx, comp, d_comp, comp_bytes))) return rc;
+  if ((rc = unitig_components_fit(ctx, n_comps, cap_comps)) || n_comps == 0) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_UNITIG_COMP_OUT, (size_t)n_comps * sizeof *comps, &d_out))) return rc;
+  if ((rc = cfrk_unitig_components_fill(ctx, in, d_comp, (cfrk_unitig_component *)d_out, n_comps))) return rc;
+  return cfrk_memcpy_d2h(ctx, comps, d_out, (size_t)n_comps * sizeof *comps);
+}
+
+static int read_components_check(cfrk_ctx *ctx, const void *hit_ptr, int64_t nR, const void *hits, int64_t n_hits, const void *comp,
+                                 int64_t nS, const void *out, cfrk_read_component_stats *stats) {
+  if (!ctx->g_active) return cfrk_fail(ctx, CFRK_ERR_STATE, "read components before begin");
+  if (nR < 0 || n_hits < 0 || nS < 0) return cfrk_fail(ctx, CFRK_ERR_ARG, "negative size");
+  if (!stats) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL stats");
+  if (!hit_ptr) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL hit_ptr");
+  if (n_hits > 0 && !hits) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL hits with n_hits above 0");
+  if (nS > 0 && !comp) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL comp with nS above 0");
+  if (nR > 0 && !out) return cfrk_fail(ctx, CFRK_ERR_ARG, "NULL out with nR above 0");
+  if ((uint64_t)nS >= (1ull << 32)) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld unitigs: a hit names its unitig in 32 bits", (long long)nS);
+  if ((uint64_t)n_hits >= (1ull << 32)) return cfrk_fail(ctx, CFRK_ERR_ARG, "%lld hits: a hit's index inside its row is 32 bits", (long long)n_hits);
+  stats->n_assigned = stats->n_unassigned = stats->n_split = stats->n_dropped = 0;
+  return CFRK_OK;
+}
+
+int cfrk_global_read_components_device(cfrk_ctx *ctx, const int64_t *d_hit_ptr, int64_t nR, const cfrk_read_hit *d_hits, int64_t n_hits,
+                                       const uint32_t *d_comp, int64_t nS, cfrk_read_component *d_out, cfrk_read_component_stats *stats) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = read_components_check(ctx, d_hit_ptr, nR, d_hits, n_hits, d_comp, nS, d_out, stats);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cfrk_read_components_launch(ctx, d_hit_ptr, nR, d_hits, n_hits, d_comp, nS, d_out, stats);
+}
+
+int cfrk_global_read_components(cfrk_ctx *ctx, const int64_t *hit_ptr, int64_t nR, const cfrk_read_hit *hits, int64_t n_hits,
+                                const uint32_t *comp, int64_t nS, cfrk_read_component *out, cfrk_read_component_stats *stats) {
+  if (!ctx) return CFRK_ERR_ARG;
+  int rc = read_components_check(ctx, hit_ptr, nR, hits, n_hits, comp, nS, out, stats);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // [hit_ptr | hits | comp] in a slot of their own, the rows in another
+  Carve c;
+  const size_t hptr_bytes = ((size_t)nR + 1) * 8, hit_bytes = (size_t)n_hits * sizeof *hits, comp_bytes = (size_t)nS * 4,
+               out_bytes = (size_t)nR * sizeof *out;
+  const size_t o_hptr = c.part(hptr_bytes), o_hits = c.part(hit_bytes), o_comp = c.part(comp_bytes);
+  void *d_in, *d_out;
+  if ((rc = cfrk_pool_get(ctx, BUF_READ_COMP_IN, c.end, &d_in))) return rc;
+  if ((rc = cfrk_pool_get(ctx, BUF_READ_COMP_OUT, out_bytes ? out_bytes : 16, &d_out))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_hptr), hit_ptr, hptr_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (hit_bytes) HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_hits), hits, hit_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (comp_bytes) HIP_TRY(ctx, hipMemcpyAsync(carve_at<void>(d_in, o_comp), comp, comp_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = cfrk_read_components_launch(ctx, carve_at<int64_t>(d_in, o_hptr), nR, carve_at<cfrk_read_hit>(d_in, o_hits), n_hits,
+                                        carve_at<uint32_t>(d_in, o_comp), nS, (cfrk_read_component *)d_out, stats)))
+    return stage_drain(ctx, rc);
+  return out_bytes ? cfrk_memcpy_d2h(ctx, out, d_out, out_bytes) : CFRK_OK;
+}
+
 /* ------------------------------------------------------------------ digital normalisation */
 
 static int normalize_check(cfrk_ctx *ctx, int64_t nN, int64_t nS, int64_t batch_reads, const void *data, const void *start,

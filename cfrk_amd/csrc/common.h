@@ -72,6 +72,10 @@ enum {  // pool slots
   BUF_READ_PATHS_IN, BUF_READ_PATHS_OUT,      // staging of cfrk_global_read_paths alone (hit_ptr, hits, records, link_ptr, links, support in; path_ptr, paths out)
   BUF_UNITIG_WEAK,                            // weak rule (unitig_weak.hip): error / count words, the in-rows, the scan's scratch
   BUF_UNITIG_WEAK_IN, BUF_UNITIG_WEAK_OUT,    // staging of cfrk_global_unitig_weak alone (records, link_ptr, links in; weak bytes out)
+  BUF_UNITIG_COMP,                            // components (unitig_components.hip): error / count words, parent[], the roots' flags and their scan, the in-degrees, the scan's scratch
+  BUF_UNITIG_COMP_IN, BUF_UNITIG_COMP_OUT,    // staging of cfrk_global_unitig_components alone (records, link_ptr, links, drop in; comp, then the table out)
+  BUF_READ_COMP,                              // read components (unitig_components.hip): error / count words, the reads' best offers and flag words
+  BUF_READ_COMP_IN, BUF_READ_COMP_OUT,        // staging of cfrk_global_read_components alone (hit_ptr, hits, comp in; rows out)
   BUF_NSLOTS
 };
 
@@ -282,6 +286,20 @@ struct cfrk_read_paths_in {
 int cfrk_read_paths_measure(cfrk_ctx *ctx, const cfrk_read_paths_in &in, int64_t *d_path_ptr, uint32_t *d_support,
                             int64_t *n_paths, cfrk_path_stats *stats);
 int cfrk_read_paths_fill(cfrk_ctx *ctx, const cfrk_read_paths_in &in, cfrk_read_path *d_paths, int64_t n_paths);
+// unitig_components.hip: the components of 1 <= nS < 2^32 unitigs in two steps: the row check, the union-find, the scan and
+// d_comp (synchronises once: CFRK_ERR_LAYOUT, or *n_comps and *stats); then the table into d_comps (room for n_comps >= 1
+// rows), left enqueued.  The fill step reads what the measure step left in the pool.
+struct cfrk_unitig_components_in {
+  const cfrk_unitig *d_rec; int64_t nS; const int64_t *d_link_ptr; const cfrk_unitig_link *d_links; int64_t n_links; const uint8_t *d_drop;
+};
+int cfrk_unitig_components_measure(cfrk_ctx *ctx, const cfrk_unitig_components_in &in, uint32_t *d_comp, int64_t *n_comps,
+                                   cfrk_component_stats *stats);
+int cfrk_unitig_components_fill(cfrk_ctx *ctx, const cfrk_unitig_components_in &in, const uint32_t *d_comp,
+                                cfrk_unitig_component *d_comps, int64_t n_comps);
+// ... and the component of every one of nR >= 0 reads from its hits and d_comp; synchronises once, for the error word
+// (CFRK_ERR_LAYOUT naming the read) and *stats
+int cfrk_read_components_launch(cfrk_ctx *ctx, const int64_t *d_hit_ptr, int64_t nR, const cfrk_read_hit *d_hits, int64_t n_hits,
+                                const uint32_t *d_comp, int64_t nS, cfrk_read_component *d_out, cfrk_read_component_stats *stats);
 // sketch.hip: fold the valid windows of d_data into the HyperLogLog registers d_regs (max-merged); the kernels are left
 // enqueued, the call's window count in *d_windows (a word of BUF_SKETCH).  Arguments are checked by the callers (abi.hip).
 int cfrk_sketch_launch(cfrk_ctx *ctx, const int8_t *d_data, int64_t nN, int k, int flags, uint8_t *d_regs,

@@ -352,6 +352,7 @@ int run_global(const Options &o, const Inputs &in, const cfrk_batch &batch, Work
   }
   g_timing.histo = now_s() - t2;
   if ((o.clip_tips || o.pop_bubbles || o.pop_bulges || o.drop_weak) && (rc = simplify_unitigs(o, ctx))) return rc;
+  if (o.min_component_kmers && (rc = drop_small_components(o, ctx))) return rc;
   if ((o.unitigs_out || o.unitigs_gfa) && (rc = write_unitigs(o, ctx))) return rc;
   if (o.unitigs_map && (rc = write_unitigs_map(o, ctx, in.mreads))) return rc;
   if (o.query) {

@@ -1122,6 +1122,68 @@ size_t cfrk_host_format_weak(uint32_t round, const int8_t *data, const int64_t *
   return buf ? (size_t)(p - buf) : s;
 }
 
+size_t cfrk_host_format_components(const void *table, int64_t n_comps, int k, char *buf, size_t cap) {
+  (void)cap;
+  size_t s = 0;
+  char *p = buf;
+  for (int64_t c = 0; c < n_comps; ++c) {
+    uint64_t kc, nk, nl;
+    uint32_t first, nu;
+    const char *row = (const char *)table + 32 * c;
+    memcpy(&kc, row, 8); memcpy(&nk, row + 8, 8); memcpy(&nl, row + 16, 8); memcpy(&first, row + 24, 4); memcpy(&nu, row + 28, 4);
+    const uint64_t bases = nk + (uint64_t)nu * (uint64_t)(k > 0 ? k - 1 : 0);
+    const uint64_t n = nk ? nk : 1;
+    const unsigned __int128 tenths = ((unsigned __int128)kc * 10 + n / 2) / n;      // as in the S line
+    const uint64_t whole = (uint64_t)(tenths / 10), frac = (uint64_t)(tenths % 10);
+    if (!buf) {
+      s += len_u64((uint64_t)c) + 1 + len_u64(first) + 1 + len_u64(nu) + 1 + len_u64(nk) + 1 + len_u64(bases) + 1 + len_u64(kc) + 1 + len_u64(whole) + 3 +
+           len_u64(nl) + 1;
+      continue;
+    }
+    p = put_u64(p, (uint64_t)c); *p++ = '\t';
+    p = put_u64(p, first); *p++ = '\t';
+    p = put_u64(p, nu); *p++ = '\t';
+    p = put_u64(p, nk); *p++ = '\t';
+    p = put_u64(p, bases); *p++ = '\t';
+    p = put_u64(p, kc); *p++ = '\t';
+    p = put_u64(p, whole); *p++ = '.'; *p++ = (char)('0' + frac); *p++ = '\t';
+    p = put_u64(p, nl); *p++ = '\n';
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
+size_t cfrk_host_tag_components(const char *text, size_t n, int gfa, const uint32_t *comp, int64_t nS, char *buf, size_t cap) {
+  (void)cap;
+  size_t s = 0;
+  char *p = buf;
+  int64_t j = 0;                                          // the next header / S line's unitig
+  for (size_t at = 0; at < n;) {
+    const char *nl = (const char *)memchr(text + at, '\n', n - at);
+    const size_t end = nl ? (size_t)(nl - text) : n;      // the line is text[at, end), its '\n' (if any) at end
+    const bool named = gfa ? (end - at >= 2 && text[at] == 'S' && text[at + 1] == '\t') : (end > at && text[at] == '>');
+    size_t cut = end;                                     // where the tag goes: the end of the line, in FASTA before the first L tag
+    bool tag = false;
+    if (named) {
+      tag = j < nS && comp[j] != 0xFFFFFFFFu;
+      if (tag && !gfa)
+        for (size_t x = at; x + 2 < end; ++x)
+          if (text[x] == ' ' && text[x + 1] == 'L' && text[x + 2] == ':') { cut = x; break; }
+    }
+    const size_t tag_len = tag ? 6 + len_u64(comp[j]) : 0;    // " CC:i:" or "\tCC:i:" and the number
+    const size_t whole = (end - at) + tag_len + (nl ? 1 : 0);
+    if (!buf) s += whole;
+    else {
+      memcpy(p, text + at, cut - at); p += cut - at;
+      if (tag) { *p++ = gfa ? '\t' : ' '; memcpy(p, "CC:i:", 5); p += 5; p = put_u64(p, comp[j]); }
+      memcpy(p, text + cut, end - cut); p += end - cut;
+      if (nl) *p++ = '\n';
+    }
+    if (named) ++j;
+    at = end + (nl ? 1 : 0);
+  }
+  return buf ? (size_t)(p - buf) : s;
+}
+
 static void put_le(char *p, uint64_t x, int bytes) { for (int i = 0; i < bytes; ++i) p[i] = (char)(x >> (8 * i)); }
 static uint64_t get_le(const char *p, int bytes) {
   uint64_t x = 0;

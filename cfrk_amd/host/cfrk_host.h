@@ -185,6 +185,23 @@ size_t cfrk_host_format_bulges(uint32_t round, const int8_t *data, const int64_t
 size_t cfrk_host_format_weak(uint32_t round, const int8_t *data, const int64_t *start, const int32_t *length, const void *rec,
                              int64_t nS, const uint8_t *weak, char *buf, size_t cap);
 
+/* The component table as text (`cfrk --unitigs-components CFILE`): table = n_comps rows of cfrk_unitig_component
+ * (cfrk_abi.h: 32 bytes -- kc, n_kmers, n_links as uint64, first, n_unitigs as uint32) as cfrk_global_unitig_components
+ * wrote them.  One line per component in id order, eight fields separated by tabs:
+ *   <id> <first> <n_unitigs> <n_kmers> <bases> <kc> <mean> <n_links>
+ * bases = n_kmers + n_unitigs (k - 1), the bases of the members' sequences; mean = kc / n_kmers with one decimal, printed
+ * as the km:f: tag of the S line prints it (n_kmers 0 divides by 1).  Returns bytes needed / written (buf may be NULL to
+ * size). */
+size_t cfrk_host_format_components(const void *table, int64_t n_comps, int k, char *buf, size_t cap);
+
+/* The component of every unitig as a tag in a text that is already formatted (`cfrk --unitigs-component-tags`): text =
+ * n bytes as cfrk_host_format_unitigs / _unitigs_links wrote them (gfa = 0) or as cfrk_host_format_gfa / _gfa_support did
+ * (gfa = 1), comp = nS words as cfrk_global_unitig_components wrote them.  The j-th header line (it begins with '>')
+ * gets " CC:i:<comp[j]>" behind its km:f: (and CL:i:1) tag, in front of its first " L:" tag; the j-th S line gets
+ * "\tCC:i:<comp[j]>" as its last tag.  Every other byte is copied.  A unitig with comp[j] = 0xFFFFFFFF, and a line
+ * beyond nS, gets no tag.  Returns bytes needed / written (buf may be NULL to size). */
+size_t cfrk_host_tag_components(const char *text, size_t n, int gfa, const uint32_t *comp, int64_t nS, char *buf, size_t cap);
+
 /* Read hits as GAF (`cfrk --unitigs-map QFILE --unitigs-map-out MFILE`): hit_ptr = n_reads + 1 offsets, hits = rows of
  * cfrk_read_hit (cfrk_abi.h: 16 bytes -- unitig, unitig_at = off << 1 | minus, read_off, n_windows as uint32),
  * unitig_length = the unitig list's lengths (every hit's unitig is an index into it).  One line per hit, in CSR order,

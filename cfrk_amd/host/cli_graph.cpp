@@ -1,6 +1,7 @@
 // cli_graph.cpp -- the unitig graph of the finished count, for the `cfrk` command: simplify (--unitigs-clip-tips,
 // --unitigs-pop-bubbles, --unitigs-pop-bulges, --unitigs-drop-weak), write (--unitigs-out, --unitigs-links, --unitigs-gfa), map reads onto it (--unitigs-map)
-// and thread them through it (--unitigs-map-paths, --unitigs-link-support, --unitigs-map-stats).
+// and thread them through it (--unitigs-map-paths, --unitigs-link-support, --unitigs-map-stats); its connected components
+// (--unitigs-components, --unitigs-component-tags, --unitigs-min-component-kmers, --unitigs-map-components).
 #include "cli_util.h"
 
 namespace {
@@ -142,12 +143,63 @@ int simplify_unitigs(const Options &o, cfrk_ctx *ctx) {
   return o.tip_report ? write_file(o.tip_report, report) : 0;
 }
 
+namespace {
+
+// the components of a graph that has its links, through the host form: a sizes-only call, then a table of that size
+int fetch_components(cfrk_ctx *ctx, const UnitigGraph &g, std::vector<uint32_t> *comp, std::vector<cfrk_unitig_component> *table) {
+  comp->resize((size_t)g.nS);
+  int64_t n = 0;
+  cfrk_component_stats stats;
+  const int rc = sized_call([&] { return cfrk_global_unitig_components(ctx, g.rec.data(), g.nS, g.link_ptr.data(), g.links.data(), g.n_links, nullptr,
+                                                                        comp->data(), table->data(), table->size(), &n, &stats); },
+                            [&] { table->resize((size_t)n); });
+  return rc ? die(ctx, rc, "cfrk_global_unitig_components") : 0;
+}
+
+// --unitigs-component-tags: the CC:i: tags into a text that is already formatted (cfrk_host_tag_components)
+void tag_components(std::string &buf, bool gfa, const std::vector<uint32_t> &comp) {
+  std::string tagged;
+  format_into(tagged, [&](char *out, size_t room) {
+    return cfrk_host_tag_components(buf.data(), buf.size(), gfa ? 1 : 0, comp.data(), (int64_t)comp.size(), out, room);
+  });
+  buf.swap(tagged);
+}
+
+}  // namespace
+
+// --unitigs-min-component-kmers N: unitigs, links and components of the graph as it stands (after any loop), then one mask
+// of every unitig of a component of fewer than N k-mers.  The mask stays set: what is written afterwards is what is left.
+int drop_small_components(const Options &o, cfrk_ctx *ctx) {
+  UnitigGraph g;
+  int rc;
+  if ((rc = g.fetch(ctx, o.unitigs_min_count, true))) return rc;
+  std::vector<uint32_t> comp;
+  std::vector<cfrk_unitig_component> table;
+  if ((rc = fetch_components(ctx, g, &comp, &table))) return rc;
+  std::vector<uint8_t> drop((size_t)g.nS);
+  bool any = false;
+  for (size_t j = 0; j < (size_t)g.nS; ++j) any |= (drop[j] = table[comp[j]].n_kmers < o.min_component_kmers ? 1 : 0) != 0;
+  if (any && (rc = cfrk_global_mask_unitigs(ctx, g.data.data(), g.start.data(), g.length.data(), g.nN, g.nS, drop.data())))
+    return die(ctx, rc, "cfrk_global_mask_unitigs");
+  return 0;
+}
+
 int write_unitigs(const Options &o, cfrk_ctx *ctx) {
   if (!o.unitigs_out && o.link_support) return 0;         // (GFILE alone, with the RC tags: write_unitigs_map fetches the graph and writes it)
   UnitigGraph g;
-  const bool with_links = o.unitigs_links || o.unitigs_gfa;
+  const bool with_links = o.unitigs_links || o.unitigs_gfa || o.unitigs_components || o.component_tags;
   int rc;
   if ((rc = g.fetch(ctx, o.unitigs_min_count, with_links))) return rc;
+  std::vector<uint32_t> comp;
+  if (o.unitigs_components || o.component_tags) {
+    std::vector<cfrk_unitig_component> table;
+    if ((rc = fetch_components(ctx, g, &comp, &table))) return rc;
+    if (o.unitigs_components) {
+      std::string buf;
+      format_into(buf, [&](char *out, size_t room) { return cfrk_host_format_components(table.data(), (int64_t)table.size(), o.k, out, room); });
+      if ((rc = write_file(o.unitigs_components, buf))) return rc;
+    }
+  }
   if (o.unitigs_out) {
     const int64_t *lp = o.unitigs_links ? g.link_ptr.data() : nullptr;     // (without --unitigs-links: the bytes as they were)
     std::string buf;
@@ -155,6 +207,7 @@ int write_unitigs(const Options &o, cfrk_ctx *ctx) {
       return with_links ? cfrk_host_format_unitigs_links(g.data.data(), g.start.data(), g.length.data(), g.rec.data(), g.nS, lp, g.links.data(), out, room)
                         : cfrk_host_format_unitigs(g.data.data(), g.start.data(), g.length.data(), g.rec.data(), g.nS, out, room);
     });
+    if (o.component_tags) tag_components(buf, false, comp);
     if ((rc = write_file(o.unitigs_out, buf))) return rc;
   }
   if (o.unitigs_gfa && !o.link_support) {                 // (--unitigs-link-support: write_unitigs_map writes GFILE, with the RC tags)
@@ -162,6 +215,7 @@ int write_unitigs(const Options &o, cfrk_ctx *ctx) {
     format_into(buf, [&](char *out, size_t room) {
       return cfrk_host_format_gfa(g.data.data(), g.start.data(), g.length.data(), g.rec.data(), g.nS, g.link_ptr.data(), g.links.data(), o.k, out, room);
     });
+    if (o.component_tags) tag_components(buf, true, comp);
     if ((rc = write_file(o.unitigs_gfa, buf))) return rc;
   }
   return 0;
@@ -197,6 +251,25 @@ int write_unitigs_map(const Options &o, cfrk_ctx *ctx, const cfrk_batch &q) {
                   [&] { hits.resize((size_t)n_hits); });
   if (rc) return die(ctx, rc, "cfrk_global_read_hits");
   std::string buf;
+  if (o.map_components) {                                 // RFILE: the reads by component, on the graph that is written
+    UnitigGraph cg;
+    if ((rc = cg.fetch(ctx, o.unitigs_min_count, true))) return rc;
+    std::vector<uint32_t> comp;
+    std::vector<cfrk_unitig_component> table;
+    if ((rc = fetch_components(ctx, cg, &comp, &table))) return rc;
+    std::vector<cfrk_read_component> rows((size_t)q.nS);
+    cfrk_read_component_stats rstats;
+    if ((rc = cfrk_global_read_components(ctx, hit_ptr.data(), q.nS, hits.data(), n_hits, comp.data(), cg.nS, rows.data(), &rstats)))
+      return die(ctx, rc, "cfrk_global_read_components");
+    for (const cfrk_read_component &r : rows) {
+      char line[64];
+      if (r.comp == CFRK_COMP_NONE) snprintf(line, sizeof line, "*\t*\t0\t%u\n", r.flags);
+      else snprintf(line, sizeof line, "%u\t%u\t%u\t%u\n", r.comp, r.hit, r.n_windows, r.flags);
+      buf += line;
+    }
+    if ((rc = write_file(o.map_components, buf))) return rc;
+    buf.clear();
+  }
   if (!o.map_paths && !o.link_support && !o.map_stats) {
     format_into(buf, [&](char *out, size_t room) { return cfrk_host_format_gaf(q.length, q.nS, hit_ptr.data(), hits.data(), ulen.data(), o.k, out, room); });
     return write_file(o.unitigs_map_out, buf);
@@ -230,6 +303,12 @@ int write_unitigs_map(const Options &o, cfrk_ctx *ctx, const cfrk_batch &q) {
       return cfrk_host_format_gfa_support(g.data.data(), g.start.data(), g.length.data(), g.rec.data(), g.nS, g.link_ptr.data(), g.links.data(),
                                           support.data(), o.canonical ? 1 : 0, o.k, out, room);
     });
+    if (o.component_tags) {                               // (GFILE is written here: the CC tags as write_unitigs puts them)
+      std::vector<uint32_t> comp;
+      std::vector<cfrk_unitig_component> table;
+      if ((rc = fetch_components(ctx, g, &comp, &table))) return rc;
+      tag_components(buf, true, comp);
+    }
     if ((rc = write_file(o.unitigs_gfa, buf))) return rc;
   }
   if (o.map_stats) {

@@ -123,6 +123,8 @@ const Row TABLE[] = {
   str("--unitigs-out", &O::unitigs_out), str("--unitigs-gfa", &O::unitigs_gfa), str("--unitigs-map", &O::unitigs_map),
   str("--unitigs-map-out", &O::unitigs_map_out), count("--unitigs-min-count", 0, &O::unitigs_min_count, &O::unitigs_opt_set),
   flag("--unitigs-map-paths", &O::map_paths), flag("--unitigs-link-support", &O::link_support), str("--unitigs-map-stats", &O::map_stats),
+  str("--unitigs-components", &O::unitigs_components), flag("--unitigs-component-tags", &O::component_tags), str("--unitigs-map-components", &O::map_components),
+  count("--unitigs-min-component-kmers", 0, &O::min_component_kmers, &O::component_opt_set),
 };
 
 // the value v of row r into o; 1 (the refusal printed) when it is not one the kind takes
@@ -236,6 +238,10 @@ int check_options(const Options &o) {
   if ((o.tip_opt_set && !o.clip_tips) || (o.tip_report && !o.clip_tips && !o.pop_bubbles && !o.pop_bulges && !o.drop_weak)) return refuse("--tip-max-kmers, --tip-ratio, --tip-rounds and --tip-report need --unitigs-clip-tips");
   if (o.unitigs_links && !o.unitigs_out) return refuse("--unitigs-links needs --unitigs-out UFILE");
   if (o.unitigs_opt_set && !graph_out) return refuse("--unitigs-min-count needs --unitigs-out UFILE");
+  if (o.unitigs_components && !o.unitigs_out) return refuse("--unitigs-components needs --unitigs-out UFILE");
+  if (o.component_tags && !o.unitigs_out) return refuse("--unitigs-component-tags needs --unitigs-out UFILE");
+  if (o.component_opt_set && !o.unitigs_out) return refuse("--unitigs-min-component-kmers needs --unitigs-out UFILE");
+  if (o.map_components && !(o.unitigs_out && o.unitigs_map)) return refuse("--unitigs-map-components needs --unitigs-out UFILE and --unitigs-map QFILE");
   if (o.sparse && (o.global || o.binary || o.histo || o.histo_only || o.range_set || o.query || o.query_out || o.query_only || o.query_db ||
                    o.query_stats || o.stats_below_set || o.filter_out || o.filter_opt_set || o.correct_out || o.correct_opt_set))
     return refuse("--sparse is a per-read mode: not with --global, --binary, --histo, --query or --min-count / --max-count");

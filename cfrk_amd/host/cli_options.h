@@ -67,6 +67,23 @@
 //                    (joined pairs of hits), gaps (pairs that are not window-adjacent) and unlinked (adjacent pairs
 //                    without a link: 0 on the graph's own complete links).  All three act on the graph that is
 //                    written, after any tip, bubble or bulge loop; without them every byte written is what it was
+//   --unitigs-components CFILE  (with --unitigs-out) the connected components of the graph that is written, after any
+//                    loop (cfrk_global_unitig_components, cfrk_host_format_components): one line per component in id
+//                    order, ids ascending by the component's smallest unitig, eight tab-separated fields -- id, first
+//                    (that unitig), n_unitigs, n_kmers, bases = n_kmers + n_unitigs (k - 1), kc, mean = kc / n_kmers as
+//                    the km:f: tag prints it, n_links (the members' links as the rows hold them, mirrors included)
+//   --unitigs-component-tags  (with --unitigs-out) every header of UFILE gets " CC:i:<id>", the unitig's component, behind
+//                    its km:f: (and CL:i:1) tag and in front of any L: tag, and every S line of GFILE "\tCC:i:<id>" as
+//                    its last tag (cfrk_host_tag_components)
+//   --unitigs-min-component-kmers N  (with --unitigs-out) after the loop (or with none) every component of fewer than N
+//                    k-mers is dropped as a whole: unitigs, links, components, one mask of all their unitigs.  Whole
+//                    components go, so no remaining unitig gains or loses a neighbour: UFILE, the L tags, GFILE, MFILE,
+//                    CFILE and RFILE describe exactly the unitigs that are left, renumbered
+//   --unitigs-map-components RFILE  (with --unitigs-out and --unitigs-map) which read of QFILE goes with which component
+//                    (cfrk_global_read_components): one line per read, four tab-separated fields -- id, hit, n_windows,
+//                    flags: the component of the read's hit with the most windows (the earliest on a tie), that hit's
+//                    index among the read's hits, its windows, and 1 when another hit of the read lies in a different
+//                    component.  A read with no hit gets "*\t*\t0\t0"
 //   --unitigs-clip-tips [--tip-max-kmers M] [--tip-ratio R] [--tip-rounds N] [--tip-report RFILE]  (with --unitigs-out,
 //                    --unitigs-gfa or --unitigs-map) clip tips off the graph before anything is written: up to N rounds
 //                    (default 4) of unitigs, links, the tip rule and a mask of the tips' k-mers, ended by the first
@@ -257,6 +274,10 @@ struct Options {
   bool map_paths = false;             // --unitigs-map-paths
   bool link_support = false;          // --unitigs-link-support
   const char *map_stats = nullptr;    // --unitigs-map-stats SFILE
+  const char *unitigs_components = nullptr;      // --unitigs-components CFILE
+  const char *map_components = nullptr;          // --unitigs-map-components RFILE
+  bool component_tags = false;                   // --unitigs-component-tags
+  uint32_t min_component_kmers = 0;              // --unitigs-min-component-kmers N (0: nothing is dropped)
   bool clip_tips = false;             // --unitigs-clip-tips
   uint32_t tip_max_kmers = 0;         // --tip-max-kmers M (0: k)
   uint32_t tip_ratio_q8 = 512;        // --tip-ratio R, in 256ths
@@ -320,7 +341,7 @@ struct Options {
   int batch_n = -1;                                                 // --batch N (-1: not given)
   std::vector<const char *> pos;                                    // the positional arguments, in order
   // raised by the options that were given: what the cross-option rules ask about
-  bool unitigs_opt_set = false, tip_opt_set = false, tip_rounds_set = false, bubble_opt_set = false, simplify_rounds_set = false, bulge_opt_set = false, weak_opt_set = false, weak_iso_max_set = false, range_set = false, stats_below_set = false;
+  bool unitigs_opt_set = false, tip_opt_set = false, tip_rounds_set = false, bubble_opt_set = false, simplify_rounds_set = false, bulge_opt_set = false, weak_opt_set = false, weak_iso_max_set = false, component_opt_set = false, range_set = false, stats_below_set = false;
   bool filter_opt_set = false, correct_opt_set = false, correct_min_count_set = false, normalize_opt_set = false, normalize_cutoff_set = false;
   bool pair_opt_set = false, pair_mode_set = false, min_qual_set = false;
 };

@@ -105,6 +105,7 @@ inline int odd_records(const char *path, int64_t nS) {
 
 // cli_graph.cpp: each 0, or the exit status (the error reported)
 int simplify_unitigs(const Options &o, cfrk_ctx *ctx);
+int drop_small_components(const Options &o, cfrk_ctx *ctx);
 int write_unitigs(const Options &o, cfrk_ctx *ctx);
 int write_unitigs_map(const Options &o, cfrk_ctx *ctx, const cfrk_batch &q);
 

@@ -91,7 +91,15 @@ CFRK_WEAK_CONNECTION = 1             # weak rule: weak[j] of an erroneous connec
 CFRK_WEAK_ISOLATED = 2               # ... and of an isolated low-coverage unitig
 # what one weak call found (cfrk_weak_stats)
 WEAK_STATS_DTYPE = np.dtype([("connections", "<i8"), ("isolated", "<i8"), ("candidates", "<i8")])
-CFRK_COMPACT_TILE_BYTES = 4096       # unitig compaction: bytes of data_out per workgroup of the emit
+CFRK_COMP_NONE = 0xFFFFFFFF          # unitig components: comp[j] of a dropped unitig
+# cfrk_unitig_component / cfrk_component_stats: a row of the component table; what one components call counted
+UNITIG_COMPONENT_DTYPE = np.dtype([("kc", "<u8"), ("n_kmers", "<u8"), ("n_links", "<u8"), ("first", "<u4"), ("n_unitigs", "<u4")])
+COMPONENT_STATS_DTYPE = np.dtype([("n_components", "<u8"), ("n_unitigs", "<u8"), ("n_kmers", "<u8"), ("n_links", "<u8")])
+CFRK_READ_COMP_SPLIT = 1             # read components: another eligible hit lies in a different component
+CFRK_READ_COMP_DROPPED = 2           # ... some hit lies on a unitig without a component
+READ_COMPONENT_DTYPE = np.dtype([("comp", "<u4"), ("hit", "<u4"), ("n_windows", "<u4"), ("flags", "<u4")])
+READ_COMPONENT_STATS_DTYPE = np.dtype([("n_assigned", "<u8"), ("n_unassigned", "<u8"), ("n_split", "<u8"), ("n_dropped", "<u8")])
+CFRK_COMPACT_TILE_BYTES = 4096      # unitig compaction: bytes of data_out per workgroup of the emit
 # cfrk_read_path / cfrk_path_stats: a read's walk through the graph as a range of its hits; what a read_paths call counted
 READ_PATH_DTYPE = np.dtype([("hit_first", "<u4"), ("n_hits", "<u4"), ("read_off", "<u4"), ("n_windows", "<u4")])
 PATH_STATS_DTYPE = np.dtype([("n_paths", "<u8"), ("n_steps", "<u8"), ("n_gaps", "<u8"), ("n_unlinked", "<u8")])
@@ -183,6 +191,10 @@ def load_library():
         "cfrk_global_unitig_bubbles_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(i64)], C.c_int),
         "cfrk_global_unitig_weak": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp], C.c_int),
         "cfrk_global_unitig_weak_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp], C.c_int),
+        "cfrk_global_unitig_components": ([vp, vp, i64, vp, vp, i64, vp, vp, vp, u64, C.POINTER(i64), vp], C.c_int),
+        "cfrk_global_unitig_components_device": ([vp, vp, i64, vp, vp, i64, vp, vp, vp, u64, C.POINTER(i64), vp], C.c_int),
+        "cfrk_global_read_components": ([vp, vp, i64, vp, i64, vp, i64, vp, vp], C.c_int),
+        "cfrk_global_read_components_device": ([vp, vp, i64, vp, i64, vp, i64, vp, vp], C.c_int),
         "cfrk_global_unitig_bulges": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, u64, C.POINTER(i64), vp], C.c_int),
         "cfrk_global_unitig_bulges_device": ([vp, vp, i64, vp, vp, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, u64, C.POINTER(i64), vp], C.c_int),
         "cfrk_global_unitigs_compact": ([vp, vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, u64, vp, vp, vp, u64, vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
@@ -1144,6 +1156,93 @@ class GlobalCounter:
             e.n_paths, e.stats = n.value, st
             raise
         return n.value, st
+
+    def unitig_components(self, rec, link_ptr, links, drop=None):
+        """the connected components of the unitig graph -> (comp uint32[nS], table UNITIG_COMPONENT_DTYPE[n_comps],
+        stats): two unitigs with drop[j] == 0 (all of them when drop is None) belong together iff a chain of links, read
+        without strand or direction, joins them through such unitigs.  Components are numbered ascending by their
+        smallest unitig; comp[j] is CFRK_COMP_NONE for a dropped unitig.  A table row sums its members' kc and n_kmers
+        and counts their links to kept targets (n_links), names the smallest member (first) and counts the members
+        (n_unitigs).  stats = {"n_components", "n_unitigs", "n_kmers", "n_links"} over the kept unitigs.  Raises CfrkError
+        (CFRK_ERR_LAYOUT, the message naming the unitig) when the rows are not link rows.  A sizes-only call, then the
+        call into an array of exactly that size."""
+        rec = np.ascontiguousarray(rec, UNITIG_DTYPE)
+        link_ptr = np.ascontiguousarray(link_ptr, np.int64)
+        links = np.ascontiguousarray(links, UNITIG_LINK_DTYPE)
+        if len(link_ptr) != len(rec) + 1:
+            raise ValueError("link_ptr has not one entry more than rec")
+        if drop is not None:
+            drop = np.ascontiguousarray(drop, np.uint8)
+            if len(drop) != len(rec):
+                raise ValueError("drop and rec differ in length")
+        comp, stats, n = np.zeros(len(rec), np.uint32), np.zeros(1, COMPONENT_STATS_DTYPE), C.c_int64()
+        args = (self.ctx._h, _ptr(rec), len(rec), _ptr(link_ptr), _ptr(links), len(links), _ptr(drop) if drop is not None else None,
+                _ptr(comp))
+        rc = self._L.cfrk_global_unitig_components(*args, None, 0, C.byref(n), _ptr(stats))
+        if rc != CFRK_ERR_SMALL_BUF:
+            self.ctx.check(rc, "cfrk_global_unitig_components")
+        table = np.zeros(n.value, UNITIG_COMPONENT_DTYPE)
+        self.ctx.check(self._L.cfrk_global_unitig_components(*args, _ptr(table), table.size, C.byref(n), _ptr(stats)),
+                       "cfrk_global_unitig_components")
+        assert n.value == len(table) == int(stats["n_components"][0])
+        return comp, table, {f: int(stats[f][0]) for f in COMPONENT_STATS_DTYPE.names}
+
+    def unitig_components_device(self, d_rec, nS, d_link_ptr, d_links, n_links, d_drop, d_comp, d_comps=0, cap_comps=0):
+        """device form -> (n_comps, stats); d_drop may be 0 (nothing dropped); d_comps may be 0 with cap_comps 0 (sizes
+        only).  Raises CfrkError (code CFRK_ERR_SMALL_BUF, with .n_comps and .stats set, d_comp complete, nothing written
+        to d_comps) when cap_comps is too small.  Synchronises once, returns with the table's passes enqueued."""
+        n, stats = C.c_int64(), np.zeros(1, COMPONENT_STATS_DTYPE)
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = self._L.cfrk_global_unitig_components_device(self.ctx._h, vp(d_rec), nS, vp(d_link_ptr), vp(d_links), n_links, vp(d_drop),
+                                                          vp(d_comp), vp(d_comps), cap_comps, C.byref(n), _ptr(stats))
+        st = {f: int(stats[f][0]) for f in COMPONENT_STATS_DTYPE.names}
+        try:
+            self.ctx.check(rc, "cfrk_global_unitig_components_device")
+        except CfrkError as e:
+            e.n_comps, e.stats = n.value, st
+            raise
+        return n.value, st
+
+    def read_components(self, hit_ptr, hits, comp):
+        """the component every read goes with -> (rows READ_COMPONENT_DTYPE[nR], stats): from the hits of read_hits() and
+        comp of unitig_components().  A read's deciding hit is the one with the most windows among those whose unitig
+        has a component, the earliest on a tie: comp, hit (its index inside the read's row), n_windows; flags has
+        CFRK_READ_COMP_SPLIT when another such hit lies in a different component and CFRK_READ_COMP_DROPPED when some hit
+        lies on a unitig without one.  A read with no deciding hit gets comp = hit = 0xFFFFFFFF, n_windows = 0.  stats =
+        {"n_assigned", "n_unassigned", "n_split", "n_dropped"}, counting reads.  Raises CfrkError (CFRK_ERR_LAYOUT, the
+        message naming the read) when the hits are not hits on a list of len(comp) unitigs."""
+        hit_ptr = np.ascontiguousarray(hit_ptr, np.int64)
+        hits = np.ascontiguousarray(hits, READ_HIT_DTYPE)
+        comp = np.ascontiguousarray(comp, np.uint32)
+        if len(hit_ptr) < 1:
+            raise ValueError("hit_ptr is empty")
+        nR = len(hit_ptr) - 1
+        rows, stats = np.zeros(nR, READ_COMPONENT_DTYPE), np.zeros(1, READ_COMPONENT_STATS_DTYPE)
+        self.ctx.check(self._L.cfrk_global_read_components(self.ctx._h, _ptr(hit_ptr), nR, _ptr(hits), len(hits), _ptr(comp), len(comp),
+                                                           _ptr(rows), _ptr(stats)), "cfrk_global_read_components")
+        return rows, {f: int(stats[f][0]) for f in READ_COMPONENT_STATS_DTYPE.names}
+
+    def read_components_device(self, d_hit_ptr, nR, d_hits, n_hits, d_comp, nS, d_out):
+        """device form -> stats; synchronises once, for the counts and the check of the hits"""
+        stats = np.zeros(1, READ_COMPONENT_STATS_DTYPE)
+        vp = lambda p: C.c_void_p(p) if p else None
+        self.ctx.check(self._L.cfrk_global_read_components_device(self.ctx._h, vp(d_hit_ptr), nR, vp(d_hits), n_hits, vp(d_comp), nS,
+                                                                  vp(d_out), _ptr(stats)), "cfrk_global_read_components_device")
+        return {f: int(stats[f][0]) for f in READ_COMPONENT_STATS_DTYPE.names}
+
+    def drop_small_components(self, min_kmers, min_count=1):
+        """drop every component of fewer than min_kmers k-mers from the graph: unitigs -> links -> components, one
+        mask_unitigs() call with every unitig of such a component, unitigs again -> ((data, start, length, rec) of what is
+        left, (n_components_dropped, n_unitigs_dropped)).  Whole components go, so no remaining unitig gains or loses a
+        neighbour: the returned list is the kept unitigs of the first list, byte for byte and in their order."""
+        data, start, length, rec = self.unitigs(min_count)
+        link_ptr, links = self.unitig_links(data, start, length, min_count)
+        comp, table, _ = self.unitig_components(rec, link_ptr, links)
+        small = table["n_kmers"] < np.uint64(min_kmers)
+        drop = small[comp].astype(np.uint8) if len(comp) else np.zeros(0, np.uint8)
+        if drop.any():
+            self.mask_unitigs(data, start, length, drop)
+        return self.unitigs(min_count), (int(small.sum()), int(drop.sum()))
 
     def mask_keys(self, keys_lo, keys_hi=None):
         """add keys to the graph mask: a masked key is no longer solid for neighbors(), unitigs(), unitig_links(),

@@ -999,6 +999,106 @@ int cfrk_global_read_paths(cfrk_ctx *ctx, const int64_t *hit_ptr /* nR + 1 */, i
                            cfrk_read_path *paths, uint64_t cap_paths, int64_t *n_paths_out,
                            uint32_t *support /* n_links, added to; may be NULL */, cfrk_path_stats *stats);
 
+/* Unitig components: which unitigs of the graph belong together.  Like the four rules a pure function of the unitigs'
+ * records (rec[nS]; kc and n_kmers are summed, nothing else is read), the link CSR (link_ptr[nS + 1], links[n_links]) and
+ * the job's strand rule, which is used for the row check alone.  No sequence, no index, no counts.
+ *   KEPT: unitig j is kept iff drop is NULL or drop[j] == 0.
+ *   CONNECTED: two kept unitigs are connected iff some link of either row names the other.  Strand flags and direction
+ *   are ignored: in a job that is not canonical the rows are directed, and the classes are the WEAKLY connected
+ *   components.  A link whose source or target is not kept does not exist.  Self-links, hairpins and
+ *   CFRK_UNITIG_CIRCULAR change nothing.
+ *   COMPONENT: a class of the transitive closure over the kept unitigs.  Components are numbered 0, 1, ... ascending by
+ *   their smallest unitig; comp[j] is that number, CFRK_COMP_NONE for a unitig that is not kept.  Every word of comp is
+ *   written.  The output is one byte string for a given input: it depends neither on scheduling nor on the order of the
+ *   links inside a row.
+ *   TABLE: comps[c] is cfrk_unitig_component: the sums of the members' kc (modulo 2^64) and n_kmers, the links of the
+ *   members' rows whose target is kept, as written (so with the mirrors a canonical link set holds), the smallest member
+ *   and the number of members.  STATISTICS (cfrk_component_stats): the components, and the kept unitigs, their k-mers and
+ *   their links to kept targets: the sums of the table's columns.
+ *   With drop, the components are those of the graph cfrk_global_unitigs_compact makes of the same arguments, pulled
+ *   back through its `into`: compaction merges only unitigs that a link joined.
+ * Capacity (the select's protocol): when n_comps > cap_comps the call returns CFRK_ERR_SMALL_BUF with comp, *n_comps_out
+ *   and stats complete and nothing written to comps; NULL comps with cap_comps 0 is that "sizes only" call; cap_comps =
+ *   nS is always enough.
+ * Untrusted input: the row check of "Unitig tips" runs in front, with the same five CFRK_ERR_LAYOUT reasons naming the
+ *   first offending unitig, and only checked rows are followed.  After a refusal comp is all CFRK_COMP_NONE and the
+ *   sizes and stats are 0.  For any input whatever nothing outside the buffers is accessed and no loop is unbounded
+ *   (cfrk_amd/csrc/unitig_components.hip states the bound of the union-find).
+ * CFRK_ERR_STATE: no job.  CFRK_ERR_ARG: negative sizes, NULL n_comps_out or stats, NULL rec / link_ptr / comp with
+ *   nS > 0, NULL links with n_links > 0, NULL comps with cap_comps > 0, nS >= 2^32.  nS = 0 is fine.  The job, the index,
+ *   the position map and the mask are neither read nor changed: same digest before and after.
+ * Device form: a lock-free union-find over the rows (init, hook, flatten), a hipCUB exclusive sum over the roots'
+ *   flags, a pass that writes comp and sums the statistics per wave; n_comps_out and stats are host memory, the call
+ *   synchronises ONCE, for them and the error word, and returns with the passes that zero and fill comps enqueued.
+ *   d_comps is 8-byte aligned.  Temporary device memory, kept in the context's pool: 8 bytes per unitig and the scan's
+ *   scratch; not canonical: 8 more per unitig for the in-degrees the row check counts.  Host form: stages through the
+ *   pool; synchronous. */
+#define CFRK_COMP_NONE 0xFFFFFFFF
+typedef struct cfrk_unitig_component {   /* 32 bytes, no padding */
+  uint64_t kc;          /* sum of the members' kc                                      */
+  uint64_t n_kmers;     /* sum of the members' n_kmers                                 */
+  uint64_t n_links;     /* links of the members' rows whose target is kept, as written */
+  uint32_t first;       /* the smallest member unitig                                  */
+  uint32_t n_unitigs;   /* number of member unitigs                                    */
+} cfrk_unitig_component;
+typedef struct cfrk_component_stats {    /* 32 bytes, no padding */
+  uint64_t n_components;
+  uint64_t n_unitigs;   /* kept                          */
+  uint64_t n_kmers;     /* of the kept unitigs           */
+  uint64_t n_links;     /* of kept rows, to kept targets */
+} cfrk_component_stats;
+int cfrk_global_unitig_components_device(cfrk_ctx *ctx, const cfrk_unitig *d_rec, int64_t nS, const int64_t *d_link_ptr /* nS + 1 */,
+                                         const cfrk_unitig_link *d_links, int64_t n_links, const uint8_t *d_drop /* nS; may be NULL */,
+                                         uint32_t *d_comp /* nS, every one written */, cfrk_unitig_component *d_comps /* may be NULL */,
+                                         uint64_t cap_comps, int64_t *n_comps_out, cfrk_component_stats *stats);
+int cfrk_global_unitig_components(cfrk_ctx *ctx, const cfrk_unitig *rec, int64_t nS, const int64_t *link_ptr /* nS + 1 */,
+                                  const cfrk_unitig_link *links, int64_t n_links, const uint8_t *drop /* nS; may be NULL */,
+                                  uint32_t *comp /* nS */, cfrk_unitig_component *comps /* may be NULL */, uint64_t cap_comps,
+                                  int64_t *n_comps_out, cfrk_component_stats *stats);
+
+/* Read components: which read goes with which component (khmer's partitioning of reads), from the hit CSR as
+ * cfrk_global_read_hits wrote it for nR reads (hit_ptr[nR + 1], hits[n_hits]; of a hit only unitig and n_windows are
+ * read) and comp[nS] of cfrk_global_unitig_components alone.  Needs no job state beyond a begun job.
+ *   ELIGIBLE: a hit whose unitig has a component, comp[unitig] != CFRK_COMP_NONE.
+ *   The read's DECIDING HIT is the eligible hit with the most windows, on a tie the earliest.  A row of out is
+ *   cfrk_read_component: comp = that hit's component, hit = its index inside the read's row, n_windows = its window
+ *   count, flags: CFRK_READ_COMP_SPLIT when some other eligible hit of the read lies in a different component,
+ *   CFRK_READ_COMP_DROPPED when some hit of the read is not eligible.  A read with no eligible hit gets comp = hit =
+ *   0xFFFFFFFF and n_windows = 0 (and CFRK_READ_COMP_DROPPED iff it has a hit at all).
+ *   STATISTICS (cfrk_read_component_stats), counting reads: n_assigned, n_unassigned, n_split, n_dropped.
+ * Untrusted input: CFRK_ERR_LAYOUT, cfrk_last_error naming the first offending read, when hit_ptr does not start at 0,
+ *   descends or leaves [0, n_hits] (hit_ptr[nR] may lie below n_hits: the hits behind it belong to no read and are not
+ *   looked at), when a hit's unitig is >= nS or its n_windows is 0.  A refused hit_ptr wins over a refused hit.  After
+ *   a refusal out is unspecified and the stats are 0.  Any value of comp[] is taken as given: nothing is indexed by it.
+ * CFRK_ERR_ARG: negative sizes, NULL stats or hit_ptr, NULL hits with n_hits > 0, NULL comp with nS > 0, NULL out with
+ *   nR > 0, nS >= 2^32, n_hits >= 2^32 (a hit's index inside its row is 32 bits).  CFRK_ERR_STATE: no job.  nR = 0 and
+ *   n_hits = 0 are fine.  The job is neither read nor changed.
+ * Device form (cfrk_amd/csrc/unitig_components.hip): balanced by HITS.  One lane per hit finds its read by binary
+ *   search in hit_ptr and offers (n_windows << 32) | (0xFFFFFFFF - index in row) to a 64-bit atomic maximum per read; a
+ *   second pass per hit compares its component with the winner's and ORs the flag bits; one lane per read writes the
+ *   row.  A read of 10^5 hits costs what its hits cost.  stats is host memory; the call synchronises ONCE.  Temporary
+ *   device memory, kept in the context's pool: 12 bytes per read.  Host form: stages through the pool; synchronous. */
+#define CFRK_READ_COMP_SPLIT 1
+#define CFRK_READ_COMP_DROPPED 2
+typedef struct cfrk_read_component {     /* 16 bytes, no padding */
+  uint32_t comp;        /* the deciding hit's component; 0xFFFFFFFF: none */
+  uint32_t hit;         /* its index inside the read's hit row; 0xFFFFFFFF: none */
+  uint32_t n_windows;   /* its windows */
+  uint32_t flags;       /* CFRK_READ_COMP_* */
+} cfrk_read_component;
+typedef struct cfrk_read_component_stats {   /* 32 bytes, no padding */
+  uint64_t n_assigned;
+  uint64_t n_unassigned;
+  uint64_t n_split;
+  uint64_t n_dropped;
+} cfrk_read_component_stats;
+int cfrk_global_read_components_device(cfrk_ctx *ctx, const int64_t *d_hit_ptr /* nR + 1 */, int64_t nR, const cfrk_read_hit *d_hits,
+                                       int64_t n_hits, const uint32_t *d_comp /* nS */, int64_t nS,
+                                       cfrk_read_component *d_out /* nR */, cfrk_read_component_stats *stats);
+int cfrk_global_read_components(cfrk_ctx *ctx, const int64_t *hit_ptr /* nR + 1 */, int64_t nR, const cfrk_read_hit *hits,
+                                int64_t n_hits, const uint32_t *comp /* nS */, int64_t nS, cfrk_read_component *out /* nR */,
+                                cfrk_read_component_stats *stats);
+
 /* ---- distinct k-mer estimate: a HyperLogLog sketch of the reads, 1 <= k <= 64 --------------------------------- */
 
 /* How many DISTINCT k-mers will a job hold?  One streaming pass over the reads answers it to about 1 % before anything

@@ -61,7 +61,15 @@ with an error breaks where the error's k-mers were dropped, as it should; an err
 eaten -- the check on the rule's default ratio.  A third "rounds" line with
 no rule at all gives the same numbers on the graph as counted.
 
-  python tools/bench_unitigs.py [--links | --tips [--parent-lib SO] | --bubbles [--parent-lib SO] | --bulges | --compact | --weak] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
+With --components the tool "bench_components" writes, per case: a line "components" with the components call
+(cfrk_global_unitig_components_device, the table at exact capacity) alternating in the same repetitions with its
+sizes-only call, the weak call and the links call, and the census of the graph: components, the largest one's k-mers,
+unitigs and share of all k-mers, the components below 2k k-mers and their k-mers, the components of one unitig; a line
+"crafted_pair" with the call on two crafted link sets of the same nS and n_links over the same records -- (a) all one
+component, (b) links only inside blocks of 8 unitigs -- which read the same bytes, and their ratio; and, case b, a line
+"components_after_loop" with the census of the graph the four-rule loop leaves.
+
+  python tools/bench_unitigs.py [--links | --tips [--parent-lib SO] | --bubbles [--parent-lib SO] | --bulges | --compact | --weak | --components] [--cases a,b,c] [--split 8,10,12] [--reads R] [--L L] [--glen G] [--k K] [--reps N]
 """
 import argparse
 import json
@@ -436,6 +444,132 @@ def weak_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf, 
     g.mask_clear()
 
 
+def components_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf, case):
+    """--components: the components call beside the weak and the links call; the census of the graph (and, case b, of the
+    graph the four-rule loop leaves); a crafted pair at the same nS and n_links: one component against blocks of 8"""
+    k = a.k
+    tip_q8, bub_q8, bulge_q8 = int(round(a.tip_ratio * 256)), int(round(a.bubble_ratio * 256)), int(round(a.bulge_ratio * 256))
+    weak_q8, iso_q8 = int(round(a.weak_ratio * 256)), int(round(a.weak_iso_mean * 256))
+    max_hops = min(k + a.bulge_max_diff, cfrk_amd.CFRK_BULGE_MAX_HOPS)
+
+    def graph_args(gr):
+        return (gr.out[3].data_ptr(), gr.nS, gr.ptr.data_ptr(), gr.rows.data_ptr(), gr.n_links)
+
+    def sizes_only(args, d_comp):
+        try:
+            return g.unitig_components_device(*args, 0, d_comp.data_ptr())
+        except cfrk_amd.CfrkError as e:
+            if e.code != cfrk_amd.CFRK_ERR_SMALL_BUF:
+                raise
+            return e.n_comps, e.stats
+
+    def census(args):
+        """the components of a graph -> (figures, d_comp, d_tab, n)"""
+        nS = args[1]
+        d_comp = buf(nS * 4)
+        n, st = sizes_only(args, d_comp)
+        d_tab = buf(max(n, 1) * 32)
+        g.unitig_components_device(*args, 0, d_comp.data_ptr(), d_tab.data_ptr(), n)
+        ctx.sync()
+        torch.cuda.synchronize()
+        tab = d_tab[:n * 32].view(torch.int64).view(n, 4)
+        nk = tab[:, 1]
+        members = tab[:, 3] >> 32                                # (first in the low word, n_unitigs in the high one)
+        big = int(nk.argmax()) if n else 0
+        fig = {"components": n, "kept_unitigs": st["n_unitigs"], "kmers": st["n_kmers"], "kept_links": st["n_links"],
+               "largest_kmers": int(nk[big]) if n else 0, "largest_unitigs": int(members[big]) if n else 0,
+               "largest_share_of_kmers": (int(nk[big]) / max(st["n_kmers"], 1)) if n else 0.0,
+               "components_below_2k_kmers": int((nk < 2 * k).sum()), "kmers_in_components_below_2k": int(nk[nk < 2 * k].sum()),
+               "components_of_one_unitig": int((members == 1).sum())}
+        return fig, d_comp, d_tab, n
+
+    new = _Graph(cfrk_amd, g, min_count, buf)
+    ctx.sync()
+    fig, d_comp, d_tab, n = census(graph_args(new))
+    d_weak = buf(new.nS)
+    calls = {"components": lambda: g.unitig_components_device(*graph_args(new), 0, d_comp.data_ptr(), d_tab.data_ptr(), n),
+             "components_sizes_only": lambda: sizes_only(graph_args(new), d_comp),
+             "weak": lambda: g.unitig_weak_device(*graph_args(new), k, weak_q8, 2 * k, iso_q8, d_weak.data_ptr()), "links_call": new.links}
+    t = {name: [] for name in calls}
+    for rep in range(a.reps + 1):
+        for name, fn in calls.items():                          # alternating in one process
+            ms = timed(fn)
+            if rep:                                             # (the first round warms up: code objects, pool buffers)
+                t[name].append(ms)
+    ctx.sync()
+    torch.cuda.synchronize()
+    row = dict(common, line="components", nodes=new.nodes(torch), unitigs=new.nS, links=new.n_links, census=fig)
+    row.update({name: dict(stats(ts), series=ts) for name, ts in t.items()})
+    row["components_over_links"] = row["components"]["ms"] / row["links_call"]["ms"]
+    row["components_over_weak"] = row["components"]["ms"] / row["weak"]["ms"]
+    row["ns_per_unitig"] = row["components"]["ms"] * 1e6 / max(new.nS, 1)
+    print(json.dumps(row), flush=True)
+
+    # the crafted pair: the real records, rows of n_links / nS links each (the remainder spread over the first rows), link p
+    # of row j to (a) j + 1 + p, all one component, (b) the same inside j's block of 8.  The two read the same bytes.
+    nS, deg, rem = new.nS, new.n_links // max(new.nS, 1), new.n_links % max(new.nS, 1)
+    if nS >= 16 and 1 <= deg < 16:
+        j = torch.arange(nS, device="cuda", dtype=torch.int64)
+        d = deg + (j < rem).to(torch.int64)
+        ptr = buf((nS + 1) * 8)
+        p64 = ptr[:(nS + 1) * 8].view(torch.int64)
+        p64[0] = 0
+        p64[1:] = torch.cumsum(d, 0)
+        src = torch.repeat_interleave(j, d)
+        pos = torch.arange(new.n_links, device="cuda", dtype=torch.int64) - p64[:-1][src]
+        pair = {}
+        for name, to in (("one_component", (src + 1 + pos) % nS), ("blocks_of_8", torch.minimum((src & ~7) + ((src + 1 + pos) & 7), j[-1]))):
+            rows = buf(new.n_links * 8)
+            r32 = rows[:new.n_links * 8].view(torch.int32).view(new.n_links, 2)
+            r32[:, 0] = to.to(torch.int32)
+            r32[:, 1] = 0
+            torch.cuda.synchronize()
+            args = (new.out[3].data_ptr(), nS, ptr.data_ptr(), rows.data_ptr(), new.n_links)
+            cfig, c_comp, c_tab, cn = census(args)
+            ts = []
+            for rep in range(a.reps + 1):
+                ms = timed(lambda: g.unitig_components_device(*args, 0, c_comp.data_ptr(), c_tab.data_ptr(), cn))
+                if rep:
+                    ts.append(ms)
+            pair[name] = dict(stats(ts), series=ts, components=cn, largest_unitigs=cfig["largest_unitigs"])
+            del rows, c_comp, c_tab
+        print(json.dumps(dict(common, line="crafted_pair", unitigs=nS, links=new.n_links, links_per_row=deg, **pair,
+                              one_over_blocks=pair["one_component"]["ms"] / pair["blocks_of_8"]["ms"])), flush=True)
+        del ptr, src, pos, j, d
+    del new, d_comp, d_tab, d_weak
+    torch.cuda.empty_cache()
+    if case != "b":
+        return
+    # the 1 % case: the census again on the graph the four-rule loop leaves
+    rounds, cur = 0, _Graph(cfrk_amd, g, min_count, buf)
+    for r in range(a.tip_rounds):
+        if r:
+            cur = _Graph(cfrk_amd, g, min_count, buf)
+        d_tip, d_bub, d_pop, d_weak = buf(cur.nS), buf(cur.nS), buf(cur.nS), buf(cur.nS)
+        n_tips = g.unitig_tips_device(*graph_args(cur), k, tip_q8, d_tip.data_ptr())
+        n_bub = g.unitig_bubbles_device(*graph_args(cur), k, a.bubble_max_diff, bub_q8, d_bub.data_ptr(), 0)
+        bst = g.unitig_bulges_device(*graph_args(cur), k, a.bulge_max_diff, max_hops, a.bulge_max_visits, bulge_q8, d_pop.data_ptr())[1]
+        wst = g.unitig_weak_device(*graph_args(cur), k, weak_q8, 2 * k, iso_q8, d_weak.data_ptr())
+        found = n_tips or n_bub or bst["popped"] or wst["connections"] or wst["isolated"]
+        rounds += 1
+        if found:
+            ctx.sync()
+            d_tip[:cur.nS] |= d_bub[:cur.nS] | d_pop[:cur.nS] | d_weak[:cur.nS].ne(0).to(torch.uint8)
+            torch.cuda.synchronize()
+            g.mask_unitigs_device(*cur.args, d_tip.data_ptr())
+        del d_tip, d_bub, d_pop, d_weak
+        if not found:
+            break
+    if found:
+        cur = _Graph(cfrk_amd, g, min_count, buf)
+    ctx.sync()
+    fig, d_comp, d_tab, n = census(graph_args(cur))
+    print(json.dumps(dict(common, line="components_after_loop", rules="tips+bubbles+bulges+weak", rounds=rounds, nodes=cur.nodes(torch),
+                          unitigs=cur.nS, links=cur.n_links, masked_keys=g.mask_count(), census=fig)), flush=True)
+    del cur, d_comp, d_tab
+    g.mask_clear()
+
+
 def compact_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf, stream):
     k = a.k
     tip_q8, bub_q8, bulge_q8 = int(round(a.tip_ratio * 256)), int(round(a.bubble_ratio * 256)), int(round(a.bulge_ratio * 256))
@@ -569,6 +703,7 @@ def main():
     ap.add_argument("--bulge-max-visits", type=int, default=1024)
     ap.add_argument("--compact", action="store_true")
     ap.add_argument("--weak", action="store_true")
+    ap.add_argument("--components", action="store_true")
     ap.add_argument("--weak-ratio", type=float, default=4.0)
     ap.add_argument("--weak-iso-mean", type=float, default=2.0)
     ap.add_argument("--loop-reps", type=int, default=3)
@@ -651,6 +786,13 @@ def main():
             weak_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf, (reads.data_ptr(), r_start.data_ptr(), r_length.data_ptr(), nN, R),
                       (clean.data_ptr(), r_start.data_ptr(), r_length.data_ptr(), nN, R))
             del g, out, reads, clean, r_start, r_length
+            torch.cuda.empty_cache()
+            continue
+        if a.components:
+            common = {"tool": "bench_components", "case": case, "reads": R, "L": L, "glen": a.glen, "k": k, "reps": a.reps,
+                      "error_rate": 0.0 if case == "a" else a.error_rate, "min_count": min_count, "distinct_keys": distinct}
+            components_case(a, torch, cfrk_amd, ctx, g, min_count, common, timed, stats, buf, case)
+            del g, out, reads
             torch.cuda.empty_cache()
             continue
         if a.compact:
