@@ -380,12 +380,28 @@ __device__ __forceinline__ void dev_load_chunk32(const int8_t *__restrict__ data
                                                  int64_t nN, uint32_t &b0, uint32_t &b1,
                                                  uint32_t &bad) {
   if (off + 32 <= nN) {
+    // The eight words as dev_pack4 / dev_bad4 would do them one by one, without the moves to their places:
+    // eight instructions per word and three per 16 bases.
     const uint4 *p = reinterpret_cast<const uint4 *>(data + off);
-    uint4 v0 = p[0], v1 = p[1];
-    uint32_t m0, m1;
-    dev_pack16(v0, b0, m0);
-    dev_pack16(v1, b1, m1);
-    bad = (m0 << 16) | m1;
+    const uint4 v0 = p[0], v1 = p[1];
+    const uint32_t w[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+    // bases: the packed byte of a word is the TOP byte of its product; two v_perm_b32 put four of them side by
+    // side (selector bytes 4..7 = bytes of the first operand, 0..3 = of the second, 0x0c = zero)
+    uint32_t pr[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) pr[i] = (w[i] & 0x03030303u) * 0x40100401u;
+    b0 = __builtin_amdgcn_perm(pr[0], pr[1], 0x07030c0cu) | __builtin_amdgcn_perm(pr[2], pr[3], 0x0c0c0703u);
+    b1 = __builtin_amdgcn_perm(pr[4], pr[5], 0x07030c0cu) | __builtin_amdgcn_perm(pr[6], pr[7], 0x0c0c0703u);
+    // invalid flags: the gather of dev_bad4 leaves a word's four flags in bits 0..3 with other partial products
+    // above them.  From the last word to the first, each v_alignbit takes the low nibble in at the top and
+    // moves the earlier ones down by four: the junk falls out, word 0 ends in the top nibble.
+    uint32_t acc = 0;
+#pragma unroll
+    for (int i = 7; i >= 0; --i) {
+      const uint32_t f = (((w[i] & 0x7C7C7C7Cu) + 0x7F7F7F7Fu) | w[i]) & 0x80808080u;
+      acc = __builtin_amdgcn_alignbit(__umulhi(f, 0x10080402u), acc, 4);
+    }
+    bad = acc;
   } else {
     b0 = 0; b1 = 0; bad = 0;
     for (int j = 0; j < 32; ++j) {

@@ -199,23 +199,26 @@ __device__ __forceinline__ void p1_tile(uint4 *pool, const int8_t *__restrict__ 
   const uint32_t nbad = dev_lane_next(bad), nnbad = dev_lane_next(dev_lane_next(bad));
   const uint64_t hi = ((uint64_t)b0 << 32) | b1;
   const uint64_t mid = ((uint64_t)n0 << 32) | n1;
-  uint64_t Yh = ((uint64_t)bad << 32) | nbad, Yl = (uint64_t)nnbad << 32;
+  // invalid bases smeared over the k - 1 positions before them, by doubling, on the three words there are
+  // (every shift is between 1 and 16: one v_alignbit and one v_or per word and step)
+  uint32_t Q0 = bad, Q1 = nbad, Q2 = nnbad;
   {
     int w = 1;
 #pragma unroll
     for (int st = 0; st < 5; ++st) {
       if (2 * w <= k) {
-        Yh |= (Yh << w) | (Yl >> (64 - w));
-        Yl |= Yl << w;
+        Q0 |= __builtin_amdgcn_alignbit(Q0, Q1, 32 - w);
+        Q1 |= __builtin_amdgcn_alignbit(Q1, Q2, 32 - w);
+        Q2 |= Q2 << w;
         w *= 2;
       }
     }
     if (k > w) {
-      Yh |= (Yh << (k - w)) | (Yl >> (64 - (k - w)));
-      Yl |= Yl << (k - w);
+      Q0 |= __builtin_amdgcn_alignbit(Q0, Q1, 32 - (k - w));
+      Q1 |= __builtin_amdgcn_alignbit(Q1, Q2, 32 - (k - w));
     }
   }
-  const uint64_t Vx = ~Yh;
+  const uint64_t Vx = ~(((uint64_t)Q0 << 32) | Q1);
   const uint32_t V = (uint32_t)(Vx >> 32);
   const uint32_t prevV = dev_lane_prev(V) & 1u;
 

@@ -235,8 +235,10 @@ __device__ __forceinline__ void block_scan(const uint32_t *cnt, uint32_t *off, u
 // (Measured in round 3 and not kept, profiles/r03/raw_order_minimizers_ab.txt: ordering the RAW
 // canonical m-mers, top-aligned in their windows -- four instructions per position instead of seven
 // -- makes 9.4 % more records (lexicographic minimizers are denser) and clumps the leaves: P1
-// unchanged, P2 +1.0 ms, P3 +3.0 ms; keeping the multiply but extracting both strands top-aligned
-// (six instructions) makes 2.2 % more records for no gain in P1.)
+// unchanged, P2 +1.0 ms, P3 +3.0 ms; keeping the multiply but hashing the top-aligned words as they
+// are makes 2.2 % more records for no gain in P1.  What is here extracts both strands top-aligned
+// and shifts the MINIMUM down before the multiply: six instructions per position instead of seven,
+// the same values bit for bit.)
 template <int W>
 __device__ __forceinline__ uint64_t msp_minimizers(uint64_t hi, uint64_t mid, int64_t chunk, int m,
                                                    uint32_t (&H)[32 + W - 1]) {
@@ -248,30 +250,37 @@ __device__ __forceinline__ uint64_t msp_minimizers(uint64_t hi, uint64_t mid, in
   // shorter than 32 positions, and only minima of overlapping windows are ever compared): a run
   // then never exceeds W k-mers
   {
-    // Both strands by extraction instead of rolling: the 16 bases from position j are one
-    // v_alignbit of two string words (static shift), the m-mer is their top 2m bits; its
-    // reverse complement is the low 2m bits of a 32-bit window of the reverse-complemented string
-    // ending where the m-mer starts.  Four instructions per position for the two m-mers.
+    // Both strands by extraction instead of rolling, both TOP-aligned: the 16 bases from position j
+    // are one v_alignbit of two string words (static shift), the m-mer is their top 2m bits; its
+    // reverse complement ends, in the reverse-complemented string, where the m-mer starts, and that
+    // string is moved left by 32 - 2m bits once per lane (three v_alignbit; m is uniform), so the
+    // same static v_alignbit gives a window whose top 2m bits are the reverse complement.  (As a
+    // 64-bit shift per word the move costs the same and a VGPR more.)  The bits below are
+    // neighbouring bases: they decide the minimum only when the top bits tie, and then both m-mers
+    // are the same value (a palindrome, even m).  Six instructions per position: two v_alignbit,
+    // the minimum, its shift down, the multiply, and the tag (v_and_or).
     (void)chunk;
     const uint32_t D[3] = {(uint32_t)(hi >> 32), (uint32_t)hi, (uint32_t)(mid >> 32)};
-    uint32_t R[4];
+    uint32_t R[5];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       uint32_t x = __brev(D[i]);
       x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
       R[3 - i] = ~x;
     }
-    R[0] = 0;
-    const uint32_t mmask = (m == 16) ? 0xFFFFFFFFu : ((1u << (2 * m)) - 1u);
-    const int fsh = 32 - 2 * m;
+    R[0] = 0; R[4] = 0;
+    const int fsh = 32 - 2 * m;                    // 0 at m = 16, where RS = R
+    uint32_t RS[4];
+    RS[0] = 0;                                     // (no window reaches it: 96 - 2j >= 34)
+#pragma unroll
+    for (int i = 1; i < 4; ++i) RS[i] = fsh ? __builtin_amdgcn_alignbit(R[i], R[i + 1], 32 - fsh) : R[i];
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
       const int o = 2 * j, q = o >> 5, r = o & 31;
       const uint32_t X = r ? __builtin_amdgcn_alignbit(D[q], D[q + 1], 32 - r) : D[q];
       const int o2 = 96 - 2 * j, q2 = o2 >> 5, r2 = o2 & 31;
-      const uint32_t Y = r2 ? __builtin_amdgcn_alignbit(R[q2], R[q2 + 1], 32 - r2) : R[q2];
-      const uint32_t fm = X >> fsh, rm = Y & mmask;
-      H[j] = (hash_mmer(min(fm, rm)) & ~127u) | (uint32_t)j;
+      const uint32_t Y = r2 ? __builtin_amdgcn_alignbit(RS[q2], RS[q2 + 1], 32 - r2) : RS[q2];
+      H[j] = (hash_mmer(min(X, Y) >> fsh) & ~127u) | (uint32_t)j;
     }
   }
 #pragma unroll
